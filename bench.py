@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- CD-1 updates/s of the headline RBM (10000 <-> 1500, batch 64 per GPU) on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Both forms work: with ``--gpus N > 1`` and no torchrun environment the process starts N fresh rank
@@ -16,10 +16,18 @@ global batch; one exchange per step over RCCL (all-gather of the factor blocks b
 the packed statistics that north_star names is timed right after it and reported beside it); `value` counts
 batch-64 updates per second summed over the ranks (= N x global steps/s, weak scaling: 64 rows per GPU).
 
-One JSON line on rank 0.  `roofline` is for the dominant kernel (K3 assoc_update): algorithmic bytes
+One JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline
+(`value`, `ms_per_step`); everything else is measured only with `--full`:
+`roofline` is for the dominant kernel (K3 assoc_update): algorithmic bytes
 16*V*H per launch over the HIP-event-measured mean launch time on the launch stream.
 `cpu_baseline` times the numpy oracle (a port of the reference arithmetic) on the same workload.
 `other_configs` times the other BASELINE.json configs (C2 stack, C3, C5) after the headline region.
+With N>1, `dp_other_exchange` times the other exchange and `replicas_identical` compares the replicas.
+Without `--full` these fields are null.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step handed its caller: the loss and
+the updated parameters W, hid_bias, vis_bias of rank 0 (DIR/<name>.npy, float32, ~60 MB in all).  The inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -294,7 +302,14 @@ def main():
                     help="diagnostic: mark the resident batches as 0/1 (what a DeviceLoader does); by default they are plain, untagged "
                          "tensors and the device finds out what they contain")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse the multi-rank flow on one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's loss and updated W / hid_bias / vis_bias as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: K3 roofline, host enqueue times, other configs, CPU "
+                         "baseline, the other data-parallel exchange and the replica check")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # (before anything initialises the GPU; see _spawn_ranks)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -381,7 +396,8 @@ def main():
         stamps = []
         for i in range(i0, i0 + args.steps):      # continues the batch sequence of the warm-up steps
             loss = step(i)
-            stamps.append(time.perf_counter())
+            if args.full:
+                stamps.append(time.perf_counter())
         t_enq = time.perf_counter() - t0          # host time to enqueue all steps (== dt when host-bound)
         sync()
         dt = time.perf_counter() - t0
@@ -393,7 +409,7 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
         assert torch.isfinite(loss).item(), "loss is not finite"
-        return dt, t_enq, stamps, t0, k3, float(loss)
+        return dt, t_enq, stamps, t0, k3, loss
 
     # Any failure below (an engine error, a HIP or RCCL error) ends the run with a non-zero exit code: no fallback to another
     # exchange in a process that has seen a GPU error, and no rank ever switches collectives on its own.
@@ -409,10 +425,17 @@ def main():
     for i in range(n_prime):
         step(i)
     sync()
-    dt, t_enq, stamps, t0, (k3_ms, k3_n), loss = timed_region(not args.no_k3_events and (not use_dp or args.dp_mode == "factors"))
+    dt, t_enq, stamps, t0, (k3_ms, k3_n), loss_t = timed_region(args.full and not args.no_k3_events and (not use_dp or args.dp_mode == "factors"))
+    loss = float(loss_t)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step returned (the loss) and left in the model its caller holds (rank 0's replica)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in (("loss", loss_t), ("W", rbm.W.data), ("hid_bias", rbm.hid_bias.data), ("vis_bias", rbm.vis_bias.data)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.detach().float().contiguous().cpu().numpy())
 
     def replicas_identical():
-        if world == 1:
+        if world == 1 or not args.full:
             return None      # every rank applied the same update, so the replicas must agree bit for bit
         chk = torch.stack([rbm.W.data.double().sum(), rbm.W.data.double().abs().sum(), rbm.hid_bias.data.double().sum()])
         allc = [torch.zeros_like(chk) for _ in range(world)]
@@ -426,12 +449,12 @@ def main():
 
     ident = replicas_identical()
     other_exchange = None
-    if use_dp:      # the other exchange, same K steps, reported beside the headline one
+    if use_dp and args.full:      # the other exchange, same K steps, reported beside the headline one
         other = "allreduce" if args.dp_mode == "factors" else "factors"
         E.dp.enable(force=args.force_dp, mode=other, binary_data=not args.dp_full_planes)
         dt2, _, _, _, _, loss2 = timed_region(False)
         other_exchange = {"dp_exchange": exchange_name(other), "value": world * args.steps / dt2, "unit": "updates/s",
-                          "ms_per_step": 1e3 * dt2 / args.steps, "final_loss": loss2, "replicas_identical": replicas_identical()}
+                          "ms_per_step": 1e3 * dt2 / args.steps, "final_loss": float(loss2), "replicas_identical": replicas_identical()}
 
     if rank == 0:
         # unit = one batch-64 CD-1 update; every rank processes one per step (the step updates the shared weights
@@ -451,7 +474,7 @@ def main():
                        "final_loss": loss, "replicas_identical": ident},
             "global_steps_per_s": args.steps / dt,
             "setup_steps_before_warmup": n_prime,
-            "host_enqueue_us_per_step": 1e6 * t_enq / args.steps,
+            "host_enqueue_us_per_step": 1e6 * t_enq / args.steps if args.full else None,
             "host_enqueue_us_p50_max": _p50_max(t0, stamps),
             "frac_hbm_roofline_whole_step": (ups / world) * 16.0 * V * H / (HBM_PEAK_GBS * 1e9),
             "frac_bf16_mfma_roofline_whole_step": (ups / world) * 10.0 * B * V * H / (BF16_PEAK_TFLOPS * 1e12),
@@ -495,8 +518,8 @@ def main():
                     pass
         else:
             out["roofline"] = None
-        out["other_configs"] = other_configs(dev) if (world == 1 and not use_dp and not args.no_other_configs) else None
-        out["cpu_baseline"] = cpu_baseline() if (world == 1 and not args.no_cpu_baseline) else None
+        out["other_configs"] = other_configs(dev) if (args.full and world == 1 and not use_dp and not args.no_other_configs) else None
+        out["cpu_baseline"] = cpu_baseline() if (args.full and world == 1 and not args.no_cpu_baseline) else None
         print(json.dumps(out), flush=True)
     if use_dp:
         dist.destroy_process_group()

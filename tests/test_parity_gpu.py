@@ -880,7 +880,7 @@ def test_bench_multi_gpu_form_starts_its_own_ranks():
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "6", "--warmup", "2",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -889,3 +889,27 @@ def test_bench_multi_gpu_form_starts_its_own_ranks():
     assert d["config"]["replicas_identical"] is True and d["config"]["dp_exchange"].startswith("factors")
     o = d["dp_other_exchange"]
     assert o["dp_exchange"].startswith("allreduce") and o["replicas_identical"] is True and o["value"] > 0
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps, measures nothing beside the headline, and with
+    --dump-outputs writes the last step's loss and the updated parameters (float32, within 64 MB)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "updates/s" and d["higher_is_better"] is True
+    assert d["ms_per_step"] > 0 and abs(d["value"] * d["ms_per_step"] - 1e3) < 1e-6 * 1e3
+    assert d["roofline"] is None and d["other_configs"] is None and d["cpu_baseline"] is None
+    arrays = {n: np.load(out_dir / f"{n}.npy") for n in ("loss", "W", "hid_bias", "vis_bias")}
+    assert arrays["W"].shape == (10000, 1500) and arrays["hid_bias"].shape == (1500,) and arrays["vis_bias"].shape == (10000,)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert float(arrays["loss"]) == np.float32(d["config"]["final_loss"])
+    assert sum(f.stat().st_size for f in out_dir.iterdir()) <= 64 * 10**6
