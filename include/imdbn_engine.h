@@ -294,6 +294,40 @@ typedef struct imdbn_chain_spec {
 int imdbn_rbm_chain_pair(const imdbn_rbm_desc* d, int B, const imdbn_chain_spec* a, const imdbn_chain_spec* b,
                          imdbn_rng* rng, void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- convergence traces of conditional chains (imdbn/utils/conditional_steps.py) ------------------------------------
+ * imdbn_rbm_chain_traced = imdbn_rbm_chain(a) (b == NULL) or imdbn_rbm_chain_pair(a, b), recording at every step the visible
+ * probability p the step computes (after the mu-pull, BEFORE re-clamping and sampling) of the columns [c0, c1).  Recording only
+ * observes: the final states, the draws and draws_used are those of the untraced calls, bit for bit.  A NULL trace records
+ * nothing. */
+typedef struct imdbn_chain_trace {
+    int32_t c0, c1;          /* visible columns recorded, [c0, c1) */
+    int32_t with_baseline;   /* 1: slot 0 = p(v | p(h | v0)) at T = 1 -- no sampling, no state change, no draws */
+    int32_t _pad;
+    float*  out;             /* slot s, row b at out + s*step_stride + b*ld_row; slots = n_steps + with_baseline */
+    int64_t ld_row, step_stride;
+} imdbn_chain_trace;
+int imdbn_rbm_chain_traced(const imdbn_rbm_desc* d, int B, const imdbn_chain_spec* a, const imdbn_chain_trace* ta,
+                           const imdbn_chain_spec* b, const imdbn_chain_trace* tb, imdbn_rng* rng,
+                           void* ws, size_t ws_bytes, imdbn_stream_t stream);
+/* IMG->TXT scan of a label trace of T steps after a baseline (slot 0), rows of K <= 256 probabilities (conditional_steps.py:40-130).
+ * Per step, [B][T]: p_top1, p_top2, k1, k2 (ties to the lower index), p_gt (gt nullable; then p_gt may be NULL), l1 = |y_t - y_{t-1}|_1.
+ * Per row: steps = first t with l1 < eps_l1, argmax streak >= stable_steps and p1 - p2 >= gap_thresh (T + 1: never); pred = argmax
+ * at that step (at step T without convergence). */
+int imdbn_trace_label_scan(const float* trace, int64_t step_stride, int64_t ld_row, int T, int B, int K, const int32_t* gt,
+                           double eps_l1, int stable_steps, double gap_thresh, float* p_top1, float* p_top2, int32_t* k1,
+                           int32_t* k2, float* p_gt, float* l1, int32_t* steps, int32_t* pred, imdbn_stream_t stream);
+/* TXT->IMG code scan (conditional_steps.py:195-215): z_new[T][B][Dz] = (1-beta) z_prev + beta z_t (beta > 0) or z_t, starting from
+ * z_init[B][Dz]; dz[B][T] = ||z_new_t - z_prev||_2. */
+int imdbn_trace_code_scan(const float* trace, int64_t step_stride, int64_t ld_row, int T, int B, int Dz, const float* z_init,
+                          int64_t ld_init, float ema_beta, float* z_new, float* dz, imdbn_stream_t stream);
+/* TXT->IMG stop rule (conditional_steps.py:217-234) over dz[B][T] and mse[B][T]: steps[B] (T + 1: never) and best_mse[B]. */
+int imdbn_trace_patience_scan(const float* dz, const float* mse, int T, int B, double eps_z, double mse_tol, int patience,
+                              int32_t* steps, float* best_mse, imdbn_stream_t stream);
+/* out_mse[i] = mean_c (p(v|h_i)_c - ref[ref_row[i]]_c)^2 with p(v|h) computed exactly as imdbn_rbm_prop_down at T = 1 (ref_row
+ * nullable: row i).  The decoded rows stay in the workspace; the per-row sums run in a fixed order (deterministic).  No softmax groups. */
+int imdbn_rbm_prop_down_sqerr(const imdbn_rbm_desc* d, const float* h, int64_t ldh, int B, const float* ref, int64_t ldr,
+                              const int32_t* ref_row, float* out_mse, void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- whole RBM.train_epoch_clamped (rbm.py:402-483) -------------------------------------- */
 /* positive phase = chain(n_init steps) ; negative = cd_k steps from v+ ; update with o->lr */
 int imdbn_rbm_clamped_step(const imdbn_rbm_desc* d, const float* v_known, const float* mask, int64_t ldk, int B,

@@ -20,6 +20,7 @@
 #include "kernels_gemm.hpp"
 #include "kernels_chain.hpp"
 #include "kernels_stream.hpp"
+#include "kernels_trace.hpp"
 
 using namespace imdbn;
 
@@ -843,6 +844,9 @@ bool chain_kernel_ok(const Ctx& c, int n_steps) {
 struct ChainSpec {
     const float* vk; const float* mask; int64_t ldk; int init_uniform; int n_steps; const imdbn_chain_step* st;
     const float* mu; int64_t ldmu; int Dz; float* out; int64_t ldo;
+    const imdbn_chain_trace* tr = nullptr;           // imdbn_rbm_chain_traced: what to record (nullable)
+    int base() const { return tr && tr->with_baseline ? 1 : 0; }
+    int n_recs() const { return n_steps + base(); }  // with a baseline, record 0 is an observe-only step (no draws, no state change)
 };
 
 // v0 = vk*m + (1-m)*U   (rbm.py:271,333,392) into `out` (and, for the per-launch path, the operand forms of vis_rm[0])
@@ -873,12 +877,14 @@ int chain_records(Ctx& c, const ChainSpec& s, int off) {
     const imdbn_rbm_desc* d = c.d;
     const int B = L.B;
     ChainRecBatch batch;
-    for (int t0 = 0; t0 < s.n_steps; t0 += CHAIN_REC_BATCH) {
-        const int n = std::min(CHAIN_REC_BATCH, s.n_steps - t0);
+    const int nr = s.n_recs(), b0 = s.base();
+    for (int t0 = 0; t0 < nr; t0 += CHAIN_REC_BATCH) {
+        const int n = std::min(CHAIN_REC_BATCH, nr - t0);
         memset(&batch, 0, sizeof(batch));
         for (int i = 0; i < n; ++i) {
-            const imdbn_chain_step& st = s.st[t0 + i];
             ChainRec& r = batch.r[i];
+            if (t0 + i < b0) { r.T = 1.0f; r.flags = 16; continue; }      // the traced baseline p(v | p(h | v0)) at T = 1
+            const imdbn_chain_step& st = s.st[t0 + i - b0];
             r.T = st.T; r.sigma = st.sigma; r.eta = st.eta;
             r.flags = (st.sample_h ? 1 : 0) | ((st.vmode & 3) << 1) | (st.clamp ? 8 : 0);
             auto cd = [](const DrawSrc& x) { ChainDraw y; y.tape = x.tape; y.draw = x.draw; return y; };
@@ -920,6 +926,9 @@ int launch_k4(Ctx& c, const ChainSpec& s0, int off0, const ChainSpec* s1, int of
         K4Seg g;
         g.state = s.out; g.lds = s.ldo; g.recs = L.chain_recs + off; g.n_steps = s.n_steps;
         g.mu = s.mu; g.ldmu = s.ldmu; g.Dz = s.Dz; g.vk = s.vk; g.mask = s.mask; g.ldk = s.ldk; g.B = B;
+        g.n_steps = s.n_recs();
+        g.tr = nullptr; g.tr_ld = g.tr_ss = 0; g.tr_c0 = g.tr_c1 = 0;
+        if (s.tr) { g.tr = s.tr->out; g.tr_ld = s.tr->ld_row; g.tr_ss = s.tr->step_stride; g.tr_c0 = s.tr->c0; g.tr_c1 = s.tr->c1; }
         return g;
     };
     a.s0 = seg(s0, off0);
@@ -946,8 +955,8 @@ int run_chain(Ctx& c, const ChainSpec& s, bool want_stats) {
     const int n_steps = s.n_steps, Dz = s.Dz; const imdbn_chain_step* st = s.st; const float* mu = s.mu; float* out = s.out;
     if (n_steps < 0 || (n_steps > 0 && !st)) return fail(IMDBN_E_INVALID, "bad chain steps");
     if (mu && (Dz <= 0 || Dz > L.V)) return fail(IMDBN_E_INVALID, "mu-pull width %d outside (0,%d]", Dz, L.V);
-    const bool k4 = chain_kernel_ok(c, n_steps);
-    CHK(chain_init(c, s, !k4 || n_steps == 0, want_stats && n_steps == 0));
+    const bool k4 = chain_kernel_ok(c, s.n_recs());
+    CHK(chain_init(c, s, !k4 || s.n_recs() == 0, want_stats && n_steps == 0));
     if (k4) {
         CHK(chain_records(c, s, 0));
         CHK(launch_k4(c, s, 0, nullptr, 0));
@@ -955,6 +964,25 @@ int run_chain(Ctx& c, const ChainSpec& s, bool want_stats) {
         if (want_stats) CHK(prep(c, out, ldo, L.V, L.vis_rm[0], L.Vpad, L.vis_tr[0], nullptr, L.cs_vpos, c.rt));
         c.hid_bits_ok = false;
         return 0;
+    }
+    const int s_base = s.base();
+    auto record = [&](int slot) -> int {             // the trace of the per-launch path: the window of the step's fp32 v_prob
+        if (!s.tr) return 0;
+        const int w = s.tr->c1 - s.tr->c0;
+        const int blocks = (int)std::min<int64_t>(((int64_t)B * w + 255) / 256, 1024);
+        hipLaunchKernelGGL(trace_copy, dim3(std::max(blocks, 1)), dim3(256), 0, c.s, L.f_vp, (int64_t)L.V, B, s.tr->c0, s.tr->c1,
+                           s.tr->out + (int64_t)slot * s.tr->step_stride, s.tr->ld_row);
+        HIPCHK(hipGetLastError());
+        return 0;
+    };
+    if (s.base()) {      // observe-only baseline step: p(v | p(h | v0)) at T = 1, no draws; vis_rm[0] keeps v0
+        FinishArgs fh = new_finish();
+        fh.op.rm = L.hid_rm; fh.op.rm_terms = c.rt; fh.rm_src = 1;
+        CHK(prop(c, true, OpIn{L.vis_rm[0], c.rt, nullptr}, fh));
+        FinishArgs fv = new_finish();
+        fv.out_prob = L.f_vp; fv.ld_prob = L.V;
+        CHK(prop(c, false, OpIn{L.hid_rm, c.rt, nullptr}, fv));
+        CHK(record(0));
     }
     for (int t = 0; t < n_steps; ++t) {
         const imdbn_chain_step& s = st[t];
@@ -984,6 +1012,7 @@ int run_chain(Ctx& c, const ChainSpec& s, bool want_stats) {
             }
             CHK(prop(c, false, OpIn{L.hid_rm, s.sample_h ? 1 : c.rt, nullptr}, f));
         }
+        CHK(record(t + s_base));
     }
     return 0;
 }
@@ -1613,6 +1642,100 @@ int imdbn_rbm_chain_pair(const imdbn_rbm_desc* d, int B, const imdbn_chain_spec*
         CHK(run_chain(c, sb, false));
     }
     return c.rng.finish();
+}
+
+// imdbn_rbm_chain / imdbn_rbm_chain_pair with the visible probabilities of a column window recorded at every step (the convergence
+// traces of imdbn/utils/conditional_steps.py).  Recording only observes: same draws, same final state as the untraced calls.
+static int check_trace(const imdbn_rbm_desc* d, const imdbn_chain_trace* t) {
+    if (!t) return 0;
+    if (!t->out || t->c0 < 0 || t->c1 <= t->c0 || t->c1 > d->V || t->ld_row < t->c1 - t->c0 || t->step_stride < 0 ||
+        (t->with_baseline != 0 && t->with_baseline != 1))
+        return fail(IMDBN_E_INVALID, "chain_traced: bad trace [%d, %d) ld %lld", t->c0, t->c1, (long long)t->ld_row);
+    return 0;
+}
+
+int imdbn_rbm_chain_traced(const imdbn_rbm_desc* d, int B, const imdbn_chain_spec* a, const imdbn_chain_trace* ta,
+                           const imdbn_chain_spec* b, const imdbn_chain_trace* tb, imdbn_rng* rng, void* ws, size_t ws_bytes,
+                           imdbn_stream_t stream) {
+    CHK(check_desc(d, false));
+    if (!a || (tb && !b)) return fail(IMDBN_E_INVALID, "chain_traced: null chain");
+    for (const imdbn_chain_spec* s : {a, b})
+        if (s && (!s->v_known || !s->mask || !s->out_v || s->ldk < d->V || s->ldo < d->V || s->n_steps < 0 || (s->n_steps > 0 && !s->steps) ||
+                  (s->mu && (s->Dz <= 0 || s->Dz > d->V))))
+            return fail(IMDBN_E_INVALID, "chain_traced: bad argument");
+    if (b && a->out_v == b->out_v) return fail(IMDBN_E_INVALID, "chain_traced: the two chains need separate output buffers");
+    CHK(check_trace(d, ta));
+    CHK(check_trace(d, tb));
+    Ctx c(d, rng, S(stream));
+    CHK(setup(c, B, ws, ws_bytes));
+    ChainSpec sa{a->v_known, a->mask, a->ldk, a->init_uniform, a->n_steps, a->steps, a->mu, a->ldmu, a->Dz, a->out_v, a->ldo};
+    sa.tr = ta;
+    if (!b) {
+        CHK(run_chain(c, sa, false));
+        return c.rng.finish();
+    }
+    ChainSpec sb{b->v_known, b->mask, b->ldk, b->init_uniform, b->n_steps, b->steps, b->mu, b->ldmu, b->Dz, b->out_v, b->ldo};
+    sb.tr = tb;
+    if (chain_kernel_ok(c, sa.n_recs()) && chain_kernel_ok(c, sb.n_recs()) && sa.n_recs() + sb.n_recs() <= CHAIN_MAX_STEPS && !g_no_chain_pair) {
+        CHK(chain_init(c, sa, false, false));
+        CHK(chain_records(c, sa, 0));
+        CHK(chain_init(c, sb, false, false));
+        CHK(chain_records(c, sb, sa.n_recs()));
+        CHK(launch_k4(c, sa, 0, &sb, sa.n_recs()));
+        c.hid_bits_ok = false;
+    } else {
+        CHK(run_chain(c, sa, false));
+        CHK(run_chain(c, sb, false));
+    }
+    return c.rng.finish();
+}
+
+int imdbn_trace_label_scan(const float* trace, int64_t step_stride, int64_t ld_row, int T, int B, int K, const int32_t* gt,
+                           double eps_l1, int stable_steps, double gap_thresh, float* p_top1, float* p_top2, int32_t* k1, int32_t* k2,
+                           float* p_gt, float* l1, int32_t* steps, int32_t* pred, imdbn_stream_t stream) {
+    if (!trace || T < 1 || B < 1 || K < 2 || K > TRACE_KMAX || ld_row < K || step_stride < (int64_t)B * ld_row || !p_top1 || !p_top2 ||
+        !k1 || !k2 || !l1 || !steps || !pred || (gt && !p_gt))
+        return fail(IMDBN_E_INVALID, "trace_label_scan: bad argument (T=%d B=%d K=%d)", T, B, K);
+    hipLaunchKernelGGL(trace_label_scan, dim3(cdiv(B, 4)), dim3(256), 0, S(stream), trace, step_stride, ld_row, T, B, K, gt, eps_l1,
+                       stable_steps, gap_thresh, p_top1, p_top2, k1, k2, gt ? p_gt : nullptr, l1, steps, pred);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int imdbn_trace_code_scan(const float* trace, int64_t step_stride, int64_t ld_row, int T, int B, int Dz, const float* z_init,
+                          int64_t ld_init, float ema_beta, float* z_new, float* dz, imdbn_stream_t stream) {
+    if (!trace || !z_init || !z_new || !dz || T < 1 || B < 1 || Dz < 1 || ld_row < Dz || ld_init < Dz || step_stride < (int64_t)B * ld_row)
+        return fail(IMDBN_E_INVALID, "trace_code_scan: bad argument (T=%d B=%d Dz=%d)", T, B, Dz);
+    hipLaunchKernelGGL(trace_code_scan, dim3(cdiv(B, 4)), dim3(256), 0, S(stream), trace, step_stride, ld_row, T, B, Dz, z_init, ld_init,
+                       ema_beta, z_new, dz);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int imdbn_trace_patience_scan(const float* dz, const float* mse, int T, int B, double eps_z, double mse_tol, int patience,
+                              int32_t* steps, float* best_mse, imdbn_stream_t stream) {
+    if (!dz || !mse || !steps || !best_mse || T < 1 || B < 1)
+        return fail(IMDBN_E_INVALID, "trace_patience_scan: bad argument (T=%d B=%d)", T, B);
+    hipLaunchKernelGGL(trace_patience_scan, dim3(cdiv(B, 64)), dim3(64), 0, S(stream), dz, mse, T, B, eps_z, mse_tol, patience, steps, best_mse);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int imdbn_rbm_prop_down_sqerr(const imdbn_rbm_desc* d, const float* h, int64_t ldh, int B, const float* ref, int64_t ldr,
+                              const int32_t* ref_row, float* out_mse, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(check_desc(d, false));
+    if (!h || !ref || !out_mse || ldh < d->H || ldr < d->V || B < 1) return fail(IMDBN_E_INVALID, "prop_down_sqerr: bad tensor argument");
+    if (d->n_groups != 0) return fail(IMDBN_E_UNSUPPORTED, "prop_down_sqerr: softmax groups");
+    Ctx c(d, nullptr, S(stream));
+    CHK(setup(c, B, ws, ws_bytes));
+    // imdbn_rbm_prop_down at T = 1 into the workspace's [Bp][V] fp32 buffer, then the per-row error in a fixed order
+    CHK(prep(c, h, ldh, d->H, c.L.hid_rm, c.L.Hpad, nullptr, c.L.flags_h));
+    FinishArgs f = new_finish();
+    f.out_prob = c.L.f_vp; f.ld_prob = d->V;
+    CHK(prop(c, false, OpIn{c.L.hid_rm, c.nw == 1 ? 1 : 0, c.L.flags_h}, f));
+    hipLaunchKernelGGL(row_sqerr, dim3(B), dim3(256), 0, S(stream), c.L.f_vp, (int64_t)d->V, B, d->V, ref, ldr, ref_row, out_mse);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 // rbm.py:443-471: v+ by conditional inference, H+, CD-k from v+ (optionally re-clamped / sampled), H-.

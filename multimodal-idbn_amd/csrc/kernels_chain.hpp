@@ -59,7 +59,7 @@ __device__ __forceinline__ f32x4 k4_mfma(const uint4& a, const uint4& b, const f
 struct ChainDraw { const float* tape; uint64_t draw; };
 struct ChainRec {                 // one chain step (imdbn_chain_step + the draw cursors the host assigned to it)
     float T, sigma, eta;
-    int flags;                    // bit 0 sample_h | bits 1-2 vmode | bit 3 clamp
+    int flags;                    // bit 0 sample_h | bits 1-2 vmode | bit 3 clamp | bit 4 observe only (traced baseline: the state is not changed)
     ChainDraw noise_h, uni_h, noise_v, uni_v, cat_uni;
     const int32_t* cat_tape;
 };
@@ -114,6 +114,7 @@ struct K4Seg {
     const float* mu; int64_t ldmu; int Dz;
     const float* vk; const float* mask; int64_t ldk;
     int B;
+    float* tr; int64_t tr_ld, tr_ss; int tr_c0, tr_c1;   // nullable trace: p(v|h) of columns [tr_c0, tr_c1) of step t at tr + t*tr_ss + b*tr_ld
 };
 struct K4Args {
     const bf16_t* planes; int64_t plane_stride;     // [2][3] planes
@@ -262,6 +263,8 @@ __global__ __launch_bounds__(K4_THREADS, 1) void k4_chain(const K4Args a) {
     const float* const c_mu = second ? a.s1.mu : a.s0.mu; const int64_t c_ldmu = second ? a.s1.ldmu : a.s0.ldmu; const int c_Dz = second ? a.s1.Dz : a.s0.Dz;
     const float* const c_vk = second ? a.s1.vk : a.s0.vk; const float* const c_mask = second ? a.s1.mask : a.s0.mask;
     const int64_t c_ldk = second ? a.s1.ldk : a.s0.ldk; const int c_B = second ? a.s1.B : a.s0.B;
+    float* const c_tr = second ? a.s1.tr : a.s0.tr; const int64_t c_tld = second ? a.s1.tr_ld : a.s0.tr_ld, c_tss = second ? a.s1.tr_ss : a.s0.tr_ss;
+    const int c_tc0 = second ? a.s1.tr_c0 : a.s0.tr_c0, c_tc1 = second ? a.s1.tr_c1 : a.s0.tr_c1;
     const int VK = (a.V + 31) / 32 * 32 + 8, HK = (a.H + 31) / 32 * 32 + 8;      // LDS row pitch (elements): 16-B skew against bank conflicts
     constexpr int at = NW;                                                          // activation terms kept (= a.rt)
     const int gs0 = a.gs[0], gwd = a.n_groups > 0 ? a.ge[0] - a.gs[0] : 0;          // the (single) softmax group
@@ -291,7 +294,8 @@ __global__ __launch_bounds__(K4_THREADS, 1) void k4_chain(const K4Args a) {
         const ChainRec r = c_recs[t];
         const bool st = a.dbg && t == 2;
         stamp(st, blockIdx.x, 0);
-        const bool sample_h = (r.flags & 1) != 0, clamp = (r.flags & 8) != 0, last = t == c_nsteps - 1;
+        const bool sample_h = (r.flags & 1) != 0, clamp = (r.flags & 8) != 0, obs = (r.flags & 16) != 0, last = t == c_nsteps - 1 && !obs;
+        float* const trs = c_tr ? c_tr + (int64_t)t * c_tss - c_tc0 : nullptr;      // this step's trace slot (block-uniform)
         const int vmode = (r.flags >> 1) & 3;
         const float T = fmaxf(r.T, 1e-6f);                       // max(1e-6, T)  rbm.py:92,96
         const bool pull_on = c_mu && r.eta != 0.f;
@@ -366,6 +370,8 @@ __global__ __launch_bounds__(K4_THREADS, 1) void k4_chain(const K4Args a) {
                     }
                     float p = sigmoidf_ref(x);
                     if (pull_on && col < c_Dz) p = (1.0f - r.eta) * p + r.eta * c_mu[(int64_t)bd * c_ldmu + col];
+                    if (trs && col >= c_tc0 && col < c_tc1 && b < c_B) trs[(int64_t)b * c_tld + col] = p;
+                    if (obs) continue;
                     const float m = clamp ? c_mask[(int64_t)bd * c_ldk + col] : 0.f;
                     const float kn = clamp ? c_vk[(int64_t)bd * c_ldk + col] : 0.f;
                     const float mixed = clamp ? (p * (1.0f - m) + kn * m) : p;
@@ -481,6 +487,8 @@ __global__ __launch_bounds__(K4_THREADS, 1) void k4_chain(const K4Args a) {
                 const int row = i / gwd, j = i - row * gwd, col = gs0 + j, b = b0 + row, bd = min(b, c_B - 1);
                 float p = glog[row * GW + j] / gaux[row * 4 + 1];
                 if (pull_on && col < c_Dz) p = (1.0f - r.eta) * p + r.eta * c_mu[(int64_t)bd * c_ldmu + col];
+                if (trs && col >= c_tc0 && col < c_tc1 && b < c_B) trs[(int64_t)b * c_tld + col] = p;
+                if (obs) continue;
                 const float m = clamp ? c_mask[(int64_t)bd * c_ldk + col] : 0.f;
                 const float kn = clamp ? c_vk[(int64_t)bd * c_ldk + col] : 0.f;
                 const int idx = __float_as_int(gaux[row * 4 + 2]);

@@ -656,6 +656,118 @@ class HipEngine:
         self._done(rng, r, sched)
         return outs[0], outs[1]
 
+    def chain_traced(self, rbm, a: dict, b: Optional[dict], rng):
+        """``chain(a)`` (b None) or ``chain_pair(a, b)`` recording, per step, p(v|h) of a column window (imdbn_rbm_chain_traced).  Each
+        chain dict may carry ``trace=(c0, c1, with_baseline)``; returns one ``(final_v, trace)`` per chain, ``trace`` = ``[slots, B,
+        c1 - c0]`` (slots = steps + with_baseline; slot 0 of a baseline = p(v | p(h | v0)) at T = 1) or None.  Same draws, same final
+        states as the untraced calls."""
+        d = self._desc(rbm, False)
+        keep, specs, traces, outs, trs, sched = [], [], [], [], [], []
+        B = dev = None
+        for ch in (a, b):
+            if ch is None:
+                specs.append(None); traces.append(None); continue
+            vk, km = _f32c(ch["v_known"], "v_known"), _f32c(ch["mask"], "mask")
+            if vk.stride(0) != km.stride(0):
+                vk, km = vk.contiguous(), km.contiguous()
+            if B is None:
+                B, dev = vk.size(0), vk.device
+            elif vk.size(0) != B:
+                raise N.EngineError("chain_traced: the two chains need the same batch size")
+            steps, init_uniform = ch["steps"], bool(ch.get("init_uniform", True))
+            out = torch.empty(B, d.V, device=dev)
+            mu = ch.get("mu")
+            mu_t = _f32c(mu, "mu") if mu is not None else None
+            arr = self._steps(steps)
+            sp = N.ChainSpec()
+            sp.v_known, sp.mask, sp.ldk = vk.data_ptr(), km.data_ptr(), vk.stride(0)
+            sp.init_uniform, sp.n_steps, sp.steps = int(init_uniform), len(steps), arr
+            sp.mu, sp.ldmu, sp.Dz = (mu_t.data_ptr() if mu_t is not None else 0), (mu_t.stride(0) if mu_t is not None else 0), (mu_t.size(1) if mu_t is not None else 0)
+            sp.out_v, sp.ldo = out.data_ptr(), out.stride(0)
+            tr, tt = None, None
+            if ch.get("trace") is not None:
+                c0, c1, base = (int(x) for x in ch["trace"])
+                tr = torch.empty(len(steps) + (1 if base else 0), B, c1 - c0, device=dev)
+                tt = N.ChainTrace()
+                tt.c0, tt.c1, tt.with_baseline = c0, c1, 1 if base else 0
+                tt.out, tt.ld_row, tt.step_stride = tr.data_ptr(), tr.stride(1), tr.stride(0)
+            specs.append(sp); traces.append(tt); outs.append(out); trs.append(tr); keep.append((vk, km, mu_t, arr))
+            sched += R.sched_chain(d.V, d.H, self._groups(rbm), steps, init_uniform)
+        r, keep_r = self._rng(rng, sched, B, dev)
+        ws = self._workspace(dev, d.V, d.H, B)
+        ref = lambda x: C.byref(x) if x is not None else None
+        N.check(self._lib.imdbn_rbm_chain_traced(C.byref(d), B, ref(specs[0]), ref(traces[0]), ref(specs[1]), ref(traces[1]), C.byref(r),
+                                                  _ptr(ws), ws.numel(), self._stream(dev)), "imdbn_rbm_chain_traced")
+        self._done(rng, r, sched)
+        return list(zip(outs, trs))
+
+    def label_scan(self, trace: torch.Tensor, gt: Optional[torch.Tensor], eps_l1: float, stable_steps: int, gap_thresh: float) -> dict:
+        """IMG->TXT scan of a label trace ``[T + 1, B, K]`` (slot 0 = baseline): per-step ``[B, T]`` p_top1 / p_top2 / k1 / k2 / p_gt / l1
+        and per-row ``steps`` (T + 1 = not converged) / ``pred`` (imdbn_trace_label_scan)."""
+        S, B, K = trace.shape
+        T = S - 1
+        if trace.stride(2) != 1:
+            trace = trace.contiguous()
+        dev = trace.device
+        f = lambda: torch.empty(B, T, device=dev)
+        i = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)
+        o = {"p_top1": f(), "p_top2": f(), "k1": i(B, T), "k2": i(B, T), "p_gt": f() if gt is not None else None, "l1": f(),
+             "steps": i(B), "pred": i(B)}
+        g = gt.to(device=dev, dtype=torch.int32).contiguous() if gt is not None else None
+        N.check(self._lib.imdbn_trace_label_scan(_ptr(trace), trace.stride(0), trace.stride(1), T, B, K, _ptr(g), float(eps_l1),
+                                                  int(stable_steps), float(gap_thresh), _ptr(o["p_top1"]), _ptr(o["p_top2"]), _ptr(o["k1"]),
+                                                  _ptr(o["k2"]), _ptr(o["p_gt"]), _ptr(o["l1"]), _ptr(o["steps"]), _ptr(o["pred"]),
+                                                  self._stream(dev)), "imdbn_trace_label_scan")
+        return o
+
+    def code_scan(self, trace: torch.Tensor, z_init: torch.Tensor, ema_beta: float):
+        """TXT->IMG code scan of a z trace ``[T, B, Dz]``: ``(z_new [T, B, Dz], dz [B, T])`` (imdbn_trace_code_scan)."""
+        T, B, Dz = trace.shape
+        if trace.stride(2) != 1:
+            trace = trace.contiguous()
+        z0 = _f32c(z_init, "z_init")
+        dev = trace.device
+        zn, dz = torch.empty(T, B, Dz, device=dev), torch.empty(B, T, device=dev)
+        N.check(self._lib.imdbn_trace_code_scan(_ptr(trace), trace.stride(0), trace.stride(1), T, B, Dz, _ptr(z0), z0.stride(0),
+                                                 float(ema_beta), _ptr(zn), _ptr(dz), self._stream(dev)), "imdbn_trace_code_scan")
+        return zn, dz
+
+    def patience_scan(self, dz: torch.Tensor, mse: torch.Tensor, eps_z: float, mse_tol: float, patience: int):
+        """TXT->IMG stop rule over ``dz``, ``mse`` ``[B, T]``: ``(steps [B] int32, best_mse [B])`` (imdbn_trace_patience_scan)."""
+        dz, mse = dz.float().contiguous(), mse.float().contiguous()
+        B, T = dz.shape
+        dev = dz.device
+        steps, best = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, device=dev)
+        N.check(self._lib.imdbn_trace_patience_scan(_ptr(dz), _ptr(mse), T, B, float(eps_z), float(mse_tol), int(patience), _ptr(steps),
+                                                     _ptr(best), self._stream(dev)), "imdbn_trace_patience_scan")
+        return steps, best
+
+    def decode_sqerr(self, idbn_layers, z: torch.Tensor, ref: torch.Tensor, ref_row: Optional[torch.Tensor] = None,
+                     chunk: int = 1024) -> torch.Tensor:
+        """``((decode(z) - ref[ref_row])**2).mean(1)`` without the decoded images: the layers above the bottom one decode with
+        ``prop_down`` (RBM.backward), the bottom layer with imdbn_rbm_prop_down_sqerr.  Rows go in chunks of ``chunk``."""
+        layers = list(idbn_layers)
+        dev = layers[0].W.device
+        z = z.to(device=dev, dtype=torch.float32)
+        R_ = _f32c(ref.to(device=dev), "ref")
+        n = z.size(0)
+        rows = (ref_row.to(device=dev, dtype=torch.int32).contiguous() if ref_row is not None
+                else torch.arange(n, dtype=torch.int32, device=dev))
+        out = torch.empty(n, device=dev)
+        d = self._desc(layers[0], False)
+        for s in range(0, n, int(chunk)):
+            e = min(n, s + int(chunk))
+            cur = z[s:e]
+            for rbm in reversed(layers[1:]):
+                cur = self.prop_down(rbm, cur)
+            cur = _f32c(cur, "h")
+            B = e - s
+            ws = self._workspace(dev, d.V, d.H, B)
+            rr = rows[s:e]
+            N.check(self._lib.imdbn_rbm_prop_down_sqerr(C.byref(d), _ptr(cur), cur.stride(0), B, _ptr(R_), R_.stride(0), _ptr(rr),
+                                                         _ptr(out[s:e]), _ptr(ws), ws.numel(), self._stream(dev)), "imdbn_rbm_prop_down_sqerr")
+        return out
+
     def clamped_step(self, rbm, v_known, mask, init_steps: List[dict], mu, lr, mom, cd_k, sample_h, sample_v, reclamp, rng):
         d = self._desc(rbm, True)
         vk, km = _f32c(v_known, "v_known"), _f32c(mask, "mask")

@@ -52,6 +52,11 @@ class ChainSpec(C.Structure):
                 ("out_v", C.c_void_p), ("ldo", C.c_int64)]
 
 
+class ChainTrace(C.Structure):
+    _fields_ = [("c0", C.c_int32), ("c1", C.c_int32), ("with_baseline", C.c_int32), ("_pad", C.c_int32),
+                ("out", C.c_void_p), ("ld_row", C.c_int64), ("step_stride", C.c_int64)]
+
+
 class CdOpts(C.Structure):
     _fields_ = [("cd_k", C.c_int32), ("lr", C.c_float), ("momentum", C.c_float), ("weight_decay", C.c_float),
                 ("sparsity", C.c_int32), ("sparsity_target", C.c_float),
@@ -107,6 +112,12 @@ SIGNATURES = {
     "imdbn_rbm_chain": (_INT, [C.POINTER(RbmDesc), _P, _P, _I64, _INT, _INT, _INT, C.POINTER(ChainStep), _P, _I64, _INT,
                                C.POINTER(Rng), _P, _I64, _P, _SZ, _P]),
     "imdbn_rbm_chain_pair": (_INT, [C.POINTER(RbmDesc), _INT, C.POINTER(ChainSpec), C.POINTER(ChainSpec), C.POINTER(Rng), _P, _SZ, _P]),
+    "imdbn_rbm_chain_traced": (_INT, [C.POINTER(RbmDesc), _INT, C.POINTER(ChainSpec), C.POINTER(ChainTrace), C.POINTER(ChainSpec),
+                                      C.POINTER(ChainTrace), C.POINTER(Rng), _P, _SZ, _P]),
+    "imdbn_trace_label_scan": (_INT, [_P, _I64, _I64, _INT, _INT, _INT, _P, C.c_double, _INT, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "imdbn_trace_code_scan": (_INT, [_P, _I64, _I64, _INT, _INT, _INT, _P, _I64, _F, _P, _P, _P]),
+    "imdbn_trace_patience_scan": (_INT, [_P, _P, _INT, _INT, C.c_double, C.c_double, _INT, _P, _P, _P]),
+    "imdbn_rbm_prop_down_sqerr": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _P, _I64, _P, _P, _P, _SZ, _P]),
     "imdbn_rbm_clamped_step": (_INT, [C.POINTER(RbmDesc), _P, _P, _I64, _INT, _INT, C.POINTER(ChainStep), _P, _I64, _INT,
                                       C.POINTER(CdOpts), C.POINTER(Rng), _P, _P, _SZ, _P]),
     "imdbn_rbm_assoc_update": (_INT, [C.POINTER(RbmDesc), _P, _I64, _P, _I64, _P, _I64, _P, _I64, _INT, C.POINTER(CdOpts), _P, _SZ, _P]),
