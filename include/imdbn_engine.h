@@ -328,6 +328,30 @@ int imdbn_trace_patience_scan(const float* dz, const float* mse, int T, int B, d
 int imdbn_rbm_prop_down_sqerr(const imdbn_rbm_desc* d, const float* h, int64_t ldh, int B, const float* ref, int64_t ldr,
                               const int32_t* ref_row, float* out_mse, void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- latent nearest-neighbour search (imdbn/utils/imdbn_logging.py) ---------------------------------------------------
+ * imdbn_row_stats: out_sum[r] = sum_c x[r][c], out_sumsq[r] = sum_c x[r][c]^2 in fp32, in a fixed order (the same bits on every
+ * call; exact integers for 0/1 rows).  Either output may be NULL, not both.
+ *
+ * imdbn_latent_topk: for every query row q, the first k candidates of the bank rows b in rank order.
+ *   score   metric 0 (cosine): <q / max(|q|, 1e-12), b / max(|b|, 1e-12)>; 1 (inner): <q, b>;
+ *           2 (l2): -((|q|^2 + |b|^2) - 2 <q, b>), the expansion (not clamped, not the direct difference).
+ *           <q, b> is one k-ordered fp32 fma chain (zero-padded to a multiple of 32): a (query row, bank row) pair scores the
+ *           same bits whatever Q, N, k or the other rows -- identical bank rows tie exactly.
+ *   rank    score descending, the lower bank index on ties; NaN scores are never candidates.
+ *   exclude [Q] nullable: bank row exclude[q] (-1: none) is not a candidate of query q.
+ *   key     [N][2] nullable: only the best-ranked row of each exactly equal key pair is a candidate (the reference's
+ *           dedup="image" walk over the sorted scores).
+ *   out     out_idx[Q][k] (int32), out_score[Q][k]; fewer than k candidates: padded with -1 / -inf.
+ *   bank_sumsq [N] nullable: |b|^2 as imdbn_row_stats gives it (metrics 0 / 2; computed into the workspace when NULL).
+ *   Limits: 1 <= k <= 64 (IMDBN_E_INVALID otherwise), N, D, Q >= 1, ldb, ldq >= D.
+ *   Workspace: at least A(4 Q) + A(4 N) + 2 A(4 Q k) bytes, A(x) = x rounded up to 256 (IMDBN_E_WORKSPACE below that);
+ *           every further 2 A(4 Q k) bytes let the bank split into one more chunk (up to ceil(N / 64)) -- more blocks, the
+ *           same result. */
+int imdbn_row_stats(const float* x, int64_t ldx, int N, int D, float* out_sum, float* out_sumsq, imdbn_stream_t stream);
+int imdbn_latent_topk(const float* bank, int64_t ldb, int N, int D, const float* bank_sumsq, const float* queries, int64_t ldq, int Q,
+                      int metric, int k, const int32_t* exclude, const float* key, int32_t* out_idx, float* out_score, void* ws,
+                      size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- whole RBM.train_epoch_clamped (rbm.py:402-483) -------------------------------------- */
 /* positive phase = chain(n_init steps) ; negative = cd_k steps from v+ ; update with o->lr */
 int imdbn_rbm_clamped_step(const imdbn_rbm_desc* d, const float* v_known, const float* mask, int64_t ldk, int B,

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstring>
 #include <dlfcn.h>
+#include <mutex>
 #include <new>
 #include <vector>
 
@@ -21,6 +22,7 @@
 #include "kernels_chain.hpp"
 #include "kernels_stream.hpp"
 #include "kernels_trace.hpp"
+#include "kernels_knn.hpp"
 
 using namespace imdbn;
 
@@ -1734,6 +1736,70 @@ int imdbn_rbm_prop_down_sqerr(const imdbn_rbm_desc* d, const float* h, int64_t l
     f.out_prob = c.L.f_vp; f.ld_prob = d->V;
     CHK(prop(c, false, OpIn{c.L.hid_rm, c.nw == 1 ? 1 : 0, c.L.flags_h}, f));
     hipLaunchKernelGGL(row_sqerr, dim3(B), dim3(256), 0, S(stream), c.L.f_vp, (int64_t)d->V, B, d->V, ref, ldr, ref_row, out_mse);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ---- latent nearest-neighbour search (imdbn/utils/imdbn_logging.py; kernels_knn.hpp) ----------------------------------------
+int imdbn_row_stats(const float* x, int64_t ldx, int N, int D, float* out_sum, float* out_sumsq, imdbn_stream_t stream) {
+    if (!x || N < 1 || D < 1 || ldx < D || (!out_sum && !out_sumsq)) return fail(IMDBN_E_INVALID, "row_stats: bad argument (N=%d D=%d)", N, D);
+    hipLaunchKernelGGL(knn_row_stats, dim3(cdiv(N, 4)), dim3(256), 0, S(stream), x, ldx, N, D, out_sum, out_sumsq);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static size_t knn_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int imdbn_latent_topk(const float* bank, int64_t ldb, int N, int D, const float* bank_sumsq, const float* queries, int64_t ldq, int Q,
+                      int metric, int k, const int32_t* exclude, const float* key, int32_t* out_idx, float* out_score, void* ws,
+                      size_t ws_bytes, imdbn_stream_t stream) {
+    if (k < 1 || k > KNN_KMAX) return fail(IMDBN_E_INVALID, "latent_topk: k = %d outside [1, %d]", k, KNN_KMAX);
+    if (!bank || !queries || !out_idx || !out_score || N < 1 || D < 1 || Q < 1 || ldb < D || ldq < D || metric < 0 || metric > 2)
+        return fail(IMDBN_E_INVALID, "latent_topk: bad argument (N=%d D=%d Q=%d metric=%d)", N, D, Q, metric);
+    // workspace: ||q||^2 [Q], ||b||^2 [N] (when not given), then the chunk lists (scores, indices) [chunks][Q][k]
+    const bool norms = metric != 1, own_bss = norms && !bank_sumsq;
+    const size_t head = knn_align(sizeof(float) * (size_t)Q) + (own_bss ? knn_align(sizeof(float) * (size_t)N) : 0);
+    const size_t per_chunk = 2 * knn_align(sizeof(float) * (size_t)Q * k);
+    if (!ws || ws_bytes < head + per_chunk)
+        return fail(IMDBN_E_WORKSPACE, "latent_topk: workspace %zu < %zu bytes", ws_bytes, head + per_chunk);
+    // about 2048 blocks over (query tiles x bank chunks), as many chunks as the workspace holds
+    const int qtiles = cdiv(Q, KNN_QT), max_chunks = cdiv(N, KNN_BT);
+    int chunks = std::min(std::max(1, cdiv(2048, qtiles)), max_chunks);
+    chunks = (int)std::min<size_t>((size_t)chunks, (ws_bytes - head) / per_chunk);
+    const int chunk = rup(cdiv(N, chunks), KNN_BT);
+    chunks = cdiv(N, chunk);
+    char* p = (char*)ws;
+    float* qss = (float*)p; p += knn_align(sizeof(float) * (size_t)Q);
+    const float* bss = bank_sumsq;
+    if (own_bss) { bss = (const float*)p; p += knn_align(sizeof(float) * (size_t)N); }
+    float* part_s = (float*)p;
+    int32_t* part_i = (int32_t*)(p + knn_align(sizeof(float) * (size_t)Q * k) * chunks);
+    const hipStream_t st = S(stream);
+    if (norms) {
+        hipLaunchKernelGGL(knn_row_stats, dim3(cdiv(Q, 4)), dim3(256), 0, st, queries, ldq, Q, D, nullptr, qss);
+        HIPCHK(hipGetLastError());
+        if (own_bss) {
+            hipLaunchKernelGGL(knn_row_stats, dim3(cdiv(N, 4)), dim3(256), 0, st, bank, ldb, N, D, nullptr, (float*)bss);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    static std::once_flag attr;
+    hipError_t ae = hipSuccess;
+    std::call_once(attr, [&] {
+        ae = hipFuncSetAttribute((const void*)knn_topk_chunk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_chunk_lds(KNN_KMAX));
+        if (ae == hipSuccess)
+            ae = hipFuncSetAttribute((const void*)knn_topk_merge, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_merge_lds(KNN_KMAX));
+    });
+    HIPCHK(ae);
+    KnnArgs a;
+    a.bank = bank; a.ldb = ldb; a.N = N; a.D = D; a.bss = bss;
+    a.q = queries; a.ldq = ldq; a.Q = Q; a.qss = qss;
+    a.metric = metric; a.k = k; a.chunk = chunk; a.exclude = exclude; a.key = key;
+    a.part_s = part_s; a.part_i = part_i;
+    hipLaunchKernelGGL(knn_topk_chunk, dim3(qtiles, chunks), dim3(256), knn_chunk_lds(k), st, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(knn_topk_merge, dim3(qtiles), dim3(KNN_QT), knn_merge_lds(k), st, part_s, part_i, chunks, Q, k, key, out_idx,
+                       out_score);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -768,6 +768,63 @@ class HipEngine:
                                                          _ptr(out[s:e]), _ptr(ws), ws.numel(), self._stream(dev)), "imdbn_rbm_prop_down_sqerr")
         return out
 
+    # ---- latent nearest-neighbour search (imdbn/utils/imdbn_logging.py) ----------------------------------------------------
+    LATENT_METRICS = {"cosine": 0, "inner": 1, "ip": 1, "l2": 2}
+
+    def row_stats(self, x: torch.Tensor) -> torch.Tensor:
+        """``[N, 2]`` fp32 device tensor: per-row sum and sum of squares of ``x`` (rows flattened), in a fixed order
+        (imdbn_row_stats; exact integers for 0/1 rows).  No host sync."""
+        if not x.is_cuda:
+            raise N.EngineError("row_stats needs a HIP tensor")
+        x = _f32c(x.reshape(x.size(0), -1), "x")
+        n, d = x.shape
+        out = torch.empty(2, n, device=x.device)
+        N.check(self._lib.imdbn_row_stats(_ptr(x), x.stride(0), n, d, _ptr(out[0]), _ptr(out[1]), self._stream(x.device)),
+                "imdbn_row_stats")
+        return out.t()
+
+    def _topk_workspace(self, dev, N_: int, Q: int, k: int) -> torch.Tensor:
+        """Workspace of imdbn_latent_topk: the header's minimum plus room for up to ceil(N / 64) bank chunks of about 2048
+        blocks in all (fewer chunks: fewer blocks, the same result)."""
+        A = lambda b: (int(b) + 255) // 256 * 256
+        chunks = min(max(1, -(-2048 // -(-Q // 64))), -(-N_ // 64))
+        need = A(4 * Q) + A(4 * N_) + chunks * 2 * A(4 * Q * k)
+        key = ("topk", dev, torch.cuda.current_stream(dev).cuda_stream)
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            self._ws[key] = ws
+        return ws
+
+    def latent_topk(self, bank: torch.Tensor, queries: torch.Tensor, metric, k: int, exclude: Optional[torch.Tensor] = None,
+                    key: Optional[torch.Tensor] = None, bank_sumsq: Optional[torch.Tensor] = None):
+        """Per query row the first ``k`` bank rows in rank order (imdbn_latent_topk): ``(idx [Q, k] int32, score [Q, k] fp32)``
+        device tensors, padded with -1 / -inf.  ``metric``: 0 / "cosine", 1 / "inner" / "ip", 2 / "l2"; ``exclude`` [Q]
+        (-1: none) removes one bank row per query; ``key`` [N, 2] keeps only the best-ranked row of every equal key pair;
+        ``bank_sumsq`` [N] = ``row_stats(bank)[:, 1]`` (computed when None).  No host sync."""
+        m = self.LATENT_METRICS[metric] if isinstance(metric, str) else int(metric)
+        if not (bank.is_cuda and queries.is_cuda):
+            raise N.EngineError("latent_topk needs HIP tensors")
+        dev = bank.device
+        B_ = _f32c(bank, "bank")
+        Qt = _f32c(queries.to(dev), "queries")
+        if B_.dim() != 2 or Qt.dim() != 2 or Qt.size(1) != B_.size(1):
+            raise N.EngineError(f"latent_topk: bank {tuple(B_.shape)} and queries {tuple(Qt.shape)} must be [N, D] and [Q, D]")
+        n, d = B_.shape
+        q = Qt.size(0)
+        k = int(k)
+        ex = exclude.to(device=dev, dtype=torch.int32).contiguous() if exclude is not None else None
+        ky = key.to(device=dev, dtype=torch.float32).contiguous() if key is not None else None
+        bss = bank_sumsq.to(device=dev, dtype=torch.float32).contiguous() if bank_sumsq is not None else None
+        if (ex is not None and ex.numel() != q) or (ky is not None and ky.shape != (n, 2)) or (bss is not None and bss.numel() != n):
+            raise N.EngineError("latent_topk: exclude [Q], key [N, 2] and bank_sumsq [N] must match the bank and queries")
+        idx = torch.empty(q, max(k, 1), dtype=torch.int32, device=dev)
+        sc = torch.empty(q, max(k, 1), device=dev)
+        ws = self._topk_workspace(dev, n, q, max(1, min(k, 64)))
+        N.check(self._lib.imdbn_latent_topk(_ptr(B_), B_.stride(0), n, d, _ptr(bss), _ptr(Qt), Qt.stride(0), q, m, k, _ptr(ex), _ptr(ky),
+                                            _ptr(idx), _ptr(sc), _ptr(ws), ws.numel(), self._stream(dev)), "imdbn_latent_topk")
+        return idx, sc
+
     def clamped_step(self, rbm, v_known, mask, init_steps: List[dict], mu, lr, mom, cd_k, sample_h, sample_v, reclamp, rng):
         d = self._desc(rbm, True)
         vk, km = _f32c(v_known, "v_known"), _f32c(mask, "mask")

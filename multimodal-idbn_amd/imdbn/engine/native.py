@@ -118,6 +118,8 @@ SIGNATURES = {
     "imdbn_trace_code_scan": (_INT, [_P, _I64, _I64, _INT, _INT, _INT, _P, _I64, _F, _P, _P, _P]),
     "imdbn_trace_patience_scan": (_INT, [_P, _P, _INT, _INT, C.c_double, C.c_double, _INT, _P, _P, _P]),
     "imdbn_rbm_prop_down_sqerr": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _P, _I64, _P, _P, _P, _SZ, _P]),
+    "imdbn_row_stats": (_INT, [_P, _I64, _INT, _INT, _P, _P, _P]),
+    "imdbn_latent_topk": (_INT, [_P, _I64, _INT, _INT, _P, _P, _I64, _INT, _INT, _INT, _P, _P, _P, _P, _P, _SZ, _P]),
     "imdbn_rbm_clamped_step": (_INT, [C.POINTER(RbmDesc), _P, _P, _I64, _INT, _INT, C.POINTER(ChainStep), _P, _I64, _INT,
                                       C.POINTER(CdOpts), C.POINTER(Rng), _P, _P, _SZ, _P]),
     "imdbn_rbm_assoc_update": (_INT, [C.POINTER(RbmDesc), _P, _I64, _P, _I64, _P, _I64, _P, _I64, _INT, C.POINTER(CdOpts), _P, _SZ, _P]),
