@@ -154,9 +154,13 @@ int    imdbn_device_info(int* cu_count, char* arch, size_t n);
 size_t imdbn_ws_bytes(int V, int H, int B);
 /* tuning knobs (split-K factors); 0 = automatic */
 int    imdbn_set_tuning(int ksplit_up, int ksplit_down);
-/* named tuning/testing knobs (process-wide defaults): "ksplit_up", "ksplit_down", "generic_k3" (1 = force the unaligned-shape
- * K3), "k1s_ks", "k2s_rows", "down_rows", "chain_rows", "no_k1s", "no_k2s", "no_bits", "no_prefetch", "no_chain_kernel", ...;
- * none of them changes results beyond fp32 summation order, none is needed for normal use */
+/* named tuning/testing knobs (process-wide defaults).  Tuning (0 = automatic): "ksplit_up", "ksplit_down", "k1s_ks",
+ * "down_rows" (0 or a multiple of 4 in [4, 32]), "k2s_rows" (0 or a multiple of 8 in [8, 48]), "chain_rows" ([0, 16]),
+ * "min_rank_loop".  Testing, 1 = take the other kernel path: "generic_k3" (the unaligned-shape K3), "generic_k1",
+ * "no_fused_up", "no_k1s", "no_k1s_real", "no_k2s", "no_bits", "no_prefetch", "no_adaptive", "no_chain_kernel",
+ * "no_chain_pair", "no_down_chunks", "no_down_tiled", "no_rank_loop", "no_rank_acc".  Experiments: "k1s_lds_pad" (bytes,
+ * clamped to [0, 65536]), "k1s_force_na".  Process-wide only: "dbg" (timeline stamps).  None of them changes results
+ * beyond fp32 summation order, none is needed for normal use */
 int    imdbn_set_option(const char* name, int value);
 /* The same knobs per caller instead of per process: a handle starts as a copy of the process defaults, takes
  * imdbn_options_set(name, value) (every name of imdbn_set_option but "dbg"), and imdbn_use_options(handle) binds it to the

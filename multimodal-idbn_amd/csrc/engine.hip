@@ -3,11 +3,14 @@
 // Everything here is launch orchestration: carve the caller's workspace, advance the draw cursor in
 // the reference's draw order, and enqueue kernels on the caller's stream.
 // No host synchronisation, no allocation, no global state besides tuning knobs, the thread-local
-// error string and the optional profiling events.
+// error string, what is known per device ordinal and the optional profiling events.
+// The host code is one translation unit in four files: this one (context, CD / chain / factor orchestration, the C entries),
+// host_layout.hpp (knobs, workspace layout, Route), host_prop.hpp (propagation launchers), host_update.hpp (update launchers).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -29,64 +32,6 @@ using namespace imdbn;
 namespace {
 
 thread_local char g_err[512] = "";
-// Tuning / testing knobs.  The process-wide defaults are set by imdbn_set_option / imdbn_set_tuning; a caller that wants its own
-// (two engines with different settings in one process) creates an imdbn_options handle and binds it to its thread with
-// imdbn_use_options: every engine call made by that thread then reads the handle instead of the defaults.  Knobs that shape the
-// workspace layout (split-K factors, tile heights) must be the same for all calls that share a workspace.
-struct Tuning {
-    int ks_up = 0, ks_down = 0;      // split-K factors of the generic propagation kernels (0 = automatic)
-    bool no_fast_k3 = false;         // testing: force the unaligned-shape update kernel
-    bool no_fast_k1 = false;
-    bool no_fused_up = false;
-    int k4_rows = 0;                 // tuning: batch rows per chain-kernel block (0 = automatic)
-    int no_rank_loop = 0;            // testing: one update-kernel launch per gathered rank block
-    int no_chain_kernel = 0;         // testing: run chains as one launch per half step
-    int no_rank_acc = 0;             // testing: tile-wise rank loop (k3_body_ranks) even when the accumulating form applies
-    int min_rank_loop = 2;           // apply_factors: rank blocks from which the single-launch rank loop is used (1 block: the plain update kernel, 46 vs 60 us)
-    int no_prefetch = 0;             // testing: ignore imdbn_cd_opts.next_data
-    int no_bits = 0;                 // testing: never use the bit-packed hidden operand
-    int down_tr = 0;                 // tuning: rows per fused-K2 block (0 = automatic)
-    int no_k1s = 0;                  // testing: never use the LDS-DMA streaming K1 for binary operands (k1_stream)
-    int k1s_ks = 0;                  // tuning: K slices of k1_stream (0 = automatic)
-    int no_k2s = 0;                  // testing: never use k2_stream (the fused K2 for a bit-plane hidden operand, one tile per CU)
-    int k2s_tr = 0;                  // tuning: rows per k2_stream block (0 = automatic; multiple of 8, <= 48)
-    int no_k1s_real = 0;             // testing: real-valued operands of K1 take the partial GEMM + finish launches, not k1_stream
-    int no_adaptive = 0;             // testing: a prefetched batch of unknown content gets all three-term forms (no per-item choice)
-    int k1s_lds_pad = 0;             // experiment: extra dynamic LDS (bytes) for the bit-plane k1_stream
-    int no_chain_pair = 0;           // testing: imdbn_rbm_chain_pair runs its chains one after the other
-    int no_down_tiled = 0;           // testing: multi-chunk real-valued K2 without the LDS-tiled kernel
-    int no_down_chunks = 0;          // testing: the fused K2 of a multi-chunk batch runs one block per (tile, 64-row chunk)
-    int k1s_force_na = 0;            // experiment: bit-plane operands run on the kernel instantiation that can also read bf16 terms
-};
-Tuning g_defaults;
-thread_local const Tuning* t_bound = nullptr;
-inline const Tuning& tune() { return t_bound ? *t_bound : g_defaults; }
-#define g_ks_up (tune().ks_up)
-#define g_ks_down (tune().ks_down)
-#define g_no_fast_k3 (tune().no_fast_k3)
-#define g_no_fast_k1 (tune().no_fast_k1)
-#define g_no_fused_up (tune().no_fused_up)
-#define g_k4_rows (tune().k4_rows)
-#define g_no_rank_loop (tune().no_rank_loop)
-#define g_no_chain_kernel (tune().no_chain_kernel)
-#define g_no_rank_acc (tune().no_rank_acc)
-#define g_min_rank_loop (tune().min_rank_loop)
-#define g_no_prefetch (tune().no_prefetch)
-#define g_no_bits (tune().no_bits)
-#define g_down_tr (tune().down_tr)
-#define g_no_k1s (tune().no_k1s)
-#define g_k1s_ks (tune().k1s_ks)
-#define g_no_k2s (tune().no_k2s)
-#define g_k2s_tr (tune().k2s_tr)
-#define g_no_k1s_real (tune().no_k1s_real)
-#define g_no_adaptive (tune().no_adaptive)
-#define g_k1s_lds_pad (tune().k1s_lds_pad)
-#define g_k1s_force_na (tune().k1s_force_na)
-#define g_no_chain_pair (tune().no_chain_pair)
-#define g_no_down_chunks (tune().no_down_chunks)
-#define g_no_down_tiled (tune().no_down_tiled)
-int g_dbg = 0;    // tuning aid: kernels that record per-block timeline stamps (64 K1, 128 K2, 256 finish, 512 K3; tools/stamps_probe.py)
-
 int fail(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -106,163 +51,7 @@ int fail(int code, const char* fmt, ...) {
         if (rc_ != 0) return rc_;   \
     } while (0)
 
-inline int rup(int x, int m) { return (x + m - 1) / m * m; }
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-
-// ---- profiling of the update kernel (bench.py roofline leg) --------------------------------
-struct Prof {
-    bool on = false;
-    std::vector<hipEvent_t> ev;   // pairs
-    size_t used = 0;
-    unsigned calls = 0;           // only every 8th update launch is bracketed (the 4th, 12th, ...): a bracket costs the stream ~10 us
-                                  // (two event records: measured in the kernel trace as +5 us on the bracketed step and +5 on the next)
-} g_prof;
-
-// ---- split-K plan --------------------------------------------------------------------------
-struct Split { int ks; int kchunk; };
-Split plan_split(int Kpad, int n_tiles, int m_blocks, int forced, int cap) {
-    int ks = forced;
-    if (ks <= 0) {
-        const int target = 768;    // ~3 workgroups per CU on 256 CUs
-        ks = std::max(1, (int)((double)target / (double)(n_tiles * m_blocks) + 0.5));
-    }
-    ks = std::min(ks, cap);
-    ks = std::min(ks, cdiv(Kpad, 64));
-    ks = std::max(ks, 1);
-    const int kchunk = rup(cdiv(Kpad, ks), 64);
-    return {cdiv(Kpad, kchunk), kchunk};
-}
-
-// ---- workspace layout ----------------------------------------------------------------------
-struct Layout {
-    int V, H, B, Bp, Vpad, Hpad, P;
-    Split up, down;
-    bool up4;
-    int* flags; int* flags_h;
-    bf16_t* vis_rm[2];
-    bf16_t* vis_tr[2];
-    bf16_t* hid_rm;
-    bf16_t* hid_tr[2];
-    uint8_t* hid_bits; int ldbits;       // bit plane of the sampled hidden states, byte-major [Hpad64/8][Bp]
-    uint8_t* vis_bits[2];                // bit planes of the visible operands (0: data, 1: negative-phase sample), [Vpad64/8][Bp]
-    uint8_t* pf_bits[2];                 // ... of the prefetch slots
-    float* partial;
-    float* f_h;
-    float* f_vp;
-    float* f_v[2];
-    float* cs_hpos; float* cs_hneg; float* cs_vpos; float* cs_vneg;
-    float* loss_part; int n_loss_slots;
-    size_t fb_off, fb_bytes;      // the factor block inside the workspace
-    // prefetch slots 1 / 2: operand forms of a batch prepared ahead of its CD step (imdbn_cd_opts.next_data)
-    bf16_t* pf_rm[2]; bf16_t* pf_tr[2]; int* pf_flags[2]; float* pf_cs[2];
-    ChainRec* chain_recs;   // per-step schedule of the row-parallel chain kernel
-    bf16_t* k4_planes; int64_t k4_plane_stride;      // fragment-ordered bf16 weight planes [2 directions][3 terms]
-    int down_tr;            // visible rows per block of the fused K2 (<= 32): balances the row tiles over the CUs
-    int k2s_tr;             // rows per k2_stream block: one tile per CU where the layer is large enough
-    int k1s_tiles, k1s_ks, k1s_kchunk; int* k1s_cnt;      // k1_stream: 32-column tiles, K slices, arrival counters [Bp/64][tiles]
-    size_t bytes;
-};
-
-int cu_count() {
-    static int cus = 0;
-    if (cus <= 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cus = n;
-        else return 256;
-    }
-    return cus;
-}
-
-// Fused K2 streams W once, one tile of `tr` visible rows per block, and every block costs the same; the kernel
-// ends when the CU with the most rows ends (blocks are dealt round-robin).  10000 rows as 313 tiles of 32 put two
-// tiles (64 rows) on 57 of the 256 CUs and one on the rest: the main loop ran 13 us at the median and 20 us on
-// those 57.  20-row tiles (500 blocks, two per CU, 40 rows each) level it.  The MFMA tile stays 32 wide.
-int plan_down_rows(int V) {
-    if (g_down_tr > 0) return g_down_tr;
-    const int cus = cu_count();
-    int best = 32, best_cost = 1 << 30;
-    for (int tr = 32; tr >= 16; tr -= 4) {
-        const int cost = cdiv(cdiv(V, tr), cus) * tr;       // rows streamed by the busiest CU
-        if (cost < best_cost) { best_cost = cost; best = tr; }
-    }
-    return best;
-}
-
-Layout make_layout(int V, int H, int B, char* base) {
-    Layout L{};
-    L.V = V; L.H = H; L.B = B;
-    L.Bp = rup(std::max(B, 1), 64);
-    L.Vpad = rup(V, 16); L.Hpad = rup(H, 16);
-    L.P = L.Bp / 8;
-    const int mb = L.Bp / 64;
-    L.up4 = (H % 4 == 0) && H >= 4 && !g_no_fast_k1;      // float4 K1 (also needs 16-B aligned W: checked at launch)
-    if (L.up4) {
-        const int tiles = cdiv(H, 128) * mb;
-        const int want = g_ks_up > 0 ? g_ks_up : std::max(1, 252 / std::max(1, tiles));
-        L.up = plan_split(L.Vpad, cdiv(H, 128), mb, want, 64);
-    } else {
-        L.up = plan_split(L.Vpad, cdiv(H, 64), mb, g_ks_up, 64);
-    }
-    L.down = plan_split(L.Hpad, cdiv(V, 64), mb, g_ks_down, 16);
-    L.down_tr = plan_down_rows(V);
-    L.k2s_tr = g_k2s_tr > 0 ? g_k2s_tr : std::min(48, std::max(8, 8 * cdiv(V, 8 * cu_count())));
-    size_t off = 0;
-    auto take = [&](size_t nbytes) { char* p = base ? base + off : nullptr; off += (nbytes + 255) / 256 * 256; return p; };
-    // exactness maps of caller-supplied operands (prep rewrites them every call): visible side, hidden side
-    // ---- factor block: everything the weight / bias update needs from one CD pass, contiguous, so that the
-    // data-parallel "factor exchange" can all-gather it in one piece (imdbn_factor_block): exactness map of the data,
-    // hidden planes (pos, negated neg), column-sum and squared-error partials, visible planes (pos: 3 terms; neg: its
-    // FIRST term only is inside the block -- the negative visible state of train_epoch is a sample, one term)
-    L.fb_off = off;
-    L.flags = (int*)take((size_t)L.P * cdiv(L.Vpad, 64) * 4);
-    for (int i = 0; i < 2; ++i) L.hid_tr[i] = (bf16_t*)take((size_t)3 * H * L.Bp * 2);
-    L.cs_hpos = (float*)take((size_t)L.P * H * 4);
-    L.cs_hneg = (float*)take((size_t)L.P * H * 4);
-    L.cs_vpos = (float*)take((size_t)L.P * V * 4);
-    L.cs_vneg = (float*)take((size_t)L.P * V * 4);
-    L.n_loss_slots = std::max(cdiv(std::max(V, H), 64) * L.P, (cdiv(V, 8) + 2) * (L.Bp / 64)) + IMDBN_MAX_GROUPS * (L.Bp / 64);
-    L.loss_part = (float*)take((size_t)L.n_loss_slots * 4);
-    for (int i = 0; i < 2; ++i) {
-        L.vis_tr[i] = (bf16_t*)take((size_t)3 * V * L.Bp * 2);
-        if (i == 1) L.fb_bytes = (off - (((size_t)3 * V * L.Bp * 2 + 255) / 256 * 256)) + ((size_t)V * L.Bp * 2 + 255) / 256 * 256 - L.fb_off;
-    }
-    // ---- the rest
-    L.flags_h = (int*)take((size_t)L.P * cdiv(L.Hpad, 64) * 4);
-    for (int i = 0; i < 2; ++i) L.vis_rm[i] = (bf16_t*)take((size_t)3 * L.Bp * L.Vpad * 2);
-    L.hid_rm = (bf16_t*)take((size_t)3 * L.Bp * L.Hpad * 2);
-    L.ldbits = 2 * cdiv(L.Hpad, 64);
-    L.hid_bits = (uint8_t*)take((size_t)L.Bp * rup(H, 64) / 8);
-    for (int i = 0; i < 2; ++i) L.vis_bits[i] = (uint8_t*)take((size_t)L.Bp * rup(V, 64) / 8);
-    {   // k1_stream: ~one block per CU; a K slice is a multiple of 64 rows and at most K1S_MAX_KCHUNK (its bits sit in LDS)
-        L.k1s_tiles = cdiv(H, 32);
-        int ks = g_k1s_ks > 0 ? g_k1s_ks : std::max(1, (int)((double)cu_count() / (double)(L.k1s_tiles * mb) + 0.5));
-        ks = std::min(ks, std::max(1, L.Vpad / 192));      // at least three K16 steps per wave and slice (1500 <-> 500: 8 slices of 192 rows, 45.5 us per update against 47.9 with 12 of 128)
-        ks = std::max(ks, cdiv(L.Vpad, K1S_MAX_KCHUNK));
-        L.k1s_kchunk = rup(cdiv(L.Vpad, ks), 64);
-        L.k1s_ks = cdiv(L.Vpad, L.k1s_kchunk);
-    }
-    const size_t pf = std::max(std::max((size_t)L.up.ks * L.Bp * H, (size_t)L.down.ks * L.Bp * V), (size_t)L.k1s_ks * L.Bp * 32 * L.k1s_tiles);
-    L.partial = (float*)take(pf * 4);
-    L.k1s_cnt = (int*)take((size_t)mb * L.k1s_tiles * 4);
-    L.f_h = (float*)take((size_t)L.Bp * H * 4);
-    L.f_vp = (float*)take((size_t)L.Bp * V * 4);
-    for (int i = 0; i < 2; ++i) L.f_v[i] = (float*)take((size_t)L.Bp * V * 4);
-    L.chain_recs = (ChainRec*)take(sizeof(ChainRec) * CHAIN_MAX_STEPS);
-    for (int i = 0; i < 2; ++i) {
-        L.pf_rm[i] = (bf16_t*)take((size_t)3 * L.Bp * L.Vpad * 2);
-        L.pf_tr[i] = (bf16_t*)take((size_t)3 * V * L.Bp * 2);
-        L.pf_flags[i] = (int*)take((size_t)L.P * cdiv(L.Vpad, 64) * 4);
-        L.pf_cs[i] = (float*)take((size_t)L.P * V * 4);
-        L.pf_bits[i] = (uint8_t*)take((size_t)L.Bp * rup(V, 64) / 8);
-    }
-    L.k4_plane_stride = 0; L.k4_planes = nullptr;
-    if (V <= 1024 && H <= 1024) {
-        L.k4_plane_stride = (int64_t)std::max(cdiv(H, 16) * cdiv(V, 32), cdiv(V, 16) * cdiv(H, 32)) * 512;
-        L.k4_planes = (bf16_t*)take((size_t)6 * L.k4_plane_stride * 2);
-    }
-    L.bytes = off;
-    return L;
-}
+#include "host_layout.hpp"
 
 // ---- draw cursor -----------------------------------------------------------------------------
 struct Rng {
@@ -284,7 +73,6 @@ struct Rng {
         ++draws;
         return s;
     }
-    void skip_floats(int B, int N) { (void)floats(B, N); }
     // categorical draws for all groups of one sample_visible call
     void cats(int B, int n_groups, const int32_t** tape, DrawSrc* uni) {
         *tape = nullptr;
@@ -322,7 +110,8 @@ struct Ctx {
                     // and flipped a sample of the train_joint fixture (margin 9e-6).  Exact products stay.
     bool hid_bits_ok = false;      // L.hid_bits describes the current contents of L.hid_rm
     bool data_prepped = false;     // cd_phases: the data-side operands are already in place (prefetch slot)
-    int down_blocks = 0;           // blocks (per batch chunk) of the last K2 launch: the number of squared-error partials it left
+    Route r{};                     // which kernel runs what in this call (setup)
+    int k2_blocks = 0;             // blocks (per batch chunk) of the last K2 launch = the squared-error partials it left (prop())
     bool pos_phase = false;        // tuning aid: the propagation being launched is the positive phase of a CD pass (dbg bit 2048 stamps it, bit 64 the others)
     bool cnt_ok = false;           // the arrival counters of k1_stream are known to be zero: a launch of THIS call cleared them (prep / chain_init), or the
                                    // data-side operands come from a prefetch slot (an earlier call on this workspace ran, and every launch leaves them
@@ -358,16 +147,6 @@ int check_desc(const imdbn_rbm_desc* d, bool need_momentum) {
     return 0;
 }
 
-// the CD step reads its data-side operands from prefetch slot `slot` (1 / 2) instead of the default buffers
-void use_slot(Layout& L, int slot) {
-    if (slot < 1 || slot > 2) return;
-    std::swap(L.vis_rm[0], L.pf_rm[slot - 1]);
-    std::swap(L.vis_tr[0], L.pf_tr[slot - 1]);
-    std::swap(L.flags, L.pf_flags[slot - 1]);
-    std::swap(L.cs_vpos, L.pf_cs[slot - 1]);
-    std::swap(L.vis_bits[0], L.pf_bits[slot - 1]);
-}
-
 int setup(Ctx& c, int B, void* ws, size_t ws_bytes) {
     if (B <= 0) return fail(IMDBN_E_INVALID, "batch %d", B);
     if (!ws) return fail(IMDBN_E_WORKSPACE, "null workspace");
@@ -375,388 +154,12 @@ int setup(Ctx& c, int B, void* ws, size_t ws_bytes) {
     c.L = make_layout(c.d->V, c.d->H, B, (char*)ws);
     if (c.L.bytes > ws_bytes)
         return fail(IMDBN_E_WORKSPACE, "workspace %zu < %zu bytes needed for V=%d H=%d B=%d", ws_bytes, c.L.bytes, c.d->V, c.d->H, B);
+    c.r = make_route(c.d, c.L);
     return 0;
 }
 
-// An activation operand in row-major form: pointer + static term count (0 = look at flag)
-// bits / binary: the operand also exists as a bit plane; binary = 1: it is 0/1 by construction (a sample), 2: the caller
-// says so (checked on the device against the exactness map `flag`), 3: nobody knows -- the streaming K1 decides per
-// 64-column item from the exactness map (bit plane where the item is all 0/1, the bf16 terms in `rm` elsewhere)
-struct OpIn { const bf16_t* rm; int terms; const int* flag; const uint8_t* bits = nullptr; int binary = 0; };
-
-// visible tiles (128 rows) per block of the streaming update kernel
-int k3_tiles_per_block(int V, int H) {
-    const int nh = cdiv(H, 128), nv = cdiv(V, 128);
-    return std::max(1, cdiv(nh * nv, std::max(cu_count(), 1)));
-}
-// The per-item choice of k1_stream (K1S_ADAPTIVE) holds one exactness-map entry per thread for a K slice's items (<= 32) and one
-// for a span of the update kernel (<= 256 entries); layers outside that read data of unknown content from the bf16 terms throughout
-// (same numbers, all three-term forms prepared).
-bool adaptive_shape_ok(const Layout& L) {
-    // ... and one block of the (first batch chunk of the) positive-phase K1 per span of the update kernel for the fix-up of mixed
-    // spans: a narrow hidden layer has too few (found by tools/stress_parity.py: 1576 x 12, 1437 x 32, 2116 x 28)
-    const int tpb = k3_tiles_per_block(L.V, L.H);
-    return L.k1s_kchunk <= 2048 && 2 * tpb * L.P <= 256 && cdiv(cdiv(L.V, 128), tpb) <= L.k1s_tiles * L.k1s_ks;
-}
-
-bool vec4_weights(const imdbn_rbm_desc* d) {
-    return d->H % 4 == 0 && d->H >= 4 && d->ldw % 4 == 0 && (((uintptr_t)d->W) & 15) == 0;
-}
-
-void base_finish_args(Ctx& c, bool up, FinishArgs& f) {
-    const Layout& L = c.L;
-    f.partial = L.partial;
-    f.ks = up ? L.up.ks : L.down.ks;
-    f.B = L.B; f.Bp = L.Bp;
-    f.N = up ? L.H : L.V;
-    f.slab = (int64_t)L.Bp * f.N;
-    f.bias = up ? c.d->hid_bias : c.d->vis_bias;
-    f.n_groups = up ? 0 : c.d->n_groups;
-    for (int g = 0; g < IMDBN_MAX_GROUPS; ++g) { f.gs[g] = up ? 0 : c.d->group_start[g]; f.ge[g] = up ? 0 : c.d->group_end[g]; }
-    f.op.ldrm = up ? L.Hpad : L.Vpad;
-    f.op.rm_ts = (int64_t)L.Bp * f.op.ldrm;
-    f.op.Bp = L.Bp;
-    f.op.tr_ts = (int64_t)f.N * L.Bp;
-}
-
-FinishArgs new_finish() {
-    FinishArgs f;
-    memset(&f, 0, sizeof(f));
-    f.T = 1.0f;
-    return f;
-}
-
-// one propagation: partial GEMM + finish (+ group kernel)
-int prop(Ctx& c, bool up, OpIn in, FinishArgs f, const PrepArgs* next = nullptr) {
-    const Layout& L = c.L;
-    const imdbn_rbm_desc* d = c.d;
-    base_finish_args(c, up, f);
-    if (f.T < 1e-6f) f.T = 1e-6f;                           // max(1e-6, T)  rbm.py:92,96
-    // lean epilogue specialisation (kernels_ew.hpp finish_rows_impl<R, false>)
-    f.simple = (f.T == 1.0f && !(f.sigma > 0.f) && !f.mu && !f.clamp && f.n_groups == 0 && !f.logits_only) ? 1 : 0;
-    // lean epilogue of the streaming kernels (kernels_ew.hpp finish_lean8): decided once all outputs are known (below)
-    auto lean_ok = [&](const FinishArgs& g) {
-        return g.simple && (g.vmode == 0 || g.vmode == 1) && !g.out_final && !(g.rm_src && g.op.rm) &&
-               (g.vmode == 0 || g.uni.tape || (g.uni.row0 & 3) == 0) ? 1 : 0;
-    };
-    const int mb = L.Bp / 64;
-    // hidden samples (exactly 0/1, not mixed with clamped values) also leave as a bit plane for the fused K2
-    const bool want_hbits = up && f.op.rm == L.hid_rm && f.rm_src == 2 && f.vmode == 1 && !f.clamp && f.n_groups == 0 && !f.logits_only;
-    if (up && L.Vpad <= 1024 && !g_no_fused_up) {
-        // short K: fused GEMM + epilogue, no split-K slabs (one launch per half step of a chain)
-        dim3 grid(cdiv(L.H, 32), 1, mb);
-        const int64_t ats = (int64_t)L.Bp * L.Vpad;
-        f.dbg = 0;
-        f.op.bits = want_hbits ? L.hid_bits : nullptr; f.op.bits_shape = 1; f.op.bits_cols = 32;      // epilogue lanes: 32 columns x 2 row octets
-        if (f.op.rm == L.hid_rm) c.hid_bits_ok = want_hbits;
-        if (c.nw == 3)
-            hipLaunchKernelGGL(gemm_up_fused<3>, grid, dim3(256), 0, c.s, d->W, d->ldw, L.V, L.H, in.rm, ats, L.Vpad, in.flag, in.terms, f);
-        else
-            hipLaunchKernelGGL(gemm_up_fused<1>, grid, dim3(256), 0, c.s, d->W, d->ldw, L.V, L.H, in.rm, ats, L.Vpad, in.flag, in.terms, f);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    // streaming K1: weights through LDS by LDS-DMA, split-K combined by the last arriver, epilogue fused.  The operand is a bit
-    // plane (0/1 by construction or by the caller's word), bf16 terms (real values), or either per 64-column item (unknown)
-    const bool k1s_bits = in.bits && (in.binary == 1 || in.binary == 2);
-    const bool k1s_real = !k1s_bits && in.rm && !g_no_k1s_real && (in.binary == 0 || (in.binary == 3 && in.bits && in.flag));
-    if (up && (k1s_bits || k1s_real) && vec4_weights(d) && !g_no_k1s && !f.logits_only) {
-        if (!c.cnt_ok) {
-            HIPCHK(hipMemsetAsync(L.k1s_cnt, 0, (size_t)mb * L.k1s_tiles * sizeof(int), c.s));
-            c.cnt_ok = true;
-        }
-        K1sArgs a;
-        memset(&a, 0, sizeof(a));
-        a.W = d->W; a.ldw = d->ldw; a.K = L.V; a.N = L.H;
-        a.abits = in.bits; a.Bp = L.Bp;
-        a.aflag = in.binary >= 2 ? in.flag : nullptr; a.ncb = cdiv(L.Vpad, 64); a.P = L.P;
-        a.slabs = L.partial; a.counters = L.k1s_cnt; a.kchunk = L.k1s_kchunk; a.ks = L.k1s_ks;
-        a.amode = k1s_bits ? (in.binary == 2 ? K1S_ASSERTED : K1S_BITS) : ((in.binary == 3 && adaptive_shape_ok(L)) ? K1S_ADAPTIVE : K1S_REAL);
-        a.arm = in.rm; a.arm_ts = (int64_t)L.Bp * L.Vpad;
-        if (a.amode == K1S_ADAPTIVE && c.fix_slot && in.rm == L.vis_rm[0]) {
-            const int tpb = k3_tiles_per_block(L.V, L.H);
-            a.fix_tr = L.vis_tr[0]; a.fix_ts = (int64_t)L.V * L.Bp; a.fix_span = 2 * tpb; a.fix_ranges = cdiv(cdiv(L.V, 128), tpb);
-            if (a.fix_ranges > L.k1s_tiles * a.ks) return fail(IMDBN_E_INVALID, "internal: k1_stream fix-up ranges");
-            c.fix_slot = false;
-        }
-        // terms the kernel multiplies per element: the operand form carries `in.terms` of them (0 = prep's three, nw in FAST mode)
-        const int na = k1s_bits ? ((g_k1s_force_na && !next) ? c.nw : 0) : ((in.terms == 1 || c.nw == 1) ? 1 : 3);
-        f.dbg = c.pos_phase ? ((g_dbg & 2048) ? 64 : 0) : (g_dbg & ~2048);
-        f.op.bits = want_hbits ? L.hid_bits : nullptr; f.op.bits_shape = 1; f.op.bits_cols = 32;
-        if (f.op.rm == L.hid_rm) c.hid_bits_ok = want_hbits;
-        if (want_hbits && !g_no_bits) f.op.rm = nullptr, f.rm_src = 0;      // the fused K2 reads the bit plane, nobody reads the bf16 form
-        // 80 KB at the headline shape: two workgroups per CU (the bit-plane kernel carries the next batch's preparation blocks)
-        a.region = k1s_bits ? K1S_RING : K1S_REGION_REAL;
-        const size_t lds = (size_t)K1S_WAVES * a.region + (size_t)8 * a.kchunk + (k1s_bits ? (next ? 0 : g_k1s_lds_pad) : K1S_LDS_EXTRA);
-        f.lean = lean_ok(f);
-        // + block rows that prepare the next batch (one 64-column item each, or a few)
-        PrepArgs pz;
-        memset(&pz, 0, sizeof(pz));
-        const int items = next ? cdiv(std::max(next->N, next->op.ldrm), 64) : 0;
-        const int pr = next ? std::min(8, cdiv(items, L.k1s_tiles)) : 0;
-        if (pr > 0 && na != 0) return fail(IMDBN_E_INVALID, "internal: preparation blocks ride on the bit-plane k1_stream only");
-        dim3 grid(L.k1s_tiles, a.ks + pr, mb);
-        const PrepArgs& pa = next ? *next : pz;
-        hipError_t le = hipSuccess;
-#define LAUNCH_K1S(NWV, NAV, GEV, RV) do { \
-        static bool attr = false; \
-        if (!attr) { le = hipFuncSetAttribute((const void*)k1_stream<NWV, NAV, GEV, RV>, hipFuncAttributeMaxDynamicSharedMemorySize, K1S_WAVES * K1S_REGION_REAL + 8 * K1S_MAX_KCHUNK + K1S_LDS_EXTRA); attr = true; } \
-        if (le == hipSuccess) hipLaunchKernelGGL((k1_stream<NWV, NAV, GEV, RV>), grid, dim3(64 * K1S_WAVES), lds, c.s, a, f, pa); } while (0)
-#define LAUNCH_K1S_G(NWV, NAV, RV) do { if (f.lean) LAUNCH_K1S(NWV, NAV, false, RV); else LAUNCH_K1S(NWV, NAV, true, RV); } while (0)
-        // (one instantiation per case: code that a launch does not run -- the general epilogue, the preparation blocks, the loop over
-        //  bf16 terms -- still costs it time)
-        if (c.nw == 3) { if (na == 0) { if (pr > 0) LAUNCH_K1S_G(3, 0, true); else LAUNCH_K1S_G(3, 0, false); } else if (na == 1) LAUNCH_K1S_G(3, 1, false); else LAUNCH_K1S_G(3, 3, false); }
-        else           { if (na == 0) { if (pr > 0) LAUNCH_K1S_G(1, 0, true); else LAUNCH_K1S_G(1, 0, false); } else LAUNCH_K1S_G(1, 1, false); }
-#undef LAUNCH_K1S_G
-#undef LAUNCH_K1S
-        HIPCHK(le);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    if (up) {
-        const int64_t ats = (int64_t)L.Bp * L.Vpad;
-        const bool fast = L.up4 && d->ldw % 4 == 0 && (((uintptr_t)d->W) & 15) == 0;
-        if (fast) {
-            dim3 grid(cdiv(L.H, 128), L.up.ks, mb);
-            if (c.nw == 3)
-                hipLaunchKernelGGL(gemm_up4_partial<3>, grid, dim3(256), 0, c.s, d->W, d->ldw, L.V, L.H, in.rm, ats, L.Vpad, in.flag, in.terms, L.partial, L.Bp, L.up.kchunk, g_dbg >> 4);
-            else
-                hipLaunchKernelGGL(gemm_up4_partial<1>, grid, dim3(256), 0, c.s, d->W, d->ldw, L.V, L.H, in.rm, ats, L.Vpad, in.flag, in.terms, L.partial, L.Bp, L.up.kchunk, g_dbg >> 4);
-        } else {
-            dim3 grid(cdiv(L.H, 64), L.up.ks, mb);
-            if (c.nw == 3)
-                hipLaunchKernelGGL(gemm_up_partial<3>, grid, dim3(256), 0, c.s, d->W, d->ldw, L.V, L.H, in.rm, ats, L.Vpad, in.flag, in.terms, L.partial, L.Bp, L.up.kchunk);
-            else
-                hipLaunchKernelGGL(gemm_up_partial<1>, grid, dim3(256), 0, c.s, d->W, d->ldw, L.V, L.H, in.rm, ats, L.Vpad, in.flag, in.terms, L.partial, L.Bp, L.up.kchunk);
-        }
-    } else {
-        // K2: fused GEMM + epilogue (no split-K slabs)
-        if (f.n_groups > 0 && !f.logits_only && !f.out_prob) f.out_prob = L.f_vp, f.ld_prob = L.V;
-        if (f.n_groups > 0 && !f.logits_only && !f.out_final) f.out_final = L.f_v[1], f.ld_final = L.V;
-        const uint8_t* hb = (c.hid_bits_ok && in.rm == L.hid_rm && in.terms == 1 && !g_no_bits) ? L.hid_bits : nullptr;
-        if (hb && vec4_weights(d) && !g_no_k2s) {
-            // 0/1 hidden operand as a bit plane: one tile of k2s_tr rows per CU, 16x16x32 MFMA (kernels_stream.hpp)
-            K2sArgs a;
-            memset(&a, 0, sizeof(a));
-            a.W = d->W; a.ldw = d->ldw; a.K = L.H; a.N = L.V; a.abits = hb; a.Bp = L.Bp; a.TR = L.k2s_tr;
-            const int nbx = cdiv(L.Vpad, a.TR), MT = cdiv(a.TR, 16);
-            c.down_blocks = nbx;
-            if ((nbx + IMDBN_MAX_GROUPS) * mb > L.n_loss_slots) return fail(IMDBN_E_INVALID, "internal: loss slots");
-            f.dbg = g_dbg;
-            if (f.op.bits && (f.n_groups > 0 || f.vmode == 0)) f.op.bits = nullptr;      // not a pure 0/1 sample
-            f.lean = lean_ok(f);
-            if (next) return fail(IMDBN_E_INVALID, "internal: k2_stream carries no next-batch blocks");
-            const int nsteps = cdiv(L.H, 32);
-            const size_t lds = (size_t)((nsteps * 256 + 255) & ~255) + (size_t)std::max(K2S_LW * 16 * MT * K2S_LDR * 4, 64);
-            dim3 grid(nbx, 1, mb);
-            hipError_t le = hipSuccess;
-#define LAUNCH_K2S(NW, MTV, GEV) do { \
-        static bool attr = false; \
-        if (!attr) { le = hipFuncSetAttribute((const void*)k2_stream<NW, MTV, GEV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-        if (le == hipSuccess) hipLaunchKernelGGL((k2_stream<NW, MTV, GEV>), grid, dim3(64 * K2S_W), lds, c.s, a, f); } while (0)
-#define LAUNCH_K2S_G(NW, MTV) do { if (f.lean) LAUNCH_K2S(NW, MTV, false); else LAUNCH_K2S(NW, MTV, true); } while (0)
-#define LAUNCH_K2S_M(NW) do { if (MT == 1) LAUNCH_K2S_G(NW, 1); else if (MT == 2) LAUNCH_K2S_G(NW, 2); else LAUNCH_K2S_G(NW, 3); } while (0)
-            if (lds > 160 * 1024) return fail(IMDBN_E_UNSUPPORTED, "internal: k2_stream LDS");
-            if (c.nw == 3) LAUNCH_K2S_M(3); else LAUNCH_K2S_M(1);
-#undef LAUNCH_K2S_M
-#undef LAUNCH_K2S_G
-#undef LAUNCH_K2S
-            HIPCHK(le);
-            HIPCHK(hipGetLastError());
-            if (f.n_groups > 0 && !f.logits_only) {
-                hipLaunchKernelGGL(finish_groups, dim3(f.n_groups, L.Bp / 64), dim3(256), 0, c.s, f, (int)(nbx * mb));
-                HIPCHK(hipGetLastError());
-            }
-            return 0;
-        }
-        // tiles cover [0, Vpad): the K16-blocked operand form must have its padding columns [V, Vpad) written (zeros) -- the
-        // next K1 multiplies them with clamped (non-zero) weight rows.  Tiles of 20 / 24 / 28 rows (chosen for V in
-        // (4096, 7168]) do not end on a multiple of 16 by themselves; found by tools/stress_parity.py.
-        // sampled hidden states left by `finish` in bit-packed form: 16x less activation traffic per block
-        const uint8_t* abits = (c.hid_bits_ok && in.rm == L.hid_rm && in.terms == 1 && !g_no_bits) ? L.hid_bits : nullptr;
-        const int64_t ats = (int64_t)L.Bp * L.Hpad;
-        const bool vec4 = (d->ldw % 4 == 0) && (((uintptr_t)d->W & 15) == 0) && (L.H % 4 == 0) && L.H >= 4;
-        // several 64-row batch chunks: one block per weight tile takes 2 or 4 of them, a wave (pair) per chunk, on full 32-row
-        // tiles (decode / visible_probs of a 256-row batch: 4 x 500 blocks of 20 rows in four rounds -> 313 blocks in one)
-        const bool multi = mb >= 2 && !abits && !next && vec4 && !(f.rm_src && f.op.rm) && L.Vpad >= 128 * 32;      // (fewer than 128 weight tiles: the per-chunk grid fills the chip better)
-        const int mbb = (multi && !g_no_down_chunks) ? (mb % 4 == 0 ? 4 : (mb % 2 == 0 ? 2 : 1)) : 1;
-        const int down_tr = mbb > 1 ? 32 : L.down_tr;
-        dim3 grid(cdiv(L.Vpad, down_tr), 1, mb / mbb);
-        c.down_blocks = (int)grid.x;
-        f.dbg = g_dbg;
-        if (f.op.bits && (down_tr % 8 != 0 || f.n_groups > 0 || f.vmode == 0)) f.op.bits = nullptr;      // not a 0/1 plane the epilogue can write byte-wise
-        f.op.bits_shape = 1; f.op.bits_cols = down_tr;
-        // ... and, where the squared-error partials of 32-row tiles fit, the LDS-tiled kernel: 128 weight rows x 64 batch rows per block,
-        // the activation terms staged once per block (kernels_gemm.hpp gemm_down_tiled)
-        if (multi && !g_no_down_tiled && !g_no_down_chunks && (4 * cdiv(L.Vpad, 128) + IMDBN_MAX_GROUPS) * mb <= L.n_loss_slots) {
-            dim3 gt(cdiv(L.Vpad, 128), 1, mb);
-            c.down_blocks = 4 * (int)gt.x;
-            f.op.bits_cols = 32;
-            if (c.nw == 3) hipLaunchKernelGGL((gemm_down_tiled<3>), gt, dim3(256), 0, c.s, d->W, d->ldw, L.H, L.V, in.rm, ats, L.Hpad, in.flag, in.terms, f);
-            else           hipLaunchKernelGGL((gemm_down_tiled<1>), gt, dim3(256), 0, c.s, d->W, d->ldw, L.H, L.V, in.rm, ats, L.Hpad, in.flag, in.terms, f);
-            HIPCHK(hipGetLastError());
-            if (f.n_groups > 0 && !f.logits_only) {
-                hipLaunchKernelGGL(finish_groups, dim3(f.n_groups, L.Bp / 64), dim3(256), 0, c.s, f, (int)(c.down_blocks * mb));
-                HIPCHK(hipGetLastError());
-            }
-            return 0;
-        }
-        if ((int)((grid.x + IMDBN_MAX_GROUPS) * mb) > L.n_loss_slots) return fail(IMDBN_E_INVALID, "internal: loss slots");
-#define LAUNCH_DOWN_M(NW, MBBV) \
-    hipLaunchKernelGGL((gemm_down_fused<NW, true, 0, false, MBBV>), grid, dim3(256), 0, c.s, d->W, d->ldw, L.H, L.V, in.rm, ats, L.Hpad, in.flag, in.terms, f, down_tr, abits, L.ldbits)
-        if (mbb > 1) {
-            if (c.nw == 3) { if (mbb == 4) LAUNCH_DOWN_M(3, 4); else LAUNCH_DOWN_M(3, 2); }
-            else           { if (mbb == 4) LAUNCH_DOWN_M(1, 4); else LAUNCH_DOWN_M(1, 2); }
-        } else
-#define LAUNCH_DOWN(NW, V4, NAK, BITS) \
-    hipLaunchKernelGGL((gemm_down_fused<NW, V4, NAK, BITS>), grid, dim3(256), 0, c.s, d->W, d->ldw, L.H, L.V, in.rm, ats, L.Hpad, in.flag, in.terms, f, down_tr, abits, L.ldbits)
-#define LAUNCH_DOWN_A(NW, V4) \
-    do { if (abits) LAUNCH_DOWN(NW, V4, 1, true); else if (in.terms == 1) LAUNCH_DOWN(NW, V4, 1, false); \
-         else if (in.terms == 3) LAUNCH_DOWN(NW, V4, 3, false); else LAUNCH_DOWN(NW, V4, 0, false); } while (0)
-        if (next) {
-            // + one block per (64-column tile, batch chunk) of the NEXT batch behind the weight tiles (prep_item_body)
-            if (!vec4 || in.terms != 1) return fail(IMDBN_E_INVALID, "internal: next-batch prep on an ineligible K2");
-            const int main_nbx = (int)grid.x;
-            dim3 gn(grid.x + cdiv(std::max(next->N, next->op.ldrm), 64), 1, mb);
-#define LAUNCH_DOWN_N(NW, BITS) \
-    hipLaunchKernelGGL((gemm_down_fused_next<NW, BITS>), gn, dim3(256), 0, c.s, d->W, d->ldw, L.H, L.V, in.rm, ats, L.Hpad, f, down_tr, abits, L.ldbits, *next, main_nbx)
-            if (c.nw == 3) { if (abits) LAUNCH_DOWN_N(3, true); else LAUNCH_DOWN_N(3, false); }
-            else           { if (abits) LAUNCH_DOWN_N(1, true); else LAUNCH_DOWN_N(1, false); }
-#undef LAUNCH_DOWN_N
-        }
-        else if (c.nw == 3) { if (vec4) LAUNCH_DOWN_A(3, true); else LAUNCH_DOWN_A(3, false); }
-        else                { if (vec4) LAUNCH_DOWN_A(1, true); else LAUNCH_DOWN_A(1, false); }
-#undef LAUNCH_DOWN_A
-#undef LAUNCH_DOWN
-        HIPCHK(hipGetLastError());
-        if (f.n_groups > 0 && !f.logits_only) {
-            hipLaunchKernelGGL(finish_groups, dim3(f.n_groups, L.Bp / 64), dim3(256), 0, c.s, f, (int)(grid.x * mb));
-            HIPCHK(hipGetLastError());
-        }
-        return 0;
-    }
-    HIPCHK(hipGetLastError());
-    if (f.n_groups > 0 && !f.logits_only && !f.out_prob) f.out_prob = L.f_vp, f.ld_prob = L.V;
-    if (f.n_groups > 0 && !f.logits_only && !f.out_final) f.out_final = L.f_v[1], f.ld_final = L.V;
-    dim3 fgrid(cdiv(f.N, 64), L.P);
-    if ((int)(fgrid.x * fgrid.y) + IMDBN_MAX_GROUPS * (L.Bp / 64) > L.n_loss_slots) return fail(IMDBN_E_INVALID, "internal: loss slots");
-    f.dbg = g_dbg;
-    f.op.bits = want_hbits ? L.hid_bits : nullptr; f.op.bits_shape = 0;
-    if (up && f.op.rm == L.hid_rm) c.hid_bits_ok = want_hbits;
-    hipLaunchKernelGGL(finish, fgrid, dim3(256), 0, c.s, f);
-    HIPCHK(hipGetLastError());
-    if (f.n_groups > 0 && !f.logits_only) {
-        hipLaunchKernelGGL(finish_groups, dim3(f.n_groups, L.Bp / 64), dim3(256), 0, c.s, f, (int)(fgrid.x * fgrid.y));
-        HIPCHK(hipGetLastError());
-    }
-    return 0;
-}
-// k2_stream runs the K2 of a CD pass (its hidden operand is always a sample with a bit plane) whenever the weight rows allow
-bool k2s_for_cd(const imdbn_rbm_desc* d) { return vec4_weights(d) && !g_no_k2s && !g_no_bits; }
-int n_loss_used(const Ctx& c, bool up) {
-    if (up) return cdiv(c.L.H, 64) * c.L.P;
-    const int blocks = c.down_blocks > 0 ? c.down_blocks : cdiv(c.L.Vpad, k2s_for_cd(c.d) ? c.L.k2s_tr : c.L.down_tr);
-    return (blocks + c.d->n_groups) * (c.L.Bp / 64);    // fused K2: one partial per block (+ per group block)
-}
-
-// caller fp32 tensor -> operand forms in the workspace
-int prep(Ctx& c, const float* in, int64_t ld, int N, bf16_t* rm, int ldrm, bf16_t* tr, int* flag,
-         float* colsum = nullptr, int terms = 3, uint8_t* bits = nullptr) {
-    PrepArgs p;
-    memset(&p, 0, sizeof(p));
-    p.op.bits = bits; p.op.bits_shape = 0;
-    p.zero = c.L.k1s_cnt; p.n_zero = (c.L.Bp / 64) * c.L.k1s_tiles;      // first launch of a call: arrival counters of k1_stream
-    c.cnt_ok = true;
-    p.in = in; p.ld = ld; p.B = c.L.B; p.Bp = c.L.Bp; p.N = N;
-    p.op.rm = rm; p.op.ldrm = ldrm; p.op.rm_ts = (int64_t)c.L.Bp * ldrm; p.op.rm_terms = rm ? terms : 0; p.op.Bp = c.L.Bp;
-    p.op.tr = tr; p.op.tr_ts = (int64_t)N * c.L.Bp; p.op.tr_terms = terms;
-    p.flag = flag;
-    p.colsum_part = colsum;
-    hipLaunchKernelGGL(prep_operand, dim3(cdiv(std::max(N, ldrm), 64), c.L.P), dim3(256), 0, c.s, p);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-int launch_bias(Ctx& c, const BiasArgs& b);
-
-// Next-batch preparation rides on the fused K2 of the first negative-phase step (gemm_down_fused_next: float4 weight
-// rows, single-term hidden activations -- what imdbn_rbm_cd_step always launches when the weight rows are aligned).
-bool prefetch_available(const imdbn_rbm_desc* d) {
-    return !g_no_prefetch && d->H % 4 == 0 && d->H >= 4 && d->ldw % 4 == 0 && (((uintptr_t)d->W) & 15) == 0;
-}
-
-int launch_assoc(Ctx& c, int mode_stats, const imdbn_cd_opts* o, int vpos_terms, const int* vpos_flag, int vneg_terms,
-                 float n, float* delta, const BiasArgs* bias = nullptr) {
-    const Layout& L = c.L;
-    AssocArgs a;
-    memset(&a, 0, sizeof(a));
-    a.W = c.d->W; a.Wm = c.d->W_m; a.ldw = c.d->ldw; a.V = L.V; a.H = L.H;
-    a.vpos = L.vis_tr[0]; a.vpos_flag = vpos_flag; a.vpos_terms = vpos_terms;
-    a.hpos = L.hid_tr[0]; a.hpos_terms = c.ht;
-    a.vneg = L.vis_tr[1]; a.vneg_flag = vpos_flag; a.vneg_terms = vneg_terms;
-    a.hneg = L.hid_tr[1]; a.hneg_terms = c.ht;
-    a.vts = (int64_t)L.V * L.Bp; a.hts = (int64_t)L.H * L.Bp; a.Bp = L.Bp;
-    a.lr = o->lr; a.mom = o->momentum; a.wd = o->weight_decay; a.n = n;
-    a.delta = delta;
-    const bool prof = g_prof.on && !mode_stats && (g_prof.calls++ % 8 == 3) && g_prof.used + 2 <= g_prof.ev.size();
-    if (prof) HIPCHK(hipEventRecord(g_prof.ev[g_prof.used], c.s));
-    // fast path: every W / W_m / delta row start 16-B aligned -> float4 weight tiles, LDS-staged planes
-    const bool fast = L.H % 4 == 0 && L.H >= 4 && c.d->ldw % 4 == 0 && (((uintptr_t)c.d->W) & 15) == 0 &&
-                      (mode_stats ? ((((uintptr_t)delta) & 15) == 0) : ((((uintptr_t)c.d->W_m) & 15) == 0)) && !g_no_fast_k3;
-    if (fast) {
-        AssocPlanesArgs f;
-        memset(&f, 0, sizeof(f));
-        f.W = a.W; f.Wm = a.Wm; f.ldw = a.ldw; f.V = a.V; f.H = a.H;
-        f.vpos = a.vpos; f.vpos_flag = a.vpos_flag; f.vpos_terms = a.vpos_terms;
-        f.hpos = a.hpos; f.vneg = a.vneg; f.vneg_terms = a.vneg_terms; f.hneg = a.hneg;
-        f.vts = a.vts; f.hts = a.hts; f.Bp = a.Bp;
-        f.lr = a.lr; f.mom = a.mom; f.wd = a.wd; f.n = a.n; f.delta = a.delta; f.dbg = (g_dbg & 512) ? 1 : 0;
-        // ~one block per CU: each block streams `tpb` visible tiles with its hidden planes resident in LDS
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        const int nh = cdiv(L.H, 128), nv = cdiv(L.V, 128);
-        const int tpb = std::max(1, cdiv(nh * nv, std::max(cus, 1)));
-        // + one extra block row for the bias / loss update when the caller wants it fused
-        const int brows = bias ? (nh >= 2 ? 1 : 2) : 0;     // >= 2 blocks: one reduces the loss, the rest stride the biases
-        BiasArgs bz;
-        memset(&bz, 0, sizeof(bz));
-        const BiasArgs& bb = bias ? *bias : bz;
-        // one launch per 64-row batch chunk (kernels_gemm.hpp AssocPlanesArgs::pass); the bias / loss blocks ride on the last
-        const int nchunk = L.Bp / 64;
-        for (int ch = 0; ch < nchunk; ++ch) {
-            f.b0 = 64 * ch;
-            const int pass = nchunk == 1 ? 0 : (ch == 0 ? 1 : (ch == nchunk - 1 ? 3 : 2));
-            const int br = (ch == nchunk - 1) ? brows : 0;
-            dim3 g(nh, cdiv(nv, tpb) + br);
-#define LAUNCH_K3(M, HTV, PS) hipLaunchKernelGGL((assoc_update_planes<M, HTV, PS>), g, dim3(256), 0, c.s, f, tpb, bb, br)
-#define LAUNCH_K3_P(M, HTV) do { if (pass == 0) LAUNCH_K3(M, HTV, 0); else if (pass == 1) LAUNCH_K3(M, HTV, 1); \
-                                 else if (pass == 2) LAUNCH_K3(M, HTV, 2); else LAUNCH_K3(M, HTV, 3); } while (0)
-            if (c.ht == 3) { if (mode_stats) LAUNCH_K3_P(1, 3); else LAUNCH_K3_P(0, 3); }
-            else           { if (mode_stats) LAUNCH_K3_P(1, 1); else LAUNCH_K3_P(0, 1); }
-#undef LAUNCH_K3_P
-#undef LAUNCH_K3
-        }
-        HIPCHK(hipGetLastError());
-        if (prof) { HIPCHK(hipEventRecord(g_prof.ev[g_prof.used + 1], c.s)); g_prof.used += 2; }
-        return 0;
-    } else {
-        dim3 grid(cdiv(L.H, 128), cdiv(L.V, 64));
-        if (c.ht == 3) {
-            if (mode_stats) hipLaunchKernelGGL((assoc_update<1, 3>), grid, dim3(256), 0, c.s, a);
-            else            hipLaunchKernelGGL((assoc_update<0, 3>), grid, dim3(256), 0, c.s, a);
-        } else {
-            if (mode_stats) hipLaunchKernelGGL((assoc_update<1, 1>), grid, dim3(256), 0, c.s, a);
-            else            hipLaunchKernelGGL((assoc_update<0, 1>), grid, dim3(256), 0, c.s, a);
-        }
-    }
-    HIPCHK(hipGetLastError());
-    if (prof) { HIPCHK(hipEventRecord(g_prof.ev[g_prof.used + 1], c.s)); g_prof.used += 2; }
-    if (bias) CHK(launch_bias(c, *bias));          // generic K3: bias update as its own launch
-    return 0;
-}
-
-// imdbn_cd_opts.data_binary (0 unknown, 1 asserted 0/1, 2 real) -> OpIn::binary of the data operand
-int data_operand_kind(int data_binary) { return data_binary == IMDBN_DATA_BINARY ? 2 : (data_binary == IMDBN_DATA_UNKNOWN ? 3 : 0); }
+#include "host_prop.hpp"
+#include "host_update.hpp"
 
 // rbm.py:199-209: positive phase, CD-k Gibbs, statistics left in the workspace operand buffers.
 int cd_phases(Ctx& c, const float* data, int64_t ldd, const imdbn_cd_opts* o, const PrepArgs* next = nullptr) {
@@ -764,12 +167,8 @@ int cd_phases(Ctx& c, const float* data, int64_t ldd, const imdbn_cd_opts* o, co
     const int B = L.B;
     if (o->cd_k < 1) return fail(IMDBN_E_INVALID, "CD=%d (the reference needs CD>=1, rbm.py:204-209)", o->cd_k);
     if (!c.data_prepped) CHK(prep(c, data, ldd, L.V, L.vis_rm[0], L.Vpad, L.vis_tr[0], L.flags, L.cs_vpos, 3, L.vis_bits[0]));
-    // the visible sample of the negative phase leaves the fused K2 as a bit plane too when its tiles are whole bytes wide
-    const bool vbits = c.d->n_groups == 0 && (k2s_for_cd(c.d) || L.down_tr % 8 == 0);
-    const bool k1s_neg = vec4_weights(c.d) && !g_no_k1s && L.Vpad > 1024;      // the negative-phase K1 will be k1_stream (prop())
-    // the next batch's preparation rides on the old fused K2 (gemm_down_fused_next) or, with k2_stream (a 512-thread block per
-    // CU: nothing fits beside it), on the negative-phase k1_stream
-    const bool next_on_k1 = next && k2s_for_cd(c.d) && vbits && k1s_neg;
+    // (Route: the visible sample of the negative phase leaves its K2 as a bit plane, and which launch carries `next`)
+    const bool vbits = c.r.vbits, next_on_k1 = next && c.r.next_on_k1;
     // positive phase: P+ = up(data); h = 1[P+ > U]
     {
         FinishArgs f = new_finish();
@@ -792,7 +191,7 @@ int cd_phases(Ctx& c, const float* data, int64_t ldd, const imdbn_cd_opts* o, co
             // scratch for them when groups exist): without groups nobody needs them -> 5 MB of stores saved
             // the K16-blocked bf16 form only feeds a K1 that cannot read the bit plane (its 2-byte scattered stores were most
             // of the fused K2's 3.8 us epilogue)
-            if (!(vbits && k1s_neg)) { f.op.rm = L.vis_rm[1]; f.op.rm_terms = 1; f.rm_src = 2; }
+            if (c.r.neg_rm) { f.op.rm = L.vis_rm[1]; f.op.rm_terms = 1; f.rm_src = 2; }
             f.op.tr = L.vis_tr[1]; f.op.tr_terms = 1; f.tr_src = 2;
             f.colsum_part = L.cs_vneg; f.colsum_src = 2;
             f.loss_ref = data; f.ld_ref = ldd; f.loss_src = 1; f.loss_part = L.loss_part;
@@ -811,28 +210,10 @@ int cd_phases(Ctx& c, const float* data, int64_t ldd, const imdbn_cd_opts* o, co
     return 0;
 }
 
-BiasArgs make_bias(Ctx& c, const imdbn_cd_opts* o, bool sparsity, float n, float* loss_out) {
-    const Layout& L = c.L;
-    BiasArgs b;
-    memset(&b, 0, sizeof(b));
-    b.hid_bias = c.d->hid_bias; b.hb_m = c.d->hb_m; b.H = L.H; b.hpos = L.cs_hpos; b.hneg = L.cs_hneg;
-    b.vis_bias = c.d->vis_bias; b.vb_m = c.d->vb_m; b.V = L.V; b.vpos = L.cs_vpos; b.vneg = L.cs_vneg;
-    b.P = L.P; b.lr = o->lr; b.mom = o->momentum; b.n = n;
-    b.sparsity = sparsity ? 1 : 0; b.target = o->sparsity_target;
-    b.loss_part = L.loss_part; b.n_loss = n_loss_used(c, false); b.loss_den = n * (float)L.V; b.loss_out = loss_out;
-    return b;
-}
-
-int launch_bias(Ctx& c, const BiasArgs& b) {
-    hipLaunchKernelGGL(bias_update, dim3(cdiv(std::max(c.L.V, c.L.H), 256) + 1), dim3(256), 0, c.s, b);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
 // ---- row-parallel chain kernel (kernels_chain.hpp) -------------------------------------------
 bool chain_kernel_ok(const Ctx& c, int n_steps) {
     const Layout& L = c.L;
-    if (g_no_chain_kernel || !L.k4_planes || n_steps < 2 || n_steps > CHAIN_MAX_STEPS) return false;
+    if (tune().no_chain_kernel || !L.k4_planes || n_steps < 2 || n_steps > CHAIN_MAX_STEPS) return false;
     if (c.d->n_groups > 1) return false;                   // the kernel keeps ONE softmax group's logits in LDS
     const int gw = c.d->n_groups ? c.d->group_end[0] - c.d->group_start[0] : 0;
     const size_t lds = (size_t)(c.nw == 3 ? 2 : 1) * K4_ROWS * ((rup(L.V, 32) + 8) + (rup(L.H, 32) + 8)) * 2      // activation terms
@@ -937,9 +318,10 @@ int launch_k4(Ctx& c, const ChainSpec& s0, int off0, const ChainSpec* s1, int of
     a.s1 = s1 ? seg(*s1, off1) : a.s0;
     // rows per block: enough blocks to spread the per-element work (Philox, Box-Muller, sigmoid) over the CUs;
     // one block per CU at most (every block streams all of W from L2)
+    const Tuning& t = tune();
     a.dbg = (g_dbg & 1024) ? 1 : 0;
     const int nch = s1 ? 2 : 1, BT = B * nch;
-    a.rows = g_k4_rows > 0 ? g_k4_rows : (BT <= 2 * cu_count() ? 2 : (BT <= 4 * cu_count() ? 4 : (BT <= 8 * cu_count() ? 8 : 16)));      // measured: 0.90 / 0.99 / 1.19 / 1.59 ms for 2 / 4 / 8 / 16 rows (30 steps, 532<->256)
+    a.rows = t.k4_rows > 0 ? t.k4_rows : (BT <= 2 * cu_count() ? 2 : (BT <= 4 * cu_count() ? 4 : (BT <= 8 * cu_count() ? 8 : 16)));      // measured: 0.90 / 0.99 / 1.19 / 1.59 ms for 2 / 4 / 8 / 16 rows (30 steps, 532<->256)
     a.nblk0 = cdiv(B, a.rows);
     const dim3 grid(a.nblk0 * nch);
     if (c.nw == 3) hipLaunchKernelGGL(k4_chain<2>, grid, dim3(64 * K4_WAVES), 0, c.s, a);      // PARITY: fp16 hi + lo terms
@@ -1019,6 +401,31 @@ int run_chain(Ctx& c, const ChainSpec& s, bool want_stats) {
     return 0;
 }
 
+ChainSpec chain_spec(const imdbn_chain_spec* s, const imdbn_chain_trace* tr = nullptr) {
+    ChainSpec r{s->v_known, s->mask, s->ldk, s->init_uniform, s->n_steps, s->steps, s->mu, s->ldmu, s->Dz, s->out_v, s->ldo};
+    r.tr = tr;
+    return r;
+}
+bool chain_spec_ok(const imdbn_rbm_desc* d, const imdbn_chain_spec* s) {
+    return s->v_known && s->mask && s->out_v && s->ldk >= d->V && s->ldo >= d->V && s->n_steps >= 0 && (s->n_steps == 0 || s->steps) &&
+           (!s->mu || (s->Dz > 0 && s->Dz <= d->V));
+}
+// two independent chains of one RBM: ONE launch of the chain kernel where it applies (chain a on the first half of the grid,
+// chain b on the second), else one after the other; the draws are those of two single runs (a, then b) either way
+int run_chain_pair(Ctx& c, const ChainSpec& sa, const ChainSpec& sb) {
+    if (chain_kernel_ok(c, sa.n_recs()) && chain_kernel_ok(c, sb.n_recs()) && sa.n_recs() + sb.n_recs() <= CHAIN_MAX_STEPS && !tune().no_chain_pair) {
+        CHK(chain_init(c, sa, false, false));
+        CHK(chain_records(c, sa, 0));
+        CHK(chain_init(c, sb, false, false));
+        CHK(chain_records(c, sb, sa.n_recs()));
+        CHK(launch_k4(c, sa, 0, &sb, sa.n_recs()));
+        c.hid_bits_ok = false;
+        return 0;
+    }
+    CHK(run_chain(c, sa, false));
+    return run_chain(c, sb, false);
+}
+
 hipStream_t S(imdbn_stream_t s) { return (hipStream_t)s; }
 
 }  // namespace
@@ -1053,37 +460,6 @@ size_t imdbn_ws_bytes(int V, int H, int B) {
 int imdbn_set_tuning(int ksplit_up, int ksplit_down) {
     g_defaults.ks_up = std::max(0, ksplit_up);
     g_defaults.ks_down = std::max(0, ksplit_down);
-    return 0;
-}
-
-static int set_opt(Tuning& t, const char* name, int value) {
-    if (!name) return fail(IMDBN_E_INVALID, "null option name");
-    if (!strcmp(name, "ksplit_up")) t.ks_up = std::max(0, value);
-    else if (!strcmp(name, "ksplit_down")) t.ks_down = std::max(0, value);
-    else if (!strcmp(name, "generic_k3")) t.no_fast_k3 = value != 0;
-    else if (!strcmp(name, "down_rows")) { if (value != 0 && (value < 4 || value > 32 || value % 4)) return fail(IMDBN_E_INVALID, "down_rows must be 0 or a multiple of 4 in [4, 32]"); t.down_tr = value; }
-    else if (!strcmp(name, "no_rank_loop")) t.no_rank_loop = value;
-    else if (!strcmp(name, "no_chain_kernel")) t.no_chain_kernel = value;
-    else if (!strcmp(name, "chain_rows")) { if (value < 0 || value > 16) return fail(IMDBN_E_INVALID, "chain_rows must be in [0, 16]"); t.k4_rows = value; }
-    else if (!strcmp(name, "no_bits")) t.no_bits = value;
-    else if (!strcmp(name, "no_prefetch")) t.no_prefetch = value;
-    else if (!strcmp(name, "no_rank_acc")) t.no_rank_acc = value;
-    else if (!strcmp(name, "min_rank_loop")) t.min_rank_loop = value;
-    else if (!strcmp(name, "dbg")) g_dbg = value;
-    else if (!strcmp(name, "no_k1s")) t.no_k1s = value;
-    else if (!strcmp(name, "k1s_ks")) t.k1s_ks = std::max(0, value);
-    else if (!strcmp(name, "no_k2s")) t.no_k2s = value;
-    else if (!strcmp(name, "k2s_rows")) { if (value != 0 && (value < 8 || value > 48 || value % 8)) return fail(IMDBN_E_INVALID, "k2s_rows must be 0 or a multiple of 8 in [8, 48]"); t.k2s_tr = value; }
-    else if (!strcmp(name, "generic_k1")) t.no_fast_k1 = value != 0;
-    else if (!strcmp(name, "no_k1s_real")) t.no_k1s_real = value;
-    else if (!strcmp(name, "no_adaptive")) t.no_adaptive = value;
-    else if (!strcmp(name, "k1s_force_na")) t.k1s_force_na = value;
-    else if (!strcmp(name, "no_chain_pair")) t.no_chain_pair = value;
-    else if (!strcmp(name, "no_down_chunks")) t.no_down_chunks = value;
-    else if (!strcmp(name, "no_down_tiled")) t.no_down_tiled = value;
-    else if (!strcmp(name, "k1s_lds_pad")) t.k1s_lds_pad = std::max(0, std::min(value, 64 * 1024));
-    else if (!strcmp(name, "no_fused_up")) t.no_fused_up = value != 0;
-    else return fail(IMDBN_E_INVALID, "unknown option %s", name);
     return 0;
 }
 
@@ -1187,12 +563,11 @@ int imdbn_rbm_forward(const imdbn_rbm_desc* d, const float* v, int64_t ldv, int 
     Ctx c(d, nullptr, S(stream));
     CHK(setup(c, B, ws, ws_bytes));
     if (data_binary < 0 || data_binary > 2) return fail(IMDBN_E_INVALID, "forward: data_binary %d", data_binary);
-    const bool k1s = vec4_weights(d) && !g_no_k1s && c.L.Vpad > 1024;       // prop() then launches k1_stream
-    const bool bits = k1s && data_binary != IMDBN_DATA_REAL, only_bits = k1s && data_binary == IMDBN_DATA_BINARY;
-    CHK(prep(c, v, ldv, d->V, only_bits ? nullptr : c.L.vis_rm[0], c.L.Vpad, nullptr, c.L.flags, nullptr, 3, bits ? c.L.vis_bits[0] : nullptr));
+    CHK(prep(c, v, ldv, d->V, c.r.data_needs_rm(data_binary) ? c.L.vis_rm[0] : nullptr, c.L.Vpad, nullptr, c.L.flags, nullptr, 3,
+             c.r.data_bits(data_binary) ? c.L.vis_bits[0] : nullptr));
     FinishArgs f = new_finish();
     f.out_prob = out_prob; f.ld_prob = ldo;
-    CHK(prop(c, true, OpIn{c.L.vis_rm[0], c.nw == 1 ? 1 : 0, c.L.flags, bits ? c.L.vis_bits[0] : nullptr, bits ? data_operand_kind(data_binary) : 0}, f));
+    CHK(prop(c, true, data_operand(c, data_binary), f));
     return 0;
 }
 
@@ -1279,9 +654,9 @@ static int cd_prologue(Ctx& c, const imdbn_cd_opts* o, PrepArgs& pn, bool& rides
     const imdbn_rbm_desc* d = c.d;
     if (o->data_slot < 0 || o->data_slot > 2 || (o->next_data && (o->next_slot < 1 || o->next_slot > 2 || o->next_slot == o->data_slot || o->ld_next < d->V)))
         return fail(IMDBN_E_INVALID, "cd: bad prefetch slots (data %d, next %d)", o->data_slot, o->next_slot);
-    const int next_rows = (o->next_data && prefetch_available(d)) ? 1 : 0;
+    const bool has_next = o->next_data && c.r.prefetch;
     memset(&pn, 0, sizeof(pn));
-    if (next_rows > 0) {            // target buffers are taken before the data slot is swapped in
+    if (has_next) {            // target buffers are taken before the data slot is swapped in
         const Layout& L = c.L;
         const int t = o->next_slot - 1;
         pn.in = o->next_data; pn.ld = o->ld_next; pn.B = L.B; pn.Bp = L.Bp; pn.N = L.V;
@@ -1292,22 +667,31 @@ static int cd_prologue(Ctx& c, const imdbn_cd_opts* o, PrepArgs& pn, bool& rides
     }
     // Where the next batch is prepared: as extra blocks of the fused K2 (gemm_down_fused_next) or of the negative-phase
     // k1_stream (cd_phases decides); where neither can carry them, a prep_operand launch of its own, first thing.
-    rides = next_rows > 0 && (!k2s_for_cd(d) || (d->n_groups == 0 && vec4_weights(d) && !g_no_k1s && c.L.Vpad > 1024));
-    if (next_rows > 0 && allow_compact && vec4_weights(d) && !g_no_k1s && c.L.Vpad > 1024) {
+    rides = has_next && c.r.rides;
+    if (has_next && allow_compact && c.r.k1s) {
         if (o->next_binary == IMDBN_DATA_BINARY) {
             // a 0/1 batch: the positive phase reads the bit plane, the update kernel one bf16 plane (the exactness map says "one term")
             pn.op.rm = nullptr; pn.op.rm_terms = 0; pn.op.tr_terms = 1;
-        } else if (o->next_binary == IMDBN_DATA_UNKNOWN && rides && !g_no_adaptive && !g_no_k1s_real && adaptive_shape_ok(c.L)) {
+        } else if (o->next_binary == IMDBN_DATA_UNKNOWN && c.r.adaptive_next) {
             pn.adaptive = 1;      // the same slim set for every 64-column item that turns out to be all 0/1, decided by the preparing block
         }
     }
-    if (next_rows > 0 && !rides) {
+    if (has_next && !rides) {
         pn.zero = nullptr; pn.n_zero = 0;
         hipLaunchKernelGGL(prep_operand, dim3(cdiv(std::max(pn.N, pn.op.ldrm), 64), c.L.P), dim3(256), 0, c.s, pn);
         HIPCHK(hipGetLastError());
     }
     if (o->data_slot) { use_slot(c.L, o->data_slot); c.data_prepped = true; c.cnt_ok = true; c.fix_slot = o->data_binary == IMDBN_DATA_UNKNOWN; }
     return 0;
+}
+
+// the CD pass of imdbn_rbm_cd_step / _cd_stats / _cd_factors_wire: next-batch preparation and prefetch slot, phases, draw cursor
+static int cd_pass(Ctx& c, const float* data, int64_t ldd, const imdbn_cd_opts* o, bool allow_compact = true) {
+    PrepArgs pn;
+    bool rides = false;
+    CHK(cd_prologue(c, o, pn, rides, allow_compact));
+    CHK(cd_phases(c, data, ldd, o, rides ? &pn : nullptr));
+    return c.rng.finish();
 }
 
 int imdbn_rbm_cd_step(const imdbn_rbm_desc* d, const float* data, int64_t ldd, int B, const imdbn_cd_opts* o,
@@ -1317,11 +701,7 @@ int imdbn_rbm_cd_step(const imdbn_rbm_desc* d, const float* data, int64_t ldd, i
     if (o->data_binary < 0 || o->data_binary > 2 || o->next_binary < 0 || o->next_binary > 2) return fail(IMDBN_E_INVALID, "cd_step: data_binary / next_binary outside 0..2");
     Ctx c(d, rng, S(stream));
     CHK(setup(c, B, ws, ws_bytes));
-    PrepArgs pn;
-    bool rides = false;
-    CHK(cd_prologue(c, o, pn, rides));
-    CHK(cd_phases(c, data, ldd, o, rides ? &pn : nullptr));
-    CHK(c.rng.finish());
+    CHK(cd_pass(c, data, ldd, o));
     const BiasArgs bias = make_bias(c, o, o->sparsity != 0, (float)B, loss_out);
     CHK(launch_assoc(c, 0, o, c.nw == 1 ? 1 : 0, c.L.flags, 1, (float)B, nullptr, &bias));
     if (o->fwd_out) {
@@ -1330,27 +710,14 @@ int imdbn_rbm_cd_step(const imdbn_rbm_desc* d, const float* data, int64_t ldd, i
         if (o->ld_fwd < d->H) return fail(IMDBN_E_INVALID, "cd_step: ld_fwd %lld < H %d", (long long)o->ld_fwd, d->H);
         FinishArgs f = new_finish();
         f.out_prob = o->fwd_out; f.ld_prob = o->ld_fwd;
-        const bool bits = o->data_binary != IMDBN_DATA_REAL && vec4_weights(d) && !g_no_k1s && c.L.Vpad > 1024;      // as imdbn_rbm_forward
-        CHK(prop(c, true, OpIn{c.L.vis_rm[0], c.nw == 1 ? 1 : 0, c.L.flags, bits ? c.L.vis_bits[0] : nullptr, bits ? data_operand_kind(o->data_binary) : 0}, f));
+        CHK(prop(c, true, data_operand(c, o->data_binary), f));
     }
     return 0;
 }
 
 int imdbn_rbm_prefetch_ok(const imdbn_rbm_desc* d, int B) {
     if (check_desc(d, true) != 0 || B <= 0) return 0;
-    return prefetch_available(d) ? 1 : 0;
-}
-
-// bias / sparsity / error tail of the packed statistics buffer (after the V*H delta-W floats): written by the extra block row of the
-// statistics kernel (BiasArgs::pack_tail) instead of a launch of its own
-static BiasArgs make_pack(Ctx& c, float* packed) {
-    const imdbn_rbm_desc* d = c.d;
-    BiasArgs b;
-    memset(&b, 0, sizeof(b));
-    b.pack_tail = packed + (size_t)d->V * d->H; b.H = d->H; b.V = d->V;
-    b.hpos = c.L.cs_hpos; b.hneg = c.L.cs_hneg; b.vpos = c.L.cs_vpos; b.vneg = c.L.cs_vneg; b.P = c.L.P;
-    b.loss_part = c.L.loss_part; b.n_loss = n_loss_used(c, false);
-    return b;
+    return make_route(d, make_layout(d->V, d->H, B, nullptr)).prefetch ? 1 : 0;
 }
 
 size_t imdbn_packed_delta_floats(int V, int H) {
@@ -1364,11 +731,7 @@ int imdbn_rbm_cd_stats(const imdbn_rbm_desc* d, const float* data, int64_t ldd, 
     if (!data || !o || !packed || ldd < d->V) return fail(IMDBN_E_INVALID, "cd_stats: bad argument");
     Ctx c(d, rng, S(stream));
     CHK(setup(c, B, ws, ws_bytes));
-    PrepArgs pn;
-    bool rides = false;
-    CHK(cd_prologue(c, o, pn, rides));          // the next-batch preparation / prefetch slot of imdbn_rbm_cd_step
-    CHK(cd_phases(c, data, ldd, o, rides ? &pn : nullptr));
-    CHK(c.rng.finish());
+    CHK(cd_pass(c, data, ldd, o));
     const BiasArgs pack = make_pack(c, packed);
     CHK(launch_assoc(c, 1, o, c.nw == 1 ? 1 : 0, c.L.flags, 1, 1.0f, packed, &pack));
     return 0;
@@ -1386,7 +749,7 @@ int imdbn_factor_block(int V, int H, int B, size_t* offset, size_t* bytes) {
 }
 
 static bool factor_mode_ok(const imdbn_rbm_desc* d, int B, bool with_momentum) {
-    return B >= 1 && B <= 64 && d->H % 4 == 0 && d->H >= 4 && d->ldw % 4 == 0 && (((uintptr_t)d->W) & 15) == 0 &&
+    return B >= 1 && B <= 64 && vec4_rows(d) &&
            (!with_momentum || (d->W_m && (((uintptr_t)d->W_m) & 15) == 0)) && d->n_groups == 0;
 }
 
@@ -1474,12 +837,8 @@ int imdbn_rbm_cd_factors_wire(const imdbn_rbm_desc* d, const float* data, int64_
     if (!factor_mode_ok(d, B, false)) return fail(IMDBN_E_UNSUPPORTED, "cd_factors_wire: needs <= 64 rows per rank, 16-B aligned weight rows, no softmax groups");
     Ctx c(d, rng, S(stream));
     CHK(setup(c, B, ws, ws_bytes));
-    PrepArgs pn;
-    bool rides = false;
     // (a wire form that carries the data as three bf16 planes needs all three written: no compact slot form then)
-    CHK(cd_prologue(c, o, pn, rides, binary_data != 0));
-    CHK(cd_phases(c, data, ldd, o, rides ? &pn : nullptr));
-    CHK(c.rng.finish());
+    CHK(cd_pass(c, data, ldd, o, binary_data != 0));
     FactorWireArgs w = wire_layout(d->V, d->H, B, binary_data, nullptr);
     w.src = (const char*)ws + c.L.fb_off; w.dst = (char*)wire; w.n_ranks = 1;
     if (o->data_slot) { w.alt_flags = (const char*)c.L.flags; w.alt_cs_vpos = (const char*)c.L.cs_vpos; w.alt_vpos = (const char*)c.L.vis_tr[0]; }
@@ -1500,6 +859,7 @@ static int apply_factors_impl(const imdbn_rbm_desc* d, const void* head, size_t 
     Ctx c(d, nullptr, S(stream));
     char* fake = reinterpret_cast<char*>((uintptr_t)1 << 30);                   // only offsets inside the factor block are used
     c.L = make_layout(d->V, d->H, rows_per_rank, fake);
+    c.r = make_route(d, c.L);
     const Layout& L = c.L;
     const char* fb = fake + L.fb_off;
     if (((head_stride | planes_stride) & 255) || ((((uintptr_t)head) | ((uintptr_t)planes)) & 255) || planes_stride < L.fb_bytes ||
@@ -1513,57 +873,37 @@ static int apply_factors_impl(const imdbn_rbm_desc* d, const void* head, size_t 
     f.vpos_terms = c.nw == 1 ? 1 : 0; f.vneg_terms = 1;
     f.vts = (int64_t)L.V * L.Bp; f.hts = (int64_t)L.H * L.Bp; f.Bp = L.Bp;
     f.lr = o->lr; f.mom = o->momentum; f.wd = o->weight_decay; f.n = (float)global_B;
-    BiasArgs b;
-    memset(&b, 0, sizeof(b));
-    b.hid_bias = d->hid_bias; b.hb_m = d->hb_m; b.H = L.H; b.vis_bias = d->vis_bias; b.vb_m = d->vb_m; b.V = L.V;
+    BiasArgs b = make_bias(c, o, o->sparsity != 0, (float)global_B, loss_out);      // ... reading rank 0's block, R blocks `rs` floats apart
     b.hpos = (const float*)at_h(L.cs_hpos, 0); b.hneg = (const float*)at_h(L.cs_hneg, 0);
     b.vpos = (const float*)at_h(L.cs_vpos, 0); b.vneg = (const float*)at_h(L.cs_vneg, 0);
-    b.P = L.P; b.lr = o->lr; b.mom = o->momentum; b.n = (float)global_B;
-    b.sparsity = o->sparsity ? 1 : 0; b.target = o->sparsity_target;
-    b.loss_part = (const float*)at_h(L.loss_part, 0); b.n_loss = n_loss_used(c, false);
-    b.loss_den = (float)global_B * (float)L.V; b.loss_out = loss_out;
+    b.loss_part = (const float*)at_h(L.loss_part, 0);
     b.R = n_ranks; b.rs = (int64_t)(head_stride / 4);
     BiasArgs bz;
     memset(&bz, 0, sizeof(bz));
-    const int nh = cdiv(L.H, 128), nv = cdiv(L.V, 128);
-    const int tpb = std::max(1, cdiv(nh * nv, std::max(cu_count(), 1)));
-    const int brows = nh >= 2 ? 1 : 2;
-    // (bench.py roofline at N > 1: the update kernel bracketed with HIP events on its stream, every 4th call)
-    const bool prof = g_prof.on && (g_prof.calls++ % 8 == 3) && g_prof.used + 2 <= g_prof.ev.size();
-    if (prof) HIPCHK(hipEventRecord(g_prof.ev[g_prof.used], c.s));
-    auto prof_end = [&]() -> int { if (prof) { HIPCHK(hipEventRecord(g_prof.ev[g_prof.used + 1], c.s)); g_prof.used += 2; } return 0; };
+    const int tpb = c.r.tpb, brows = k3_bias_rows(L);
+    ProfBracket prof;      // (bench.py roofline at N > 1)
+    CHK(prof.begin(c.s, true));
     // all rank blocks inside one launch (the weights move once) when the visible operands need <= 4 plane slices
-    if (n_ranks >= g_min_rank_loop && !g_no_rank_loop && f.vneg_terms == 1) {
+    if (n_ranks >= tune().min_rank_loop && !tune().no_rank_loop && f.vneg_terms == 1) {
         f.vpos = (const bf16_t*)at_v(L.vis_tr[0], 0); f.vpos_flag = (const int*)at_h(L.flags, 0);
         f.hpos = (const bf16_t*)at_h(L.hid_tr[0], 0);
         f.vneg = (const bf16_t*)at_v(L.vis_tr[1], 0); f.hneg = (const bf16_t*)at_h(L.hid_tr[1], 0);
         RankLoopArgs rl{n_ranks, (int64_t)(head_stride / 2), (int64_t)(planes_stride / 2)};
-        dim3 g(nh, cdiv(nv, tpb) + brows);
-        const bool acc = tpb <= 4 && !g_no_rank_acc;       // rank loop outside the tile loop: hidden planes staged once per rank
-        if (c.ht == 3) { if (acc) hipLaunchKernelGGL((assoc_update_planes_ranks<3, true>), g, dim3(256), 0, c.s, f, rl, tpb, b, brows);
-                         else     hipLaunchKernelGGL((assoc_update_planes_ranks<3, false>), g, dim3(256), 0, c.s, f, rl, tpb, b, brows); }
-        else           { if (acc) hipLaunchKernelGGL((assoc_update_planes_ranks<1, true>), g, dim3(256), 0, c.s, f, rl, tpb, b, brows);
-                         else     hipLaunchKernelGGL((assoc_update_planes_ranks<1, false>), g, dim3(256), 0, c.s, f, rl, tpb, b, brows); }
+        const bool acc = tpb <= 4 && !tune().no_rank_acc;       // rank loop outside the tile loop: hidden planes staged once per rank
+        const auto k = c.ht == 3 ? (acc ? assoc_update_planes_ranks<3, true> : assoc_update_planes_ranks<3, false>)
+                                 : (acc ? assoc_update_planes_ranks<1, true> : assoc_update_planes_ranks<1, false>);
+        hipLaunchKernelGGL(k, k3_grid(c, brows), dim3(256), 0, c.s, f, rl, tpb, b, brows);
         HIPCHK(hipGetLastError());
-        return prof_end();
+        return prof.end(c.s);
     }
     for (int rk = 0; rk < n_ranks; ++rk) {
         f.vpos = (const bf16_t*)at_v(L.vis_tr[0], rk); f.vpos_flag = (const int*)at_h(L.flags, rk);
         f.hpos = (const bf16_t*)at_h(L.hid_tr[0], rk);
         f.vneg = (const bf16_t*)at_v(L.vis_tr[1], rk); f.hneg = (const bf16_t*)at_h(L.hid_tr[1], rk);
-        const int pass = n_ranks == 1 ? 0 : (rk == 0 ? 1 : (rk == n_ranks - 1 ? 3 : 2));
         const int br = (rk == n_ranks - 1) ? brows : 0;
-        const BiasArgs& bb = br ? b : bz;
-        dim3 g(nh, cdiv(nv, tpb) + br);
-#define LAUNCH_K3F(HTV, PS) hipLaunchKernelGGL((assoc_update_planes<0, HTV, PS>), g, dim3(256), 0, c.s, f, tpb, bb, br)
-#define LAUNCH_K3F_P(HTV) do { if (pass == 0) LAUNCH_K3F(HTV, 0); else if (pass == 1) LAUNCH_K3F(HTV, 1); \
-                               else if (pass == 2) LAUNCH_K3F(HTV, 2); else LAUNCH_K3F(HTV, 3); } while (0)
-        if (c.ht == 3) LAUNCH_K3F_P(3); else LAUNCH_K3F_P(1);
-#undef LAUNCH_K3F_P
-#undef LAUNCH_K3F
+        CHK(launch_k3_planes(c, 0, f, k3_pass(rk, n_ranks), br ? b : bz, br));
     }
-    HIPCHK(hipGetLastError());
-    return prof_end();
+    return prof.end(c.s);
 }
 
 int imdbn_rbm_apply_factors(const imdbn_rbm_desc* d, const void* gathered, int n_ranks, size_t rank_stride, int rows_per_rank,
@@ -1595,7 +935,7 @@ int imdbn_rbm_apply_delta(const imdbn_rbm_desc* d, const float* packed, int glob
     a.lr = o->lr; a.mom = o->momentum; a.wd = o->weight_decay; a.n = (float)global_B;
     a.sparsity = o->sparsity; a.target = o->sparsity_target; a.loss_out = loss_out;
     const int64_t total = (int64_t)d->V * d->H;
-    const bool vec4 = d->H % 4 == 0 && d->ldw % 4 == 0 && ((((uintptr_t)d->W) | ((uintptr_t)d->W_m) | ((uintptr_t)packed)) & 15) == 0;
+    const bool vec4 = vec4_rows(d) && ((((uintptr_t)d->W_m) | ((uintptr_t)packed)) & 15) == 0;
     const int64_t items = vec4 ? total / 4 : total;
     const int grid = (int)std::max<int64_t>(std::min<int64_t>((items + 255) / 256, 8192), cdiv(std::max(d->V, d->H), 256));
     if (vec4) hipLaunchKernelGGL(apply_delta<true>, dim3(grid), dim3(256), 0, S(stream), a);
@@ -1623,26 +963,11 @@ int imdbn_rbm_chain_pair(const imdbn_rbm_desc* d, int B, const imdbn_chain_spec*
                          void* ws, size_t ws_bytes, imdbn_stream_t stream) {
     CHK(check_desc(d, false));
     if (!a || !b) return fail(IMDBN_E_INVALID, "chain_pair: null chain");
-    for (const imdbn_chain_spec* s : {a, b})
-        if (!s->v_known || !s->mask || !s->out_v || s->ldk < d->V || s->ldo < d->V || s->n_steps < 0 || (s->n_steps > 0 && !s->steps) ||
-            (s->mu && (s->Dz <= 0 || s->Dz > d->V)))
-            return fail(IMDBN_E_INVALID, "chain_pair: bad argument");
+    if (!chain_spec_ok(d, a) || !chain_spec_ok(d, b)) return fail(IMDBN_E_INVALID, "chain_pair: bad argument");
     if (a->out_v == b->out_v) return fail(IMDBN_E_INVALID, "chain_pair: the two chains need separate output buffers");
     Ctx c(d, rng, S(stream));
     CHK(setup(c, B, ws, ws_bytes));
-    const ChainSpec sa{a->v_known, a->mask, a->ldk, a->init_uniform, a->n_steps, a->steps, a->mu, a->ldmu, a->Dz, a->out_v, a->ldo};
-    const ChainSpec sb{b->v_known, b->mask, b->ldk, b->init_uniform, b->n_steps, b->steps, b->mu, b->ldmu, b->Dz, b->out_v, b->ldo};
-    if (chain_kernel_ok(c, sa.n_steps) && chain_kernel_ok(c, sb.n_steps) && sa.n_steps + sb.n_steps <= CHAIN_MAX_STEPS && !g_no_chain_pair) {
-        CHK(chain_init(c, sa, false, false));
-        CHK(chain_records(c, sa, 0));
-        CHK(chain_init(c, sb, false, false));
-        CHK(chain_records(c, sb, sa.n_steps));
-        CHK(launch_k4(c, sa, 0, &sb, sa.n_steps));
-        c.hid_bits_ok = false;
-    } else {
-        CHK(run_chain(c, sa, false));
-        CHK(run_chain(c, sb, false));
-    }
+    CHK(run_chain_pair(c, chain_spec(a), chain_spec(b)));
     return c.rng.finish();
 }
 
@@ -1661,34 +986,14 @@ int imdbn_rbm_chain_traced(const imdbn_rbm_desc* d, int B, const imdbn_chain_spe
                            imdbn_stream_t stream) {
     CHK(check_desc(d, false));
     if (!a || (tb && !b)) return fail(IMDBN_E_INVALID, "chain_traced: null chain");
-    for (const imdbn_chain_spec* s : {a, b})
-        if (s && (!s->v_known || !s->mask || !s->out_v || s->ldk < d->V || s->ldo < d->V || s->n_steps < 0 || (s->n_steps > 0 && !s->steps) ||
-                  (s->mu && (s->Dz <= 0 || s->Dz > d->V))))
-            return fail(IMDBN_E_INVALID, "chain_traced: bad argument");
+    if (!chain_spec_ok(d, a) || (b && !chain_spec_ok(d, b))) return fail(IMDBN_E_INVALID, "chain_traced: bad argument");
     if (b && a->out_v == b->out_v) return fail(IMDBN_E_INVALID, "chain_traced: the two chains need separate output buffers");
     CHK(check_trace(d, ta));
     CHK(check_trace(d, tb));
     Ctx c(d, rng, S(stream));
     CHK(setup(c, B, ws, ws_bytes));
-    ChainSpec sa{a->v_known, a->mask, a->ldk, a->init_uniform, a->n_steps, a->steps, a->mu, a->ldmu, a->Dz, a->out_v, a->ldo};
-    sa.tr = ta;
-    if (!b) {
-        CHK(run_chain(c, sa, false));
-        return c.rng.finish();
-    }
-    ChainSpec sb{b->v_known, b->mask, b->ldk, b->init_uniform, b->n_steps, b->steps, b->mu, b->ldmu, b->Dz, b->out_v, b->ldo};
-    sb.tr = tb;
-    if (chain_kernel_ok(c, sa.n_recs()) && chain_kernel_ok(c, sb.n_recs()) && sa.n_recs() + sb.n_recs() <= CHAIN_MAX_STEPS && !g_no_chain_pair) {
-        CHK(chain_init(c, sa, false, false));
-        CHK(chain_records(c, sa, 0));
-        CHK(chain_init(c, sb, false, false));
-        CHK(chain_records(c, sb, sa.n_recs()));
-        CHK(launch_k4(c, sa, 0, &sb, sa.n_recs()));
-        c.hid_bits_ok = false;
-    } else {
-        CHK(run_chain(c, sa, false));
-        CHK(run_chain(c, sb, false));
-    }
+    if (b) CHK(run_chain_pair(c, chain_spec(a, ta), chain_spec(b, tb)));
+    else CHK(run_chain(c, chain_spec(a, ta), false));
     return c.rng.finish();
 }
 
@@ -1783,14 +1088,7 @@ int imdbn_latent_topk(const float* bank, int64_t ldb, int N, int D, const float*
             HIPCHK(hipGetLastError());
         }
     }
-    static std::once_flag attr;
-    hipError_t ae = hipSuccess;
-    std::call_once(attr, [&] {
-        ae = hipFuncSetAttribute((const void*)knn_topk_chunk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_chunk_lds(KNN_KMAX));
-        if (ae == hipSuccess)
-            ae = hipFuncSetAttribute((const void*)knn_topk_merge, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_merge_lds(KNN_KMAX));
-    });
-    HIPCHK(ae);
+    CHK(kernel_attrs_ready());
     KnnArgs a;
     a.bank = bank; a.ldb = ldb; a.N = N; a.D = D; a.bss = bss;
     a.q = queries; a.ldq = ldq; a.Q = Q; a.qss = qss;
