@@ -356,6 +356,33 @@ int imdbn_latent_topk(const float* bank, int64_t ldb, int N, int D, const float*
                       int metric, int k, const int32_t* exclude, const float* key, int32_t* out_idx, float* out_score, void* ws,
                       size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- IMG->TXT energy trace (imdbn/utils/energy_utils.py; reference energy_utils.py:60-195) for a panel of N clamped codes ------
+ * z[N][Dz] is the clamped code (columns [0, Dz) of the joint RBM `d`), the labels are columns [Dz, Dz + K), Wy = W[Dz:Dz+K].
+ *   base  = z W[:Dz] + hid_bias: one K1 propagation (the logits path of imdbn_rbm_prop_up on the first Dz weight rows), then ONE kernel:
+ *   F_k   = -(z.bz + by_k) - sum_j softplus(base_j + Wy[k][j]); kstar = argmin (lowest index on ties); margin_energy = F(2) - F(1);
+ *           fe_top1 / fe_gap = top-1 and top-1 minus top-2 of softmax(-F).
+ *   chain y_0 = y_start (NULL: uniform 1/K), pred_0 = argmax y_0, then for t = 1..steps
+ *           h = sigmoid(base + y Wy), y_t = softmax(sigmoid(h Wy^T + by)) -- a softmax over the SIGMOID outputs of the label slice,
+ *           whatever the descriptor's softmax groups say (the reference's step, energy_utils.py:69-79);
+ *           per step [N][steps]: p_top1, p_top2, k1 (ties to the lower index), p_gt (gt nullable; then p_gt may be NULL),
+ *           l1 = |y_t - y_{t-1}|_1, deltaF_pred = F[k1] - min F.
+ *   stop    steps_to_converge = first t with l1 < eps_l1, argmax streak >= stable_steps and (k1 == kstar or p1 - p2 >= gap_thresh)
+ *           (steps + 1: never); predT = k1 at that step (at the last step without convergence).  All `steps` run for every row.
+ *   Every sum runs in a fixed order that depends on (Dz, K, H) only: a row gives the same bits alone or inside any panel.
+ *   Limits: 2 <= K <= 256, Dz >= 1, Dz + K <= V, steps >= 1, ldz >= Dz, ldy >= K (IMDBN_E_INVALID otherwise).
+ *   Workspace: imdbn_ws_bytes(Dz, H, N). */
+typedef struct imdbn_energy_out {
+    float*   p_top1; float* p_top2; float* p_gt; float* deltaF_pred; float* l1;   /* [N][steps] */
+    int32_t* k1;                                                                   /* [N][steps] */
+    int32_t* steps_to_converge; int32_t* kstar; int32_t* predT;                    /* [N] */
+    float*   margin_energy; float* fe_top1; float* fe_gap;                         /* [N] */
+    float*   F;                                                                    /* [N][K] */
+    float*   y_final;                                                              /* [N][K], nullable: y after the last step */
+} imdbn_energy_out;
+int imdbn_energy_trace(const imdbn_rbm_desc* d, const float* z, int64_t ldz, int N, int Dz, int K, int steps, const int32_t* gt,
+                       const float* y_start, int64_t ldy, double eps_l1, int stable_steps, double gap_thresh,
+                       const imdbn_energy_out* out, void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- whole RBM.train_epoch_clamped (rbm.py:402-483) -------------------------------------- */
 /* positive phase = chain(n_init steps) ; negative = cd_k steps from v+ ; update with o->lr */
 int imdbn_rbm_clamped_step(const imdbn_rbm_desc* d, const float* v_known, const float* mask, int64_t ldk, int B,

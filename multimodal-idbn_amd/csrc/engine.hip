@@ -26,6 +26,7 @@
 #include "kernels_stream.hpp"
 #include "kernels_trace.hpp"
 #include "kernels_knn.hpp"
+#include "kernels_energy.hpp"
 
 using namespace imdbn;
 
@@ -427,6 +428,15 @@ int run_chain_pair(Ctx& c, const ChainSpec& sa, const ChainSpec& sb) {
 }
 
 hipStream_t S(imdbn_stream_t s) { return (hipStream_t)s; }
+
+// the label kernel of imdbn_energy_trace (kernels_energy.hpp): Wy in LDS or global, base / h rows in LDS or global
+template <bool WLDS, bool HLDS>
+int launch_energy(const EnergyArgs& a, hipStream_t st) {
+    const size_t lds = (WLDS ? sizeof(float) * (size_t)a.K * a.H : 0) + (HLDS ? sizeof(float) * 2 * ENERGY_ROWS * (size_t)a.H : 0);
+    hipLaunchKernelGGL((energy_trace_rows<WLDS, HLDS>), dim3(cdiv(a.N, ENERGY_ROWS)), dim3(64 * ENERGY_ROWS), lds, st, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 
 }  // namespace
 
@@ -1100,6 +1110,46 @@ int imdbn_latent_topk(const float* bank, int64_t ldb, int N, int D, const float*
                        out_score);
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+// ---- IMG->TXT energy trace (imdbn/utils/energy_utils.py; kernels_energy.hpp) ------------------------------------------------
+int imdbn_energy_trace(const imdbn_rbm_desc* d, const float* z, int64_t ldz, int N, int Dz, int K, int steps, const int32_t* gt,
+                       const float* y_start, int64_t ldy, double eps_l1, int stable_steps, double gap_thresh,
+                       const imdbn_energy_out* out, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(check_desc(d, false));
+    if (K < 2 || K > TRACE_KMAX) return fail(IMDBN_E_INVALID, "energy_trace: K = %d outside [2, %d]", K, TRACE_KMAX);
+    if (Dz < 1 || (int64_t)Dz + K > d->V) return fail(IMDBN_E_INVALID, "energy_trace: Dz = %d, K = %d do not fit V = %d", Dz, K, d->V);
+    if (steps < 1 || N < 1) return fail(IMDBN_E_INVALID, "energy_trace: steps = %d, N = %d (both must be >= 1)", steps, N);
+    if (!z || ldz < Dz || (y_start && ldy < K)) return fail(IMDBN_E_INVALID, "energy_trace: bad tensor argument (ldz=%lld ldy=%lld)", (long long)ldz, (long long)ldy);
+    if (!out || !out->p_top1 || !out->p_top2 || !out->deltaF_pred || !out->l1 || !out->k1 || !out->steps_to_converge || !out->kstar ||
+        !out->predT || !out->margin_energy || !out->fe_top1 || !out->fe_gap || !out->F || (gt && !out->p_gt))
+        return fail(IMDBN_E_INVALID, "energy_trace: null output");
+    // phase A: base = z W[:Dz] + c -- the logits path of prop_up on the descriptor cut to its first Dz weight rows
+    imdbn_rbm_desc dz = *d;
+    dz.V = Dz; dz.n_groups = 0;
+    Ctx c(&dz, nullptr, S(stream));
+    CHK(setup(c, N, ws, ws_bytes));
+    CHK(prep(c, z, ldz, Dz, c.L.vis_rm[0], c.L.Vpad, nullptr, c.L.flags));
+    FinishArgs f = new_finish();
+    f.logits_only = 1;
+    f.out_prob = c.L.f_h; f.ld_prob = d->H;
+    CHK(prop(c, true, OpIn{c.L.vis_rm[0], c.nw == 1 ? 1 : 0, c.L.flags}, f));
+    // phase B: everything else, one wave per row
+    EnergyArgs a{};
+    a.base = c.L.f_h; a.ldb = d->H;
+    a.z = z; a.ldz = ldz;
+    a.bz = d->vis_bias; a.by = d->vis_bias + Dz;
+    a.Wy = d->W + (int64_t)Dz * d->ldw; a.ldw = d->ldw;
+    a.N = N; a.Dz = Dz; a.K = K; a.H = d->H; a.steps = steps;
+    a.gt = gt; a.y0 = y_start; a.ldy0 = ldy;
+    a.eps_l1 = eps_l1; a.stable_steps = stable_steps; a.gap_thresh = gap_thresh;
+    a.hscr = (float*)c.L.hid_tr[0];             // 6 H Bp bytes, untouched by a logits-only K1: room for [N][H] floats
+    a.p1 = out->p_top1; a.p2 = out->p_top2; a.pgt = gt ? out->p_gt : nullptr; a.dF = out->deltaF_pred; a.l1 = out->l1; a.k1 = out->k1;
+    a.conv = out->steps_to_converge; a.kstar = out->kstar; a.predT = out->predT;
+    a.margin = out->margin_energy; a.fe_top1 = out->fe_top1; a.fe_gap = out->fe_gap; a.F = out->F; a.y_out = out->y_final;
+    const bool wl = sizeof(float) * (size_t)K * d->H <= (size_t)ENERGY_WY_LDS, hl = d->H <= ENERGY_H_LDS;
+    if (wl) return hl ? launch_energy<true, true>(a, c.s) : launch_energy<true, false>(a, c.s);
+    return hl ? launch_energy<false, true>(a, c.s) : launch_energy<false, false>(a, c.s);
 }
 
 // rbm.py:443-471: v+ by conditional inference, H+, CD-k from v+ (optionally re-clamped / sampled), H-.

@@ -768,6 +768,42 @@ class HipEngine:
                                                          _ptr(out[s:e]), _ptr(ws), ws.numel(), self._stream(dev)), "imdbn_rbm_prop_down_sqerr")
         return out
 
+    def energy_trace(self, rbm, z: torch.Tensor, K: int, steps: int, gt: Optional[torch.Tensor] = None,
+                     y_start: Optional[torch.Tensor] = None, eps_l1: float = 1e-3, stable_steps: int = 3, gap_thresh: float = 0.25,
+                     want_y: bool = False) -> dict:
+        """IMG->TXT energy trace of a panel of clamped codes ``z`` ``[N, Dz]`` on the joint RBM (imdbn_energy_trace): one K1
+        propagation and one label kernel, no host sync.  Device tensors: per step ``[N, steps]`` ``p_top1, p_top2, p_gt`` (None
+        without ``gt``), ``deltaF_pred, l1, k1``; per row ``steps`` (``steps + 1`` = not converged), ``kstar, predT, margin_energy,
+        fe_top1, fe_gap``; ``F`` ``[N, K]``; ``y`` ``[N, K]`` after the last step when ``want_y``.  ``y_start`` None = uniform."""
+        d = self._desc(rbm, False)
+        if not z.is_cuda or z.dim() != 2:
+            raise N.EngineError("energy_trace needs a HIP tensor z [N, Dz]")
+        z = _f32c(z, "z")
+        n, Dz = z.shape
+        dev = z.device
+        K, T = int(K), int(steps)
+        if n < 1 or T < 1:
+            raise N.EngineError(f"energy_trace: N = {n}, steps = {T} (both must be >= 1)")
+        f = lambda *s: torch.empty(*s, device=dev)
+        i = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)
+        o = {"p_top1": f(n, T), "p_top2": f(n, T), "p_gt": f(n, T) if gt is not None else None, "deltaF_pred": f(n, T), "l1": f(n, T),
+             "k1": i(n, T), "steps": i(n), "kstar": i(n), "predT": i(n), "margin_energy": f(n), "fe_top1": f(n), "fe_gap": f(n),
+             "F": f(n, max(K, 1)), "y": f(n, max(K, 1)) if want_y else None}
+        g = gt.to(device=dev, dtype=torch.int32).contiguous() if gt is not None else None
+        y0 = _f32c(y_start.to(dev), "y_start") if y_start is not None else None
+        if (g is not None and g.numel() != n) or (y0 is not None and (y0.dim() != 2 or y0.size(0) != n or y0.size(1) != K)):
+            raise N.EngineError("energy_trace: gt [N] and y_start [N, K] must match z")
+        out = N.EnergyOut()
+        for name, key in (("p_top1", "p_top1"), ("p_top2", "p_top2"), ("p_gt", "p_gt"), ("deltaF_pred", "deltaF_pred"), ("l1", "l1"),
+                          ("k1", "k1"), ("steps_to_converge", "steps"), ("kstar", "kstar"), ("predT", "predT"),
+                          ("margin_energy", "margin_energy"), ("fe_top1", "fe_top1"), ("fe_gap", "fe_gap"), ("F", "F"), ("y_final", "y")):
+            setattr(out, name, o[key].data_ptr() if o[key] is not None else None)
+        ws = self._workspace(dev, Dz, d.H, n)
+        N.check(self._lib.imdbn_energy_trace(C.byref(d), _ptr(z), z.stride(0), n, Dz, K, T, _ptr(g), _ptr(y0),
+                                             y0.stride(0) if y0 is not None else 0, float(eps_l1), int(stable_steps), float(gap_thresh),
+                                             C.byref(out), _ptr(ws), ws.numel(), self._stream(dev)), "imdbn_energy_trace")
+        return o
+
     # ---- latent nearest-neighbour search (imdbn/utils/imdbn_logging.py) ----------------------------------------------------
     LATENT_METRICS = {"cosine": 0, "inner": 1, "ip": 1, "l2": 2}
 

@@ -66,6 +66,11 @@ class CdOpts(C.Structure):
                 ("fwd_out", C.c_void_p), ("ld_fwd", C.c_int64)]
 
 
+class EnergyOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("p_top1", "p_top2", "p_gt", "deltaF_pred", "l1", "k1", "steps_to_converge", "kstar", "predT",
+                                          "margin_energy", "fe_top1", "fe_gap", "F", "y_final")]
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 _INT = C.c_int
@@ -120,6 +125,8 @@ SIGNATURES = {
     "imdbn_rbm_prop_down_sqerr": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _P, _I64, _P, _P, _P, _SZ, _P]),
     "imdbn_row_stats": (_INT, [_P, _I64, _INT, _INT, _P, _P, _P]),
     "imdbn_latent_topk": (_INT, [_P, _I64, _INT, _INT, _P, _P, _I64, _INT, _INT, _INT, _P, _P, _P, _P, _P, _SZ, _P]),
+    "imdbn_energy_trace": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _INT, _INT, _INT, _P, _P, _I64, C.c_double, _INT, C.c_double,
+                                  C.POINTER(EnergyOut), _P, _SZ, _P]),
     "imdbn_rbm_clamped_step": (_INT, [C.POINTER(RbmDesc), _P, _P, _I64, _INT, _INT, C.POINTER(ChainStep), _P, _I64, _INT,
                                       C.POINTER(CdOpts), C.POINTER(Rng), _P, _P, _SZ, _P]),
     "imdbn_rbm_assoc_update": (_INT, [C.POINTER(RbmDesc), _P, _I64, _P, _I64, _P, _I64, _P, _I64, _INT, C.POINTER(CdOpts), _P, _SZ, _P]),
