@@ -4,6 +4,9 @@ PyTorch is plumbing here (device memory, current stream); every arithmetic step 
 runs in ``libimdbn_hip.so``.  Parameters are read from the RBM object at EVERY call (callers may
 mutate or re-bind ``W``/biases behind the RBM's back); the engine holds only
 scratch workspaces keyed on (device, V, H, B).
+
+One public method per operation; what they share lives in the private helpers: ``_call``, ``_ws_tail``,
+``_desc_key``, ``_reset_caches``, ``_clamped`` / ``_mu``, ``_chain_specs``, ``_cd``, ``_apply``, ``_buffer``, ``_f32`` / ``_i32``.
 """
 from __future__ import annotations
 
@@ -17,7 +20,7 @@ from . import native as N
 from . import rng as R
 
 
-def _f32c(t: torch.Tensor, what: str) -> torch.Tensor:
+def _f32c(t: torch.Tensor) -> torch.Tensor:
     if t.dtype != torch.float32:
         t = t.float()
     if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.size(1):
@@ -29,6 +32,23 @@ def _f32c(t: torch.Tensor, what: str) -> torch.Tensor:
 
 def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+def _ref(x):
+    return C.byref(x) if x is not None else None
+
+
+def _f32(dev, *shape) -> torch.Tensor:
+    return torch.empty(*shape, device=dev)
+
+
+def _i32(dev, *shape) -> torch.Tensor:
+    return torch.empty(*shape, dtype=torch.int32, device=dev)
+
+
+def _on(t: Optional[torch.Tensor], dev, dtype) -> Optional[torch.Tensor]:
+    """An optional side input as a contiguous `dtype` tensor on `dev`."""
+    return None if t is None else t.to(device=dev, dtype=dtype).contiguous()
 
 
 class HipEngine:
@@ -47,19 +67,27 @@ class HipEngine:
             self.set_option(k.strip(), int(v or 1))
 
     # ---- plumbing -----------------------------------------------------------------------------
+    def _call(self, name: str, *args):
+        """Call the status-returning entry `name` of the library; a non-zero status raises with the entry's name."""
+        N.check(getattr(self._lib, name)(*args), name)
+
+    def _reset_caches(self):
+        """Knobs changed: workspace sizes, prefetch records and prefetch eligibility may all differ."""
+        self._ws.clear(); self._pf.clear(); self._pf_ok.clear()
+
     def device_info(self):
         cu = C.c_int(0)
         buf = C.create_string_buffer(64)
-        N.check(self._lib.imdbn_device_info(C.byref(cu), buf, 64), "imdbn_device_info")
+        self._call("imdbn_device_info", C.byref(cu), buf, 64)
         return cu.value, buf.value.decode()
 
     def set_tuning(self, ksplit_up: int = 0, ksplit_down: int = 0):
-        N.check(self._lib.imdbn_set_tuning(int(ksplit_up), int(ksplit_down)), "imdbn_set_tuning")
-        self._ws.clear(); self._pf.clear(); self._pf_ok.clear()
+        self._call("imdbn_set_tuning", int(ksplit_up), int(ksplit_down))
+        self._reset_caches()
 
     def set_option(self, name: str, value: int):
-        N.check(self._lib.imdbn_set_option(name.encode(), int(value)), "imdbn_set_option")
-        self._ws.clear(); self._pf.clear(); self._pf_ok.clear()
+        self._call("imdbn_set_option", name.encode(), int(value))
+        self._reset_caches()
 
     # per-caller knobs (imdbn_options): a handle bound to the calling thread overrides the process defaults
     def options_create(self, **knobs):
@@ -67,13 +95,13 @@ class HipEngine:
         if not h:
             raise N.EngineError("imdbn_options_create failed")
         for k, v in knobs.items():
-            N.check(self._lib.imdbn_options_set(h, k.encode(), int(v)), "imdbn_options_set")
+            self._call("imdbn_options_set", h, k.encode(), int(v))
         return h
 
     def use_options(self, handle):
         """Bind `handle` (None: the process defaults) to this thread; workspaces are re-derived (the layout may differ)."""
-        N.check(self._lib.imdbn_use_options(handle), "imdbn_use_options")
-        self._ws.clear(); self._pf.clear(); self._pf_ok.clear()
+        self._call("imdbn_use_options", handle)
+        self._reset_caches()
 
     def options_destroy(self, handle):
         self._lib.imdbn_options_destroy(handle)
@@ -81,20 +109,20 @@ class HipEngine:
     def rng_advance(self, counter: torch.Tensor, n: int):
         """counter[0] += n on the current stream (a node of the graph being captured)."""
         assert counter.dtype == torch.int64 and counter.numel() == 1 and counter.is_cuda
-        N.check(self._lib.imdbn_rng_advance(_ptr(counter), int(n), self._stream(counter.device)), "imdbn_rng_advance")
+        self._call("imdbn_rng_advance", _ptr(counter), int(n), self._stream(counter.device))
 
     def profile(self, on: bool):
-        N.check(self._lib.imdbn_profile_enable(1 if on else 0), "imdbn_profile_enable")
+        self._call("imdbn_profile_enable", 1 if on else 0)
 
     def profile_read(self) -> Tuple[float, int]:
         ms, n = C.c_double(0), C.c_int(0)
-        N.check(self._lib.imdbn_profile_read(C.byref(ms), C.byref(n)), "imdbn_profile_read")
+        self._call("imdbn_profile_read", C.byref(ms), C.byref(n))
         return ms.value, n.value
 
     def debug_buffer(self, dev, V, H, B, name: str, nbytes: int) -> torch.Tensor:
         """Test aid: uint8 view of a named internal buffer of the (V, H, B) workspace (imdbn_debug_ws_offset)."""
         off = C.c_size_t(0)
-        N.check(self._lib.imdbn_debug_ws_offset(int(V), int(H), int(B), name.encode(), C.byref(off)), "imdbn_debug_ws_offset")
+        self._call("imdbn_debug_ws_offset", int(V), int(H), int(B), name.encode(), C.byref(off))
         ws = self._workspace(torch.device(dev), V, H, B)
         return ws[off.value:off.value + nbytes]
 
@@ -108,37 +136,50 @@ class HipEngine:
             self._ws[key] = ws
         return ws
 
+    def _ws_tail(self, dev, V, H, B):
+        """``(workspace, bytes, stream)``: the last three arguments of every entry that takes a workspace."""
+        ws = self._workspace(dev, V, H, B)
+        return _ptr(ws), ws.numel(), self._stream(dev)
+
+    def _buffer(self, key: tuple, make, at_least: int = 0) -> torch.Tensor:
+        """Get-or-create a reusable buffer in the workspace dict (re-made when smaller than `at_least` elements)."""
+        buf = self._ws.get(key)
+        if buf is None or buf.numel() < at_least:
+            buf = self._ws[key] = make()
+        return buf
+
     @staticmethod
     def _stream(dev):
         return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
+    def _desc_key(self, rbm, need_momentum: bool):
+        """What a cached descriptor of `rbm` is valid for: the addresses / pitches of the parameter and momentum tensors as
+        they are NOW, the softmax groups and the mode.  None: parameters missing, nothing is cached."""
+        p, dct = rbm._parameters, rbm.__dict__
+        Wp, hbp, vbp = p.get("W"), p.get("hid_bias"), p.get("vis_bias")
+        if Wp is None or hbp is None or vbp is None:
+            return None
+        Wm, hbm, vbm = dct.get("W_m"), dct.get("hb_m"), dct.get("vb_m")
+        g = dct.get("softmax_groups")
+        return (Wp.data_ptr(), Wp.stride(0), Wp.shape, hbp.data_ptr(), vbp.data_ptr(),
+                Wm.data_ptr() if isinstance(Wm, torch.Tensor) else 0, hbm.data_ptr() if isinstance(hbm, torch.Tensor) else 0,
+                vbm.data_ptr() if isinstance(vbm, torch.Tensor) else 0, Wm.stride(0) if isinstance(Wm, torch.Tensor) and Wm.dim() == 2 else 0,
+                tuple(map(tuple, g)) if g else (), self.mode, need_momentum)
+
     def _desc(self, rbm, need_momentum: bool) -> N.RbmDesc:
         """The native descriptor of `rbm`.  Built (and validated) once per state of the parameter tensors: callers may re-bind
         or move W / biases / momentum buffers at any time (SURVEY b-1), so the cached descriptor is keyed on their addresses."""
-        p = rbm._parameters
-        Wp, hbp, vbp = p.get("W"), p.get("hid_bias"), p.get("vis_bias")
-        dct = rbm.__dict__
-        if Wp is not None and hbp is not None and vbp is not None:
-            Wm, hbm, vbm = dct.get("W_m"), dct.get("hb_m"), dct.get("vb_m")
-            g = dct.get("softmax_groups")
-            key = (Wp.data_ptr(), Wp.stride(0), Wp.shape, hbp.data_ptr(), vbp.data_ptr(),
-                   Wm.data_ptr() if isinstance(Wm, torch.Tensor) else 0, hbm.data_ptr() if isinstance(hbm, torch.Tensor) else 0,
-                   vbm.data_ptr() if isinstance(vbm, torch.Tensor) else 0, Wm.stride(0) if isinstance(Wm, torch.Tensor) and Wm.dim() == 2 else 0,
-                   tuple(map(tuple, g)) if g else (), self.mode, bool(need_momentum))
-            cache = dct.get("_imdbn_desc")
-            hit = cache.get(bool(need_momentum)) if cache is not None else None
+        need_momentum = bool(need_momentum)
+        key = self._desc_key(rbm, need_momentum)
+        if key is not None:
+            cache = rbm.__dict__.get("_imdbn_desc")
+            hit = cache.get(need_momentum) if cache is not None else None
             if hit is not None and hit[0] == key:
                 return hit[1]
         d = self._build_desc(rbm, need_momentum)
-        if Wp is not None and hbp is not None and vbp is not None:
-            # (re-homing may have replaced the momentum buffers: key on what is there now)
-            Wm, hbm, vbm = dct.get("W_m"), dct.get("hb_m"), dct.get("vb_m")
-            g = dct.get("softmax_groups")
-            key = (Wp.data_ptr(), Wp.stride(0), Wp.shape, hbp.data_ptr(), vbp.data_ptr(),
-                   Wm.data_ptr() if isinstance(Wm, torch.Tensor) else 0, hbm.data_ptr() if isinstance(hbm, torch.Tensor) else 0,
-                   vbm.data_ptr() if isinstance(vbm, torch.Tensor) else 0, Wm.stride(0) if isinstance(Wm, torch.Tensor) and Wm.dim() == 2 else 0,
-                   tuple(map(tuple, g)) if g else (), self.mode, bool(need_momentum))
-            dct.setdefault("_imdbn_desc", {})[bool(need_momentum)] = (key, d)
+        key = self._desc_key(rbm, need_momentum)        # re-homing may have replaced the momentum buffers: key on what is there now
+        if key is not None:
+            rbm.__dict__.setdefault("_imdbn_desc", {})[need_momentum] = (key, d)
         return d
 
     def _build_desc(self, rbm, need_momentum: bool) -> N.RbmDesc:
@@ -225,19 +266,33 @@ class HipEngine:
             arr[i].sample_h, arr[i].vmode, arr[i].clamp = int(s["sample_h"]), int(s["vmode"]), int(s["clamp"])
         return arr
 
+    @staticmethod
+    def _clamped(v_known, mask):
+        """The clamped operands as fp32 with ONE row stride (the C ABI has one leading dimension for both)."""
+        vk, km = _f32c(v_known), _f32c(mask)
+        if vk.stride(0) != km.stride(0):
+            vk, km = vk.contiguous(), km.contiguous()
+        return vk, km
+
+    @staticmethod
+    def _mu(mu):
+        """The optional prior mean: ``(fp32 tensor to keep alive or None, (address, ld, Dz))``; all zero without one."""
+        if mu is None:
+            return None, (0, 0, 0)
+        t = _f32c(mu)
+        return t, (t.data_ptr(), t.stride(0), t.size(1))
+
     # ---- propagations -------------------------------------------------------------------------
     def prop_up(self, rbm, v, T=1.0, sample=False, rng=None):
         d = self._desc(rbm, False)
-        v = _f32c(v, "v")
+        v = _f32c(v)
         B, dev = v.size(0), v.device
         out = torch.empty(B, d.H, device=dev)
         smp = torch.empty(B, d.H, device=dev) if sample else None
         sched = [("u", d.H)] if sample else []
         r, keep = self._rng(rng, sched, B, dev) if sample else (None, None)
-        ws = self._workspace(dev, d.V, d.H, B)
-        N.check(self._lib.imdbn_rbm_prop_up(C.byref(d), _ptr(v), v.stride(0), B, float(T), C.byref(r) if r else None,
-                                             _ptr(out), out.stride(0), _ptr(smp), d.H, _ptr(ws), ws.numel(),
-                                             self._stream(dev)), "imdbn_rbm_prop_up")
+        self._call("imdbn_rbm_prop_up", C.byref(d), _ptr(v), v.stride(0), B, float(T), _ref(r), _ptr(out), out.stride(0), _ptr(smp), d.H,
+                   *self._ws_tail(dev, d.V, d.H, B))
         if sample:
             self._done(rng, r, sched)
             return out, smp
@@ -246,60 +301,52 @@ class HipEngine:
     def forward(self, rbm, v, data_binary=None):
         """forward(v) at T = 1 (imdbn_rbm_forward): the streaming K1 reads 0/1 pieces of the batch as a bit plane."""
         d = self._desc(rbm, False)
-        x = _f32c(v, "v")
+        x = _f32c(v)
         B, dev = x.size(0), x.device
         out = torch.empty(B, d.H, device=dev)
-        ws = self._workspace(dev, d.V, d.H, B)
-        binary = self._hint(v, data_binary)
-        N.check(self._lib.imdbn_rbm_forward(C.byref(d), _ptr(x), x.stride(0), B, binary, _ptr(out), out.stride(0), _ptr(ws), ws.numel(),
-                                             self._stream(dev)), "imdbn_rbm_forward")
+        binary = self._hint(v, data_binary)         # the caller's tensor: the fp32 form `x` may be a copy without the tag
+        self._call("imdbn_rbm_forward", C.byref(d), _ptr(x), x.stride(0), B, binary, _ptr(out), out.stride(0),
+                   *self._ws_tail(dev, d.V, d.H, B))
         return out
 
     def free_energy(self, rbm, v):
         d = self._desc(rbm, False)
-        v = _f32c(v, "v")
+        v = _f32c(v)
         B, dev = v.size(0), v.device
         out = torch.empty(B, device=dev)
-        ws = self._workspace(dev, d.V, d.H, B)
-        N.check(self._lib.imdbn_rbm_free_energy(C.byref(d), _ptr(v), v.stride(0), B, _ptr(out), _ptr(ws), ws.numel(),
-                                                 self._stream(dev)), "imdbn_rbm_free_energy")
+        self._call("imdbn_rbm_free_energy", C.byref(d), _ptr(v), v.stride(0), B, _ptr(out), *self._ws_tail(dev, d.V, d.H, B))
         return out
 
     def prop_down(self, rbm, h, T=1.0, logits_only=False):
         d = self._desc(rbm, False)
-        h = _f32c(h, "h")
+        h = _f32c(h)
         B, dev = h.size(0), h.device
         out = torch.empty(B, d.V, device=dev)
-        ws = self._workspace(dev, d.V, d.H, B)
-        N.check(self._lib.imdbn_rbm_prop_down(C.byref(d), _ptr(h), h.stride(0), B, float(T), 1 if logits_only else 0,
-                                               _ptr(out), out.stride(0), _ptr(ws), ws.numel(), self._stream(dev)),
-                "imdbn_rbm_prop_down")
+        self._call("imdbn_rbm_prop_down", C.byref(d), _ptr(h), h.stride(0), B, float(T), 1 if logits_only else 0, _ptr(out), out.stride(0),
+                   *self._ws_tail(dev, d.V, d.H, B))
         return out
 
     def sample_visible(self, rbm, v_prob, rng):
         d = self._desc(rbm, False)
-        p = _f32c(v_prob, "v_prob")
+        p = _f32c(v_prob)
         B, dev = p.size(0), p.device
         out = torch.empty(B, d.V, device=dev)
         sched = R.sched_sample_visible(d.V, self._groups(rbm))
         r, keep = self._rng(rng, sched, B, dev)
-        N.check(self._lib.imdbn_rbm_sample_visible(C.byref(d), _ptr(p), p.stride(0), B, C.byref(r), _ptr(out),
-                                                    out.stride(0), self._stream(dev)), "imdbn_rbm_sample_visible")
+        self._call("imdbn_rbm_sample_visible", C.byref(d), _ptr(p), p.stride(0), B, C.byref(r), _ptr(out), out.stride(0), self._stream(dev))
         self._done(rng, r, sched)
         return out
 
     def gibbs_step(self, rbm, v, sample_h, sample_v, rng):
         d = self._desc(rbm, False)
-        v = _f32c(v, "v")
+        v = _f32c(v)
         B, dev = v.size(0), v.device
         v_next, v_prob = torch.empty(B, d.V, device=dev), torch.empty(B, d.V, device=dev)
         h, h_prob = torch.empty(B, d.H, device=dev), torch.empty(B, d.H, device=dev)
         sched = ([("u", d.H)] if sample_h else []) + (R.sched_sample_visible(d.V, self._groups(rbm)) if sample_v else [])
         r, keep = self._rng(rng, sched, B, dev)
-        ws = self._workspace(dev, d.V, d.H, B)
-        N.check(self._lib.imdbn_rbm_gibbs_step(C.byref(d), _ptr(v), v.stride(0), B, int(bool(sample_h)), int(bool(sample_v)),
-                                                C.byref(r), _ptr(v_next), _ptr(v_prob), _ptr(h), _ptr(h_prob),
-                                                _ptr(ws), ws.numel(), self._stream(dev)), "imdbn_rbm_gibbs_step")
+        self._call("imdbn_rbm_gibbs_step", C.byref(d), _ptr(v), v.stride(0), B, int(bool(sample_h)), int(bool(sample_v)), C.byref(r),
+                   _ptr(v_next), _ptr(v_prob), _ptr(h), _ptr(h_prob), *self._ws_tail(dev, d.V, d.H, B))
         self._done(rng, r, sched)
         return v_next, v_prob, h, h_prob
 
@@ -351,7 +398,7 @@ class HipEngine:
 
     def _prefetch_opts(self, o, d, x, next_data):
         """Fill the next-batch fields of the options of a CD pass on batch `x` (imdbn_cd_opts.next_* / data_slot); returns the
-        key of the prefetch state and the accepted hint (None: none) -- the caller records ``self._pf[key]`` after the call."""
+        key of the prefetch state and the accepted hint (None: none) -- ``_cd`` records ``self._pf[key]`` after the call."""
         B, dev = x.size(0), x.device
         key = (dev, d.V, d.H, B, torch.cuda.current_stream(dev).cuda_stream)
         st = self._pf.pop(key, None)
@@ -365,30 +412,37 @@ class HipEngine:
             o.next_binary = self.binary_hint(next_data)
         return key, nxt
 
+    def _cd(self, name: str, rbm, d, data, o, rng, data_binary, *outs, next_data=None, prefetch: bool = True):
+        """The CD pass behind cd_step / cd_stats / cd_factors / cd_factors_wire: entry `name`(desc, batch, ld, B, opts, rng,
+        *outs, workspace tail).  `d` is the caller's descriptor (each method asks for its own ``need_momentum``), `o` its
+        options.  With `prefetch` (cd_factors has none) this is the one place that consumes and records the next-batch state: the
+        record of this shape is popped before the call, the new one stored only after the call and its draw count came out right."""
+        x = _f32c(data)
+        B, dev = x.size(0), x.device
+        o.data_binary = self._hint(data, data_binary)       # the caller's tensor: a fp32 copy `x` has lost the tag
+        sched = R.sched_cd(d.V, d.H, self._groups(rbm), o.cd_k)
+        r, keep = self._rng(rng, sched, B, dev)
+        tail = self._ws_tail(dev, d.V, d.H, B)
+        key, nxt = self._prefetch_opts(o, d, x, next_data) if prefetch else (None, None)
+        self._call(name, C.byref(d), _ptr(x), x.stride(0), B, C.byref(o), C.byref(r), *outs, *tail)
+        self._done(rng, r, sched)
+        if nxt is not None:                      # the strong reference keeps the address from being recycled
+            self._pf[key] = (self._ident(nxt), int(o.next_slot), nxt)
+
     def cd_step(self, rbm, data, lr, mom, cd_k, rng, next_data=None, data_binary=None, forward=False):
         """One CD-k update.  ``next_data``: the batch the NEXT cd_step of this shape will get -- its operand forms are
         then prepared by extra blocks of this call's first negative-phase launch and the
         next call skips its own preparation when it is handed that very tensor, unmodified.
         ``forward``: also return ``forward(data)`` under the updated weights (one more propagation in the same call)."""
         d = self._desc(rbm, True)
-        x = _f32c(data, "data")
-        B, dev = x.size(0), x.device
+        B, dev = data.size(0), data.device
         o = self._opts(rbm, lr, mom, cd_k, sparsity=getattr(rbm, "sparsity", False))
-        o.data_binary = self._hint(data, data_binary)
-        sched = R.sched_cd(d.V, d.H, self._groups(rbm), cd_k)
-        r, keep = self._rng(rng, sched, B, dev)
         loss = torch.empty(1, device=dev)
-        ws = self._workspace(dev, d.V, d.H, B)
-        key, nxt = self._prefetch_opts(o, d, x, next_data)
         fwd = None
         if forward:
             fwd = torch.empty(B, d.H, device=dev)
             o.fwd_out, o.ld_fwd = fwd.data_ptr(), fwd.stride(0)
-        N.check(self._lib.imdbn_rbm_cd_step(C.byref(d), _ptr(x), x.stride(0), B, C.byref(o), C.byref(r), _ptr(loss),
-                                             _ptr(ws), ws.numel(), self._stream(dev)), "imdbn_rbm_cd_step")
-        self._done(rng, r, sched)
-        if nxt is not None:                      # the strong reference keeps the address from being recycled
-            self._pf[key] = (self._ident(nxt), int(o.next_slot), nxt)
+        self._cd("imdbn_rbm_cd_step", rbm, d, data, o, rng, data_binary, _ptr(loss), next_data=next_data)
         if forward:
             return loss.reshape(()), fwd
         return loss.reshape(())
@@ -396,37 +450,34 @@ class HipEngine:
     def assoc_update(self, rbm, vpos, hpos, vneg, hneg, lr, mom):
         """The weight / bias update alone (rbm.py:209-224) from the four phase tensors (imdbn_rbm_assoc_update)."""
         d = self._desc(rbm, True)
-        ts = [_f32c(t, "t") for t in (vpos, hpos, vneg, hneg)]
+        ts = [_f32c(t) for t in (vpos, hpos, vneg, hneg)]
         B, dev = ts[0].size(0), ts[0].device
         o = self._opts(rbm, lr, mom, 1, sparsity=getattr(rbm, "sparsity", False))
-        ws = self._workspace(dev, d.V, d.H, B)
-        N.check(self._lib.imdbn_rbm_assoc_update(C.byref(d), _ptr(ts[0]), ts[0].stride(0), _ptr(ts[1]), ts[1].stride(0), _ptr(ts[2]),
-                                                  ts[2].stride(0), _ptr(ts[3]), ts[3].stride(0), B, C.byref(o), _ptr(ws), ws.numel(),
-                                                  self._stream(dev)), "imdbn_rbm_assoc_update")
+        self._call("imdbn_rbm_assoc_update", C.byref(d), _ptr(ts[0]), ts[0].stride(0), _ptr(ts[1]), ts[1].stride(0), _ptr(ts[2]),
+                   ts[2].stride(0), _ptr(ts[3]), ts[3].stride(0), B, C.byref(o), *self._ws_tail(dev, d.V, d.H, B))
 
     # ---- RCCL through the C ABI (a binder without torch.distributed; the classes use torch.distributed) ---------------
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(128)
-        N.check(self._lib.imdbn_comm_unique_id(buf), "imdbn_comm_unique_id")
+        self._call("imdbn_comm_unique_id", buf)
         return buf.raw
 
     def comm_init(self, world: int, rank: int, uid: bytes):
         comm = C.c_void_p(0)
-        N.check(self._lib.imdbn_comm_init(C.byref(comm), int(world), int(rank), C.create_string_buffer(uid, 128)), "imdbn_comm_init")
+        self._call("imdbn_comm_init", C.byref(comm), int(world), int(rank), C.create_string_buffer(uid, 128))
         return comm
 
     def comm_destroy(self, comm):
-        N.check(self._lib.imdbn_comm_destroy(comm), "imdbn_comm_destroy")
+        self._call("imdbn_comm_destroy", comm)
 
     def comm_allreduce_sum(self, comm, t: torch.Tensor):
         assert t.dtype == torch.float32 and t.is_contiguous()
-        N.check(self._lib.imdbn_allreduce_sum_f32(comm, _ptr(t), t.numel(), self._stream(t.device)), "imdbn_allreduce_sum_f32")
+        self._call("imdbn_allreduce_sum_f32", comm, _ptr(t), t.numel(), self._stream(t.device))
         return t
 
     def comm_allgather(self, comm, send: torch.Tensor, recv: torch.Tensor):
         assert send.is_contiguous() and recv.is_contiguous() and recv.numel() * recv.element_size() % (send.numel() * send.element_size()) == 0
-        N.check(self._lib.imdbn_allgather_bytes(comm, _ptr(send), _ptr(recv), send.numel() * send.element_size(), self._stream(send.device)),
-                "imdbn_allgather_bytes")
+        self._call("imdbn_allgather_bytes", comm, _ptr(send), _ptr(recv), send.numel() * send.element_size(), self._stream(send.device))
         return recv
 
     def packed_floats(self, V, H) -> int:
@@ -436,37 +487,21 @@ class HipEngine:
         """Reusable all-reduce buffer for this RBM's shape (every entry but the <=3 pad floats is rewritten by
         cd_stats, so no per-step zeroing)."""
         W = rbm.W.data
-        key = ("packed", W.device, W.shape[0], W.shape[1])
-        buf = self._ws.get(key)
-        if buf is None:
-            buf = self._ws[key] = torch.zeros(self.packed_floats(W.shape[0], W.shape[1]), device=W.device)
-        return buf
+        V, H = W.shape
+        return self._buffer(("packed", W.device, V, H), lambda: torch.zeros(self.packed_floats(V, H), device=W.device))
 
     def cd_stats(self, rbm, data, cd_k, rng, out: Optional[torch.Tensor] = None, data_binary=None, next_data=None):
         """The shard's packed statistics (data-parallel all-reduce exchange); ``next_data``: the next-batch hint of ``cd_step``."""
         d = self._desc(rbm, True)       # (imdbn_rbm_prefetch_ok wants the full descriptor)
-        x = _f32c(data, "data")
-        B, dev = x.size(0), x.device
-        o = self._opts(rbm, 0.0, 0.0, cd_k)
-        o.data_binary = self._hint(data, data_binary)
-        sched = R.sched_cd(d.V, d.H, self._groups(rbm), cd_k)
-        r, keep = self._rng(rng, sched, B, dev)
-        n = self.packed_floats(d.V, d.H)
-        packed = out if out is not None else torch.zeros(n, device=dev)
-        ws = self._workspace(dev, d.V, d.H, B)
-        key, nxt = self._prefetch_opts(o, d, x, next_data)
-        N.check(self._lib.imdbn_rbm_cd_stats(C.byref(d), _ptr(x), x.stride(0), B, C.byref(o), C.byref(r), _ptr(packed),
-                                              _ptr(ws), ws.numel(), self._stream(dev)), "imdbn_rbm_cd_stats")
-        self._done(rng, r, sched)
-        if nxt is not None:
-            self._pf[key] = (self._ident(nxt), int(o.next_slot), nxt)
+        packed = out if out is not None else torch.zeros(self.packed_floats(d.V, d.H), device=data.device)
+        self._cd("imdbn_rbm_cd_stats", rbm, d, data, self._opts(rbm, 0.0, 0.0, cd_k), rng, data_binary, _ptr(packed), next_data=next_data)
         return packed
 
     # ---- data-parallel factor exchange (include/imdbn_engine.h) --------------------------------------
     def factor_block(self, V, H, B):
         """(offset, bytes) of the factor block inside the workspace of an (V, H, B) call."""
         off, nb = C.c_size_t(0), C.c_size_t(0)
-        N.check(self._lib.imdbn_factor_block(int(V), int(H), int(B), C.byref(off), C.byref(nb)), "imdbn_factor_block")
+        self._call("imdbn_factor_block", int(V), int(H), int(B), C.byref(off), C.byref(nb))
         return int(off.value), int(nb.value)
 
     def factor_mode_ok(self, rbm, B) -> bool:
@@ -478,84 +513,63 @@ class HipEngine:
         """The CD pass of this rank's rows; returns the factor block (a uint8 VIEW of the workspace: consume it --
         e.g. all-gather it -- before the next engine call on this RBM shape)."""
         d = self._desc(rbm, False)
-        x = _f32c(data, "data")
-        B, dev = x.size(0), x.device
-        o = self._opts(rbm, 0.0, 0.0, cd_k)
-        o.data_binary = self._hint(data, data_binary)
-        sched = R.sched_cd(d.V, d.H, self._groups(rbm), cd_k)
-        r, keep = self._rng(rng, sched, B, dev)
-        ws = self._workspace(dev, d.V, d.H, B)
-        N.check(self._lib.imdbn_rbm_cd_factors(C.byref(d), _ptr(x), x.stride(0), B, C.byref(o), C.byref(r), _ptr(ws), ws.numel(),
-                                                self._stream(dev)), "imdbn_rbm_cd_factors")
-        self._done(rng, r, sched)
+        B, dev = data.size(0), data.device
+        self._cd("imdbn_rbm_cd_factors", rbm, d, data, self._opts(rbm, 0.0, 0.0, cd_k), rng, data_binary, prefetch=False)
         off, nb = self.factor_block(d.V, d.H, B)
-        return ws[off:off + nb]
+        return self._workspace(dev, d.V, d.H, B)[off:off + nb]
 
     def cd_factors_wire(self, rbm, data, cd_k, rng, binary: bool, next_data=None, data_binary=None) -> torch.Tensor:
         """The CD pass of this rank's rows straight into the wire form of its factor block (imdbn_rbm_cd_factors_wire =
         cd_factors + pack_factors in one call), with the next-batch hint of ``cd_step``.  Returns a reusable buffer."""
         d = self._desc(rbm, True)       # (imdbn_rbm_prefetch_ok wants the full descriptor)
-        x = _f32c(data, "data")
-        B, dev = x.size(0), x.device
-        o = self._opts(rbm, 0.0, 0.0, cd_k)
-        o.data_binary = self._hint(data, data_binary)
-        sched = R.sched_cd(d.V, d.H, self._groups(rbm), cd_k)
-        r, keep = self._rng(rng, sched, B, dev)
-        ws = self._workspace(dev, d.V, d.H, B)
-        key, nxt = self._prefetch_opts(o, d, x, next_data)
-        out = self._wire_buffer("wire1", rbm, B, 1, binary)[0]
-        N.check(self._lib.imdbn_rbm_cd_factors_wire(C.byref(d), _ptr(x), x.stride(0), B, C.byref(o), C.byref(r), int(bool(binary)), _ptr(out),
-                                                     _ptr(ws), ws.numel(), self._stream(dev)), "imdbn_rbm_cd_factors_wire")
-        self._done(rng, r, sched)
-        if nxt is not None:
-            self._pf[key] = (self._ident(nxt), int(o.next_slot), nxt)
+        out = self._wire_buffer("wire1", rbm, data.size(0), 1, binary)[0]
+        self._cd("imdbn_rbm_cd_factors_wire", rbm, d, data, self._opts(rbm, 0.0, 0.0, cd_k), rng, data_binary,
+                 int(bool(binary)), _ptr(out), next_data=next_data)
         return out
+
+    def _apply(self, name: str, rbm, dev, lr, mom, sparsity, *args):
+        """The update behind the apply_* methods: entry `name`(desc, *args, opts, loss, stream); returns the 0-d loss.
+        ``sparsity`` None: the RBM's own setting."""
+        d = self._desc(rbm, True)
+        o = self._opts(rbm, lr, mom, 1, sparsity=getattr(rbm, "sparsity", False) if sparsity is None else sparsity)
+        loss = torch.empty(1, device=dev)
+        self._call(name, C.byref(d), *args, C.byref(o), _ptr(loss), self._stream(dev))
+        return loss.reshape(())
 
     def apply_wire(self, rbm, wires: torch.Tensor, rows_per_rank, global_B, binary: bool, lr, mom):
         """The update from the gathered wire blocks (imdbn_rbm_apply_wire = unpack_factors(planes_only) + apply_factors_wire)."""
-        d = self._desc(rbm, True)
-        dev = wires.device
         world = int(wires.size(0))
         assert wires.dtype == torch.uint8 and wires.dim() == 2 and wires.is_contiguous()
         planes = self.gather_buffer(rbm, rows_per_rank, world)
-        o = self._opts(rbm, lr, mom, 1, sparsity=getattr(rbm, "sparsity", False))
-        loss = torch.empty(1, device=dev)
-        N.check(self._lib.imdbn_rbm_apply_wire(C.byref(d), _ptr(wires), int(wires.stride(0)), world, int(rows_per_rank), int(global_B),
-                                                int(bool(binary)), _ptr(planes), int(planes.stride(0)), C.byref(o), _ptr(loss),
-                                                self._stream(dev)), "imdbn_rbm_apply_wire")
-        return loss.reshape(())
+        return self._apply("imdbn_rbm_apply_wire", rbm, wires.device, lr, mom, None, _ptr(wires), int(wires.stride(0)), world,
+                           int(rows_per_rank), int(global_B), int(bool(binary)), _ptr(planes), int(planes.stride(0)))
 
     def gather_buffer(self, rbm, B, world) -> torch.Tensor:
         """Reusable [world, block bytes] uint8 buffer for the all-gather of the factor blocks."""
         W = rbm.W.data
         _, nb = self.factor_block(W.shape[0], W.shape[1], B)
-        key = ("gather", W.device, W.shape[0], W.shape[1], B, world)
-        buf = self._ws.get(key)
-        if buf is None:
-            buf = self._ws[key] = torch.empty(world, nb, dtype=torch.uint8, device=W.device)
-        return buf
+        return self._buffer(("gather", W.device, W.shape[0], W.shape[1], B, world),
+                            lambda: torch.empty(world, nb, dtype=torch.uint8, device=W.device))
 
     # wire form of the factor block (include/imdbn_engine.h): bit-packed visible planes
     def compact_bytes(self, V, H, B, binary: bool) -> int:
         nb = C.c_size_t(0)
-        N.check(self._lib.imdbn_factor_compact_bytes(int(V), int(H), int(B), int(bool(binary)), C.byref(nb)), "imdbn_factor_compact_bytes")
+        self._call("imdbn_factor_compact_bytes", int(V), int(H), int(B), int(bool(binary)), C.byref(nb))
         return int(nb.value)
 
     def _wire_buffer(self, tag, rbm, B, world, binary) -> torch.Tensor:
         W = rbm.W.data
-        key = (tag, W.device, W.shape[0], W.shape[1], B, world, bool(binary))
-        buf = self._ws.get(key)
-        if buf is None:
-            # zeros: the block trailer's `bad` mark must not match a pack epoch by accident (include/imdbn_engine.h)
-            buf = self._ws[key] = torch.zeros(world, self.compact_bytes(W.shape[0], W.shape[1], B, binary), dtype=torch.uint8, device=W.device)
-        return buf
+        V, H = W.shape
+        # zeros: the block trailer's `bad` mark must not match a pack epoch by accident (include/imdbn_engine.h)
+        return self._buffer((tag, W.device, V, H, B, world, bool(binary)),
+                            lambda: torch.zeros(world, self.compact_bytes(V, H, B, binary), dtype=torch.uint8, device=W.device))
 
     def pack_factors(self, rbm, block: torch.Tensor, B, binary: bool) -> torch.Tensor:
         """This rank's factor block -> its compact wire form (a reusable buffer)."""
         W = rbm.W.data
         out = self._wire_buffer("wire1", rbm, B, 1, binary)[0]
-        N.check(self._lib.imdbn_rbm_pack_factors(int(W.shape[0]), int(W.shape[1]), int(B), int(bool(binary)), _ptr(block), _ptr(out),
-                                                  self._stream(W.device)), "imdbn_rbm_pack_factors")
+        self._call("imdbn_rbm_pack_factors", int(W.shape[0]), int(W.shape[1]), int(B), int(bool(binary)), _ptr(block), _ptr(out),
+                   self._stream(W.device))
         return out
 
     def compact_gather_buffer(self, rbm, B, world, binary: bool) -> torch.Tensor:
@@ -568,93 +582,81 @@ class HipEngine:
         world = int(compact.size(0))
         full = self.gather_buffer(rbm, B, world)
         assert compact.dtype == torch.uint8 and compact.dim() == 2 and compact.is_contiguous()
-        N.check(self._lib.imdbn_rbm_unpack_factors(int(W.shape[0]), int(W.shape[1]), int(B), int(bool(binary)), _ptr(compact),
-                                                    int(compact.stride(0)), world, _ptr(full), int(full.stride(0)),
-                                                    int(bool(planes_only)), self._stream(W.device)), "imdbn_rbm_unpack_factors")
+        self._call("imdbn_rbm_unpack_factors", int(W.shape[0]), int(W.shape[1]), int(B), int(bool(binary)), _ptr(compact),
+                   int(compact.stride(0)), world, _ptr(full), int(full.stride(0)), int(bool(planes_only)), self._stream(W.device))
         return full
 
     def apply_factors_wire(self, rbm, wires: torch.Tensor, planes: torch.Tensor, rows_per_rank, global_B, lr, mom):
         """apply_factors with the blocks' head read from the gathered wire blocks and the visible planes from `planes`."""
-        d = self._desc(rbm, True)
-        dev = wires.device
-        o = self._opts(rbm, lr, mom, 1, sparsity=getattr(rbm, "sparsity", False))
-        loss = torch.empty(1, device=dev)
-        N.check(self._lib.imdbn_rbm_apply_factors_wire(C.byref(d), _ptr(wires), int(wires.stride(0)), _ptr(planes), int(planes.stride(0)),
-                                                        int(wires.size(0)), int(rows_per_rank), int(global_B), C.byref(o), _ptr(loss),
-                                                        self._stream(dev)), "imdbn_rbm_apply_factors_wire")
-        return loss.reshape(())
+        return self._apply("imdbn_rbm_apply_factors_wire", rbm, wires.device, lr, mom, None, _ptr(wires), int(wires.stride(0)),
+                           _ptr(planes), int(planes.stride(0)), int(wires.size(0)), int(rows_per_rank), int(global_B))
 
     def apply_factors(self, rbm, gathered, rows_per_rank, global_B, lr, mom):
-        d = self._desc(rbm, True)
-        dev = gathered.device
-        o = self._opts(rbm, lr, mom, 1, sparsity=getattr(rbm, "sparsity", False))
-        loss = torch.empty(1, device=dev)
         assert gathered.dtype == torch.uint8 and gathered.dim() == 2 and gathered.is_contiguous()
-        N.check(self._lib.imdbn_rbm_apply_factors(C.byref(d), _ptr(gathered), int(gathered.size(0)), int(gathered.stride(0)),
-                                                   int(rows_per_rank), int(global_B), C.byref(o), _ptr(loss), self._stream(dev)),
-                "imdbn_rbm_apply_factors")
-        return loss.reshape(())
+        return self._apply("imdbn_rbm_apply_factors", rbm, gathered.device, lr, mom, None, _ptr(gathered), int(gathered.size(0)),
+                           int(gathered.stride(0)), int(rows_per_rank), int(global_B))
 
     def apply_delta(self, rbm, packed, global_B, lr, mom, sparsity: Optional[bool] = None):
-        d = self._desc(rbm, True)
-        dev = packed.device
-        o = self._opts(rbm, lr, mom, 1, sparsity=getattr(rbm, "sparsity", False) if sparsity is None else sparsity)
-        loss = torch.empty(1, device=dev)
-        N.check(self._lib.imdbn_rbm_apply_delta(C.byref(d), _ptr(packed), int(global_B), C.byref(o), _ptr(loss),
-                                                 self._stream(dev)), "imdbn_rbm_apply_delta")
-        return loss.reshape(())
+        return self._apply("imdbn_rbm_apply_delta", rbm, packed.device, lr, mom, sparsity, _ptr(packed), int(global_B))
 
     # ---- chains -------------------------------------------------------------------------------
     def chain(self, rbm, v_known, mask, steps: List[dict], rng, init_uniform=True, mu=None):
         d = self._desc(rbm, False)
-        vk, km = _f32c(v_known, "v_known"), _f32c(mask, "mask")
-        if vk.stride(0) != km.stride(0):
-            vk, km = vk.contiguous(), km.contiguous()
+        vk, km = self._clamped(v_known, mask)
         B, dev = vk.size(0), vk.device
         out = torch.empty(B, d.V, device=dev)
         sched = R.sched_chain(d.V, d.H, self._groups(rbm), steps, init_uniform)
         r, keep = self._rng(rng, sched, B, dev)
-        mu_t = _f32c(mu, "mu") if mu is not None else None
-        ws = self._workspace(dev, d.V, d.H, B)
-        N.check(self._lib.imdbn_rbm_chain(C.byref(d), _ptr(vk), _ptr(km), vk.stride(0), B, int(bool(init_uniform)), len(steps),
-                                           self._steps(steps), _ptr(mu_t), mu_t.stride(0) if mu_t is not None else 0,
-                                           mu_t.size(1) if mu_t is not None else 0, C.byref(r), _ptr(out), out.stride(0),
-                                           _ptr(ws), ws.numel(), self._stream(dev)), "imdbn_rbm_chain")
+        mu_t, mu_args = self._mu(mu)
+        self._call("imdbn_rbm_chain", C.byref(d), _ptr(vk), _ptr(km), vk.stride(0), B, int(bool(init_uniform)), len(steps),
+                   self._steps(steps), *mu_args, C.byref(r), _ptr(out), out.stride(0), *self._ws_tail(dev, d.V, d.H, B))
         self._done(rng, r, sched)
         return out
+
+    def _chain_specs(self, who: str, rbm, d, chains, traced: bool):
+        """Chain dicts ``dict(v_known, mask, steps, init_uniform=True, mu=None, trace=None)`` (None after the first: no such
+        chain) -> ``(B, dev, specs, traces, results, sched, keep)``: per chain its N.ChainSpec and N.ChainTrace (None unless `traced`
+        and the dict has a ``trace``) and ``(final_v, trace tensor or None)``; the schedules concatenated in chain order (ONE rng per engine
+        call); `keep` holds everything the structs point into and must live until the C call has returned."""
+        specs, traces, results, sched, keep = [], [], [], [], []
+        B = dev = None
+        for ch in chains:
+            if ch is None:
+                specs.append(None); traces.append(None); continue
+            vk, km = self._clamped(ch["v_known"], ch["mask"])
+            if B is None:
+                B, dev = vk.size(0), vk.device
+            elif vk.size(0) != B:
+                raise N.EngineError(f"{who}: the two chains need the same batch size")
+            steps, init_uniform = ch["steps"], bool(ch.get("init_uniform", True))
+            out = torch.empty(B, d.V, device=dev)
+            mu_t, mu_args = self._mu(ch.get("mu"))
+            arr = self._steps(steps)
+            sp = N.ChainSpec()
+            sp.v_known, sp.mask, sp.ldk = vk.data_ptr(), km.data_ptr(), vk.stride(0)
+            sp.init_uniform, sp.n_steps, sp.steps = int(init_uniform), len(steps), arr
+            sp.mu, sp.ldmu, sp.Dz = mu_args
+            sp.out_v, sp.ldo = out.data_ptr(), out.stride(0)
+            tr, tt = None, None
+            if traced and ch.get("trace") is not None:
+                c0, c1, base = (int(x) for x in ch["trace"])
+                tr = torch.empty(len(steps) + (1 if base else 0), B, c1 - c0, device=dev)
+                tt = N.ChainTrace()
+                tt.c0, tt.c1, tt.with_baseline = c0, c1, 1 if base else 0
+                tt.out, tt.ld_row, tt.step_stride = tr.data_ptr(), tr.stride(1), tr.stride(0)
+            specs.append(sp); traces.append(tt); results.append((out, tr)); keep.append((vk, km, mu_t, arr))
+            sched += R.sched_chain(d.V, d.H, self._groups(rbm), steps, init_uniform)
+        return B, dev, specs, traces, results, sched, keep
 
     def chain_pair(self, rbm, a: dict, b: dict, rng):
         """Two independent chains of `rbm` on batches of the same size as one engine call (imdbn_rbm_chain_pair); each of `a`, `b` =
         dict(v_known, mask, steps, init_uniform=True, mu=None).  Same draws, same results as ``chain(a)`` then ``chain(b)``."""
         d = self._desc(rbm, False)
-        keep, specs, outs, sched = [], [], [], []
-        B = dev = None
-        for ch in (a, b):
-            vk, km = _f32c(ch["v_known"], "v_known"), _f32c(ch["mask"], "mask")
-            if vk.stride(0) != km.stride(0):
-                vk, km = vk.contiguous(), km.contiguous()
-            if B is None:
-                B, dev = vk.size(0), vk.device
-            elif vk.size(0) != B:
-                raise N.EngineError("chain_pair: the two chains need the same batch size")
-            steps, init_uniform = ch["steps"], bool(ch.get("init_uniform", True))
-            out = torch.empty(B, d.V, device=dev)
-            mu = ch.get("mu")
-            mu_t = _f32c(mu, "mu") if mu is not None else None
-            arr = self._steps(steps)
-            sp = N.ChainSpec()
-            sp.v_known, sp.mask, sp.ldk = vk.data_ptr(), km.data_ptr(), vk.stride(0)
-            sp.init_uniform, sp.n_steps, sp.steps = int(init_uniform), len(steps), arr
-            sp.mu, sp.ldmu, sp.Dz = (mu_t.data_ptr() if mu_t is not None else 0), (mu_t.stride(0) if mu_t is not None else 0), (mu_t.size(1) if mu_t is not None else 0)
-            sp.out_v, sp.ldo = out.data_ptr(), out.stride(0)
-            specs.append(sp); outs.append(out); keep.append((vk, km, mu_t, arr))
-            sched += R.sched_chain(d.V, d.H, self._groups(rbm), steps, init_uniform)
+        B, dev, specs, _, results, sched, keep = self._chain_specs("chain_pair", rbm, d, (a, b), False)
         r, keep_r = self._rng(rng, sched, B, dev)
-        ws = self._workspace(dev, d.V, d.H, B)
-        N.check(self._lib.imdbn_rbm_chain_pair(C.byref(d), B, C.byref(specs[0]), C.byref(specs[1]), C.byref(r), _ptr(ws), ws.numel(),
-                                                self._stream(dev)), "imdbn_rbm_chain_pair")
+        self._call("imdbn_rbm_chain_pair", C.byref(d), B, C.byref(specs[0]), C.byref(specs[1]), C.byref(r), *self._ws_tail(dev, d.V, d.H, B))
         self._done(rng, r, sched)
-        return outs[0], outs[1]
+        return results[0][0], results[1][0]
 
     def chain_traced(self, rbm, a: dict, b: Optional[dict], rng):
         """``chain(a)`` (b None) or ``chain_pair(a, b)`` recording, per step, p(v|h) of a column window (imdbn_rbm_chain_traced).  Each
@@ -662,44 +664,12 @@ class HipEngine:
         c1 - c0]`` (slots = steps + with_baseline; slot 0 of a baseline = p(v | p(h | v0)) at T = 1) or None.  Same draws, same final
         states as the untraced calls."""
         d = self._desc(rbm, False)
-        keep, specs, traces, outs, trs, sched = [], [], [], [], [], []
-        B = dev = None
-        for ch in (a, b):
-            if ch is None:
-                specs.append(None); traces.append(None); continue
-            vk, km = _f32c(ch["v_known"], "v_known"), _f32c(ch["mask"], "mask")
-            if vk.stride(0) != km.stride(0):
-                vk, km = vk.contiguous(), km.contiguous()
-            if B is None:
-                B, dev = vk.size(0), vk.device
-            elif vk.size(0) != B:
-                raise N.EngineError("chain_traced: the two chains need the same batch size")
-            steps, init_uniform = ch["steps"], bool(ch.get("init_uniform", True))
-            out = torch.empty(B, d.V, device=dev)
-            mu = ch.get("mu")
-            mu_t = _f32c(mu, "mu") if mu is not None else None
-            arr = self._steps(steps)
-            sp = N.ChainSpec()
-            sp.v_known, sp.mask, sp.ldk = vk.data_ptr(), km.data_ptr(), vk.stride(0)
-            sp.init_uniform, sp.n_steps, sp.steps = int(init_uniform), len(steps), arr
-            sp.mu, sp.ldmu, sp.Dz = (mu_t.data_ptr() if mu_t is not None else 0), (mu_t.stride(0) if mu_t is not None else 0), (mu_t.size(1) if mu_t is not None else 0)
-            sp.out_v, sp.ldo = out.data_ptr(), out.stride(0)
-            tr, tt = None, None
-            if ch.get("trace") is not None:
-                c0, c1, base = (int(x) for x in ch["trace"])
-                tr = torch.empty(len(steps) + (1 if base else 0), B, c1 - c0, device=dev)
-                tt = N.ChainTrace()
-                tt.c0, tt.c1, tt.with_baseline = c0, c1, 1 if base else 0
-                tt.out, tt.ld_row, tt.step_stride = tr.data_ptr(), tr.stride(1), tr.stride(0)
-            specs.append(sp); traces.append(tt); outs.append(out); trs.append(tr); keep.append((vk, km, mu_t, arr))
-            sched += R.sched_chain(d.V, d.H, self._groups(rbm), steps, init_uniform)
+        B, dev, specs, traces, results, sched, keep = self._chain_specs("chain_traced", rbm, d, (a, b), True)
         r, keep_r = self._rng(rng, sched, B, dev)
-        ws = self._workspace(dev, d.V, d.H, B)
-        ref = lambda x: C.byref(x) if x is not None else None
-        N.check(self._lib.imdbn_rbm_chain_traced(C.byref(d), B, ref(specs[0]), ref(traces[0]), ref(specs[1]), ref(traces[1]), C.byref(r),
-                                                  _ptr(ws), ws.numel(), self._stream(dev)), "imdbn_rbm_chain_traced")
+        self._call("imdbn_rbm_chain_traced", C.byref(d), B, _ref(specs[0]), _ref(traces[0]), _ref(specs[1]), _ref(traces[1]), C.byref(r),
+                   *self._ws_tail(dev, d.V, d.H, B))
         self._done(rng, r, sched)
-        return list(zip(outs, trs))
+        return results
 
     def label_scan(self, trace: torch.Tensor, gt: Optional[torch.Tensor], eps_l1: float, stable_steps: int, gap_thresh: float) -> dict:
         """IMG->TXT scan of a label trace ``[T + 1, B, K]`` (slot 0 = baseline): per-step ``[B, T]`` p_top1 / p_top2 / k1 / k2 / p_gt / l1
@@ -709,15 +679,12 @@ class HipEngine:
         if trace.stride(2) != 1:
             trace = trace.contiguous()
         dev = trace.device
-        f = lambda: torch.empty(B, T, device=dev)
-        i = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)
-        o = {"p_top1": f(), "p_top2": f(), "k1": i(B, T), "k2": i(B, T), "p_gt": f() if gt is not None else None, "l1": f(),
-             "steps": i(B), "pred": i(B)}
-        g = gt.to(device=dev, dtype=torch.int32).contiguous() if gt is not None else None
-        N.check(self._lib.imdbn_trace_label_scan(_ptr(trace), trace.stride(0), trace.stride(1), T, B, K, _ptr(g), float(eps_l1),
-                                                  int(stable_steps), float(gap_thresh), _ptr(o["p_top1"]), _ptr(o["p_top2"]), _ptr(o["k1"]),
-                                                  _ptr(o["k2"]), _ptr(o["p_gt"]), _ptr(o["l1"]), _ptr(o["steps"]), _ptr(o["pred"]),
-                                                  self._stream(dev)), "imdbn_trace_label_scan")
+        o = {"p_top1": _f32(dev, B, T), "p_top2": _f32(dev, B, T), "k1": _i32(dev, B, T), "k2": _i32(dev, B, T),
+             "p_gt": _f32(dev, B, T) if gt is not None else None, "l1": _f32(dev, B, T), "steps": _i32(dev, B), "pred": _i32(dev, B)}
+        g = _on(gt, dev, torch.int32)
+        self._call("imdbn_trace_label_scan", _ptr(trace), trace.stride(0), trace.stride(1), T, B, K, _ptr(g), float(eps_l1),
+                   int(stable_steps), float(gap_thresh), _ptr(o["p_top1"]), _ptr(o["p_top2"]), _ptr(o["k1"]), _ptr(o["k2"]),
+                   _ptr(o["p_gt"]), _ptr(o["l1"]), _ptr(o["steps"]), _ptr(o["pred"]), self._stream(dev))
         return o
 
     def code_scan(self, trace: torch.Tensor, z_init: torch.Tensor, ema_beta: float):
@@ -725,11 +692,11 @@ class HipEngine:
         T, B, Dz = trace.shape
         if trace.stride(2) != 1:
             trace = trace.contiguous()
-        z0 = _f32c(z_init, "z_init")
+        z0 = _f32c(z_init)
         dev = trace.device
-        zn, dz = torch.empty(T, B, Dz, device=dev), torch.empty(B, T, device=dev)
-        N.check(self._lib.imdbn_trace_code_scan(_ptr(trace), trace.stride(0), trace.stride(1), T, B, Dz, _ptr(z0), z0.stride(0),
-                                                 float(ema_beta), _ptr(zn), _ptr(dz), self._stream(dev)), "imdbn_trace_code_scan")
+        zn, dz = _f32(dev, T, B, Dz), _f32(dev, B, T)
+        self._call("imdbn_trace_code_scan", _ptr(trace), trace.stride(0), trace.stride(1), T, B, Dz, _ptr(z0), z0.stride(0),
+                   float(ema_beta), _ptr(zn), _ptr(dz), self._stream(dev))
         return zn, dz
 
     def patience_scan(self, dz: torch.Tensor, mse: torch.Tensor, eps_z: float, mse_tol: float, patience: int):
@@ -737,9 +704,9 @@ class HipEngine:
         dz, mse = dz.float().contiguous(), mse.float().contiguous()
         B, T = dz.shape
         dev = dz.device
-        steps, best = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, device=dev)
-        N.check(self._lib.imdbn_trace_patience_scan(_ptr(dz), _ptr(mse), T, B, float(eps_z), float(mse_tol), int(patience), _ptr(steps),
-                                                     _ptr(best), self._stream(dev)), "imdbn_trace_patience_scan")
+        steps, best = _i32(dev, B), _f32(dev, B)
+        self._call("imdbn_trace_patience_scan", _ptr(dz), _ptr(mse), T, B, float(eps_z), float(mse_tol), int(patience), _ptr(steps),
+                   _ptr(best), self._stream(dev))
         return steps, best
 
     def decode_sqerr(self, idbn_layers, z: torch.Tensor, ref: torch.Tensor, ref_row: Optional[torch.Tensor] = None,
@@ -749,10 +716,9 @@ class HipEngine:
         layers = list(idbn_layers)
         dev = layers[0].W.device
         z = z.to(device=dev, dtype=torch.float32)
-        R_ = _f32c(ref.to(device=dev), "ref")
+        R_ = _f32c(ref.to(device=dev))
         n = z.size(0)
-        rows = (ref_row.to(device=dev, dtype=torch.int32).contiguous() if ref_row is not None
-                else torch.arange(n, dtype=torch.int32, device=dev))
+        rows = _on(ref_row, dev, torch.int32) if ref_row is not None else torch.arange(n, dtype=torch.int32, device=dev)
         out = torch.empty(n, device=dev)
         d = self._desc(layers[0], False)
         for s in range(0, n, int(chunk)):
@@ -760,12 +726,11 @@ class HipEngine:
             cur = z[s:e]
             for rbm in reversed(layers[1:]):
                 cur = self.prop_down(rbm, cur)
-            cur = _f32c(cur, "h")
+            cur = _f32c(cur)
             B = e - s
-            ws = self._workspace(dev, d.V, d.H, B)
             rr = rows[s:e]
-            N.check(self._lib.imdbn_rbm_prop_down_sqerr(C.byref(d), _ptr(cur), cur.stride(0), B, _ptr(R_), R_.stride(0), _ptr(rr),
-                                                         _ptr(out[s:e]), _ptr(ws), ws.numel(), self._stream(dev)), "imdbn_rbm_prop_down_sqerr")
+            self._call("imdbn_rbm_prop_down_sqerr", C.byref(d), _ptr(cur), cur.stride(0), B, _ptr(R_), R_.stride(0), _ptr(rr),
+                       _ptr(out[s:e]), *self._ws_tail(dev, d.V, d.H, B))
         return out
 
     def energy_trace(self, rbm, z: torch.Tensor, K: int, steps: int, gt: Optional[torch.Tensor] = None,
@@ -778,30 +743,28 @@ class HipEngine:
         d = self._desc(rbm, False)
         if not z.is_cuda or z.dim() != 2:
             raise N.EngineError("energy_trace needs a HIP tensor z [N, Dz]")
-        z = _f32c(z, "z")
+        z = _f32c(z)
         n, Dz = z.shape
         dev = z.device
         K, T = int(K), int(steps)
         if n < 1 or T < 1:
             raise N.EngineError(f"energy_trace: N = {n}, steps = {T} (both must be >= 1)")
-        f = lambda *s: torch.empty(*s, device=dev)
-        i = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)
-        o = {"p_top1": f(n, T), "p_top2": f(n, T), "p_gt": f(n, T) if gt is not None else None, "deltaF_pred": f(n, T), "l1": f(n, T),
-             "k1": i(n, T), "steps": i(n), "kstar": i(n), "predT": i(n), "margin_energy": f(n), "fe_top1": f(n), "fe_gap": f(n),
-             "F": f(n, max(K, 1)), "y": f(n, max(K, 1)) if want_y else None}
-        g = gt.to(device=dev, dtype=torch.int32).contiguous() if gt is not None else None
-        y0 = _f32c(y_start.to(dev), "y_start") if y_start is not None else None
+        o = {"p_top1": _f32(dev, n, T), "p_top2": _f32(dev, n, T), "p_gt": _f32(dev, n, T) if gt is not None else None,
+             "deltaF_pred": _f32(dev, n, T), "l1": _f32(dev, n, T), "k1": _i32(dev, n, T), "steps": _i32(dev, n), "kstar": _i32(dev, n),
+             "predT": _i32(dev, n), "margin_energy": _f32(dev, n), "fe_top1": _f32(dev, n), "fe_gap": _f32(dev, n),
+             "F": _f32(dev, n, max(K, 1)), "y": _f32(dev, n, max(K, 1)) if want_y else None}
+        g = _on(gt, dev, torch.int32)
+        y0 = _f32c(y_start.to(dev)) if y_start is not None else None
         if (g is not None and g.numel() != n) or (y0 is not None and (y0.dim() != 2 or y0.size(0) != n or y0.size(1) != K)):
             raise N.EngineError("energy_trace: gt [N] and y_start [N, K] must match z")
         out = N.EnergyOut()
-        for name, key in (("p_top1", "p_top1"), ("p_top2", "p_top2"), ("p_gt", "p_gt"), ("deltaF_pred", "deltaF_pred"), ("l1", "l1"),
-                          ("k1", "k1"), ("steps_to_converge", "steps"), ("kstar", "kstar"), ("predT", "predT"),
-                          ("margin_energy", "margin_energy"), ("fe_top1", "fe_top1"), ("fe_gap", "fe_gap"), ("F", "F"), ("y_final", "y")):
-            setattr(out, name, o[key].data_ptr() if o[key] is not None else None)
-        ws = self._workspace(dev, Dz, d.H, n)
-        N.check(self._lib.imdbn_energy_trace(C.byref(d), _ptr(z), z.stride(0), n, Dz, K, T, _ptr(g), _ptr(y0),
-                                             y0.stride(0) if y0 is not None else 0, float(eps_l1), int(stable_steps), float(gap_thresh),
-                                             C.byref(out), _ptr(ws), ws.numel(), self._stream(dev)), "imdbn_energy_trace")
+        alias = {"steps_to_converge": "steps", "y_final": "y"}      # the struct's field names are the dict's keys, but for these two
+        for field, _ in N.EnergyOut._fields_:
+            t = o[alias.get(field, field)]
+            setattr(out, field, t.data_ptr() if t is not None else None)
+        self._call("imdbn_energy_trace", C.byref(d), _ptr(z), z.stride(0), n, Dz, K, T, _ptr(g), _ptr(y0),
+                   y0.stride(0) if y0 is not None else 0, float(eps_l1), int(stable_steps), float(gap_thresh), C.byref(out),
+                   *self._ws_tail(dev, Dz, d.H, n))       # phase A is a (Dz, H, N) propagation: its workspace, not (V, H, N)
         return o
 
     # ---- latent nearest-neighbour search (imdbn/utils/imdbn_logging.py) ----------------------------------------------------
@@ -812,11 +775,10 @@ class HipEngine:
         (imdbn_row_stats; exact integers for 0/1 rows).  No host sync."""
         if not x.is_cuda:
             raise N.EngineError("row_stats needs a HIP tensor")
-        x = _f32c(x.reshape(x.size(0), -1), "x")
+        x = _f32c(x.reshape(x.size(0), -1))
         n, d = x.shape
         out = torch.empty(2, n, device=x.device)
-        N.check(self._lib.imdbn_row_stats(_ptr(x), x.stride(0), n, d, _ptr(out[0]), _ptr(out[1]), self._stream(x.device)),
-                "imdbn_row_stats")
+        self._call("imdbn_row_stats", _ptr(x), x.stride(0), n, d, _ptr(out[0]), _ptr(out[1]), self._stream(x.device))
         return out.t()
 
     def _topk_workspace(self, dev, N_: int, Q: int, k: int) -> torch.Tensor:
@@ -825,12 +787,8 @@ class HipEngine:
         A = lambda b: (int(b) + 255) // 256 * 256
         chunks = min(max(1, -(-2048 // -(-Q // 64))), -(-N_ // 64))
         need = A(4 * Q) + A(4 * N_) + chunks * 2 * A(4 * Q * k)
-        key = ("topk", dev, torch.cuda.current_stream(dev).cuda_stream)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            self._ws[key] = ws
-        return ws
+        return self._buffer(("topk", dev, torch.cuda.current_stream(dev).cuda_stream),
+                            lambda: torch.empty(need, dtype=torch.uint8, device=dev), at_least=need)
 
     def latent_topk(self, bank: torch.Tensor, queries: torch.Tensor, metric, k: int, exclude: Optional[torch.Tensor] = None,
                     key: Optional[torch.Tensor] = None, bank_sumsq: Optional[torch.Tensor] = None):
@@ -842,65 +800,46 @@ class HipEngine:
         if not (bank.is_cuda and queries.is_cuda):
             raise N.EngineError("latent_topk needs HIP tensors")
         dev = bank.device
-        B_ = _f32c(bank, "bank")
-        Qt = _f32c(queries.to(dev), "queries")
+        B_ = _f32c(bank)
+        Qt = _f32c(queries.to(dev))
         if B_.dim() != 2 or Qt.dim() != 2 or Qt.size(1) != B_.size(1):
             raise N.EngineError(f"latent_topk: bank {tuple(B_.shape)} and queries {tuple(Qt.shape)} must be [N, D] and [Q, D]")
         n, d = B_.shape
         q = Qt.size(0)
         k = int(k)
-        ex = exclude.to(device=dev, dtype=torch.int32).contiguous() if exclude is not None else None
-        ky = key.to(device=dev, dtype=torch.float32).contiguous() if key is not None else None
-        bss = bank_sumsq.to(device=dev, dtype=torch.float32).contiguous() if bank_sumsq is not None else None
+        ex, ky, bss = _on(exclude, dev, torch.int32), _on(key, dev, torch.float32), _on(bank_sumsq, dev, torch.float32)
         if (ex is not None and ex.numel() != q) or (ky is not None and ky.shape != (n, 2)) or (bss is not None and bss.numel() != n):
             raise N.EngineError("latent_topk: exclude [Q], key [N, 2] and bank_sumsq [N] must match the bank and queries")
-        idx = torch.empty(q, max(k, 1), dtype=torch.int32, device=dev)
-        sc = torch.empty(q, max(k, 1), device=dev)
+        idx, sc = _i32(dev, q, max(k, 1)), _f32(dev, q, max(k, 1))
         ws = self._topk_workspace(dev, n, q, max(1, min(k, 64)))
-        N.check(self._lib.imdbn_latent_topk(_ptr(B_), B_.stride(0), n, d, _ptr(bss), _ptr(Qt), Qt.stride(0), q, m, k, _ptr(ex), _ptr(ky),
-                                            _ptr(idx), _ptr(sc), _ptr(ws), ws.numel(), self._stream(dev)), "imdbn_latent_topk")
+        self._call("imdbn_latent_topk", _ptr(B_), B_.stride(0), n, d, _ptr(bss), _ptr(Qt), Qt.stride(0), q, m, k, _ptr(ex), _ptr(ky),
+                   _ptr(idx), _ptr(sc), _ptr(ws), ws.numel(), self._stream(dev))
         return idx, sc
+
+    # ---- clamped CD (the joint RBM's update) ----------------------------------------------------------------------------
+    def _clamped_cd(self, name: str, rbm, d, v_known, mask, init_steps, mu, o, sample_h, sample_v, rng, out: torch.Tensor):
+        """clamped_step / clamped_stats: entry `name`(desc, v_known, mask, ld, B, init steps, mu, opts, rng, out, workspace tail)."""
+        vk, km = self._clamped(v_known, mask)
+        B, dev = vk.size(0), vk.device
+        sched = R.sched_clamped(d.V, d.H, self._groups(rbm), init_steps, o.cd_k, sample_h, sample_v)
+        r, keep = self._rng(rng, sched, B, dev)
+        mu_t, mu_args = self._mu(mu)
+        self._call(name, C.byref(d), _ptr(vk), _ptr(km), vk.stride(0), B, len(init_steps), self._steps(init_steps), *mu_args,
+                   C.byref(o), C.byref(r), _ptr(out), *self._ws_tail(dev, d.V, d.H, B))
+        self._done(rng, r, sched)
 
     def clamped_step(self, rbm, v_known, mask, init_steps: List[dict], mu, lr, mom, cd_k, sample_h, sample_v, reclamp, rng):
         d = self._desc(rbm, True)
-        vk, km = _f32c(v_known, "v_known"), _f32c(mask, "mask")
-        if vk.stride(0) != km.stride(0):
-            vk, km = vk.contiguous(), km.contiguous()
-        B, dev = vk.size(0), vk.device
         o = self._opts(rbm, lr, mom, cd_k, sparsity=False, sample_h=sample_h, sample_v=sample_v, reclamp=reclamp)
-        sched = R.sched_clamped(d.V, d.H, self._groups(rbm), init_steps, cd_k, sample_h, sample_v)
-        r, keep = self._rng(rng, sched, B, dev)
-        mu_t = _f32c(mu, "mu") if mu is not None else None
-        loss = torch.empty(1, device=dev)
-        ws = self._workspace(dev, d.V, d.H, B)
-        N.check(self._lib.imdbn_rbm_clamped_step(C.byref(d), _ptr(vk), _ptr(km), vk.stride(0), B, len(init_steps),
-                                                  self._steps(init_steps), _ptr(mu_t),
-                                                  mu_t.stride(0) if mu_t is not None else 0,
-                                                  mu_t.size(1) if mu_t is not None else 0, C.byref(o), C.byref(r),
-                                                  _ptr(loss), _ptr(ws), ws.numel(), self._stream(dev)),
-                "imdbn_rbm_clamped_step")
-        self._done(rng, r, sched)
+        loss = torch.empty(1, device=v_known.device)
+        self._clamped_cd("imdbn_rbm_clamped_step", rbm, d, v_known, mask, init_steps, mu, o, sample_h, sample_v, rng, loss)
         return loss.reshape(())
 
     def clamped_stats(self, rbm, v_known, mask, init_steps: List[dict], mu, cd_k, sample_h, sample_v, reclamp, rng,
                       out: Optional[torch.Tensor] = None):
         """Data-parallel half of clamped_step: the shard's packed statistics (apply with apply_delta(sparsity=False))."""
         d = self._desc(rbm, False)
-        vk, km = _f32c(v_known, "v_known"), _f32c(mask, "mask")
-        if vk.stride(0) != km.stride(0):
-            vk, km = vk.contiguous(), km.contiguous()
-        B, dev = vk.size(0), vk.device
         o = self._opts(rbm, 0.0, 0.0, cd_k, sparsity=False, sample_h=sample_h, sample_v=sample_v, reclamp=reclamp)
-        sched = R.sched_clamped(d.V, d.H, self._groups(rbm), init_steps, cd_k, sample_h, sample_v)
-        r, keep = self._rng(rng, sched, B, dev)
-        mu_t = _f32c(mu, "mu") if mu is not None else None
-        packed = out if out is not None else torch.zeros(self.packed_floats(d.V, d.H), device=dev)
-        ws = self._workspace(dev, d.V, d.H, B)
-        N.check(self._lib.imdbn_rbm_clamped_stats(C.byref(d), _ptr(vk), _ptr(km), vk.stride(0), B, len(init_steps),
-                                                   self._steps(init_steps), _ptr(mu_t),
-                                                   mu_t.stride(0) if mu_t is not None else 0,
-                                                   mu_t.size(1) if mu_t is not None else 0, C.byref(o), C.byref(r),
-                                                   _ptr(packed), _ptr(ws), ws.numel(), self._stream(dev)),
-                "imdbn_rbm_clamped_stats")
-        self._done(rng, r, sched)
+        packed = out if out is not None else torch.zeros(self.packed_floats(d.V, d.H), device=v_known.device)
+        self._clamped_cd("imdbn_rbm_clamped_stats", rbm, d, v_known, mask, init_steps, mu, o, sample_h, sample_v, rng, packed)
         return packed

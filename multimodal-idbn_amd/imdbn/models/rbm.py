@@ -213,39 +213,27 @@ class RBM(nn.Module):
             ret = (lambda loss: (loss, self.forward(data))) if return_forward else (lambda loss: loss)
             if dp.mode() == "factors" and hasattr(eng, "factor_mode_ok") and eng.factor_mode_ok(self, B):
                 # exchange the factors (~7 MB per rank at 10000 x 1500; 2 MB in wire form) instead of the fp32 statistics (60 MB)
+                world = dp.world_size()
                 if hasattr(eng, "cd_factors_wire"):
-                    # three calls per step: CD pass into the wire form (with the next-batch hint), all-gather, update
+                    # three calls per step: CD pass into the wire form (the visible planes as bits: the sample always, the data
+                    # when declared binary; with the next-batch hint), all-gather, update
                     binary = dp.binary_data()
                     wire = eng.cd_factors_wire(self, x, CD, rng, binary, next_data=next_data, **kw)
-                    wires = dp.all_gather_blocks(eng.compact_gather_buffer(self, B, dp.world_size(), binary), wire)
-                    return ret(eng.apply_wire(self, wires, B, B * dp.world_size(), binary, lr, mom))
+                    wires = dp.all_gather_blocks(eng.compact_gather_buffer(self, B, world, binary), wire)
+                    return ret(eng.apply_wire(self, wires, B, B * world, binary, lr, mom))
                 block = eng.cd_factors(self, x, CD, rng, **kw)
-                if hasattr(eng, "pack_factors"):
-                    # wire form: the visible planes as bits (the sample always, the data when declared binary)
-                    binary = dp.binary_data()
-                    wire = eng.pack_factors(self, block, B, binary)
-                    wires = dp.all_gather_blocks(eng.compact_gather_buffer(self, B, dp.world_size(), binary), wire)
-                    if hasattr(eng, "apply_factors_wire"):       # the head of the blocks is read from the wire blocks in place
-                        planes = eng.unpack_factors(self, wires, B, binary, planes_only=True)
-                        return ret(eng.apply_factors_wire(self, wires, planes, B, B * dp.world_size(), lr, mom))
-                    gathered = eng.unpack_factors(self, wires, B, binary)
-                else:
-                    gathered = dp.all_gather_blocks(eng.gather_buffer(self, B, dp.world_size()), block)
-                return ret(eng.apply_factors(self, gathered, B, B * dp.world_size(), lr, mom))
+                gathered = dp.all_gather_blocks(eng.gather_buffer(self, B, world), block)
+                return ret(eng.apply_factors(self, gathered, B, B * world, lr, mom))
             buf = eng.packed_buffer(self) if hasattr(eng, "packed_buffer") else None
             packed = eng.cd_stats(self, x, CD, rng, out=buf, **kw, **({"next_data": next_data} if (next_data is not None and hasattr(eng, "prefetch_ok")) else {}))
             dp.all_reduce_sum(packed)
             return ret(eng.apply_delta(self, packed, B * dp.world_size(), lr, mom))
-        if return_forward:
-            if not getattr(eng, "fused_forward", False):
-                loss = eng.cd_step(self, x, lr, mom, CD, rng, **({"next_data": next_data} if next_data is not None else {}), **kw)
-                return loss, self.forward(data)
+        if return_forward and getattr(eng, "fused_forward", False):
             loss, h = eng.cd_step(self, x, lr, mom, CD, rng, next_data=next_data, forward=True, **kw)
             h._imdbn_binary = False
             return loss, h
-        if next_data is not None:
-            return eng.cd_step(self, x, lr, mom, CD, rng, next_data=next_data, **kw)
-        return eng.cd_step(self, x, lr, mom, CD, rng, **kw)
+        loss = eng.cd_step(self, x, lr, mom, CD, rng, next_data=next_data, **kw)
+        return (loss, self.forward(data)) if return_forward else loss
 
     # ---- schedules (rbm.py:229-238) -------------------------------------------------------------
     def _lin_schedule(self, t, t_max, start, end):
