@@ -313,6 +313,15 @@ typedef struct imdbn_chain_trace {
 int imdbn_rbm_chain_traced(const imdbn_rbm_desc* d, int B, const imdbn_chain_spec* a, const imdbn_chain_trace* ta,
                            const imdbn_chain_spec* b, const imdbn_chain_trace* tb, imdbn_rng* rng,
                            void* ws, size_t ws_bytes, imdbn_stream_t stream);
+/* imdbn_rbm_chain_traced (va / vb as ta / tb there) that can also record the HIDDEN probabilities (the joint-hidden trajectories of
+ * imdbn/utils/bimodal_logging.py).  ha / hb (nullable) reuse imdbn_chain_trace over hidden columns [c0, c1) within [0, H): slot t
+ * (0-based, n_steps slots) = sigmoid((v W + c + sigma * noise) / T) as step t computes it, with that step's T and noise -- the
+ * probability BEFORE sampling, never the sample.  with_baseline must be 0 in a hidden trace (IMDBN_E_INVALID); a baseline in the
+ * visible trace of the same chain shifts only the visible slots and writes nothing to the hidden trace.  Recording only observes,
+ * as above; with ha == hb == NULL this IS imdbn_rbm_chain_traced. */
+int imdbn_rbm_chain_traced_vh(const imdbn_rbm_desc* d, int B, const imdbn_chain_spec* a, const imdbn_chain_trace* va,
+                              const imdbn_chain_trace* ha, const imdbn_chain_spec* b, const imdbn_chain_trace* vb,
+                              const imdbn_chain_trace* hb, imdbn_rng* rng, void* ws, size_t ws_bytes, imdbn_stream_t stream);
 /* IMG->TXT scan of a label trace of T steps after a baseline (slot 0), rows of K <= 256 probabilities (conditional_steps.py:40-130).
  * Per step, [B][T]: p_top1, p_top2, k1, k2 (ties to the lower index), p_gt (gt nullable; then p_gt may be NULL), l1 = |y_t - y_{t-1}|_1.
  * Per row: steps = first t with l1 < eps_l1, argmax streak >= stable_steps and p1 - p2 >= gap_thresh (T + 1: never); pred = argmax

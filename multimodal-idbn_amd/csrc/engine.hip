@@ -229,6 +229,7 @@ struct ChainSpec {
     const float* vk; const float* mask; int64_t ldk; int init_uniform; int n_steps; const imdbn_chain_step* st;
     const float* mu; int64_t ldmu; int Dz; float* out; int64_t ldo;
     const imdbn_chain_trace* tr = nullptr;           // imdbn_rbm_chain_traced: what to record (nullable)
+    const imdbn_chain_trace* htr = nullptr;          // imdbn_rbm_chain_traced_vh: the hidden window to record (nullable; never has a baseline)
     int base() const { return tr && tr->with_baseline ? 1 : 0; }
     int n_recs() const { return n_steps + base(); }  // with a baseline, record 0 is an observe-only step (no draws, no state change)
 };
@@ -313,6 +314,8 @@ int launch_k4(Ctx& c, const ChainSpec& s0, int off0, const ChainSpec* s1, int of
         g.n_steps = s.n_recs();
         g.tr = nullptr; g.tr_ld = g.tr_ss = 0; g.tr_c0 = g.tr_c1 = 0;
         if (s.tr) { g.tr = s.tr->out; g.tr_ld = s.tr->ld_row; g.tr_ss = s.tr->step_stride; g.tr_c0 = s.tr->c0; g.tr_c1 = s.tr->c1; }
+        g.htr = nullptr; g.htr_ld = g.htr_ss = 0; g.htr_c0 = g.htr_c1 = 0; g.htr_t0 = s.base();      // hidden slot 0 = the first record that is a chain step
+        if (s.htr) { g.htr = s.htr->out; g.htr_ld = s.htr->ld_row; g.htr_ss = s.htr->step_stride; g.htr_c0 = s.htr->c0; g.htr_c1 = s.htr->c1; }
         return g;
     };
     a.s0 = seg(s0, off0);
@@ -351,15 +354,18 @@ int run_chain(Ctx& c, const ChainSpec& s, bool want_stats) {
         return 0;
     }
     const int s_base = s.base();
-    auto record = [&](int slot) -> int {             // the trace of the per-launch path: the window of the step's fp32 v_prob
-        if (!s.tr) return 0;
-        const int w = s.tr->c1 - s.tr->c0;
+    // the traces of the per-launch path: the window of the step's fp32 v_prob (f_vp), of its fp32 h_prob (f_h)
+    auto copy_window = [&](const imdbn_chain_trace* tr, const float* src, int ld, int slot) -> int {
+        if (!tr) return 0;
+        const int w = tr->c1 - tr->c0;
         const int blocks = (int)std::min<int64_t>(((int64_t)B * w + 255) / 256, 1024);
-        hipLaunchKernelGGL(trace_copy, dim3(std::max(blocks, 1)), dim3(256), 0, c.s, L.f_vp, (int64_t)L.V, B, s.tr->c0, s.tr->c1,
-                           s.tr->out + (int64_t)slot * s.tr->step_stride, s.tr->ld_row);
+        hipLaunchKernelGGL(trace_copy, dim3(std::max(blocks, 1)), dim3(256), 0, c.s, src, (int64_t)ld, B, tr->c0, tr->c1,
+                           tr->out + (int64_t)slot * tr->step_stride, tr->ld_row);
         HIPCHK(hipGetLastError());
         return 0;
     };
+    auto record = [&](int slot) -> int { return copy_window(s.tr, L.f_vp, L.V, slot); };
+    const imdbn_chain_trace* const htr = s.htr;
     if (s.base()) {      // observe-only baseline step: p(v | p(h | v0)) at T = 1, no draws; vis_rm[0] keeps v0
         FinishArgs fh = new_finish();
         fh.op.rm = L.hid_rm; fh.op.rm_terms = c.rt; fh.rm_src = 1;
@@ -378,7 +384,9 @@ int run_chain(Ctx& c, const ChainSpec& s, bool want_stats) {
             if (s.sigma > 0.f) f.noise = c.rng.floats(B, L.H);
             if (s.sample_h) { f.vmode = 1; f.uni = c.rng.floats(B, L.H); }
             f.op.rm = L.hid_rm; f.op.rm_terms = s.sample_h ? 1 : c.rt; f.rm_src = s.sample_h ? 2 : 1;
+            if (htr) { f.out_prob = L.f_h; f.ld_prob = L.H; }      // the probability before sampling, as the chain kernel records it
             CHK(prop(c, true, OpIn{L.vis_rm[0], c.rt, nullptr}, f));
+            CHK(copy_window(htr, L.f_h, L.H, t));
         }
         {   // v | h
             FinishArgs f = new_finish();
@@ -402,9 +410,9 @@ int run_chain(Ctx& c, const ChainSpec& s, bool want_stats) {
     return 0;
 }
 
-ChainSpec chain_spec(const imdbn_chain_spec* s, const imdbn_chain_trace* tr = nullptr) {
+ChainSpec chain_spec(const imdbn_chain_spec* s, const imdbn_chain_trace* tr = nullptr, const imdbn_chain_trace* htr = nullptr) {
     ChainSpec r{s->v_known, s->mask, s->ldk, s->init_uniform, s->n_steps, s->steps, s->mu, s->ldmu, s->Dz, s->out_v, s->ldo};
-    r.tr = tr;
+    r.tr = tr; r.htr = htr;
     return r;
 }
 bool chain_spec_ok(const imdbn_rbm_desc* d, const imdbn_chain_spec* s) {
@@ -983,27 +991,39 @@ int imdbn_rbm_chain_pair(const imdbn_rbm_desc* d, int B, const imdbn_chain_spec*
 
 // imdbn_rbm_chain / imdbn_rbm_chain_pair with the visible probabilities of a column window recorded at every step (the convergence
 // traces of imdbn/utils/conditional_steps.py).  Recording only observes: same draws, same final state as the untraced calls.
-static int check_trace(const imdbn_rbm_desc* d, const imdbn_chain_trace* t) {
+static int check_trace(const imdbn_rbm_desc* d, const imdbn_chain_trace* t, bool hidden = false) {
     if (!t) return 0;
-    if (!t->out || t->c0 < 0 || t->c1 <= t->c0 || t->c1 > d->V || t->ld_row < t->c1 - t->c0 || t->step_stride < 0 ||
+    const int width = hidden ? d->H : d->V;
+    if (!t->out || t->c0 < 0 || t->c1 <= t->c0 || t->c1 > width || t->ld_row < t->c1 - t->c0 || t->step_stride < 0 ||
         (t->with_baseline != 0 && t->with_baseline != 1))
-        return fail(IMDBN_E_INVALID, "chain_traced: bad trace [%d, %d) ld %lld", t->c0, t->c1, (long long)t->ld_row);
+        return fail(IMDBN_E_INVALID, "chain_traced: bad %s trace [%d, %d) ld %lld", hidden ? "hidden" : "visible", t->c0, t->c1, (long long)t->ld_row);
+    if (hidden && t->with_baseline) return fail(IMDBN_E_INVALID, "chain_traced: a hidden trace has no baseline slot");
     return 0;
 }
 
 int imdbn_rbm_chain_traced(const imdbn_rbm_desc* d, int B, const imdbn_chain_spec* a, const imdbn_chain_trace* ta,
                            const imdbn_chain_spec* b, const imdbn_chain_trace* tb, imdbn_rng* rng, void* ws, size_t ws_bytes,
                            imdbn_stream_t stream) {
+    return imdbn_rbm_chain_traced_vh(d, B, a, ta, nullptr, b, tb, nullptr, rng, ws, ws_bytes, stream);
+}
+
+// ... and with the hidden probabilities p(h|v) of a hidden column window recorded too (the joint-hidden trajectories of
+// imdbn/utils/bimodal_logging.py): slot t = what step t is about to sample, with that step's T and noise.
+int imdbn_rbm_chain_traced_vh(const imdbn_rbm_desc* d, int B, const imdbn_chain_spec* a, const imdbn_chain_trace* va,
+                              const imdbn_chain_trace* ha, const imdbn_chain_spec* b, const imdbn_chain_trace* vb,
+                              const imdbn_chain_trace* hb, imdbn_rng* rng, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
     CHK(check_desc(d, false));
-    if (!a || (tb && !b)) return fail(IMDBN_E_INVALID, "chain_traced: null chain");
+    if (!a || ((vb || hb) && !b)) return fail(IMDBN_E_INVALID, "chain_traced: null chain");
     if (!chain_spec_ok(d, a) || (b && !chain_spec_ok(d, b))) return fail(IMDBN_E_INVALID, "chain_traced: bad argument");
     if (b && a->out_v == b->out_v) return fail(IMDBN_E_INVALID, "chain_traced: the two chains need separate output buffers");
-    CHK(check_trace(d, ta));
-    CHK(check_trace(d, tb));
+    CHK(check_trace(d, va));
+    CHK(check_trace(d, vb));
+    CHK(check_trace(d, ha, true));
+    CHK(check_trace(d, hb, true));
     Ctx c(d, rng, S(stream));
     CHK(setup(c, B, ws, ws_bytes));
-    if (b) CHK(run_chain_pair(c, chain_spec(a, ta), chain_spec(b, tb)));
-    else CHK(run_chain(c, chain_spec(a, ta), false));
+    if (b) CHK(run_chain_pair(c, chain_spec(a, va, ha), chain_spec(b, vb, hb)));
+    else CHK(run_chain(c, chain_spec(a, va, ha), false));
     return c.rng.finish();
 }
 

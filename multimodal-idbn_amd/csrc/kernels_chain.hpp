@@ -115,6 +115,8 @@ struct K4Seg {
     const float* vk; const float* mask; int64_t ldk;
     int B;
     float* tr; int64_t tr_ld, tr_ss; int tr_c0, tr_c1;   // nullable trace: p(v|h) of columns [tr_c0, tr_c1) of step t at tr + t*tr_ss + b*tr_ld
+    float* htr; int64_t htr_ld, htr_ss; int htr_c0, htr_c1, htr_t0;   // nullable hidden trace: p(h|v), before sampling, of hidden columns [htr_c0, htr_c1) of
+                                                         // record t >= htr_t0 at htr + (t - htr_t0)*htr_ss + b*htr_ld (observe-only records write nothing)
 };
 struct K4Args {
     const bf16_t* planes; int64_t plane_stride;     // [2][3] planes
@@ -265,6 +267,8 @@ __global__ __launch_bounds__(K4_THREADS, 1) void k4_chain(const K4Args a) {
     const int64_t c_ldk = second ? a.s1.ldk : a.s0.ldk; const int c_B = second ? a.s1.B : a.s0.B;
     float* const c_tr = second ? a.s1.tr : a.s0.tr; const int64_t c_tld = second ? a.s1.tr_ld : a.s0.tr_ld, c_tss = second ? a.s1.tr_ss : a.s0.tr_ss;
     const int c_tc0 = second ? a.s1.tr_c0 : a.s0.tr_c0, c_tc1 = second ? a.s1.tr_c1 : a.s0.tr_c1;
+    float* const c_htr = second ? a.s1.htr : a.s0.htr; const int64_t c_hld = second ? a.s1.htr_ld : a.s0.htr_ld, c_hss = second ? a.s1.htr_ss : a.s0.htr_ss;
+    const int c_hc0 = second ? a.s1.htr_c0 : a.s0.htr_c0, c_hc1 = second ? a.s1.htr_c1 : a.s0.htr_c1, c_ht0 = second ? a.s1.htr_t0 : a.s0.htr_t0;
     const int VK = (a.V + 31) / 32 * 32 + 8, HK = (a.H + 31) / 32 * 32 + 8;      // LDS row pitch (elements): 16-B skew against bank conflicts
     constexpr int at = NW;                                                          // activation terms kept (= a.rt)
     const int gs0 = a.gs[0], gwd = a.n_groups > 0 ? a.ge[0] - a.gs[0] : 0;          // the (single) softmax group
@@ -296,6 +300,7 @@ __global__ __launch_bounds__(K4_THREADS, 1) void k4_chain(const K4Args a) {
         stamp(st, blockIdx.x, 0);
         const bool sample_h = (r.flags & 1) != 0, clamp = (r.flags & 8) != 0, obs = (r.flags & 16) != 0, last = t == c_nsteps - 1 && !obs;
         float* const trs = c_tr ? c_tr + (int64_t)t * c_tss - c_tc0 : nullptr;      // this step's trace slot (block-uniform)
+        float* const hts = (c_htr && !obs) ? c_htr + (int64_t)(t - c_ht0) * c_hss - c_hc0 : nullptr;      // ... and its hidden trace slot
         const int vmode = (r.flags >> 1) & 3;
         const float T = fmaxf(r.T, 1e-6f);                       // max(1e-6, T)  rbm.py:92,96
         const bool pull_on = c_mu && r.eta != 0.f;
@@ -332,6 +337,7 @@ __global__ __launch_bounds__(K4_THREADS, 1) void k4_chain(const K4Args a) {
                     if (T != 1.0f) x = x / T;
                     if (r.sigma > 0.f) x = x + z2[hf] * r.sigma;
                     float p = sigmoidf_ref(x);
+                    if (hts && col >= c_hc0 && col < c_hc1 && b0 + row < c_B) hts[(int64_t)(b0 + row) * c_hld + col] = p;      // the probability, never the sample
                     if (sample_h) p = (p > u2[hf]) ? 1.f : 0.f;
                     k4_put<NW>(hact, HK, row, col, (b0 + row < c_B) ? p : 0.f, sample_h);
                 }

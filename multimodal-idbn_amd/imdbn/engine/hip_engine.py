@@ -614,15 +614,16 @@ class HipEngine:
         return out
 
     def _chain_specs(self, who: str, rbm, d, chains, traced: bool):
-        """Chain dicts ``dict(v_known, mask, steps, init_uniform=True, mu=None, trace=None)`` (None after the first: no such
-        chain) -> ``(B, dev, specs, traces, results, sched, keep)``: per chain its N.ChainSpec and N.ChainTrace (None unless `traced`
-        and the dict has a ``trace``) and ``(final_v, trace tensor or None)``; the schedules concatenated in chain order (ONE rng per engine
-        call); `keep` holds everything the structs point into and must live until the C call has returned."""
-        specs, traces, results, sched, keep = [], [], [], [], []
+        """Chain dicts ``dict(v_known, mask, steps, init_uniform=True, mu=None, trace=None, trace_h=None)`` (None after the first: no
+        such chain) -> ``(B, dev, specs, traces, results, sched, keep, hidden)``: per chain its N.ChainSpec and N.ChainTrace (None unless
+        `traced` and the dict has a ``trace``) and ``(final_v, trace tensor or None)``; the schedules concatenated in chain order (ONE rng
+        per engine call); `keep` holds everything the structs point into and must live until the C call has returned; `hidden` = per
+        chain ``(N.ChainTrace, [steps, B, c1 - c0] tensor)`` of its ``trace_h=(c0, c1)`` window, ``(None, None)`` without one."""
+        specs, traces, results, sched, keep, hidden = [], [], [], [], [], []
         B = dev = None
         for ch in chains:
             if ch is None:
-                specs.append(None); traces.append(None); continue
+                specs.append(None); traces.append(None); hidden.append((None, None)); continue
             vk, km = self._clamped(ch["v_known"], ch["mask"])
             if B is None:
                 B, dev = vk.size(0), vk.device
@@ -644,15 +645,22 @@ class HipEngine:
                 tt = N.ChainTrace()
                 tt.c0, tt.c1, tt.with_baseline = c0, c1, 1 if base else 0
                 tt.out, tt.ld_row, tt.step_stride = tr.data_ptr(), tr.stride(1), tr.stride(0)
-            specs.append(sp); traces.append(tt); results.append((out, tr)); keep.append((vk, km, mu_t, arr))
+            hr, ht = None, None
+            if traced and ch.get("trace_h") is not None:
+                c0, c1 = (int(x) for x in ch["trace_h"])
+                hr = torch.empty(len(steps), B, max(c1 - c0, 0), device=dev)
+                ht = N.ChainTrace()
+                ht.c0, ht.c1, ht.with_baseline = c0, c1, 0
+                ht.out, ht.ld_row, ht.step_stride = hr.data_ptr(), hr.stride(1), hr.stride(0)
+            specs.append(sp); traces.append(tt); results.append((out, tr)); keep.append((vk, km, mu_t, arr)); hidden.append((ht, hr))
             sched += R.sched_chain(d.V, d.H, self._groups(rbm), steps, init_uniform)
-        return B, dev, specs, traces, results, sched, keep
+        return B, dev, specs, traces, results, sched, keep, hidden
 
     def chain_pair(self, rbm, a: dict, b: dict, rng):
         """Two independent chains of `rbm` on batches of the same size as one engine call (imdbn_rbm_chain_pair); each of `a`, `b` =
         dict(v_known, mask, steps, init_uniform=True, mu=None).  Same draws, same results as ``chain(a)`` then ``chain(b)``."""
         d = self._desc(rbm, False)
-        B, dev, specs, _, results, sched, keep = self._chain_specs("chain_pair", rbm, d, (a, b), False)
+        B, dev, specs, _, results, sched, keep, _ = self._chain_specs("chain_pair", rbm, d, (a, b), False)
         r, keep_r = self._rng(rng, sched, B, dev)
         self._call("imdbn_rbm_chain_pair", C.byref(d), B, C.byref(specs[0]), C.byref(specs[1]), C.byref(r), *self._ws_tail(dev, d.V, d.H, B))
         self._done(rng, r, sched)
@@ -664,12 +672,26 @@ class HipEngine:
         c1 - c0]`` (slots = steps + with_baseline; slot 0 of a baseline = p(v | p(h | v0)) at T = 1) or None.  Same draws, same final
         states as the untraced calls."""
         d = self._desc(rbm, False)
-        B, dev, specs, traces, results, sched, keep = self._chain_specs("chain_traced", rbm, d, (a, b), True)
+        B, dev, specs, traces, results, sched, keep, _ = self._chain_specs("chain_traced", rbm, d, (a, b), True)
         r, keep_r = self._rng(rng, sched, B, dev)
         self._call("imdbn_rbm_chain_traced", C.byref(d), B, _ref(specs[0]), _ref(traces[0]), _ref(specs[1]), _ref(traces[1]), C.byref(r),
                    *self._ws_tail(dev, d.V, d.H, B))
         self._done(rng, r, sched)
         return results
+
+    def chain_traced_vh(self, rbm, a: dict, b: Optional[dict], rng):
+        """``chain_traced`` that also records hidden probabilities (imdbn_rbm_chain_traced_vh).  Besides ``trace``, a chain dict may
+        carry ``trace_h=(c0, c1)``, a window of HIDDEN columns; returns one ``(final_v, trace, trace_h)`` per chain, ``trace_h`` =
+        ``[steps, B, c1 - c0]`` (slot t = p(h|v) of step t with that step's T and noise, before sampling; never a baseline slot) or
+        None.  Same draws, same final states, same visible traces as ``chain_traced``."""
+        d = self._desc(rbm, False)
+        B, dev, specs, traces, results, sched, keep, hidden = self._chain_specs("chain_traced_vh", rbm, d, (a, b), True)
+        r, keep_r = self._rng(rng, sched, B, dev)
+        self._call("imdbn_rbm_chain_traced_vh", C.byref(d), B, _ref(specs[0]), _ref(traces[0]), _ref(hidden[0][0]), _ref(specs[1]),
+                   _ref(traces[1]), _ref(hidden[1][0]), C.byref(r), *self._ws_tail(dev, d.V, d.H, B))
+        self._done(rng, r, sched)
+        present = [h for sp, h in zip(specs, hidden) if sp is not None]
+        return [(out, tr, hr) for (out, tr), (_, hr) in zip(results, present)]
 
     def label_scan(self, trace: torch.Tensor, gt: Optional[torch.Tensor], eps_l1: float, stable_steps: int, gap_thresh: float) -> dict:
         """IMG->TXT scan of a label trace ``[T + 1, B, K]`` (slot 0 = baseline): per-step ``[B, T]`` p_top1 / p_top2 / k1 / k2 / p_gt / l1

@@ -119,6 +119,8 @@ SIGNATURES = {
     "imdbn_rbm_chain_pair": (_INT, [C.POINTER(RbmDesc), _INT, C.POINTER(ChainSpec), C.POINTER(ChainSpec), C.POINTER(Rng), _P, _SZ, _P]),
     "imdbn_rbm_chain_traced": (_INT, [C.POINTER(RbmDesc), _INT, C.POINTER(ChainSpec), C.POINTER(ChainTrace), C.POINTER(ChainSpec),
                                       C.POINTER(ChainTrace), C.POINTER(Rng), _P, _SZ, _P]),
+    "imdbn_rbm_chain_traced_vh": (_INT, [C.POINTER(RbmDesc), _INT, C.POINTER(ChainSpec), C.POINTER(ChainTrace), C.POINTER(ChainTrace),
+                                         C.POINTER(ChainSpec), C.POINTER(ChainTrace), C.POINTER(ChainTrace), C.POINTER(Rng), _P, _SZ, _P]),
     "imdbn_trace_label_scan": (_INT, [_P, _I64, _I64, _INT, _INT, _INT, _P, C.c_double, _INT, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "imdbn_trace_code_scan": (_INT, [_P, _I64, _I64, _INT, _INT, _INT, _P, _I64, _F, _P, _P, _P]),
     "imdbn_trace_patience_scan": (_INT, [_P, _P, _INT, _INT, C.c_double, C.c_double, _INT, _P, _P, _P]),

@@ -4,7 +4,8 @@ Mirror of the reference ``imdbn/models/imdbn_bimodal.py`` for the training / inf
 constructor and ``_build_joint`` (:437-575), ``load_pretrained_mod{1,2}_dbn`` (:577-615),
 ``init_joint_bias_from_data`` (:617-645), ``_cross_reconstruct`` (:648-693), ``represent`` (:696-709), the
 ``train_joint`` batch loop with its online cross-modal MSE (:711-826), ``save_model`` / ``load_model`` (:1017-1076).
-The wandb / PCA / probe / trajectory / snapshot tail (:828-1015) is the observability side-car and is out of scope.
+The PCA / probe / trajectory / snapshot tail (:43-419, :856-1015) lives in ``imdbn/utils/bimodal_logging.py`` (numbers only, no figures);
+its four module-level functions are re-exported here under the reference's names, and ``_log_snapshots`` is a method as there.
 
 Data parallelism (``imdbn.engine.dp``): the RBM updates shard by rows themselves; the two host-side accumulators here (the
 bias-initialisation counters and the per-epoch cross-modal MSE sums) are all-reduced once each, as in ``iMDBN``.
@@ -26,6 +27,9 @@ from imdbn import engine as _E
 from imdbn.models.idbn import iDBN
 from imdbn.models.rbm import RBM
 from imdbn.utils import batches, rows_on_device
+from imdbn.utils import bimodal_logging as _BL
+from imdbn.utils.bimodal_logging import (compute_bimodal_joint_embeddings_and_features, log_bimodal_joint_linear_probe,  # noqa: F401
+                                         log_bimodal_latent_trajectory, log_bimodal_latent_trajectory_3d)
 
 WARMUP_EPOCHS = 8            # imdbn_bimodal.py:736
 AUX_CD = 3                   # :762,:775,:800,:814  (clamped updates run CD-3 with sampled hidden units)
@@ -253,6 +257,12 @@ class iMDBN_BiModal(nn.Module):
                 "mod2_mse": s2 / (n * npix2) if n else None,
             })
         print("[iMDBN_BiModal] joint training finished.")
+
+    # ---- snapshots (:963-1015) -------------------------------------------------------------------
+    @torch.no_grad()
+    def _log_snapshots(self, epoch: int, num: int = 8):
+        """``snap/mod1_mse`` / ``snap/mod2_mse`` of the first ``num`` validation pairs (``bimodal_logging.log_snapshots``)."""
+        return _BL.log_snapshots(self, epoch, num)
 
     # ---- persistence (:1017-1076) ------------------------------------------------------------------
     @torch.no_grad()

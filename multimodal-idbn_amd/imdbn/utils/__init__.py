@@ -4,5 +4,6 @@ from .energy_utils import class_free_energies, rbm_free_energy
 from . import probe_utils
 from . import conditional_steps
 from . import imdbn_logging
+from . import bimodal_logging
 
-__all__ = ["batches", "rows_on_device", "rbm_free_energy", "class_free_energies", "probe_utils", "conditional_steps", "imdbn_logging"]
+__all__ = ["batches", "rows_on_device", "rbm_free_energy", "class_free_energies", "probe_utils", "conditional_steps", "imdbn_logging", "bimodal_logging"]
