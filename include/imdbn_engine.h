@@ -392,6 +392,37 @@ int imdbn_energy_trace(const imdbn_rbm_desc* d, const float* z, int64_t ldz, int
                        const float* y_start, int64_t ldy, double eps_l1, int stable_steps, double gap_thresh,
                        const imdbn_energy_out* out, void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- cross-modal label metrics (imdbn/utils/cross_eval.py; reference imdbn.py:615-639, :764-813) for B rows of p(y | img) ----------
+ * p[B][K] fp32 with row stride ldp >= K; only 4-byte alignment is assumed, so the tail view v[:, Dz:] of a chain result goes in as
+ * it is.  The truth is exactly one of y[B][K] (ldy >= K; the first maximum of the row, as argmax) and gt[B] (int32).
+ *   per row (each pointer nullable)
+ *     pred    first maximum of p (the lower index on ties; NaN never wins);  gt = the truth as used;
+ *     p_pred, p_true   p[pred], p[gt] clamped to [1e-9, 1];
+ *     rank    #{j : p_j > p_gt} + #{j < gt : p_j == p_gt}: the place of the true label in a stable descending sort.
+ *   accumulators -- ADDED to, never overwritten, so a loop over batches leaves one result (zero them before the first call)
+ *     acc[8] (double, required): [0] rows, [1] top-1 hits (pred == gt), [2] top-k hits (rank < min(topk, K)),
+ *             [3] ce_sum = -sum_rows [ log pt_gt + sum_{j != gt} log(1 - pt_j) ], pt = clamp(p, 1e-6, 1 - 1e-6) in fp32, logs in fp32
+ *             (accurate logf), sums in double: F.binary_cross_entropy(reduction="sum") against the one-hot truth,
+ *             [4] mse_sum = sum_rows row_mse * npix (row_mse[B] nullable: the output of imdbn_rbm_prop_down_sqerr),
+ *             [5] skipped rows, [6], [7] untouched (zero);
+ *     confusion[K][K] (int64, nullable): rows gt, columns pred;
+ *     class_sums[K][3] (double, nullable): per true class rows, top-1 hits, sum of row_mse.
+ *   A gt entry outside [0, K) is a caller error handled without a fault: the row enters no sum and no count but acc[5]; its
+ *   p_true is NaN and its rank -1.
+ *   Every floating-point sum runs in an order fixed by (B, K): the same batches leave the same bits (no floating-point atomics;
+ *   the confusion counts are integer atomics).
+ *   Limits: B >= 1, 2 <= K <= 256, topk >= 1, npix >= 1 (IMDBN_E_INVALID otherwise, naming the value).
+ *   Workspace: 256-byte aligned, at least A(4 B) + 128 KiB bytes, A(x) = x rounded up to 256 (IMDBN_E_WORKSPACE below that). */
+typedef struct imdbn_cross_metrics_out {
+    int32_t* pred; int32_t* gt; float* p_pred; float* p_true; int32_t* rank;      /* [B] each, nullable */
+    double*  acc;                                                                  /* [8] */
+    int64_t* confusion;                                                            /* [K][K], nullable */
+    double*  class_sums;                                                           /* [K][3], nullable */
+} imdbn_cross_metrics_out;
+int imdbn_cross_metrics(const float* p, int64_t ldp, int B, int K, const float* y, int64_t ldy, const int32_t* gt,
+                        const float* row_mse, int npix, int topk, const imdbn_cross_metrics_out* out, void* ws, size_t ws_bytes,
+                        imdbn_stream_t stream);
+
 /* ---- whole RBM.train_epoch_clamped (rbm.py:402-483) -------------------------------------- */
 /* positive phase = chain(n_init steps) ; negative = cd_k steps from v+ ; update with o->lr */
 int imdbn_rbm_clamped_step(const imdbn_rbm_desc* d, const float* v_known, const float* mask, int64_t ldk, int B,

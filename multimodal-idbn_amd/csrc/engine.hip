@@ -27,6 +27,7 @@
 #include "kernels_trace.hpp"
 #include "kernels_knn.hpp"
 #include "kernels_energy.hpp"
+#include "kernels_metrics.hpp"
 
 using namespace imdbn;
 
@@ -1170,6 +1171,37 @@ int imdbn_energy_trace(const imdbn_rbm_desc* d, const float* z, int64_t ldz, int
     const bool wl = sizeof(float) * (size_t)K * d->H <= (size_t)ENERGY_WY_LDS, hl = d->H <= ENERGY_H_LDS;
     if (wl) return hl ? launch_energy<true, true>(a, c.s) : launch_energy<true, false>(a, c.s);
     return hl ? launch_energy<false, true>(a, c.s) : launch_energy<false, false>(a, c.s);
+}
+
+// ---- cross-modal label metrics (imdbn/utils/cross_eval.py; kernels_metrics.hpp) ---------------------------------------------
+int imdbn_cross_metrics(const float* p, int64_t ldp, int B, int K, const float* y, int64_t ldy, const int32_t* gt, const float* row_mse,
+                        int npix, int topk, const imdbn_cross_metrics_out* out, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    if (K < 2 || K > TRACE_KMAX) return fail(IMDBN_E_INVALID, "cross_metrics: K = %d outside [2, %d]", K, TRACE_KMAX);
+    if (B < 1) return fail(IMDBN_E_INVALID, "cross_metrics: B = %d (must be >= 1)", B);
+    if (topk < 1) return fail(IMDBN_E_INVALID, "cross_metrics: topk = %d (must be >= 1)", topk);
+    if (npix < 1) return fail(IMDBN_E_INVALID, "cross_metrics: npix = %d (must be >= 1)", npix);
+    if ((y != nullptr) == (gt != nullptr))
+        return fail(IMDBN_E_INVALID, "cross_metrics: exactly one of y and gt must be given (got %s)", y ? "both" : "neither");
+    if (!p || ldp < K) return fail(IMDBN_E_INVALID, "cross_metrics: bad p (ldp = %lld < K = %d or null)", (long long)ldp, K);
+    if (y && ldy < K) return fail(IMDBN_E_INVALID, "cross_metrics: ldy = %lld < K = %d", (long long)ldy, K);
+    if (!out || !out->acc) return fail(IMDBN_E_INVALID, "cross_metrics: null accumulator acc");
+    // workspace: the per-row codes [B], then one partial record per wave of cross_metrics_rows
+    const size_t code_bytes = knn_align(sizeof(int32_t) * (size_t)B), need = code_bytes + sizeof(CmPartial) * 4 * CM_MAX_BLOCKS;
+    if (!ws || ((uintptr_t)ws & 255) != 0 || ws_bytes < need)
+        return fail(IMDBN_E_WORKSPACE, "cross_metrics: workspace %zu < %zu bytes (or null / not 256-byte aligned)", ws_bytes, need);
+    const int nb = std::min(cdiv(B, 4), CM_MAX_BLOCKS);
+    CmArgs a{};
+    a.p = p; a.ldp = ldp; a.y = y; a.ldy = ldy; a.gt = gt; a.row_mse = row_mse;
+    a.B = B; a.K = K; a.npix = npix; a.topk = topk;
+    a.pred = out->pred; a.gt_out = out->gt; a.rank = out->rank; a.p_pred = out->p_pred; a.p_true = out->p_true;
+    a.confusion = (unsigned long long*)out->confusion;
+    a.code = (int32_t*)ws; a.part = (CmPartial*)((char*)ws + code_bytes);
+    hipLaunchKernelGGL(cross_metrics_rows, dim3(nb), dim3(256), 0, S(stream), a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(cross_metrics_combine, dim3(1 + (out->class_sums ? K : 0)), dim3(64), 0, S(stream), a.part, 4 * nb, a.code, row_mse,
+                       B, out->acc, out->class_sums);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 // rbm.py:443-471: v+ by conditional inference, H+, CD-k from v+ (optionally re-clamped / sampled), H-.

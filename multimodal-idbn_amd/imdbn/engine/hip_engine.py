@@ -789,6 +789,44 @@ class HipEngine:
                    *self._ws_tail(dev, Dz, d.H, n))       # phase A is a (Dz, H, N) propagation: its workspace, not (V, H, N)
         return o
 
+    def cross_metrics(self, p: torch.Tensor, y: Optional[torch.Tensor] = None, gt: Optional[torch.Tensor] = None,
+                      row_mse: Optional[torch.Tensor] = None, npix: int = 1, topk: int = 3, acc: Optional[torch.Tensor] = None,
+                      confusion: Optional[torch.Tensor] = None, class_sums: Optional[torch.Tensor] = None) -> dict:
+        """Label metrics of ``p`` = p(y | img) ``[B, K]`` against the truth ``y`` ``[B, K]`` (first maximum per row) or ``gt`` ``[B]``
+        (imdbn_cross_metrics): per row ``pred, gt, p_pred, p_true, rank``; ``acc`` ``[8]`` float64 (rows, top-1 hits, top-k hits,
+        ce_sum, mse_sum = sum row_mse * npix, skipped rows), ``confusion`` ``[K, K]`` int64 (rows gt, columns pred), ``class_sums``
+        ``[K, 3]`` float64 (rows, top-1 hits, sum of row_mse per true class).  The three accumulators are ADDED to: pass the ones a
+        loop over batches shares, whatever is not passed is allocated as zeros.  ``p`` may be a column view of a wider tensor.
+        Returns device tensors; no host sync."""
+        if not p.is_cuda or p.dim() != 2:
+            raise N.EngineError("cross_metrics needs a HIP tensor p [B, K]")
+        p = _f32c(p)
+        B, K = p.shape
+        dev = p.device
+        yt = _f32c(y.to(dev)) if y is not None else None
+        g, rm = _on(gt, dev, torch.int32), _on(row_mse, dev, torch.float32)
+        if (yt is not None and tuple(yt.shape) != (B, K)) or (g is not None and g.numel() != B) or (rm is not None and rm.numel() != B):
+            raise N.EngineError("cross_metrics: y [B, K], gt [B] and row_mse [B] must match p")
+        zeros = lambda shape, dt: torch.zeros(*shape, dtype=dt, device=dev)
+        acc = zeros((8,), torch.float64) if acc is None else acc
+        confusion = zeros((max(K, 1), max(K, 1)), torch.int64) if confusion is None else confusion
+        class_sums = zeros((max(K, 1), 3), torch.float64) if class_sums is None else class_sums
+        for t, shape, dt, nm in ((acc, (8,), torch.float64, "acc"), (confusion, (K, K), torch.int64, "confusion"),
+                                 (class_sums, (K, 3), torch.float64, "class_sums")):
+            if t.device != dev or t.dtype != dt or (K >= 2 and tuple(t.shape) != shape) or not t.is_contiguous():
+                raise N.EngineError(f"cross_metrics: {nm} must be a contiguous {dt} tensor {list(shape)} on {dev}")
+        o = {"pred": _i32(dev, B), "gt": _i32(dev, B), "p_pred": _f32(dev, B), "p_true": _f32(dev, B), "rank": _i32(dev, B),
+             "acc": acc, "confusion": confusion, "class_sums": class_sums}
+        out = N.CrossMetricsOut()
+        for field, _ in N.CrossMetricsOut._fields_:
+            setattr(out, field, o[field].data_ptr())
+        need = (4 * B + 255) // 256 * 256 + (128 << 10)
+        ws = self._buffer(("cross_metrics", dev, torch.cuda.current_stream(dev).cuda_stream),
+                          lambda: torch.empty(need, dtype=torch.uint8, device=dev), at_least=need)
+        self._call("imdbn_cross_metrics", _ptr(p), p.stride(0), B, K, _ptr(yt), yt.stride(0) if yt is not None else 0, _ptr(g), _ptr(rm),
+                   int(npix), int(topk), C.byref(out), _ptr(ws), ws.numel(), self._stream(dev))
+        return o
+
     # ---- latent nearest-neighbour search (imdbn/utils/imdbn_logging.py) ----------------------------------------------------
     LATENT_METRICS = {"cosine": 0, "inner": 1, "ip": 1, "l2": 2}
 

@@ -71,6 +71,10 @@ class EnergyOut(C.Structure):
                                           "margin_energy", "fe_top1", "fe_gap", "F", "y_final")]
 
 
+class CrossMetricsOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("pred", "gt", "p_pred", "p_true", "rank", "acc", "confusion", "class_sums")]
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 _INT = C.c_int
@@ -129,6 +133,7 @@ SIGNATURES = {
     "imdbn_latent_topk": (_INT, [_P, _I64, _INT, _INT, _P, _P, _I64, _INT, _INT, _INT, _P, _P, _P, _P, _P, _SZ, _P]),
     "imdbn_energy_trace": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _INT, _INT, _INT, _P, _P, _I64, C.c_double, _INT, C.c_double,
                                   C.POINTER(EnergyOut), _P, _SZ, _P]),
+    "imdbn_cross_metrics": (_INT, [_P, _I64, _INT, _INT, _P, _I64, _P, _P, _INT, _INT, C.POINTER(CrossMetricsOut), _P, _SZ, _P]),
     "imdbn_rbm_clamped_step": (_INT, [C.POINTER(RbmDesc), _P, _P, _I64, _INT, _INT, C.POINTER(ChainStep), _P, _I64, _INT,
                                       C.POINTER(CdOpts), C.POINTER(Rng), _P, _P, _SZ, _P]),
     "imdbn_rbm_assoc_update": (_INT, [C.POINTER(RbmDesc), _P, _I64, _P, _I64, _P, _I64, _P, _I64, _INT, C.POINTER(CdOpts), _P, _SZ, _P]),

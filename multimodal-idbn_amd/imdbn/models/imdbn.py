@@ -4,8 +4,9 @@ Mirror of the reference ``imdbn/models/imdbn.py`` for the hot path (SURVEY.md 8a
 constructor / ``_build_joint`` (:68-214), ``init_joint_bias_from_data`` (:216-292),
 ``load_pretrained_image_idbn`` (:294-342), ``finetune_image_last_layer`` (:344-384),
 ``_cross_reconstruct`` (:386-488), ``represent`` (:490-506), the ``train_joint`` batch loop with its
-online metrics (:553-639), ``save_model`` / ``load_model`` (:815-934).  The wandb / PCA / probe /
-snapshot tail (:641-813) is the observability side-car and is out of scope.
+online metrics (:553-639), ``save_model`` / ``load_model`` (:815-934).  ``_log_snapshots`` (:714-813) and the held-out
+``evaluate`` live in ``imdbn/utils/cross_eval.py``; the wandb / PCA / probe tail (:641-712) is the observability side-car
+(``imdbn/utils/imdbn_logging.py``) and is not wired into ``train_joint``.
 
 All RBM arithmetic goes through the engine; the few torch ops left here (concatenation, class-mean
 bookkeeping, argmax/top-k of the online metrics) are host-logic plumbing on small tensors.
@@ -25,6 +26,7 @@ from imdbn import engine as _E
 from imdbn.models.idbn import iDBN
 from imdbn.models.rbm import RBM
 from imdbn.utils import batches, rows_on_device
+from imdbn.utils import cross_eval as _CE
 
 WARMUP_Y_EPOCHS = 8          # imdbn.py:540
 Z_CLAMP_EVERY = 50           # imdbn.py:600
@@ -262,8 +264,9 @@ class iMDBN(nn.Module):
     # ---- cross-modal inference (imdbn.py:386-488) -------------------------------------------------
     @torch.no_grad()
     def _cross_reconstruct(self, z_img: torch.Tensor, y_onehot: torch.Tensor,
-                           steps: Optional[int] = None, _rbm: Optional[RBM] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Returns (img_from_txt [B,D], p_y_given_img [B,K]).
+                           steps: Optional[int] = None, _rbm: Optional[RBM] = None, _decode: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Returns (img_from_txt [B,D], p_y_given_img [B,K]); with ``_decode=False`` the first item is the code z_from_y [B,Dz]
+        that ``image_idbn.decode`` would get (imdbn.utils.cross_eval decodes it straight into a per-row error).
 
         The reference's best-of-K refinement is inert (RBM has no ``free_energy``; every candidate
         energy is 0 and argmin picks the main chain, imdbn.py:455-474), so the 4 one-step
@@ -308,7 +311,7 @@ class iMDBN(nn.Module):
         z_from_y = v_chain[:, :Dz]
         if hasattr(self, "z_affine_scale") and hasattr(self, "z_affine_bias"):       # :481-484
             z_from_y = (z_from_y - self.z_affine_bias) / (self.z_affine_scale + 1e-6)
-        return self.image_idbn.decode(z_from_y), p_y_given_img
+        return (self.image_idbn.decode(z_from_y) if _decode else z_from_y), p_y_given_img
 
     @torch.no_grad()
     def _best_of_k(self, v_chain: torch.Tensor, km: torch.Tensor, K: int, _rbm: Optional[RBM] = None):
@@ -434,6 +437,13 @@ class iMDBN(nn.Module):
         acc[1:] += torch.stack([(pred == gt).sum().double(),
                                 (topk_idx == gt.unsqueeze(1)).any(dim=1).sum().double(),
                                 ce.double(), mse.double()])
+
+    # ---- held-out evaluation and snapshots (imdbn.py:714-813; imdbn/utils/cross_eval.py) -----------
+    def _log_snapshots(self, epoch: int, num: int = 8):
+        return _CE.log_snapshots(self, epoch, num)
+
+    def evaluate(self, loader=None, **kw):
+        return _CE.evaluate_cross_modal(self, loader, **kw)
 
     # ---- persistence (imdbn.py:815-934) -------------------------------------
     def save_model(self, path: str):
