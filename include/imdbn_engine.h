@@ -203,6 +203,24 @@ int imdbn_rbm_forward(const imdbn_rbm_desc* d, const float* v, int64_t ldv, int 
 int imdbn_rbm_free_energy(const imdbn_rbm_desc* d, const float* v, int64_t ldv, int B, float* out_F,
                           void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- annealed importance sampling (imdbn/utils/likelihood.py; Salakhutdinov & Murray 2008) ----------------------------------------
+ * M independent chains from the base-rate model A (W = 0, hidden biases 0, visible biases base_vis_bias; NULL = zeros) to the RBM
+ * through the temperatures 0 = betas[0] < betas[1] < ... < betas[K] = 1 (HOST array of K + 1 floats), x(v) = hid_bias + v W,
+ * sp = softplus in double:
+ *   v_1 = 1[sigmoid(b_A) > U];  for k = 1..K:
+ *     logw += (beta_k - beta_{k-1}) sum_i (b_i - b_A,i) v_i + sum_j [sp(beta_k x_j) - sp(beta_{k-1} x_j)]     (both sums in double)
+ *     k < K:  h = 1[sigmoid(beta_k x) > U];  v_{k+1} = 1[sigmoid(beta_k (b + h W^T) + (1 - beta_k) b_A) > U]
+ *   logw[M] (device, double) is OVERWRITTEN with the log importance weights; log Z ~= H log 2 + sum_i sp(b_A,i) + logmeanexp(logw).
+ *   out_v (nullable): the final state v_K [M][V], row stride ldo >= V.
+ * Draws: ("u", V), then K - 1 times ("u", H), ("u", V): draws_used = 2 K - 1.  Both sums of logw run in an order fixed by (V, H),
+ * the logits are those of the propagations, and Philox is keyed on the row: chain i is the same chain whatever M (bit for bit
+ * while M stays within the same multiple of 64 rows); no floating-point atomics.
+ * IMDBN_E_INVALID (naming the value): M < 1, K < 1, betas[0] != 0, betas[K] != 1, betas not increasing, null betas / rng / logw;
+ * IMDBN_E_UNSUPPORTED: softmax groups.  Nothing is launched and logw is untouched on any error.
+ * Workspace: imdbn_ws_bytes(V, H, M).  The caller's parameters are only read. */
+int imdbn_rbm_ais(const imdbn_rbm_desc* d, int M, int K, const float* betas, const float* base_vis_bias, imdbn_rng* rng,
+                  double* logw, float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- K2: p(v|h)   replaces RBM.visible_probs / backward (rbm.py:94-116,137-151) -------- */
 /* out_prob[B][V] = sigmoid((h W^T + b)/T) with softmax over each group; if logits_only: raw logits */
 int imdbn_rbm_prop_down(const imdbn_rbm_desc* d, const float* h, int64_t ldh, int B, float T,

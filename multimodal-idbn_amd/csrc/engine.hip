@@ -28,6 +28,7 @@
 #include "kernels_knn.hpp"
 #include "kernels_energy.hpp"
 #include "kernels_metrics.hpp"
+#include "kernels_ais.hpp"
 
 using namespace imdbn;
 
@@ -604,6 +605,69 @@ int imdbn_rbm_free_energy(const imdbn_rbm_desc* d, const float* v, int64_t ldv, 
     hipLaunchKernelGGL(free_energy_rows, dim3(B), dim3(256), 0, c.s, v, ldv, d->vis_bias, d->V, c.L.f_h, (int64_t)d->H, d->H, out_F);
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+// Annealed importance sampling: M chains from the base-rate model (W = 0, visible biases b_A) to the RBM through the
+// caller's temperatures.  Per temperature: the up propagation's raw logits, ais_weight_sample_h (weight increment, h, effective
+// visible bias), and -- but for the last -- the down propagation at T = 1 / beta_k that samples the next visible state.
+// State buffers are scratch that only the softmax-group kernels use otherwise: logits in f_h, the effective bias in f_vp, the
+// fp32 state in f_v[0] (or the caller's out_v) -- imdbn_ws_bytes(V, H, M) covers the call.
+int imdbn_rbm_ais(const imdbn_rbm_desc* d, int M, int K, const float* betas, const float* base_vis_bias, imdbn_rng* rng, double* logw,
+                  float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(check_desc(d, false));
+    if (d->n_groups > 0) return fail(IMDBN_E_UNSUPPORTED, "ais: softmax groups are not supported (n_groups = %d)", d->n_groups);
+    if (M < 1) return fail(IMDBN_E_INVALID, "ais: M = %d chains", M);
+    if (K < 1) return fail(IMDBN_E_INVALID, "ais: K = %d temperatures", K);
+    if (!betas || !rng || !logw) return fail(IMDBN_E_INVALID, "ais: null %s", !betas ? "betas" : (!rng ? "rng" : "logw"));
+    if (out_v && ldo < d->V) return fail(IMDBN_E_INVALID, "ais: ldo %lld < V %d", (long long)ldo, d->V);
+    if (betas[0] != 0.0f) return fail(IMDBN_E_INVALID, "ais: betas[0] = %g, must be 0", (double)betas[0]);
+    if (betas[K] != 1.0f) return fail(IMDBN_E_INVALID, "ais: betas[%d] = %g, must be 1", K, (double)betas[K]);
+    for (int k = 1; k <= K; ++k)
+        if (!(betas[k] > betas[k - 1])) return fail(IMDBN_E_INVALID, "ais: betas[%d] = %g is not above betas[%d] = %g", k, (double)betas[k], k - 1, (double)betas[k - 1]);
+    imdbn_rbm_desc dl = *d;                // local copy: the down half reads the step's effective visible bias through it
+    Ctx c(&dl, rng, S(stream));
+    CHK(setup(c, M, ws, ws_bytes));
+    const Layout& L = c.L;
+    if (base_vis_bias) dl.vis_bias = L.f_vp;
+    AisArgs a;
+    memset(&a, 0, sizeof(a));
+    a.M = M; a.Bp = L.Bp; a.V = L.V; a.H = L.H; a.Vpad = L.Vpad; a.Hpad = L.Hpad;
+    a.vis_bias = d->vis_bias; a.base_bias = base_vis_bias; a.eff_bias = L.f_vp;
+    a.state = out_v ? out_v : L.f_v[0]; a.lds = out_v ? ldo : L.V;
+    a.x = L.f_h; a.ldx = L.H; a.logw = logw;
+    const dim3 grid(L.Bp / AIS_ROWS), block(64 * AIS_ROWS);
+    {   // v_1 from the base-rate model
+        AisArgs i = a;
+        i.uni = c.rng.floats(M, L.V); i.rm = L.vis_rm[0];
+        hipLaunchKernelGGL(ais_init_v, grid, block, 0, c.s, i);
+        HIPCHK(hipGetLastError());
+    }
+    for (int k = 1; k <= K; ++k) {
+        const bool last = k == K;
+        {   // x = c + v_k W
+            FinishArgs f = new_finish();
+            f.logits_only = 1;
+            f.out_prob = L.f_h; f.ld_prob = L.H;
+            CHK(prop(c, true, OpIn{L.vis_rm[0], 1, nullptr}, f));
+        }
+        AisArgs w = a;
+        w.beta_prev = betas[k - 1]; w.beta = betas[k]; w.sample = last ? 0 : 1;
+        if (!last) {
+            w.uni = c.rng.floats(M, L.H); w.rm = L.hid_rm; w.bits = L.hid_bits;
+            w.eff_scale = (1.0f - betas[k]) / betas[k];
+        }
+        hipLaunchKernelGGL(ais_weight_sample_h, grid, block, 0, c.s, w);
+        HIPCHK(hipGetLastError());
+        if (last) break;
+        c.hid_bits_ok = true;              // hid_bits describes hid_rm: the down half may read the bit plane
+        FinishArgs f = new_finish();       // v_{k+1} = 1[sigmoid(beta_k (b + h W^T) + (1 - beta_k) b_A) > U]
+        f.T = 1.0f / betas[k];
+        f.vmode = 1; f.uni = c.rng.floats(M, L.V);
+        f.out_final = a.state; f.ld_final = a.lds;
+        f.op.rm = L.vis_rm[0]; f.op.rm_terms = 1; f.rm_src = 2;
+        CHK(prop(c, false, OpIn{L.hid_rm, 1, nullptr}, f));
+    }
+    return c.rng.finish();
 }
 
 int imdbn_rbm_prop_down(const imdbn_rbm_desc* d, const float* h, int64_t ldh, int B, float T, int logits_only,

@@ -317,6 +317,28 @@ class HipEngine:
         self._call("imdbn_rbm_free_energy", C.byref(d), _ptr(v), v.stride(0), B, _ptr(out), *self._ws_tail(dev, d.V, d.H, B))
         return out
 
+    def ais(self, rbm, betas, n_chains: int, rng, base_vis_bias: Optional[torch.Tensor] = None, return_state: bool = False):
+        """Annealed importance sampling (imdbn_rbm_ais): ``n_chains`` chains from the base-rate model (visible biases
+        ``base_vis_bias``, None = zeros) to ``rbm`` through the temperatures ``betas`` (0 = betas[0] < ... < betas[K] = 1).
+        Returns the log importance weights, a float64 device tensor ``[n_chains]`` (and the final states ``[n_chains, V]`` with
+        ``return_state``); log Z ~= H log 2 + sum softplus(base_vis_bias) + logmeanexp(logw).  No host sync."""
+        d = self._desc(rbm, False)
+        dev = rbm.W.device
+        b = [float(x) for x in (betas.tolist() if hasattr(betas, "tolist") else betas)]
+        K, M = len(b) - 1, int(n_chains)
+        arr = (C.c_float * max(1, len(b)))(*b)
+        bA = _on(base_vis_bias, dev, torch.float32)
+        if bA is not None and bA.numel() != d.V:
+            raise N.EngineError(f"ais: base_vis_bias must have {d.V} elements")
+        logw = torch.empty(max(M, 1), dtype=torch.float64, device=dev)
+        vK = torch.empty(max(M, 1), d.V, device=dev) if return_state else None
+        sched = R.sched_ais(d.V, d.H, max(K, 1))
+        r, keep = self._rng(rng, sched, max(M, 1), dev)
+        self._call("imdbn_rbm_ais", C.byref(d), M, K, arr, _ptr(bA), C.byref(r), _ptr(logw), _ptr(vK), d.V,
+                   *self._ws_tail(dev, d.V, d.H, max(M, 1)))
+        self._done(rng, r, sched)
+        return (logw, vK) if return_state else logw
+
     def prop_down(self, rbm, h, T=1.0, logits_only=False):
         d = self._desc(rbm, False)
         h = _f32c(h)

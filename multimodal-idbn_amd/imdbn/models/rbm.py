@@ -150,6 +150,18 @@ class RBM(nn.Module):
         return self._eng().free_energy(self, self._in(v))
 
     @torch.no_grad()
+    def log_partition(self, **kw) -> dict:
+        """AIS estimate of log Z (``imdbn.utils.likelihood.estimate_log_partition``; binary visibles, no softmax groups)."""
+        from imdbn.utils.likelihood import estimate_log_partition
+        return estimate_log_partition(self, **kw)
+
+    @torch.no_grad()
+    def log_likelihood(self, v: torch.Tensor, log_z) -> torch.Tensor:
+        """log p(v) = -F(v) - log Z per row, float64 ``[B]`` (``imdbn.utils.likelihood.log_likelihood``)."""
+        from imdbn.utils.likelihood import log_likelihood
+        return log_likelihood(self, v, log_z)
+
+    @torch.no_grad()
     def sample_visible(self, v_prob: torch.Tensor) -> torch.Tensor:
         """Bernoulli over all columns, one categorical per softmax group (rbm.py:125-135)."""
         return self._eng().sample_visible(self, self._in(v_prob), self._rng(v_prob.size(0)))

@@ -6,6 +6,7 @@ from . import conditional_steps
 from . import imdbn_logging
 from . import bimodal_logging
 from . import cross_eval
+from . import likelihood
 
 __all__ = ["batches", "rows_on_device", "rbm_free_energy", "class_free_energies", "probe_utils", "conditional_steps", "imdbn_logging", "bimodal_logging",
-           "cross_eval"]
+           "cross_eval", "likelihood"]

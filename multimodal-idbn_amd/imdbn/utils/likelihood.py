@@ -1,0 +1,146 @@
+"""Partition function and held-out log-likelihood of a binary RBM by annealed importance sampling, on the engine.
+
+Reconstruction error and free energy do not say whether an RBM improves as a density model: log p(v) = -F(v) - log Z needs the
+partition function.  ``estimate_log_partition`` estimates log Z with AIS (Salakhutdinov & Murray 2008, "On the quantitative
+analysis of deep belief networks"): ``n_chains`` chains are annealed from the base-rate model A (no weights, visible biases
+``base_vis_bias``, whose partition function is known: log Z_A = H log 2 + sum_i softplus(b_A,i)) to the RBM through the
+temperatures ``betas``, and log Z ~= log Z_A + logmeanexp(logw).  The whole loop is ONE ``HipEngine.ais`` call
+(imdbn_rbm_ais): per temperature the engine's up propagation, one fused kernel (weight increment in double, hidden
+sample, the step's effective visible bias) and the temperature-scaled sampling down propagation.
+
+Binary visibles without softmax groups only (``ValueError`` otherwise: a softmax group is not a product of Bernoulli units and
+the estimator above does not describe it).
+
+Random draws: ``2 K - 1`` draw tensors per estimate (``imdbn.engine.rng.sched_ais``).  ``seed=None`` consumes the ambient draw
+source; ``seed=int`` runs under a ``PhiloxRng(seed)`` of its own and leaves the caller's draw counter where it was, so estimating
+between epochs does not change training (the rule of ``evaluate_cross_modal``).
+
+Data parallelism: the chains are NOT sharded over ranks -- every rank that calls runs all ``n_chains`` chains and gets the same
+estimate (same seed) or an independent one; sharding the chains is a follow-up.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import torch
+
+from imdbn import engine as _E
+from imdbn.utils.batches import batches, rows_on_device
+
+__all__ = ["base_rate_bias", "linear_betas", "estimate_log_partition", "log_likelihood", "evaluate_log_likelihood"]
+
+
+def _bottom(model):
+    """The RBM whose likelihood is meant: `model` itself, or the bottom layer of an iDBN."""
+    layers = getattr(model, "layers", None)
+    return layers[0] if layers is not None and len(layers) > 0 else model
+
+
+def _check_binary(rbm):
+    if getattr(rbm, "softmax_groups", None):
+        raise ValueError("AIS likelihood needs an RBM with binary visibles and no softmax groups")
+
+
+def _first(batch):
+    return batch[0] if isinstance(batch, (tuple, list)) else batch
+
+
+@torch.no_grad()
+def base_rate_bias(loader_or_tensor, smoothing: float = 0.05, device=None) -> torch.Tensor:
+    """Visible biases of the base-rate model: the log-odds of the smoothed pixel means, log(p / (1 - p)) with
+    p = (mean + smoothing) / (1 + 2 smoothing) (the "base-rate" start of the AIS paper: the closer A is to the data, the lower
+    the variance of the estimate).  A tensor ``[N, ...]`` or a loader of such batches; sums are accumulated on the device."""
+    if isinstance(loader_or_tensor, torch.Tensor):
+        it = [loader_or_tensor]
+    else:
+        it = batches(loader_or_tensor)
+    tot, n = None, 0
+    for b in it:
+        x = _first(b)
+        x = rows_on_device(x, device if device is not None else x.device).double()
+        tot = x.sum(0) if tot is None else tot + x.sum(0)
+        n += x.size(0)
+    if tot is None or n == 0:
+        raise ValueError("base_rate_bias: no rows")
+    p = (tot / n + smoothing) / (1.0 + 2.0 * smoothing)
+    return (torch.log(p) - torch.log1p(-p)).float()
+
+
+def linear_betas(n_betas: int) -> torch.Tensor:
+    """``n_betas`` temperature steps: K + 1 = n_betas + 1 float32 values from 0 to 1, evenly spaced."""
+    K = int(n_betas)
+    if K < 1:
+        raise ValueError("n_betas must be >= 1")
+    b = torch.arange(K + 1, dtype=torch.float64) / K
+    return b.float()
+
+
+@torch.no_grad()
+def estimate_log_partition(rbm, n_chains: int = 256, n_betas: int = 1000, betas=None, base_vis_bias: Optional[torch.Tensor] = None,
+                           seed: Optional[int] = None) -> dict:
+    """AIS estimate of log Z of ``rbm``: ``log_z``, ``log_z_base`` (log Z_A), ``logw`` (float64 device tensor ``[n_chains]``),
+    ``ess`` = (sum w)^2 / sum w^2 (effective sample size) and ``se`` = std(w) / (mean(w) sqrt(M)), the relative standard error of
+    the mean weight = the standard error of log Z to first order; both on weights shifted by their maximum.  ``betas`` overrides
+    the ``n_betas`` evenly spaced temperatures.  One device-to-host copy.  See the module docstring for ``seed``."""
+    _check_binary(rbm)
+    betas = linear_betas(n_betas) if betas is None else betas
+    eng = _E.get_engine(rbm.W.data)
+    M = int(n_chains)
+    if seed is None:
+        logw = eng.ais(rbm, betas, M, _E.get_rng(), base_vis_bias=base_vis_bias)
+    else:
+        logw = eng.ais(rbm, betas, M, _E.PhiloxRng(int(seed), row0=int(getattr(_E.get_rng(), "row0", 0))), base_vis_bias=base_vis_bias)
+    V, H = rbm.W.shape
+    if base_vis_bias is None:                      # zeros: softplus(0) = log 2 per visible unit
+        lzb = logw.new_full((1,), (V + H) * math.log(2.0))
+    else:
+        lzb = H * math.log(2.0) + torch.nn.functional.softplus(base_vis_bias.to(logw.device).double()).sum().reshape(1)
+    mx = logw.max()
+    w = torch.exp(logw - mx)
+    mean = w.mean()
+    log_z = lzb + mx + torch.log(mean)
+    ess = w.sum() ** 2 / (w * w).sum()
+    se = (w.std(unbiased=True) if M > 1 else w.new_zeros(())) / (mean * math.sqrt(M))
+    host = torch.stack([log_z.reshape(()), lzb.reshape(()), ess.reshape(()), se.reshape(())]).cpu().tolist()
+    return {"log_z": host[0], "log_z_base": host[1], "logw": logw, "ess": host[2], "se": host[3]}
+
+
+@torch.no_grad()
+def log_likelihood(rbm, v: torch.Tensor, log_z) -> torch.Tensor:
+    """log p(v) = -F(v) - log Z per row, a float64 tensor ``[B]`` on the device of ``v`` (``rbm.free_energy``; no host sync)."""
+    _check_binary(rbm)
+    return -rbm.free_energy(v).double() - log_z
+
+
+@torch.no_grad()
+def evaluate_log_likelihood(model, loader=None, log_z: Optional[float] = None, max_batches: Optional[int] = None, **ais_kwargs) -> Optional[dict]:
+    """Mean held-out log-likelihood of an ``RBM`` -- or of the BOTTOM layer of an ``iDBN`` -- over ``loader`` (default
+    ``model.val_loader``; None without one): ``mean_ll``, ``sum_ll``, ``n``, ``log_z``, ``se``, ``ess`` (the last two None when
+    ``log_z`` was passed in instead of estimated with ``estimate_log_partition(**ais_kwargs)``).  The sum is accumulated on the
+    device; the host synchronises once, after the last batch.  A ragged last batch is fine; ``max_batches`` stops early.  With a
+    ``wandb_run`` on the model the scalars are logged as ``ll/...``."""
+    rbm = _bottom(model)
+    _check_binary(rbm)
+    loader = loader if loader is not None else getattr(model, "val_loader", None)
+    if loader is None:
+        return None
+    se = ess = None
+    if log_z is None:
+        est = estimate_log_partition(rbm, **ais_kwargs)
+        log_z, se, ess = est["log_z"], est["se"], est["ess"]
+    dev = rbm.W.device
+    tot = torch.zeros((), dtype=torch.float64, device=dev)
+    n = 0
+    for b, batch in enumerate(batches(loader)):
+        if max_batches is not None and b >= int(max_batches):
+            break
+        v = rows_on_device(_first(batch), dev)
+        tot += log_likelihood(rbm, v, log_z).sum()
+        n += v.size(0)
+    s = float(tot)
+    res = {"mean_ll": s / max(1, n), "sum_ll": s, "n": n, "log_z": float(log_z), "se": se, "ess": ess}
+    run = getattr(model, "wandb_run", None)
+    if run:
+        run.log({"ll/" + k: res[k] for k in ("mean_ll", "log_z", "se", "ess") if res[k] is not None})
+    return res
