@@ -221,7 +221,25 @@ int imdbn_rbm_free_energy(const imdbn_rbm_desc* d, const float* v, int64_t ldv, 
 int imdbn_rbm_ais(const imdbn_rbm_desc* d, int M, int K, const float* betas, const float* base_vis_bias, imdbn_rng* rng,
                   double* logw, float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
-/* ---- K2: p(v|h)   replaces RBM.visible_probs / backward (rbm.py:94-116,137-151) -------- */
+/* ---- one directed layer of the DBN lower bound (imdbn/utils/likelihood.py: dbn_sample_values; the same paper, §4) -----------------
+ * For every row of v [M][V] (0/1 or real in [0, 1], row stride ldv), x = hid_bias + v W, sp = softplus in double:
+ *   h = 1[sigmoid(x) > U]                         -> out_h [M][H] fp32 0/1, row stride ldh (the decision of imdbn_rbm_prop_up's sample)
+ *   a = vis_bias + h W^T
+ *   acc[row] += sum_i (v_i a_i - sp(a_i)) + E     log p(v | h) under the directed layer, plus
+ *     IMDBN_BOUND_ENTROPY  E = sum_j (sp(x_j) - x_j sigmoid(x_j))     the entropy of q(h | v)
+ *     IMDBN_BOUND_LOGQ     E = -sum_j (h_j x_j - sp(x_j))             -log q(h | v) of the drawn h
+ *   acc[M] (device, double) is only ADDED to (the caller zeroes it); the two additions are two launches of one stream.
+ * Draws: ("u", H): draws_used = 1.  Every sum runs in an order fixed by (V, H), the logits are those of the propagations, and
+ * Philox is keyed on the row: row i is the same whatever M; no floating-point atomics.
+ * IMDBN_E_INVALID (naming the value): M < 1, unknown mode, null v / rng / acc / out_h, ldv < V, ldh < H; IMDBN_E_UNSUPPORTED:
+ * softmax groups.  Nothing is launched and acc is untouched on any error.
+ * Workspace: imdbn_ws_bytes(V, H, M).  The caller's parameters are only read. */
+#define IMDBN_BOUND_ENTROPY 0
+#define IMDBN_BOUND_LOGQ    1
+int imdbn_rbm_bound_step(const imdbn_rbm_desc* d, const float* v, int64_t ldv, int M, int mode, imdbn_rng* rng,
+                         double* acc, float* out_h, int64_t ldh, void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
+/* ---- K2: p(v|h)  replaces RBM.visible_probs / backward (rbm.py:94-116,137-151) -------- */
 /* out_prob[B][V] = sigmoid((h W^T + b)/T) with softmax over each group; if logits_only: raw logits */
 int imdbn_rbm_prop_down(const imdbn_rbm_desc* d, const float* h, int64_t ldh, int B, float T,
                         int logits_only, float* out_prob, int64_t ldo,

@@ -29,6 +29,7 @@
 #include "kernels_energy.hpp"
 #include "kernels_metrics.hpp"
 #include "kernels_ais.hpp"
+#include "kernels_bound.hpp"
 
 using namespace imdbn;
 
@@ -667,6 +668,50 @@ int imdbn_rbm_ais(const imdbn_rbm_desc* d, int M, int K, const float* betas, con
         f.op.rm = L.vis_rm[0]; f.op.rm_terms = 1; f.rm_src = 2;
         CHK(prop(c, false, OpIn{L.hid_rm, 1, nullptr}, f));
     }
+    return c.rng.finish();
+}
+
+// One directed layer of the DBN lower bound: the up propagation's raw logits, bound_entropy_sample_h (h ~ q(h | v) in
+// the caller's fp32 form and both operand forms, entropy / -log q in double), the down propagation's raw logits from that h, and
+// bound_loglik_rows (log p(v | h) in double).  Scratch as in imdbn_rbm_ais: the up logits in f_h, the down logits in f_v[0].
+int imdbn_rbm_bound_step(const imdbn_rbm_desc* d, const float* v, int64_t ldv, int M, int mode, imdbn_rng* rng, double* acc,
+                         float* out_h, int64_t ldh, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(check_desc(d, false));
+    if (d->n_groups > 0) return fail(IMDBN_E_UNSUPPORTED, "bound_step: softmax groups are not supported (n_groups = %d)", d->n_groups);
+    if (M < 1) return fail(IMDBN_E_INVALID, "bound_step: M = %d rows", M);
+    if (mode != IMDBN_BOUND_ENTROPY && mode != IMDBN_BOUND_LOGQ) return fail(IMDBN_E_INVALID, "bound_step: unknown mode %d", mode);
+    if (!v || !rng || !acc || !out_h) return fail(IMDBN_E_INVALID, "bound_step: null %s", !v ? "v" : (!rng ? "rng" : (!acc ? "acc" : "out_h")));
+    if (ldv < d->V) return fail(IMDBN_E_INVALID, "bound_step: ldv %lld < V %d", (long long)ldv, d->V);
+    if (ldh < d->H) return fail(IMDBN_E_INVALID, "bound_step: ldh %lld < H %d", (long long)ldh, d->H);
+    Ctx c(d, rng, S(stream));
+    CHK(setup(c, M, ws, ws_bytes));
+    const Layout& L = c.L;
+    BoundArgs a;
+    memset(&a, 0, sizeof(a));
+    a.M = M; a.Bp = L.Bp; a.V = L.V; a.H = L.H; a.Hpad = L.Hpad; a.mode = mode;
+    a.x = L.f_h; a.ldx = L.H; a.a = L.f_v[0]; a.lda = L.V; a.v = v; a.ldv = ldv;
+    a.out_h = out_h; a.ldh = ldh; a.rm = L.hid_rm; a.bits = L.hid_bits; a.acc = acc;
+    a.uni = c.rng.floats(M, L.H);
+    if (c.rng.bad) return c.rng.finish();      // a short replay tape is an error like the others: before the first launch
+    CHK(prep(c, v, ldv, d->V, L.vis_rm[0], L.Vpad, nullptr, L.flags));
+    {   // x = c + v W
+        FinishArgs f = new_finish();
+        f.logits_only = 1;
+        f.out_prob = L.f_h; f.ld_prob = L.H;
+        CHK(prop(c, true, OpIn{L.vis_rm[0], c.nw == 1 ? 1 : 0, L.flags}, f));
+    }
+    const dim3 grid(L.Bp / AIS_ROWS), block(64 * AIS_ROWS);
+    hipLaunchKernelGGL(bound_entropy_sample_h, grid, block, 0, c.s, a);
+    HIPCHK(hipGetLastError());
+    c.hid_bits_ok = true;                      // hid_bits describes hid_rm: the down half may read the bit plane
+    {   // a = b + h W^T
+        FinishArgs f = new_finish();
+        f.logits_only = 1;
+        f.out_prob = L.f_v[0]; f.ld_prob = L.V;
+        CHK(prop(c, false, OpIn{L.hid_rm, 1, nullptr}, f));
+    }
+    hipLaunchKernelGGL(bound_loglik_rows, grid, block, 0, c.s, a);
+    HIPCHK(hipGetLastError());
     return c.rng.finish();
 }
 

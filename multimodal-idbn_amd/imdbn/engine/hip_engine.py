@@ -339,6 +339,27 @@ class HipEngine:
         self._done(rng, r, sched)
         return (logw, vK) if return_state else logw
 
+    def bound_step(self, rbm, v, rng, acc: Optional[torch.Tensor] = None, mode: str = "entropy"):
+        """One directed layer of the DBN lower bound (imdbn_rbm_bound_step): draws ``h ~ q(h | v)`` and adds
+        ``log p(v | h)`` plus the entropy of q (``mode="entropy"``) or ``-log q(h | v)`` (``mode="logq"``) to ``acc``, a float64
+        device tensor ``[M]`` (created zeroed when None).  Returns ``(acc, h)``, ``h`` fp32 0/1 ``[M, H]``.  No host sync."""
+        d = self._desc(rbm, False)
+        v = _f32c(v)
+        M, dev = v.size(0), v.device
+        if mode not in ("entropy", "logq"):
+            raise N.EngineError(f"bound_step: mode must be 'entropy' or 'logq', got {mode!r}")
+        if acc is None:
+            acc = torch.zeros(max(M, 1), dtype=torch.float64, device=dev)
+        elif acc.dtype != torch.float64 or acc.device != dev or acc.numel() != M or not acc.is_contiguous():
+            raise N.EngineError(f"bound_step: acc must be a contiguous float64 [{M}] tensor on {dev}")
+        h = torch.empty(max(M, 1), d.H, device=dev)
+        sched = R.sched_bound(d.H)
+        r, keep = self._rng(rng, sched, max(M, 1), dev)
+        self._call("imdbn_rbm_bound_step", C.byref(d), _ptr(v), v.stride(0), M, N.BOUND_LOGQ if mode == "logq" else N.BOUND_ENTROPY,
+                   C.byref(r), _ptr(acc), _ptr(h), h.stride(0), *self._ws_tail(dev, d.V, d.H, max(M, 1)))
+        self._done(rng, r, sched)
+        return acc, h
+
     def prop_down(self, rbm, h, T=1.0, logits_only=False):
         d = self._desc(rbm, False)
         h = _f32c(h)

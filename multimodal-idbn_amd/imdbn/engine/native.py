@@ -13,6 +13,7 @@ MAX_GROUPS = 4
 ABI_VERSION = 4
 PARITY_F32, FAST_BF16 = 0, 1
 RNG_PHILOX, RNG_REPLAY = 0, 1
+BOUND_ENTROPY, BOUND_LOGQ = 0, 1                      # imdbn_rbm_bound_step mode (IMDBN_BOUND_*)
 DATA_UNKNOWN, DATA_BINARY, DATA_REAL = 0, 1, 2      # imdbn_cd_opts.data_binary / next_binary (IMDBN_DATA_*)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -102,6 +103,7 @@ SIGNATURES = {
     "imdbn_rbm_forward": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _INT, _P, _I64, _P, _SZ, _P]),
     "imdbn_rbm_free_energy": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _P, _P, _SZ, _P]),
     "imdbn_rbm_ais": (_INT, [C.POINTER(RbmDesc), _INT, _INT, C.POINTER(_F), _P, C.POINTER(Rng), _P, _P, _I64, _P, _SZ, _P]),
+    "imdbn_rbm_bound_step": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _INT, C.POINTER(Rng), _P, _P, _I64, _P, _SZ, _P]),
     "imdbn_rbm_prop_down": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _F, _INT, _P, _I64, _P, _SZ, _P]),
     "imdbn_rbm_sample_visible": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, C.POINTER(Rng), _P, _I64, _P]),
     "imdbn_rbm_gibbs_step": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _INT, _INT, C.POINTER(Rng), _P, _P, _P, _P, _P, _SZ, _P]),

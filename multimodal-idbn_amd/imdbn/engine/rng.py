@@ -100,3 +100,8 @@ def sched_clamped(V: int, H: int, groups, init_steps, cd_k: int, sample_h: bool,
 def sched_ais(V: int, H: int, K: int) -> Schedule:
     """imdbn_rbm_ais over K temperatures: the initial state, then one (h, v) transition per temperature but the last."""
     return [("u", V)] + (int(K) - 1) * [("u", H), ("u", V)]
+
+
+def sched_bound(H: int) -> Schedule:
+    """imdbn_rbm_bound_step: the one draw of h ~ q(h | v)."""
+    return [("u", int(H))]

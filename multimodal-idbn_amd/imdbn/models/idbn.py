@@ -154,6 +154,13 @@ class iDBN:
             cur = rbm.backward(cur)
         return cur
 
+    @torch.no_grad()
+    def log_likelihood_bound(self, v: torch.Tensor, log_z_top, **kw) -> torch.Tensor:
+        """Variational lower bound on log p(v) of the whole stack per row, float64 ``[B]``
+        (``imdbn.utils.likelihood.dbn_lower_bound``; ``log_z_top`` = log Z of the top RBM)."""
+        from imdbn.utils.likelihood import dbn_lower_bound
+        return dbn_lower_bound(self, v, log_z_top, **kw)
+
     def save_model(self, path: str):
         """idbn.py:370-372: pickle of {"layers", "params"} (live RBM modules)."""
         model_copy = {"layers": self.layers, "params": self.params}

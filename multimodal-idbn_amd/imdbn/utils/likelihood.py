@@ -15,6 +15,17 @@ Random draws: ``2 K - 1`` draw tensors per estimate (``imdbn.engine.rng.sched_ai
 source; ``seed=int`` runs under a ``PhiloxRng(seed)`` of its own and leaves the caller's draw counter where it was, so estimating
 between epochs does not change training (the rule of ``evaluate_cross_modal``).
 
+Stacks: what the project trains is an ``iDBN``, and the RBM likelihood above only speaks about its bottom layer.  The DBN's
+generative model is the top RBM over (h_{L-1}, h_L) with directed layers p(h_{l-1} | h_l) = Bernoulli(sigmoid(b_l + h_l W_l^T))
+below it; with h_l ~ q(h_l | h_{l-1}) = Bernoulli(sigmoid(c_l + h_{l-1} W_l)) drawn bottom-up, one sample's value is
+
+    w = sum_{l < L} [ log p(h_{l-1} | h_l) + E_l ] - F_top(h_{L-1}) - log Z_top
+
+``E_l`` = the entropy of q(h_l | h_{l-1}) (mode ``entropy``: the mean of w is an unbiased estimate of the variational lower bound
+on log p_DBN(v), ``dbn_lower_bound``) or -log q of the drawn h_l (mode ``logq``: E_q[exp w] = p_DBN(v), and the logmeanexp over
+samples approaches log p(v) from below, ``dbn_log_likelihood_is``).  Each directed layer is ONE ``HipEngine.bound_step`` call
+(imdbn_rbm_bound_step; one draw tensor, ``imdbn.engine.rng.sched_bound``); the top layer is ``free_energy``.
+
 Data parallelism: the chains are NOT sharded over ranks -- every rank that calls runs all ``n_chains`` chains and gets the same
 estimate (same seed) or an independent one; sharding the chains is a follow-up.
 """
@@ -28,7 +39,8 @@ import torch
 from imdbn import engine as _E
 from imdbn.utils.batches import batches, rows_on_device
 
-__all__ = ["base_rate_bias", "linear_betas", "estimate_log_partition", "log_likelihood", "evaluate_log_likelihood"]
+__all__ = ["base_rate_bias", "linear_betas", "estimate_log_partition", "log_likelihood", "evaluate_log_likelihood",
+           "dbn_sample_values", "dbn_lower_bound", "dbn_log_likelihood_is", "evaluate_dbn_bound"]
 
 
 def _bottom(model):
@@ -143,4 +155,104 @@ def evaluate_log_likelihood(model, loader=None, log_z: Optional[float] = None, m
     run = getattr(model, "wandb_run", None)
     if run:
         run.log({"ll/" + k: res[k] for k in ("mean_ll", "log_z", "se", "ess") if res[k] is not None})
+    return res
+
+
+# ---- the whole stack: variational lower bound and importance-sampled likelihood of the DBN ---------------------------------------
+def _stack(model):
+    """The RBMs of the stack, bottom first: the layers of an iDBN, or `model` itself as a stack of one."""
+    layers = getattr(model, "layers", None)
+    layers = list(layers) if layers is not None and len(layers) > 0 else [model]
+    for rbm in layers:
+        _check_binary(rbm)
+    return layers
+
+
+def _draws(seed):
+    """The draw source of `seed` (module docstring): the ambient one, or a private PhiloxRng on the caller's row offset."""
+    return _E.get_rng() if seed is None else _E.PhiloxRng(int(seed), row0=int(getattr(_E.get_rng(), "row0", 0)))
+
+
+def _sample_values(layers, v, log_z_top, n_samples, mode, rng) -> torch.Tensor:
+    if mode not in ("entropy", "logq"):
+        raise ValueError("mode must be 'entropy' or 'logq'")
+    S = int(n_samples)
+    if S < 1:
+        raise ValueError("n_samples must be >= 1")
+    top = layers[-1]
+    cur = rows_on_device(v, top.W.device)
+    B = cur.size(0)
+    if S > 1:
+        cur = cur.repeat_interleave(S, 0)
+    acc = None
+    for rbm in layers[:-1]:
+        acc, cur = _E.get_engine(rbm.W.data).bound_step(rbm, cur, rng, acc=acc, mode=mode)
+    w = -top.free_energy(cur).double() - log_z_top
+    if acc is not None:
+        w = acc + w
+    return w.view(B, S)
+
+
+@torch.no_grad()
+def dbn_sample_values(model, v: torch.Tensor, log_z_top, n_samples: int = 1, mode: str = "entropy", seed: Optional[int] = None) -> torch.Tensor:
+    """``w`` of the module docstring for ``n_samples`` draws of the hidden states per row of ``v``: float64 ``[B, n_samples]`` on
+    the device (row b's samples are the engine rows b S .. b S + S - 1 of the replicated batch).  One ``bound_step`` per directed
+    layer, ``free_energy`` on the top RBM, no host sync.  ``model``: an ``iDBN`` or an ``RBM`` (a stack of one: no draw, and the
+    value is ``log_likelihood``).  ``log_z_top``: log Z of the TOP RBM (``estimate_log_partition(model.layers[-1])``)."""
+    return _sample_values(_stack(model), v, log_z_top, n_samples, mode, _draws(seed))
+
+
+@torch.no_grad()
+def dbn_lower_bound(model, v: torch.Tensor, log_z_top, n_samples: int = 8, seed: Optional[int] = None) -> torch.Tensor:
+    """Monte-Carlo estimate of the variational lower bound on log p_DBN(v) per row: the mean of ``n_samples`` values in mode
+    ``entropy``; float64 ``[B]``."""
+    return dbn_sample_values(model, v, log_z_top, n_samples, "entropy", seed).mean(1)
+
+
+def _logmeanexp_rows(w: torch.Tensor) -> torch.Tensor:
+    m = w.max(1, keepdim=True).values
+    return (m + torch.log(torch.exp(w - m).mean(1, keepdim=True))).squeeze(1)
+
+
+@torch.no_grad()
+def dbn_log_likelihood_is(model, v: torch.Tensor, log_z_top, n_samples: int = 64, seed: Optional[int] = None) -> torch.Tensor:
+    """Importance-sampled estimate of log p_DBN(v) per row with q as the proposal: the logmeanexp of ``n_samples`` values in mode
+    ``logq`` (in expectation a lower bound that tightens with ``n_samples``); float64 ``[B]``."""
+    return _logmeanexp_rows(dbn_sample_values(model, v, log_z_top, n_samples, "logq", seed))
+
+
+@torch.no_grad()
+def evaluate_dbn_bound(model, loader=None, log_z_top: Optional[float] = None, n_samples: int = 8, max_batches: Optional[int] = None,
+                       importance: bool = False, **ais_kwargs) -> Optional[dict]:
+    """Mean held-out ``dbn_lower_bound`` (``importance=True``: ``dbn_log_likelihood_is``) of the stack over ``loader`` (default
+    ``model.val_loader``; None without one): ``mean_bound``, ``sum_bound``, ``n``, ``log_z_top``, ``se``, ``ess`` (of the AIS
+    estimate; None when ``log_z_top`` was passed in instead of estimated with ``estimate_log_partition(top_rbm, **ais_kwargs)``)
+    and ``n_samples``.  A ``seed`` among ``ais_kwargs`` also puts the hidden samples of all batches under ONE private draw source,
+    so evaluating between epochs does not change training.  The sum is accumulated on the device; the host synchronises once,
+    after the last batch.  A ragged last batch is fine; ``max_batches`` stops early.  With a ``wandb_run`` on the model the
+    scalars are logged as ``ll/dbn_...``."""
+    layers = _stack(model)
+    loader = loader if loader is not None else getattr(model, "val_loader", None)
+    if loader is None:
+        return None
+    se = ess = None
+    if log_z_top is None:
+        est = estimate_log_partition(layers[-1], **ais_kwargs)
+        log_z_top, se, ess = est["log_z"], est["se"], est["ess"]
+    rng = _draws(ais_kwargs.get("seed"))
+    dev = layers[-1].W.device
+    tot = torch.zeros((), dtype=torch.float64, device=dev)
+    n = 0
+    for b, batch in enumerate(batches(loader)):
+        if max_batches is not None and b >= int(max_batches):
+            break
+        v = _first(batch)
+        w = _sample_values(layers, v, log_z_top, n_samples, "logq" if importance else "entropy", rng)
+        tot += (_logmeanexp_rows(w) if importance else w.mean(1)).sum()
+        n += v.size(0)
+    s = float(tot)
+    res = {"mean_bound": s / max(1, n), "sum_bound": s, "n": n, "log_z_top": float(log_z_top), "se": se, "ess": ess, "n_samples": int(n_samples)}
+    run = getattr(model, "wandb_run", None)
+    if run:
+        run.log({"ll/dbn_" + k: res[k] for k in ("mean_bound", "log_z_top", "se", "ess", "n_samples") if res[k] is not None})
     return res

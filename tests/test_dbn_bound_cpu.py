@@ -1,0 +1,242 @@
+"""CPU-only: the numpy twin of the DBN bound (tests/bound_oracle.py) against enumeration, the host logic of the dbn_* functions of
+imdbn/utils/likelihood.py on a test double of the engine, the draw schedule and the export's declaration and binding.
+
+Twin against enumeration, stacks 10-6-5 and 10-6-5-4 (bound_cases s3 / s4: W ~ N(0, 0.5), biases ~ N(0, 0.5)), 6 rows of 0/1 input:
+ENTROPY with S = 256 samples per row, every row's mean within 3 of its own standard errors of exact_dbn_bound; LOGQ with S = 2048
+samples of the first row, logmeanexp within 3 se of exact_dbn_log_p.  Over the Philox seeds 1..8 the largest errors seen were
+2.81 se (ENTROPY, the worst of the 6 rows; se <= 0.121) and 2.31 se (LOGQ; se <= 0.082, ess >= 138 of 2048): every seed passed on
+both stacks; seed 1 is pinned (bound_cases.TRUTH_SEED).  At W ~ N(0, 1) the LOGQ weights were too heavy-tailed for this
+(ess 5..121, two of 16 runs beyond 3 se), hence the scale."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import ais_oracle as A
+import bound_cases as Cs
+import bound_oracle as B
+from imdbn import engine as E
+from imdbn.engine import native, rng as R
+from imdbn.models import RBM
+from imdbn.utils import likelihood as LK
+from oracle.draws import PhiloxStream
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture()
+def double():
+    eng = B.BoundOracleEngine()
+    E.set_engine_for_testing(eng)
+    yield eng
+    E.set_engine_for_testing(None)
+
+
+def _rbm(W, b, c, groups=None):
+    r = RBM(W.shape[0], W.shape[1], 0.1, 0.0, 0.5, softmax_groups=groups).to("cpu")
+    r.W.data = torch.from_numpy(W.copy())
+    r.vis_bias.data = torch.from_numpy(b.copy())
+    r.hid_bias.data = torch.from_numpy(c.copy())
+    return r
+
+
+class _Stack:
+    """What the dbn_* functions need of an iDBN: layers (+ val_loader, wandb_run)."""
+
+    def __init__(self, layers, **kw):
+        self.layers = [_rbm(*l) for l in layers]
+        self.__dict__.update(kw)
+
+
+_EXACT = {}
+
+
+def _truth(name):
+    """(layers, v, exact log p [B], exact bound [B], exact log Z of the top RBM), computed once."""
+    if name not in _EXACT:
+        L = Cs.stack(name)
+        v = Cs.inputs(Cs.TRUTH["B"], L[0][0].shape[0], Cs.TRUTH["in_seed"], False)
+        _EXACT[name] = (L, v, B.exact_dbn_log_p(L, v), B.exact_dbn_bound(L, v), A.exact_log_z(*L[-1]))
+    return _EXACT[name]
+
+
+# ---- 1. the twin against enumeration ----------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["s3", "s4"])
+def test_exact_bound_is_below_the_exact_log_likelihood(name):
+    L, v, lp, lb, _ = _truth(name)
+    print(f"{name}: log p {lp.round(3)}, bound {lb.round(3)}")
+    assert (lb <= lp).all() and (lp - lb > 1e-3).all() and np.isfinite(lb).all()
+    allv = ((np.arange(1 << 10)[:, None] >> np.arange(10)[None, :]) & 1).astype(np.float32)
+    la, ba = B.exact_dbn_log_p(L, allv), B.exact_dbn_bound(L, allv)
+    assert (ba <= la + 1e-12).all()
+    assert np.exp(la).sum() == pytest.approx(1.0, abs=1e-12)          # the enumerated model is a distribution over the 2^10 states
+
+
+@pytest.mark.parametrize("name", ["s3", "s4"])
+def test_twin_entropy_mean_is_within_three_standard_errors_of_the_exact_bound(name):
+    L, v, _, lb, lz = _truth(name)
+    S = Cs.TRUTH["S_entropy"]
+    w, _, _ = B.dbn_values(L, v, S, "entropy", PhiloxStream(Cs.TRUTH_SEED[name]), lz)
+    mean, se = w.mean(1), w.std(1, ddof=1) / np.sqrt(S)
+    print(f"{name}: errors {((mean - lb) / se).round(2)} se, se {se.round(3)}")
+    assert w.shape == (Cs.TRUTH["B"], S) and (se > 0).all() and (se <= 0.15).all()
+    assert (np.abs(mean - lb) <= 3 * se).all()
+
+
+@pytest.mark.parametrize("name", ["s3", "s4"])
+def test_twin_logq_logmeanexp_is_within_three_standard_errors_of_the_exact_log_likelihood(name):
+    L, v, lp, _, lz = _truth(name)
+    w, _, _ = B.dbn_values(L, v[:1], Cs.TRUTH["S_logq"], "logq", PhiloxStream(Cs.TRUTH_SEED[name]), lz)
+    lme, se, ess = A.weight_stats(w[0])
+    print(f"{name}: log p_hat {lme:.4f}, exact {lp[0]:.4f}, error {(lme - lp[0]) / se:+.2f} se, se {se:.4f}, ess {ess:.0f} of {w.size}")
+    assert 0 < se <= 0.1
+    assert abs(lme - lp[0]) <= 3 * se
+
+
+def test_both_modes_share_the_decisions_and_differ_by_log_q_plus_entropy():
+    """One draw tensor, the same h; acc(logq) - acc(entropy) = -log q(h) - H(q), and the expectation of -log q is H."""
+    c = Cs.parity_case("tiny")
+    a0, h0, m0 = B.bound_step(c["W"], c["b"], c["c"], c["v"], "entropy", PhiloxStream(3))
+    ps = PhiloxStream(3)
+    a1, h1, m1 = B.bound_step(c["W"], c["b"], c["c"], c["v"], "logq", ps)
+    assert ps.log == [("u", (c["M"], c["H"]))] and np.array_equal(h0, h1) and m0 == m1
+    x = (c["v"] @ c["W"] + c["c"]).astype(np.float64)
+    lq = (h0 * x - A.softplus(x)).sum(1)
+    ent = (A.softplus(x) - x * A.sigmoid(x)).sum(1)
+    assert np.allclose(a1 - a0, -lq - ent, rtol=1e-12, atol=1e-12)
+
+
+# ---- 2. host logic of imdbn/utils/likelihood.py on the test double ----------------------------------------------------
+def test_a_stack_of_one_is_log_likelihood_bit_for_bit(double):
+    W, b, c = Cs.stack("s3")[0]
+    r = _rbm(W, b, c)
+    v = torch.from_numpy(Cs.inputs(6, 10, 5, False))
+    E.manual_seed(9)
+    want = LK.log_likelihood(r, v, 3.25)
+    assert torch.equal(LK.dbn_sample_values(r, v, 3.25)[:, 0], want)
+    w = LK.dbn_sample_values(r, v, 3.25, n_samples=3, mode="logq")
+    assert w.shape == (6, 3) and w.dtype == torch.float64 and all(torch.equal(w[:, s], want) for s in range(3))
+    assert torch.equal(LK.dbn_lower_bound(_Stack([(W, b, c)]), v, 3.25, n_samples=1), want)
+    assert E.get_rng().offset == 0                                     # no directed layer: no draw
+
+
+@pytest.mark.parametrize("name,mode", [("s3", "entropy"), ("s4", "logq")])
+def test_sample_values_match_the_twin_row_order_and_seed_rule(double, name, mode):
+    L = Cs.stack(name)
+    m = _Stack(L)
+    v = Cs.inputs(4, 10, 6, False)
+    E.manual_seed(77)
+    E.get_rng().advance(3)
+    got = LK.dbn_sample_values(m, torch.from_numpy(v), 1.5, n_samples=3, mode=mode, seed=5)
+    assert E.get_rng().offset == 3 and E.get_rng().seed == 77          # a seed leaves the ambient counter alone
+    want, _, _ = B.dbn_values(L, v, 3, mode, PhiloxStream(5), 1.5)
+    assert got.dtype == torch.float64 and got.shape == (4, 3)
+    assert np.allclose(got.numpy(), want, rtol=1e-12, atol=1e-5)       # the double's free energy is fp32
+    # repeat_interleave: sample s of row b is engine row 3 b + s, i.e. the flat twin run on the replicated batch
+    flat, _, _ = B.dbn_values(L, np.repeat(v, 3, axis=0), 1, mode, PhiloxStream(5), 1.5)
+    assert np.array_equal(want.reshape(-1), flat[:, 0])
+    # seed=None draws from the ambient source, from where it stands: one draw per directed layer
+    got2 = LK.dbn_sample_values(m, torch.from_numpy(v), 1.5, n_samples=3, mode=mode)
+    assert E.get_rng().offset == 3 + len(L) - 1
+    want2, _, _ = B.dbn_values(L, v, 3, mode, PhiloxStream(77, 3), 1.5)
+    assert np.allclose(got2.numpy(), want2, rtol=1e-12, atol=1e-5)
+    # the reductions
+    lb = LK.dbn_lower_bound(m, torch.from_numpy(v), 1.5, n_samples=3, seed=5)
+    wl, _, _ = B.dbn_values(L, v, 3, "entropy", PhiloxStream(5), 1.5)
+    assert lb.shape == (4,) and np.allclose(lb.numpy(), wl.mean(1), rtol=1e-12, atol=1e-5)
+    li = LK.dbn_log_likelihood_is(m, torch.from_numpy(v), 1.5, n_samples=3, seed=5)
+    wq, _, _ = B.dbn_values(L, v, 3, "logq", PhiloxStream(5), 1.5)
+    assert np.allclose(li.numpy(), [A.logmeanexp(r) for r in wq], rtol=1e-12, atol=1e-5)
+
+
+def test_bad_arguments_raise_value_error(double):
+    L = Cs.stack("s3")
+    v = torch.zeros(2, 10)
+    with pytest.raises(ValueError):
+        LK.dbn_sample_values(_Stack(L), v, 0.0, mode="mean")
+    with pytest.raises(ValueError):
+        LK.dbn_sample_values(_Stack(L), v, 0.0, n_samples=0)
+    grouped = _Stack(L)
+    grouped.layers[1] = _rbm(*L[1], groups=[(2, 6)])                  # softmax groups anywhere in the stack
+    for fn in (LK.dbn_sample_values, LK.dbn_lower_bound, LK.dbn_log_likelihood_is):
+        with pytest.raises(ValueError):
+            fn(grouped, v, 0.0)
+    with pytest.raises(ValueError):
+        LK.evaluate_dbn_bound(grouped, loader=[v], log_z_top=0.0)
+
+
+class _Run:
+    def __init__(self): self.logged = []
+    def log(self, d): self.logged.append(dict(d))
+
+
+@pytest.mark.parametrize("importance", [False, True])
+def test_evaluate_over_a_ragged_loader(double, importance):
+    L = Cs.stack("s4")
+    X = torch.from_numpy(Cs.inputs(11, 10, 9, False))
+    loader = torch.utils.data.DataLoader(torch.utils.data.TensorDataset(X, torch.zeros(11)), batch_size=4)      # 4 + 4 + 3 rows
+    m = _Stack(L, val_loader=loader, wandb_run=_Run())
+    E.manual_seed(21)
+    res = LK.evaluate_dbn_bound(m, log_z_top=2.5, n_samples=3, importance=importance)
+    assert E.get_rng().offset == 3 * (len(L) - 1)                      # ambient draws: one per directed layer and batch
+    # the same draws, batch by batch
+    E.manual_seed(21)
+    fn = LK.dbn_log_likelihood_is if importance else LK.dbn_lower_bound
+    parts = torch.cat([fn(m, X[s:s + 4], 2.5, n_samples=3) for s in (0, 4, 8)])
+    assert res["n"] == 11 and res["log_z_top"] == 2.5 and res["se"] is None and res["ess"] is None and res["n_samples"] == 3
+    assert res["sum_bound"] == pytest.approx(float(parts.sum()), rel=1e-12) and res["mean_bound"] == pytest.approx(float(parts.mean()), rel=1e-12)
+    assert m.wandb_run.logged == [{"ll/dbn_mean_bound": res["mean_bound"], "ll/dbn_log_z_top": 2.5, "ll/dbn_n_samples": 3}]
+    assert LK.evaluate_dbn_bound(m, log_z_top=2.5, n_samples=2, max_batches=2)["n"] == 8
+    m.val_loader = None
+    assert LK.evaluate_dbn_bound(m, log_z_top=2.5) is None             # no loader anywhere
+    # log Z of the TOP RBM estimated under a private seed, which also carries the samples: the ambient counter stays
+    m.val_loader, m.wandb_run = loader, _Run()
+    E.manual_seed(5)
+    res = LK.evaluate_dbn_bound(m, n_samples=2, importance=importance, n_chains=8, n_betas=5, seed=3)
+    est = LK.estimate_log_partition(m.layers[-1], n_chains=8, n_betas=5, seed=3)
+    assert E.get_rng().offset == 0
+    assert res["log_z_top"] == est["log_z"] and res["se"] == est["se"] and res["ess"] == est["ess"]
+    assert set(m.wandb_run.logged[0]) == {"ll/dbn_mean_bound", "ll/dbn_log_z_top", "ll/dbn_se", "ll/dbn_ess", "ll/dbn_n_samples"}
+
+
+def test_idbn_method_is_the_lower_bound(double):
+    from imdbn.models.idbn import iDBN
+    L = Cs.stack("s3")
+    m = iDBN.__new__(iDBN)                                             # the method needs the layers only
+    m.layers = [_rbm(*l) for l in L]
+    v = torch.from_numpy(Cs.inputs(3, 10, 2, False))
+    got = m.log_likelihood_bound(v, 0.75, n_samples=4, seed=2)
+    assert torch.equal(got, LK.dbn_lower_bound(m, v, 0.75, n_samples=4, seed=2)) and got.shape == (3,)
+
+
+def test_existing_entry_points_keep_their_behaviour(double):
+    """evaluate_log_likelihood still speaks about the bottom layer, and the new names are exported."""
+    L = Cs.stack("s3")
+    X = torch.from_numpy(Cs.inputs(5, 10, 4, False))
+    m = _Stack(L, val_loader=[X])
+    res = LK.evaluate_log_likelihood(m, log_z=1.0)
+    assert res["mean_ll"] == pytest.approx(float(LK.log_likelihood(m.layers[0], X, 1.0).mean()), rel=1e-12)
+    assert {"dbn_sample_values", "dbn_lower_bound", "dbn_log_likelihood_is", "evaluate_dbn_bound"} <= set(LK.__all__)
+
+
+# ---- 3. draws and ABI -------------------------------------------------------------------------------------------------
+def test_schedule_is_what_the_double_consumed(double):
+    c = Cs.parity_case("tiny")
+    r = _rbm(c["W"], c["b"], c["c"])
+    rng = E.PhiloxRng(5)
+    acc, h = double.bound_step(r, torch.from_numpy(c["v"]), rng)
+    assert double.last_log == R.sched_bound(c["H"]) == [("u", c["H"])] and rng.offset == 1
+    assert acc.dtype == torch.float64 and acc.shape == (c["M"],) and h.shape == (c["M"], c["H"])
+    acc2, _ = double.bound_step(r, torch.from_numpy(c["v"]), E.PhiloxRng(5), acc=acc.clone())
+    assert torch.equal(acc2, 2 * acc)                                  # the call adds
+
+
+def test_export_is_declared_bound_and_present():
+    src = open(os.path.join(ROOT, "include", "imdbn_engine.h")).read()
+    assert re.search(r"\bint\s+imdbn_rbm_bound_step\s*\(", src) and "#define IMDBN_ABI_VERSION 4" in src
+    assert re.search(r"#define\s+IMDBN_BOUND_ENTROPY\s+0\b", src) and re.search(r"#define\s+IMDBN_BOUND_LOGQ\s+1\b", src)
+    assert (native.BOUND_ENTROPY, native.BOUND_LOGQ) == (0, 1)
+    res, args = native.SIGNATURES["imdbn_rbm_bound_step"]
+    assert len(args) == 12            # (test_abi_cpu.py holds the library to every declared symbol)
