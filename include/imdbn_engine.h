@@ -180,6 +180,17 @@ int    imdbn_debug_stamps(long long* out, int n);
 /* test / tuning aid: byte offset of a named internal buffer inside the workspace of an (V, H, B) call ("vis_bits0/1", "hid_bits",
  * "vis_tr0/1", "hid_tr0/1", "cs_hpos/hneg/vpos/vneg", "flags", "partial", "vis_rm1"); the layout is NOT part of the ABI */
 int    imdbn_debug_ws_offset(int V, int H, int B, const char* name, size_t* offset);
+/* test aid: which kernel family the last up (v -> h) and the last down (h -> v) propagation of the CALLING THREAD launched,
+ * recorded by the launchers where they launch (host code only; the routes themselves are NOT part of the ABI).
+ * route[0] = up family (IMDBN_ROUTE_UP_*), route[1] = 1 if that launch ran the general epilogue, 0 the lean one;
+ * route[2] = down family (IMDBN_ROUTE_DOWN_*), route[3] = its epilogue likewise, route[4] = 1 if the softmax-group kernel
+ * (finish_groups) followed it.  A family is -1 until the thread has run such a propagation.  The row-parallel chain kernel,
+ * the CD update kernel and every call that runs no propagation leave the record as it was. */
+enum { IMDBN_ROUTE_UP_FUSED = 0, IMDBN_ROUTE_UP_STREAM_BITS = 1, IMDBN_ROUTE_UP_STREAM_REAL = 2, IMDBN_ROUTE_UP_PARTIAL4 = 3,
+       IMDBN_ROUTE_UP_PARTIAL = 4 };
+enum { IMDBN_ROUTE_DOWN_K2_STREAM = 0, IMDBN_ROUTE_DOWN_FUSED = 1, IMDBN_ROUTE_DOWN_CHUNKS2 = 2, IMDBN_ROUTE_DOWN_CHUNKS4 = 3,
+       IMDBN_ROUTE_DOWN_TILED = 4 };
+int    imdbn_debug_last_route(int route[5]);
 
 /* *dev_offset += n on `stream` (see imdbn_rng.dev_offset).  Every engine call is a plain sequence of kernel launches on the caller's
  * stream -- no host synchronisation, no allocation, no memcpy -- so it can be recorded with hipStreamBeginCapture. */

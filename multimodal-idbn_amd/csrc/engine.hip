@@ -533,6 +533,12 @@ int imdbn_debug_ws_offset(int V, int H, int B, const char* name, size_t* offset)
     return 0;
 }
 
+int imdbn_debug_last_route(int route[5]) {
+    if (!route) return fail(IMDBN_E_INVALID, "imdbn_debug_last_route: null buffer");
+    route[0] = t_route.up; route[1] = t_route.up_general; route[2] = t_route.down; route[3] = t_route.down_general; route[4] = t_route.down_groups;
+    return 0;
+}
+
 int imdbn_profile_read(double* total_ms, int* launches) {
     double tot = 0.0;
     for (size_t i = 0; i + 1 < g_prof.used; i += 2) {

@@ -51,6 +51,13 @@ int kernel_attrs_ready() {
     return 0;
 }
 
+// ---- testing aid: which family the last up / the last down propagation of this THREAD launched (imdbn_debug_last_route).  Written by
+// the launchers, each where it launches, never derived again elsewhere; the codes are IMDBN_ROUTE_* of the header
+struct RouteRec { int up = -1, up_general = 0, down = -1, down_general = 0, down_groups = 0; };
+thread_local RouteRec t_route;
+inline void ran_up(int family, bool general) { t_route.up = family; t_route.up_general = general; }
+inline void ran_down(int family, bool general) { t_route.down = family; t_route.down_general = general; t_route.down_groups = 0; }
+
 // ---- the epilogue arguments every propagation shares ---------------------------------------------
 FinishArgs new_finish() {
     FinishArgs f;
@@ -100,6 +107,7 @@ int launch_up_fused(Ctx& c, const OpIn& in, FinishArgs f) {
     hipLaunchKernelGGL(c.nw == 3 ? gemm_up_fused<3> : gemm_up_fused<1>, dim3(cdiv(L.H, 32), 1, L.Bp / 64), dim3(256), 0, c.s,
                        c.d->W, c.d->ldw, L.V, L.H, in.rm, (int64_t)L.Bp * L.Vpad, L.Vpad, in.flag, in.terms, f);
     HIPCHK(hipGetLastError());
+    ran_up(IMDBN_ROUTE_UP_FUSED, !f.simple);
     return 0;
 }
 
@@ -146,6 +154,7 @@ int launch_k1_stream(Ctx& c, const OpIn& in, bool bit_plane, FinishArgs f, const
         if (k.nw != c.nw || k.na != na || k.rider != (pr > 0) || k.general != !f.lean) continue;
         hipLaunchKernelGGL(k.fn, dim3(L.k1s_tiles, a.ks + pr, mb), dim3(64 * K1S_WAVES), lds, c.s, a, f, next ? *next : pz);
         HIPCHK(hipGetLastError());
+        ran_up(bit_plane ? IMDBN_ROUTE_UP_STREAM_BITS : IMDBN_ROUTE_UP_STREAM_REAL, k.general);
         return 0;
     }
     return fail(IMDBN_E_INVALID, "internal: no k1_stream for %d weight and %d operand terms", c.nw, na);
@@ -157,7 +166,8 @@ int launch_up_partial(Ctx& c, const OpIn& in, FinishArgs f) {
     const imdbn_rbm_desc* d = c.d;
     const int mb = L.Bp / 64;
     const int64_t ats = (int64_t)L.Bp * L.Vpad;
-    if (L.up4 && c.r.vec4)
+    const bool four = L.up4 && c.r.vec4;
+    if (four)
         hipLaunchKernelGGL(c.nw == 3 ? gemm_up4_partial<3> : gemm_up4_partial<1>, dim3(cdiv(L.H, 128), L.up.ks, mb), dim3(256), 0, c.s,
                            d->W, d->ldw, L.V, L.H, in.rm, ats, L.Vpad, in.flag, in.terms, L.partial, L.Bp, L.up.kchunk, g_dbg >> 4);
     else
@@ -170,6 +180,7 @@ int launch_up_partial(Ctx& c, const OpIn& in, FinishArgs f) {
     hid_bits_out(c, f, 0, 0);
     hipLaunchKernelGGL(finish, fgrid, dim3(256), 0, c.s, f);
     HIPCHK(hipGetLastError());
+    ran_up(four ? IMDBN_ROUTE_UP_PARTIAL4 : IMDBN_ROUTE_UP_PARTIAL, !f.simple);
     return 0;
 }
 
@@ -193,6 +204,7 @@ int launch_k2_stream(Ctx& c, const uint8_t* hbits, FinishArgs& f, const PrepArgs
     if (lds > 160 * 1024 || MT > 3) return fail(IMDBN_E_UNSUPPORTED, "internal: k2_stream LDS");
     hipLaunchKernelGGL(k2s_insts[c.nw == 3][MT - 1][!f.lean], dim3(blocks, 1, mb), dim3(64 * K2S_W), lds, c.s, a, f);
     HIPCHK(hipGetLastError());
+    ran_down(IMDBN_ROUTE_DOWN_K2_STREAM, !f.lean);
     return 0;
 }
 
@@ -225,6 +237,7 @@ int launch_down_tiled(Ctx& c, const OpIn& in, const DownPlan& p, FinishArgs& f, 
     hipLaunchKernelGGL(c.nw == 3 ? gemm_down_tiled<3> : gemm_down_tiled<1>, gt, dim3(256), 0, c.s, c.d->W, c.d->ldw, L.H, L.V,
                        in.rm, (int64_t)L.Bp * L.Hpad, L.Hpad, in.flag, in.terms, f);
     HIPCHK(hipGetLastError());
+    ran_down(IMDBN_ROUTE_DOWN_TILED, !f.simple);
     return 0;
 }
 
@@ -256,6 +269,7 @@ int launch_down_fused(Ctx& c, const OpIn& in, const uint8_t* hbits, const DownPl
                            in.flag, in.terms, f, p.tr, hbits, L.ldbits);
     }
     HIPCHK(hipGetLastError());
+    ran_down(p.mbb == 4 ? IMDBN_ROUTE_DOWN_CHUNKS4 : (p.mbb == 2 ? IMDBN_ROUTE_DOWN_CHUNKS2 : IMDBN_ROUTE_DOWN_FUSED), !f.simple);
     return 0;
 }
 
@@ -290,6 +304,7 @@ int prop(Ctx& c, bool up, OpIn in, FinishArgs f, const PrepArgs* next = nullptr)
     if (groups) {
         hipLaunchKernelGGL(finish_groups, dim3(f.n_groups, L.Bp / 64), dim3(256), 0, c.s, f, (int)(blocks * (L.Bp / 64)));
         HIPCHK(hipGetLastError());
+        t_route.down_groups = 1;
     }
     return 0;
 }

@@ -126,6 +126,16 @@ class HipEngine:
         ws = self._workspace(torch.device(dev), V, H, B)
         return ws[off.value:off.value + nbytes]
 
+    def last_route(self) -> dict:
+        """Test aid: the kernel family the last up and the last down propagation of this thread launched, as the launchers
+        recorded it (imdbn_debug_last_route): ``{"up": name or None, "up_epilogue": "lean" | "general", "down": name or None,
+        "down_epilogue": ..., "finish_groups": bool}``; the names are ``native.ROUTE_UP`` / ``native.ROUTE_DOWN``."""
+        r = (C.c_int * 5)()
+        self._call("imdbn_debug_last_route", r)
+        return {"up": N.ROUTE_UP[r[0]] if r[0] >= 0 else None, "up_epilogue": "general" if r[1] else "lean",
+                "down": N.ROUTE_DOWN[r[2]] if r[2] >= 0 else None, "down_epilogue": "general" if r[3] else "lean",
+                "finish_groups": bool(r[4])}
+
     def _workspace(self, dev, V, H, B):
         # one workspace per (device, shape, STREAM): two same-shape RBMs driven from two streams must not share scratch
         key = (dev, V, H, B, torch.cuda.current_stream(dev).cuda_stream if torch.device(dev).type == "cuda" else 0)

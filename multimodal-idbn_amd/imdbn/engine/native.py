@@ -15,6 +15,8 @@ PARITY_F32, FAST_BF16 = 0, 1
 RNG_PHILOX, RNG_REPLAY = 0, 1
 BOUND_ENTROPY, BOUND_LOGQ = 0, 1                      # imdbn_rbm_bound_step mode (IMDBN_BOUND_*)
 DATA_UNKNOWN, DATA_BINARY, DATA_REAL = 0, 1, 2      # imdbn_cd_opts.data_binary / next_binary (IMDBN_DATA_*)
+ROUTE_UP = ("fused", "stream_bits", "stream_real", "partial4", "partial")                    # imdbn_debug_last_route (IMDBN_ROUTE_UP_*)
+ROUTE_DOWN = ("k2_stream", "down_fused", "down_chunks2", "down_chunks4", "down_tiled")        # ... (IMDBN_ROUTE_DOWN_*)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "lib", "libimdbn_hip.so"))
@@ -98,6 +100,7 @@ SIGNATURES = {
     "imdbn_profile_read": (_INT, [C.POINTER(C.c_double), C.POINTER(_INT)]),
     "imdbn_debug_stamps": (_INT, [C.POINTER(C.c_longlong), _INT]),
     "imdbn_debug_ws_offset": (_INT, [_INT, _INT, _INT, C.c_char_p, C.POINTER(_SZ)]),
+    "imdbn_debug_last_route": (_INT, [C.POINTER(_INT)]),
     "imdbn_rng_advance": (_INT, [_P, C.c_uint64, _P]),
     "imdbn_rbm_prop_up": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _F, C.POINTER(Rng), _P, _I64, _P, _I64, _P, _SZ, _P]),
     "imdbn_rbm_forward": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _INT, _P, _I64, _P, _SZ, _P]),

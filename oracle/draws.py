@@ -23,6 +23,15 @@ from __future__ import annotations
 import numpy as np
 
 
+# Smallest margin seen at a PhiloxStream categorical pick since the last reset (oracle.rbm_oracle.reset_margin clears it together
+# with the Bernoulli margin): the distance between the threshold u * total and the cumulative sums on either side of the pick,
+# relative to the row total.  A pick decided at rounding level (another summation order or another exp in the group's
+# probabilities moves the cumulative sums by ~1e-7 of the total) is a legitimate difference, not a kernel bug; tests that pin a seed
+# ask for a margin above that level.  The lower side of index 0 (cumulative sum exactly 0) and the upper side of the last index
+# (the pick falls through to it anyway) cannot flip and do not count.
+CATEGORICAL_MARGIN = {"min": float("inf")}
+
+
 class DrawStream:
     """Sequential float32 draws from numpy PCG64; order == reference call order."""
 
@@ -180,13 +189,18 @@ class PhiloxStream:
                 tot = np.float32(tot + probs[b, j])
             thr = np.float32(u[b] * tot)
             acc = np.float32(0.0)
+            below = np.float32(0.0)      # cumulative sum just under the pick
             pick = g - 1
             for j in range(g):
                 acc = np.float32(acc + probs[b, j])
-                if acc > thr:
+                if acc > thr or j == g - 1:
                     pick = j
                     break
+                below = acc
             idx[b] = pick
+            sides = ([float(thr) - float(below)] if pick > 0 else []) + ([float(acc) - float(thr)] if pick < g - 1 else [])
+            if sides and tot > 0:
+                CATEGORICAL_MARGIN["min"] = min(CATEGORICAL_MARGIN["min"], min(sides) / float(tot))
         return idx
 
     def uniform_silent(self, shape):

@@ -22,6 +22,8 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .draws import CATEGORICAL_MARGIN      # the same for PhiloxStream.categorical picks (oracle/draws.py); reset together
+
 F32 = np.float32
 
 # Smallest |p - u| seen at a Bernoulli draw since the last reset: an accelerator result that differs from this
@@ -31,6 +33,7 @@ BERNOULLI_MARGIN = {"min": float("inf")}
 
 def reset_margin():
     BERNOULLI_MARGIN["min"] = float("inf")
+    CATEGORICAL_MARGIN["min"] = float("inf")
 
 
 # Near ties: 1[p > u] is discontinuous, and at full size (~10^6 comparisons per update) some |p - u| are

@@ -41,6 +41,31 @@ def test_struct_sizes_match_header_layout():
     assert C.sizeof(native.CdOpts) == 88            # 9 x 4 B + pad + next_data, ld_next, next_slot, data_slot, data_binary, next_binary, fwd_out, ld_fwd
 
 
+def test_last_route_record_starts_empty_and_names_every_family():
+    """imdbn_debug_last_route (host code, a testing aid): a thread that has run no propagation reports no family; the names the
+    binding gives the codes are the launcher families of csrc/host_prop.hpp, in the order of the header's IMDBN_ROUTE_* enums."""
+    import ctypes as C
+    import threading
+    lib = native.lib()
+    assert lib.imdbn_debug_last_route(None) != 0
+    got = []
+
+    def fresh_thread():
+        r = (C.c_int * 5)(7, 7, 7, 7, 7)
+        got.append((lib.imdbn_debug_last_route(r), list(r)))
+    t = threading.Thread(target=fresh_thread); t.start(); t.join()
+    assert got == [(0, [-1, 0, -1, 0, 0])]
+    src = open(os.path.join(ROOT, "include", "imdbn_engine.h")).read()
+    for prefix, names in (("IMDBN_ROUTE_UP_", native.ROUTE_UP), ("IMDBN_ROUTE_DOWN_", native.ROUTE_DOWN)):
+        codes = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(prefix + r"([A-Z0-9_]+) = (\d+)", src)}
+        assert len(codes) == 5 and len(names) == 5
+        for i, name in enumerate(names):
+            assert codes[name.replace("down_", "")] == i, (name, codes)
+    from imdbn.engine.hip_engine import HipEngine
+    t = threading.Thread(target=lambda: got.append(HipEngine().last_route())); t.start(); t.join()
+    assert got[-1] == {"up": None, "up_epilogue": "lean", "down": None, "down_epilogue": "lean", "finish_groups": False}
+
+
 def test_options_handle_is_separate_from_the_process_defaults():
     """imdbn_options: a per-caller copy of the knobs, bound to the calling thread with imdbn_use_options."""
     import ctypes as C

@@ -3,6 +3,8 @@
 for shapes it does not take): conditional_gibbs (mean-field / sampled), conditional_gibbs_annealed,
 noisy_meanfield_annealed with and without the mu-pull, train_epoch_clamped, against the numpy oracle in PHILOX mode.
 Mismatches with a Bernoulli draw decided at rounding level are re-run with other draws (see stress_parity.py).
+The suite's pinned counterpart is tests/test_routes_gpu.py (cases in tests/route_cases.py): wide-layer chains and the clamped update
+on every kernel route with seeds whose margins are checked on the CPU; this tool stays the randomised companion.
     python tools/stress_chains.py [n_cases] [seed]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
