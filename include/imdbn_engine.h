@@ -232,6 +232,32 @@ int imdbn_rbm_free_energy(const imdbn_rbm_desc* d, const float* v, int64_t ldv, 
 int imdbn_rbm_ais(const imdbn_rbm_desc* d, int M, int K, const float* betas, const float* base_vis_bias, imdbn_rng* rng,
                   double* logw, float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- AIS over Bernoulli visibles plus softmax groups (imdbn/utils/likelihood.py: estimate_joint_log_partition) ----
+ * imdbn_rbm_ais for 0 <= n_groups <= IMDBN_MAX_GROUPS: same arguments, same checks (naming the value; logw untouched on any error).
+ * Inside a group the columns of base_vis_bias are the logits of a categorical, so
+ *   log Z_A = H log 2 + sum_{i not in a group} sp(b_A,i) + sum_g logsumexp(b_A[g]).
+ *   v_1: Bernoulli columns as imdbn_rbm_ais; each group one category from softmax(b_A[g]).
+ *   The weight increment is the formula of imdbn_rbm_ais on the one-hot state.
+ *   v_{k+1}: the sampling down propagation at T = 1 / beta_k with the bias b + ((1 - beta_k) / beta_k) b_A; a group is drawn from
+ *   softmax(beta_k (b + h W^T) + (1 - beta_k) b_A).  Every categorical is the draw of the softmax-group kernel of the propagations:
+ *   fp32 softmax, inverse CDF over clamp(p, 1e-8, 1) in column order (PHILOX), or the index on cat_tape (REPLAY).
+ * Draws: ("u", V), ("c", w_g) per group, then K - 1 times ("u", H), ("u", V), ("c", w_g) per group:
+ * draws_used = (K - 1) (2 + G) + 1 + G.  With n_groups = 0 the call is imdbn_rbm_ais bit for bit.
+ * Workspace: imdbn_ws_bytes(V, H, M).  The caller's parameters are only read. */
+int imdbn_rbm_ais_groups(const imdbn_rbm_desc* d, int M, int K, const float* betas, const float* base_vis_bias, imdbn_rng* rng,
+                         double* logw, float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
+/* ---- label side of the joint RBM's log-likelihood (imdbn/utils/likelihood.py: imdbn_sample_values) -------------
+ * d: the joint RBM, labels in the visible columns [Dz, Dz + K).  For every row of z [N][Dz] (fp32, 0/1 or real, row stride ldz), with
+ * base = hid_bias + z W[:Dz] (one up propagation on the first Dz weight rows) and a_k = z . b_z + b_{Dz+k} + sum_j sp(base_j + W[Dz+k][j]):
+ *   out_joint[row] = a_{gt[row]}          = -F([z, e_gt])               (NaN when gt[row] is outside [0, K); nothing is read through it)
+ *   out_marg[row]  = logsumexp_k a_k      = log sum_y exp(-F([z, y]))
+ * both in double (device, [N]), every sum in an order fixed by (Dz, K, H): a row gives the same bits alone and inside a batch.
+ * IMDBN_E_INVALID (naming the value) before the first launch: K outside [2, 256], Dz < 1, Dz + K > V, N < 1, ldz < Dz, a null
+ * pointer.  Workspace: imdbn_ws_bytes(Dz, H, N).  No draws.  The caller's parameters are only read. */
+int imdbn_rbm_label_loglik(const imdbn_rbm_desc* d, const float* z, int64_t ldz, int N, int Dz, int K, const int32_t* gt,
+                           double* out_joint, double* out_marg, void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- one directed layer of the DBN lower bound (imdbn/utils/likelihood.py: dbn_sample_values; the same paper, §4) -----------------
  * For every row of v [M][V] (0/1 or real in [0, 1], row stride ldv), x = hid_bias + v W, sp = softplus in double:
  *   h = 1[sigmoid(x) > U]                         -> out_h [M][H] fp32 0/1, row stride ldh (the decision of imdbn_rbm_prop_up's sample)

@@ -30,6 +30,7 @@
 #include "kernels_metrics.hpp"
 #include "kernels_ais.hpp"
 #include "kernels_bound.hpp"
+#include "kernels_joint.hpp"
 
 using namespace imdbn;
 
@@ -619,10 +620,12 @@ int imdbn_rbm_free_energy(const imdbn_rbm_desc* d, const float* v, int64_t ldv, 
 // visible bias), and -- but for the last -- the down propagation at T = 1 / beta_k that samples the next visible state.
 // State buffers are scratch that only the softmax-group kernels use otherwise: logits in f_h, the effective bias in f_vp, the
 // fp32 state in f_v[0] (or the caller's out_v) -- imdbn_ws_bytes(V, H, M) covers the call.
-int imdbn_rbm_ais(const imdbn_rbm_desc* d, int M, int K, const float* betas, const float* base_vis_bias, imdbn_rng* rng, double* logw,
-                  float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
-    CHK(check_desc(d, false));
-    if (d->n_groups > 0) return fail(IMDBN_E_UNSUPPORTED, "ais: softmax groups are not supported (n_groups = %d)", d->n_groups);
+// (the body of imdbn_rbm_ais and imdbn_rbm_ais_groups, after the descriptor checks of either)
+// With softmax groups: the initial state adds one categorical per group (ais_init_v_groups), and the down propagation
+// hands the group columns to finish_groups, which reads and writes fp32 copies of p(v | h) and of the state: the call names its own
+// targets for them (f_v[1], and the state buffer) because prop()'s defaults are f_vp -- the effective bias here -- and f_v[1].
+static int ais_run(const imdbn_rbm_desc* d, int M, int K, const float* betas, const float* base_vis_bias, imdbn_rng* rng, double* logw,
+                   float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
     if (M < 1) return fail(IMDBN_E_INVALID, "ais: M = %d chains", M);
     if (K < 1) return fail(IMDBN_E_INVALID, "ais: K = %d temperatures", K);
     if (!betas || !rng || !logw) return fail(IMDBN_E_INVALID, "ais: null %s", !betas ? "betas" : (!rng ? "rng" : "logw"));
@@ -635,6 +638,7 @@ int imdbn_rbm_ais(const imdbn_rbm_desc* d, int M, int K, const float* betas, con
     Ctx c(&dl, rng, S(stream));
     CHK(setup(c, M, ws, ws_bytes));
     const Layout& L = c.L;
+    const int G = d->n_groups;
     if (base_vis_bias) dl.vis_bias = L.f_vp;
     AisArgs a;
     memset(&a, 0, sizeof(a));
@@ -646,7 +650,16 @@ int imdbn_rbm_ais(const imdbn_rbm_desc* d, int M, int K, const float* betas, con
     {   // v_1 from the base-rate model
         AisArgs i = a;
         i.uni = c.rng.floats(M, L.V); i.rm = L.vis_rm[0];
-        hipLaunchKernelGGL(ais_init_v, grid, block, 0, c.s, i);
+        if (G > 0) {
+            AisGroupsArgs gi;
+            memset(&gi, 0, sizeof(gi));
+            gi.a = i; gi.n_groups = G;
+            for (int g = 0; g < G; ++g) { gi.gs[g] = d->group_start[g]; gi.ge[g] = d->group_end[g]; }
+            c.rng.cats(M, G, &gi.cat_tape, &gi.cat_uni);
+            hipLaunchKernelGGL(ais_init_v_groups, grid, block, 0, c.s, gi);
+        } else {
+            hipLaunchKernelGGL(ais_init_v, grid, block, 0, c.s, i);
+        }
         HIPCHK(hipGetLastError());
     }
     for (int k = 1; k <= K; ++k) {
@@ -667,14 +680,32 @@ int imdbn_rbm_ais(const imdbn_rbm_desc* d, int M, int K, const float* betas, con
         HIPCHK(hipGetLastError());
         if (last) break;
         c.hid_bits_ok = true;              // hid_bits describes hid_rm: the down half may read the bit plane
-        FinishArgs f = new_finish();       // v_{k+1} = 1[sigmoid(beta_k (b + h W^T) + (1 - beta_k) b_A) > U]
+        FinishArgs f = new_finish();       // v_{k+1} = 1[sigmoid(beta_k (b + h W^T) + (1 - beta_k) b_A) > U]; groups: one category each
         f.T = 1.0f / betas[k];
         f.vmode = 1; f.uni = c.rng.floats(M, L.V);
+        if (G > 0) {
+            c.rng.cats(M, G, &f.cat_tape, &f.cat_uni);
+            f.out_prob = L.f_v[1]; f.ld_prob = L.V;
+        }
         f.out_final = a.state; f.ld_final = a.lds;
         f.op.rm = L.vis_rm[0]; f.op.rm_terms = 1; f.rm_src = 2;
         CHK(prop(c, false, OpIn{L.hid_rm, 1, nullptr}, f));
     }
     return c.rng.finish();
+}
+
+int imdbn_rbm_ais(const imdbn_rbm_desc* d, int M, int K, const float* betas, const float* base_vis_bias, imdbn_rng* rng, double* logw,
+                  float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(check_desc(d, false));
+    if (d->n_groups > 0) return fail(IMDBN_E_UNSUPPORTED, "ais: softmax groups are not supported (n_groups = %d)", d->n_groups);
+    return ais_run(d, M, K, betas, base_vis_bias, rng, logw, out_v, ldo, ws, ws_bytes, stream);
+}
+
+// imdbn_rbm_ais over Bernoulli visibles plus softmax groups; without groups it IS imdbn_rbm_ais, launch for launch.
+int imdbn_rbm_ais_groups(const imdbn_rbm_desc* d, int M, int K, const float* betas, const float* base_vis_bias, imdbn_rng* rng,
+                         double* logw, float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(check_desc(d, false));
+    return ais_run(d, M, K, betas, base_vis_bias, rng, logw, out_v, ldo, ws, ws_bytes, stream);
 }
 
 // One directed layer of the DBN lower bound: the up propagation's raw logits, bound_entropy_sample_h (h ~ q(h | v) in
@@ -1286,6 +1317,38 @@ int imdbn_energy_trace(const imdbn_rbm_desc* d, const float* z, int64_t ldz, int
     const bool wl = sizeof(float) * (size_t)K * d->H <= (size_t)ENERGY_WY_LDS, hl = d->H <= ENERGY_H_LDS;
     if (wl) return hl ? launch_energy<true, true>(a, c.s) : launch_energy<true, false>(a, c.s);
     return hl ? launch_energy<false, true>(a, c.s) : launch_energy<false, false>(a, c.s);
+}
+
+// ---- label side of the joint RBM's log-likelihood (imdbn/utils/likelihood.py; kernels_joint.hpp) ---------------------
+int imdbn_rbm_label_loglik(const imdbn_rbm_desc* d, const float* z, int64_t ldz, int N, int Dz, int K, const int32_t* gt,
+                           double* out_joint, double* out_marg, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(check_desc(d, false));
+    if (K < 2 || K > JOINT_KMAX) return fail(IMDBN_E_INVALID, "label_loglik: K = %d outside [2, %d]", K, JOINT_KMAX);
+    if (Dz < 1 || (int64_t)Dz + K > d->V) return fail(IMDBN_E_INVALID, "label_loglik: Dz = %d, K = %d do not fit V = %d", Dz, K, d->V);
+    if (N < 1) return fail(IMDBN_E_INVALID, "label_loglik: N = %d rows", N);
+    if (ldz < Dz) return fail(IMDBN_E_INVALID, "label_loglik: ldz %lld < Dz %d", (long long)ldz, Dz);
+    if (!z || !gt || !out_joint || !out_marg)
+        return fail(IMDBN_E_INVALID, "label_loglik: null %s", !z ? "z" : (!gt ? "gt" : (!out_joint ? "out_joint" : "out_marg")));
+    // base = z W[:Dz] + c: the logits path of prop_up on the descriptor cut to its first Dz weight rows (as imdbn_energy_trace)
+    imdbn_rbm_desc dz = *d;
+    dz.V = Dz; dz.n_groups = 0;
+    Ctx c(&dz, nullptr, S(stream));
+    CHK(setup(c, N, ws, ws_bytes));
+    CHK(prep(c, z, ldz, Dz, c.L.vis_rm[0], c.L.Vpad, nullptr, c.L.flags));
+    FinishArgs f = new_finish();
+    f.logits_only = 1;
+    f.out_prob = c.L.f_h; f.ld_prob = d->H;
+    CHK(prop(c, true, OpIn{c.L.vis_rm[0], c.nw == 1 ? 1 : 0, c.L.flags}, f));
+    JointArgs a{};
+    a.base = c.L.f_h; a.ldb = d->H;
+    a.z = z; a.ldz = ldz;
+    a.bz = d->vis_bias; a.by = d->vis_bias + Dz;
+    a.Wy = d->W + (int64_t)Dz * d->ldw; a.ldw = d->ldw;
+    a.gt = gt; a.N = N; a.Dz = Dz; a.K = K; a.H = d->H;
+    a.joint = out_joint; a.marg = out_marg;
+    hipLaunchKernelGGL(joint_label_loglik, dim3(c.L.Bp / AIS_ROWS), dim3(64 * AIS_ROWS), 0, c.s, a);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 // ---- cross-modal label metrics (imdbn/utils/cross_eval.py; kernels_metrics.hpp) ---------------------------------------------

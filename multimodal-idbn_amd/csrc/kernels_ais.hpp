@@ -5,6 +5,9 @@
 //                         (both sums in double), h = 1[sigmoid(beta_k x) > U] as the bf16 form AND the bit plane the down propagation
 //                         reads, and the effective visible bias of the transition that follows.  `sample` = 0 is the last
 //                         temperature: the weight only, no draw.
+//   ais_init_v_groups     ais_init_v for a visible layer with softmax groups (imdbn_rbm_ais_groups): the Bernoulli columns
+//                         as ais_init_v draws them, and per row one category per group from softmax(b_A[group]) -- the arithmetic of
+//                         finish_groups: fp32 softmax, clamp(p, 1e-8, 1), inverse CDF in column order -- or from the replay tape.
 //
 // One wave per chain (row), four rows per block, rows dealt up to Bp (the padded rows write zeros into the operand forms and touch
 // nothing else), so M is free.  Lane l of a row's wave takes the elements l, l + 64, ... in ascending order and the 64 lane sums
@@ -58,6 +61,71 @@ __global__ __launch_bounds__(64 * AIS_ROWS) void ais_init_v(const AisArgs a) {
         if (live && i < a.V) {
             const float p = sigmoidf_ref(a.base_bias ? a.base_bias[i] : 0.f);
             one = p > draw_uniform(a.uni, row, i);
+            a.state[(int64_t)row * a.lds + i] = one ? 1.f : 0.f;
+        }
+        ais_store_rm(a.rm, a.Bp, row, i, one);
+    }
+    if (live && lane == 0) a.logw[row] = 0.0;
+}
+
+// ais_init_v + one categorical per softmax group.  Lane 0 of the row's wave walks a group's logits (the same for every row: b_A; a
+// one-time cost of the call, <= 4 groups of <= 256 columns), every lane then learns the picks and writes its columns.
+struct AisGroupsArgs {
+    AisArgs a;
+    int n_groups; int gs[4]; int ge[4];            // only ever indexed with compile-time constants (see FinishArgs)
+    const int32_t* cat_tape; DrawSrc cat_uni;      // categorical source for group g: cat_tape + g*M / draw+g
+};
+
+__device__ __forceinline__ int ais_pick_category(const AisGroupsArgs& g, int q, int s, int e, int row) {
+    const AisArgs& a = g.a;
+    if (g.cat_tape) return g.cat_tape[(int64_t)q * a.M + row];
+    const int wd = e - s;
+    float mx = -INFINITY;
+    for (int j = 0; j < wd; ++j) mx = fmaxf(mx, a.base_bias ? a.base_bias[s + j] : 0.f);
+    float sum = 0.f;
+    for (int j = 0; j < wd; ++j) sum += expf((a.base_bias ? a.base_bias[s + j] : 0.f) - mx);
+    DrawSrc cs = g.cat_uni; cs.draw += q; cs.N = 1;
+    const float thr = draw_uniform(cs, row, 0);
+    float tot = 0.f;
+    int idx = -1;
+    for (int pass = 0; pass < 2; ++pass) {
+        float acc = 0.f;
+        const float target = thr * tot;
+        for (int j = 0; j < wd; ++j) {
+            const float t = expf((a.base_bias ? a.base_bias[s + j] : 0.f) - mx) / sum;
+            acc += fminf(fmaxf(t, 1e-8f), 1.0f);
+            if (pass == 1 && acc > target) { idx = j; break; }
+        }
+        if (pass == 0) tot = acc; else if (idx < 0) idx = wd - 1;
+    }
+    return idx;
+}
+
+__global__ __launch_bounds__(64 * AIS_ROWS) void ais_init_v_groups(const AisGroupsArgs g) {
+    const AisArgs& a = g.a;
+    const int lane = threadIdx.x & 63, row = blockIdx.x * AIS_ROWS + (threadIdx.x >> 6);
+    if (row >= a.Bp) return;
+    const bool live = row < a.M;      // wave-uniform
+    int pick[4] = {-1, -1, -1, -1};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if (q < g.n_groups && live) {
+            int p = 0;
+            if (lane == 0) p = ais_pick_category(g, q, g.gs[q], g.ge[q], row);
+            pick[q] = __shfl(p, 0, 64);
+        }
+    }
+    for (int i = lane; i < a.Vpad; i += 64) {
+        bool one = false;
+        if (live && i < a.V) {
+            bool grp = false;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (q < g.n_groups && i >= g.gs[q] && i < g.ge[q]) { grp = true; one = (i - g.gs[q]) == pick[q]; }
+            if (!grp) {
+                const float p = sigmoidf_ref(a.base_bias ? a.base_bias[i] : 0.f);
+                one = p > draw_uniform(a.uni, row, i);
+            }
             a.state[(int64_t)row * a.lds + i] = one ? 1.f : 0.f;
         }
         ais_store_rm(a.rm, a.Bp, row, i, one);

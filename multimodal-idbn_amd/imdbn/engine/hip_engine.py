@@ -349,6 +349,48 @@ class HipEngine:
         self._done(rng, r, sched)
         return (logw, vK) if return_state else logw
 
+    def ais_groups(self, rbm, betas, n_chains: int, rng, base_vis_bias: Optional[torch.Tensor] = None, return_state: bool = False):
+        """``ais`` for an RBM whose visible layer has softmax groups (imdbn_rbm_ais_groups): inside a group the columns of
+        ``base_vis_bias`` are the logits of a categorical, every state holds exactly one 1 per group, and
+        log Z ~= H log 2 + sum_{i outside groups} softplus(b_A,i) + sum_g logsumexp(b_A[g]) + logmeanexp(logw).  Same returns as
+        ``ais``; without groups it is ``ais`` bit for bit.  No host sync."""
+        d = self._desc(rbm, False)
+        dev = rbm.W.device
+        b = [float(x) for x in (betas.tolist() if hasattr(betas, "tolist") else betas)]
+        K, M = len(b) - 1, int(n_chains)
+        arr = (C.c_float * max(1, len(b)))(*b)
+        bA = _on(base_vis_bias, dev, torch.float32)
+        if bA is not None and bA.numel() != d.V:
+            raise N.EngineError(f"ais_groups: base_vis_bias must have {d.V} elements")
+        logw = torch.empty(max(M, 1), dtype=torch.float64, device=dev)
+        vK = torch.empty(max(M, 1), d.V, device=dev) if return_state else None
+        sched = R.sched_ais_groups(d.V, d.H, self._groups(rbm), max(K, 1))
+        r, keep = self._rng(rng, sched, max(M, 1), dev)
+        self._call("imdbn_rbm_ais_groups", C.byref(d), M, K, arr, _ptr(bA), C.byref(r), _ptr(logw), _ptr(vK), d.V,
+                   *self._ws_tail(dev, d.V, d.H, max(M, 1)))
+        self._done(rng, r, sched)
+        return (logw, vK) if return_state else logw
+
+    def label_loglik(self, rbm, z: torch.Tensor, K: int, gt: torch.Tensor):
+        """Both label-side values of the joint RBM ``rbm`` per row of the code ``z`` ``[N, Dz]`` (imdbn_rbm_label_loglik; the labels
+        sit in the visible columns ``[Dz, Dz + K)``): ``(joint, marg)``, float64 device tensors ``[N]`` with
+        ``joint = -F([z, e_gt])`` (NaN where ``gt`` is outside ``[0, K)``) and ``marg = log sum_y exp(-F([z, y]))``.  One up
+        propagation and one kernel, no host sync."""
+        d = self._desc(rbm, False)
+        if not z.is_cuda or z.dim() != 2:
+            raise N.EngineError("label_loglik needs a HIP tensor z [N, Dz]")
+        z = _f32c(z)
+        n, Dz = z.shape
+        dev = z.device
+        g = _on(gt, dev, torch.int32)
+        if g is None or g.numel() != n:
+            raise N.EngineError("label_loglik: gt must hold one label per row of z")
+        joint = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        marg = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        self._call("imdbn_rbm_label_loglik", C.byref(d), _ptr(z), z.stride(0), n, Dz, int(K), _ptr(g), _ptr(joint), _ptr(marg),
+                   *self._ws_tail(dev, Dz, d.H, max(n, 1)))       # the propagation is (Dz, H, N): its workspace, not (V, H, N)
+        return joint, marg
+
     def bound_step(self, rbm, v, rng, acc: Optional[torch.Tensor] = None, mode: str = "entropy"):
         """One directed layer of the DBN lower bound (imdbn_rbm_bound_step): draws ``h ~ q(h | v)`` and adds
         ``log p(v | h)`` plus the entropy of q (``mode="entropy"``) or ``-log q(h | v)`` (``mode="logq"``) to ``acc``, a float64

@@ -102,6 +102,13 @@ def sched_ais(V: int, H: int, K: int) -> Schedule:
     return [("u", V)] + (int(K) - 1) * [("u", H), ("u", V)]
 
 
+def sched_ais_groups(V: int, H: int, groups: Sequence[Tuple[int, int]], K: int) -> Schedule:
+    """imdbn_rbm_ais_groups over K temperatures: the initial state (Bernoulli columns, then one categorical per softmax group), then
+    one (h, v) transition per temperature but the last: (K - 1) (2 + G) + 1 + G draws for G groups."""
+    sv = sched_sample_visible(V, groups)
+    return sv + (int(K) - 1) * ([("u", H)] + sv)
+
+
 def sched_bound(H: int) -> Schedule:
     """imdbn_rbm_bound_step: the one draw of h ~ q(h | v)."""
     return [("u", int(H))]

@@ -445,6 +445,11 @@ class iMDBN(nn.Module):
     def evaluate(self, loader=None, **kw):
         return _CE.evaluate_cross_modal(self, loader, **kw)
 
+    def log_likelihood_bound(self, img, y, log_z_joint, **kw):
+        """Per-row lower bounds on log p(img, y) and on log p(img) of the binary-z model (imdbn.utils.likelihood.imdbn_lower_bound)."""
+        from imdbn.utils import likelihood as _LK
+        return _LK.imdbn_lower_bound(self, img, y, log_z_joint, **kw)
+
     # ---- persistence (imdbn.py:815-934, SURVEY.md Appendix C) -------------------------------------
     def save_model(self, path: str):
         all_layers = list(self.image_idbn.layers) + [self.joint_rbm]

@@ -26,6 +26,21 @@ on log p_DBN(v), ``dbn_lower_bound``) or -log q of the drawn h_l (mode ``logq``:
 samples approaches log p(v) from below, ``dbn_log_likelihood_is``).  Each directed layer is ONE ``HipEngine.bound_step`` call
 (imdbn_rbm_bound_step; one draw tensor, ``imdbn.engine.rng.sched_bound``); the top layer is ``free_energy``.
 
+The multimodal model: an ``iMDBN`` is an image stack under a joint RBM whose visible layer is ``[z | one-hot label]``, the label a
+softmax group.  Its generative model, in the DBN reading, is that joint RBM over (z, y, h) with ALL L image layers directed below
+it, and z -- the top image layer's hidden state -- is BINARY.  (``train_joint`` feeds the joint RBM real-valued probabilities
+instead; the numbers below are those of the binary-z model, not of that training input.)  One sample's value is
+
+    w_joint = sum_{l <= L} [ log p(h_{l-1} | h_l) + E_l ] - F_joint([z, e_y]) - log Z_joint,      z = h_L ~ q
+    w_image = the same with log sum_y' exp(-F_joint([z, e_y'])) in place of -F_joint([z, e_y]): the label summed out
+
+(``imdbn_sample_values``; ``imdbn_lower_bound`` / ``imdbn_log_likelihood_is`` as for the DBN; ``evaluate_imdbn_bound``).  One
+``bound_step`` per image layer, then ONE ``HipEngine.label_loglik`` call (imdbn_rbm_label_loglik) for both label-side
+values.  ``log Z_joint`` comes from ``estimate_joint_log_partition``: AIS over Bernoulli columns plus softmax groups
+(``HipEngine.ais_groups``, imdbn_rbm_ais_groups; ``imdbn.engine.rng.sched_ais_groups``), whose base-rate model treats the columns
+of ``base_vis_bias`` inside a group as the logits of a categorical (``base_rate_bias_joint``).  The functions of the first two
+paragraphs keep refusing softmax groups.  ``iMDBN_BiModal`` is not covered.
+
 Data parallelism: the chains are NOT sharded over ranks -- every rank that calls runs all ``n_chains`` chains and gets the same
 estimate (same seed) or an independent one; sharding the chains is a follow-up.
 """
@@ -40,7 +55,9 @@ from imdbn import engine as _E
 from imdbn.utils.batches import batches, rows_on_device
 
 __all__ = ["base_rate_bias", "linear_betas", "estimate_log_partition", "log_likelihood", "evaluate_log_likelihood",
-           "dbn_sample_values", "dbn_lower_bound", "dbn_log_likelihood_is", "evaluate_dbn_bound"]
+           "dbn_sample_values", "dbn_lower_bound", "dbn_log_likelihood_is", "evaluate_dbn_bound",
+           "base_rate_bias_joint", "estimate_joint_log_partition", "imdbn_sample_values", "imdbn_lower_bound",
+           "imdbn_log_likelihood_is", "evaluate_imdbn_bound"]
 
 
 def _bottom(model):
@@ -255,4 +272,152 @@ def evaluate_dbn_bound(model, loader=None, log_z_top: Optional[float] = None, n_
     run = getattr(model, "wandb_run", None)
     if run:
         run.log({"ll/dbn_" + k: res[k] for k in ("mean_bound", "log_z_top", "se", "ess", "n_samples") if res[k] is not None})
+    return res
+
+
+# ---- the multimodal model: joint RBM with a softmax group above a directed image stack -------------------------------------------
+def _label_index(y: torch.Tensor) -> torch.Tensor:
+    """Class indices ``[B]`` from a one-hot / score tensor ``[B, K]`` (argmax) or from indices."""
+    return y.argmax(dim=1) if y.dim() == 2 else y
+
+
+@torch.no_grad()
+def base_rate_bias_joint(model, loader=None, smoothing: float = 0.05) -> torch.Tensor:
+    """Visible biases ``[Dz + K]`` of the base-rate model of ``model.joint_rbm``, from the ``(img, y)`` batches of ``loader``
+    (default ``model.dataloader``).  Code columns: the log-odds of the smoothed mean code, as ``base_rate_bias`` gives them for
+    ``model.image_idbn.represent(img)``.  Label columns: the log of the smoothed class frequencies
+    ``(count_k + smoothing n) / (n + K smoothing n)`` -- the logits of the base model's categorical.  Sums on the device."""
+    loader = loader if loader is not None else getattr(model, "dataloader", None)
+    if loader is None:
+        raise ValueError("base_rate_bias_joint: no loader")
+    dev = model.joint_rbm.W.device
+    K = int(model.num_labels)
+    tot, cnt, n = None, torch.zeros(K, dtype=torch.float64, device=dev), 0
+    for img, y in batches(loader):
+        z = model.image_idbn.represent(rows_on_device(img, dev)).double()
+        tot = z.sum(0) if tot is None else tot + z.sum(0)
+        cnt += torch.bincount(_label_index(y.to(dev)).long(), minlength=K)[:K].double()
+        n += z.size(0)
+    if tot is None or n == 0:
+        raise ValueError("base_rate_bias_joint: no rows")
+    p = (tot / n + smoothing) / (1.0 + 2.0 * smoothing)
+    f = (cnt / n + smoothing) / (1.0 + K * smoothing)
+    return torch.cat([torch.log(p) - torch.log1p(-p), torch.log(f)]).float()
+
+
+@torch.no_grad()
+def estimate_joint_log_partition(rbm, n_chains: int = 256, n_betas: int = 1000, betas=None, base_vis_bias: Optional[torch.Tensor] = None,
+                                 seed: Optional[int] = None) -> dict:
+    """``estimate_log_partition`` for an RBM with softmax groups (the joint RBM of an ``iMDBN``): the same dict, from
+    ``HipEngine.ais_groups``, with ``log_z_base`` = H log 2 + sum_{i outside groups} softplus(b_A,i) + sum_g logsumexp(b_A[g])
+    (no ``base_vis_bias``: zeros, i.e. log 2 per Bernoulli column and log(width) per group).  One device-to-host copy."""
+    betas = linear_betas(n_betas) if betas is None else betas
+    eng = _E.get_engine(rbm.W.data)
+    M = int(n_chains)
+    logw = eng.ais_groups(rbm, betas, M, _draws(seed), base_vis_bias=base_vis_bias)
+    V, H = rbm.W.shape
+    groups = [(int(s), int(e)) for s, e in (getattr(rbm, "softmax_groups", None) or [])]
+    bA = logw.new_zeros(V) if base_vis_bias is None else base_vis_bias.to(logw.device).double().reshape(-1)
+    free = torch.ones(V, dtype=torch.bool, device=logw.device)
+    lzb = logw.new_full((1,), H * math.log(2.0))
+    for s, e in groups:
+        free[s:e] = False
+        lzb = lzb + torch.logsumexp(bA[s:e], 0)
+    lzb = lzb + torch.nn.functional.softplus(bA[free]).sum()
+    mx = logw.max()
+    w = torch.exp(logw - mx)
+    mean = w.mean()
+    log_z = lzb + mx + torch.log(mean)
+    ess = w.sum() ** 2 / (w * w).sum()
+    se = (w.std(unbiased=True) if M > 1 else w.new_zeros(())) / (mean * math.sqrt(M))
+    host = torch.stack([log_z.reshape(()), lzb.reshape(()), ess.reshape(()), se.reshape(())]).cpu().tolist()
+    return {"log_z": host[0], "log_z_base": host[1], "logw": logw, "ess": host[2], "se": host[3]}
+
+
+def _imdbn_values(model, img, y, log_z_joint, n_samples, mode, rng):
+    if mode not in ("entropy", "logq"):
+        raise ValueError("mode must be 'entropy' or 'logq'")
+    S = int(n_samples)
+    if S < 1:
+        raise ValueError("n_samples must be >= 1")
+    layers = list(model.image_idbn.layers)
+    for rbm in layers:
+        _check_binary(rbm)
+    jr = model.joint_rbm
+    dev = jr.W.device
+    cur = rows_on_device(img, dev)
+    gt = _label_index(y.to(dev)).to(torch.int32)
+    B = cur.size(0)
+    if S > 1:
+        cur, gt = cur.repeat_interleave(S, 0), gt.repeat_interleave(S, 0)
+    acc = None
+    for rbm in layers:                                    # ALL image layers are directed: the joint RBM sits above the top one
+        acc, cur = _E.get_engine(rbm.W.data).bound_step(rbm, cur, rng, acc=acc, mode=mode)
+    joint, marg = _E.get_engine(jr.W.data).label_loglik(jr, cur, int(model.num_labels), gt)
+    return (acc + joint - log_z_joint).view(B, S), (acc + marg - log_z_joint).view(B, S)
+
+
+@torch.no_grad()
+def imdbn_sample_values(model, img: torch.Tensor, y: torch.Tensor, log_z_joint, n_samples: int = 1, mode: str = "entropy",
+                        seed: Optional[int] = None):
+    """``(joint, marginal)``: ``w_joint`` and ``w_image`` of the module docstring for ``n_samples`` draws of the hidden states per
+    row, float64 ``[B, n_samples]`` on the device (row b's samples are the engine rows b S .. b S + S - 1 of the replicated batch).
+    ``y``: one-hot ``[B, K]`` or class indices ``[B]``; a label outside ``[0, K)`` makes that row's ``joint`` NaN.  One
+    ``bound_step`` per image layer, one ``label_loglik``, no host sync.  The model meant has a BINARY code z (module docstring).
+    ``log_z_joint``: log Z of the joint RBM (``estimate_joint_log_partition(model.joint_rbm)``)."""
+    return _imdbn_values(model, img, y, log_z_joint, n_samples, mode, _draws(seed))
+
+
+@torch.no_grad()
+def imdbn_lower_bound(model, img: torch.Tensor, y: torch.Tensor, log_z_joint, n_samples: int = 8, seed: Optional[int] = None):
+    """Monte-Carlo estimates of the variational lower bounds on log p(img, y) and on log p(img) per row (binary-z model): the means
+    of ``n_samples`` values in mode ``entropy``; ``(joint, image)``, float64 ``[B]`` each."""
+    j, m = imdbn_sample_values(model, img, y, log_z_joint, n_samples, "entropy", seed)
+    return j.mean(1), m.mean(1)
+
+
+@torch.no_grad()
+def imdbn_log_likelihood_is(model, img: torch.Tensor, y: torch.Tensor, log_z_joint, n_samples: int = 64, seed: Optional[int] = None):
+    """Importance-sampled estimates of log p(img, y) and log p(img) per row (binary-z model) with q as the proposal: the logmeanexp
+    of ``n_samples`` values in mode ``logq``; ``(joint, image)``, float64 ``[B]`` each."""
+    j, m = imdbn_sample_values(model, img, y, log_z_joint, n_samples, "logq", seed)
+    return _logmeanexp_rows(j), _logmeanexp_rows(m)
+
+
+@torch.no_grad()
+def evaluate_imdbn_bound(model, loader=None, log_z_joint: Optional[float] = None, n_samples: int = 8, max_batches: Optional[int] = None,
+                         **ais_kwargs) -> Optional[dict]:
+    """Mean held-out ``imdbn_lower_bound`` of an ``iMDBN`` over the ``(img, y)`` batches of ``loader`` (default
+    ``model.val_loader``; None without one): ``mean_joint_bound`` (bound on log p(img, y)), ``mean_image_bound`` (bound on
+    log p(img), the label summed out), ``mean_label_logprob``, ``n``, ``log_z_joint``, ``se``, ``ess`` (of the AIS estimate; None
+    when ``log_z_joint`` was passed in instead of estimated with ``estimate_joint_log_partition(model.joint_rbm, **ais_kwargs)``)
+    and ``n_samples``.  ``mean_label_logprob`` is the mean over rows and samples of ``joint - marginal`` = the exact
+    log p(y | z) of the SAMPLED code z under the joint RBM: a diagnostic, NOT a bound on log p(y | img).  All numbers are those of
+    the binary-z model (module docstring).  A ``seed`` among ``ais_kwargs`` also puts the hidden samples of all batches under ONE
+    private draw source.  Sums are accumulated on the device; the host synchronises once, after the last batch.  A ragged last
+    batch is fine; ``max_batches`` stops early.  With a ``wandb_run`` on the model the scalars are logged as ``ll/imdbn_...``."""
+    loader = loader if loader is not None else getattr(model, "val_loader", None)
+    if loader is None:
+        return None
+    se = ess = None
+    if log_z_joint is None:
+        est = estimate_joint_log_partition(model.joint_rbm, **ais_kwargs)
+        log_z_joint, se, ess = est["log_z"], est["se"], est["ess"]
+    rng = _draws(ais_kwargs.get("seed"))
+    tot = torch.zeros(3, dtype=torch.float64, device=model.joint_rbm.W.device)
+    n = 0
+    for b, (img, y) in enumerate(batches(loader)):
+        if max_batches is not None and b >= int(max_batches):
+            break
+        j, m = _imdbn_values(model, img, y, log_z_joint, n_samples, "entropy", rng)
+        tot += torch.stack([j.mean(1).sum(), m.mean(1).sum(), (j - m).mean(1).sum()])
+        n += j.size(0)
+    t = tot.cpu().tolist()
+    d = max(1, n)
+    res = {"mean_joint_bound": t[0] / d, "mean_image_bound": t[1] / d, "mean_label_logprob": t[2] / d, "n": n,
+           "log_z_joint": float(log_z_joint), "se": se, "ess": ess, "n_samples": int(n_samples)}
+    run = getattr(model, "wandb_run", None)
+    if run:
+        run.log({"ll/imdbn_" + k: res[k] for k in ("mean_joint_bound", "mean_image_bound", "mean_label_logprob", "log_z_joint", "se",
+                                                  "ess", "n_samples") if res[k] is not None})
     return res
