@@ -247,6 +247,31 @@ int imdbn_rbm_ais(const imdbn_rbm_desc* d, int M, int K, const float* betas, con
 int imdbn_rbm_ais_groups(const imdbn_rbm_desc* d, int M, int K, const float* betas, const float* base_vis_bias, imdbn_rng* rng,
                          double* logw, float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- reverse annealed importance sampling (imdbn/utils/likelihood.py: reverse_ais_log_likelihood; Burda, Grosse & Salakhutdinov
+ *      2015) ---------------------------------------------------------------------------------------------------
+ * The forward AIS chain read as a generative model p_ann (v_1 ~ p_A, v_{k+1} ~ T_k(. | v_k) for k = 1..K, T_k the transition of
+ * imdbn_rbm_ais_groups at beta_k, one transition at beta_K = 1 included; the sample is v_{K+1}), run backwards from the start states
+ * v [R][V] (0/1, row stride ldv; the caller replicates a test row once per chain).  With Delta_k the increment of imdbn_rbm_ais:
+ *   logw = sum_i b_i v_i + sum_j sp(x_j(v))                                     (= -F(v))
+ *   for k = K..1:  u_k ~ T_k(. | u_{k+1});  logw -= Delta_k(u_k)                 (u_{K+1} = v)
+ * logw[R] (device, double) is OVERWRITTEN; exp(logw) / Z_A is an unbiased estimate of p_ann(v), log Z_A as imdbn_rbm_ais_groups
+ * defines it (NOT included).  out_v (nullable): the final state u_1 [R][V], row stride ldo >= V.  0 <= n_groups <= IMDBN_MAX_GROUPS.
+ * A row holding an element that is not exactly 0 or 1, or a softmax group without exactly one 1, gets logw = NaN, that row only
+ * (checked on the device).
+ * Draws: K times ("u", H), ("u", V), ("c", w_g) per group: draws_used = K (2 + G).  Sums, logits and the Philox key as in
+ * imdbn_rbm_ais: row i is the same chain whatever R (bit for bit while R stays within the same multiple of 64 rows).
+ * IMDBN_E_INVALID (naming the value): R < 1, K < 1, betas[0] != 0, betas[K] != 1, betas not increasing, null v / betas / rng / logw,
+ * ldv < V, ldo < V.  Nothing is launched and logw is untouched on any error.
+ * Workspace: imdbn_ws_bytes(V, H, R).  The caller's parameters are only read. */
+int imdbn_rbm_reverse_ais(const imdbn_rbm_desc* d, const float* v, int64_t ldv, int R, int K, const float* betas,
+                          const float* base_vis_bias, imdbn_rng* rng, double* logw, float* out_v, int64_t ldo,
+                          void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
+/* Row n owns logw[n M .. n M + M - 1] (device, double): out_lme[n] = log((1 / M) sum_m exp(logw)), out_ess[n] = (sum w)^2 / sum w^2 on
+ * the weights shifted by the row's maximum; both double [N], summed in an order fixed by M.  A NaN makes both outputs of its row NaN
+ * and no other.  IMDBN_E_INVALID: N < 1, M < 1, a null pointer. */
+int imdbn_rows_logmeanexp(const double* logw, int N, int M, double* out_lme, double* out_ess, imdbn_stream_t stream);
+
 /* ---- label side of the joint RBM's log-likelihood (imdbn/utils/likelihood.py: imdbn_sample_values) -------------
  * d: the joint RBM, labels in the visible columns [Dz, Dz + K).  For every row of z [N][Dz] (fp32, 0/1 or real, row stride ldz), with
  * base = hid_bias + z W[:Dz] (one up propagation on the first Dz weight rows) and a_k = z . b_z + b_{Dz+k} + sum_j sp(base_j + W[Dz+k][j]):

@@ -29,6 +29,7 @@
 #include "kernels_energy.hpp"
 #include "kernels_metrics.hpp"
 #include "kernels_ais.hpp"
+#include "kernels_reverse_ais.hpp"
 #include "kernels_bound.hpp"
 #include "kernels_joint.hpp"
 
@@ -706,6 +707,92 @@ int imdbn_rbm_ais_groups(const imdbn_rbm_desc* d, int M, int K, const float* bet
                          double* logw, float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
     CHK(check_desc(d, false));
     return ais_run(d, M, K, betas, base_vis_bias, rng, logw, out_v, ldo, ws, ws_bytes, stream);
+}
+
+// Reverse annealed importance sampling: R chains run the AIS transitions backwards, T_K first, from the caller's start
+// states, and logw collects -F(start) - sum_k Delta_k(u_k).  rais_load_v, then K + 1 times the up propagation's raw logits and
+// rais_weight_sample_h, and between two of those the sampling down propagation of ais_run at the temperature the weight kernel drew
+// h for.  Buffers, the local descriptor and the group targets are those of ais_run.
+int imdbn_rbm_reverse_ais(const imdbn_rbm_desc* d, const float* v, int64_t ldv, int R, int K, const float* betas, const float* base_vis_bias,
+                          imdbn_rng* rng, double* logw, float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(check_desc(d, false));
+    if (R < 1) return fail(IMDBN_E_INVALID, "reverse_ais: R = %d rows", R);
+    if (K < 1) return fail(IMDBN_E_INVALID, "reverse_ais: K = %d temperatures", K);
+    if (!v || !betas || !rng || !logw)
+        return fail(IMDBN_E_INVALID, "reverse_ais: null %s", !v ? "v" : (!betas ? "betas" : (!rng ? "rng" : "logw")));
+    if (ldv < d->V) return fail(IMDBN_E_INVALID, "reverse_ais: ldv %lld < V %d", (long long)ldv, d->V);
+    if (out_v && ldo < d->V) return fail(IMDBN_E_INVALID, "reverse_ais: ldo %lld < V %d", (long long)ldo, d->V);
+    if (betas[0] != 0.0f) return fail(IMDBN_E_INVALID, "reverse_ais: betas[0] = %g, must be 0", (double)betas[0]);
+    if (betas[K] != 1.0f) return fail(IMDBN_E_INVALID, "reverse_ais: betas[%d] = %g, must be 1", K, (double)betas[K]);
+    for (int k = 1; k <= K; ++k)
+        if (!(betas[k] > betas[k - 1]))
+            return fail(IMDBN_E_INVALID, "reverse_ais: betas[%d] = %g is not above betas[%d] = %g", k, (double)betas[k], k - 1, (double)betas[k - 1]);
+    imdbn_rbm_desc dl = *d;                // local copy: the down half reads the step's effective visible bias through it
+    Ctx c(&dl, rng, S(stream));
+    CHK(setup(c, R, ws, ws_bytes));
+    const Layout& L = c.L;
+    const int G = d->n_groups;
+    if (base_vis_bias) dl.vis_bias = L.f_vp;
+    AisArgs a;
+    memset(&a, 0, sizeof(a));
+    a.M = R; a.Bp = L.Bp; a.V = L.V; a.H = L.H; a.Vpad = L.Vpad; a.Hpad = L.Hpad;
+    a.vis_bias = d->vis_bias; a.base_bias = base_vis_bias; a.eff_bias = L.f_vp;
+    a.state = out_v ? out_v : L.f_v[0]; a.lds = out_v ? ldo : L.V;
+    a.x = L.f_h; a.ldx = L.H; a.logw = logw;
+    const dim3 grid(L.Bp / AIS_ROWS), block(64 * AIS_ROWS);
+    {   // u_{K+1} = the caller's rows
+        RaisLoadArgs l;
+        memset(&l, 0, sizeof(l));
+        l.a = a; l.a.rm = L.vis_rm[0];
+        l.v = v; l.ldv = ldv; l.n_groups = G;
+        for (int g = 0; g < G; ++g) { l.gs[g] = d->group_start[g]; l.ge[g] = d->group_end[g]; }
+        hipLaunchKernelGGL(rais_load_v, grid, block, 0, c.s, l);
+        HIPCHK(hipGetLastError());
+    }
+    for (int k = K + 1; k >= 1; --k) {     // k = K + 1: the start state's softplus term; k <= K: -Delta_k(u_k)
+        const bool first = k == K + 1, last = k == 1;
+        const float bd = first ? betas[K] : betas[k - 1];      // temperature of the transition that follows
+        {   // x = c + u_k W
+            FinishArgs f = new_finish();
+            f.logits_only = 1;
+            f.out_prob = L.f_h; f.ld_prob = L.H;
+            CHK(prop(c, true, OpIn{L.vis_rm[0], 1, nullptr}, f));
+        }
+        RaisArgs w;
+        memset(&w, 0, sizeof(w));
+        w.a = a; w.first = first ? 1 : 0; w.beta_draw = bd;
+        if (!first) { w.a.beta_prev = betas[k - 1]; w.a.beta = betas[k]; }
+        w.a.sample = last ? 0 : 1;
+        if (!last) {
+            w.a.uni = c.rng.floats(R, L.H); w.a.rm = L.hid_rm; w.a.bits = L.hid_bits;
+            w.a.eff_scale = (1.0f - bd) / bd;
+        }
+        hipLaunchKernelGGL(rais_weight_sample_h, grid, block, 0, c.s, w);
+        HIPCHK(hipGetLastError());
+        if (last) break;
+        c.hid_bits_ok = true;              // hid_bits describes hid_rm: the down half may read the bit plane
+        FinishArgs f = new_finish();       // u = 1[sigmoid(bd (b + h W^T) + (1 - bd) b_A) > U]; groups: one category each
+        f.T = 1.0f / bd;
+        f.vmode = 1; f.uni = c.rng.floats(R, L.V);
+        if (G > 0) {
+            c.rng.cats(R, G, &f.cat_tape, &f.cat_uni);
+            f.out_prob = L.f_v[1]; f.ld_prob = L.V;
+        }
+        f.out_final = a.state; f.ld_final = a.lds;
+        f.op.rm = L.vis_rm[0]; f.op.rm_terms = 1; f.rm_src = 2;
+        CHK(prop(c, false, OpIn{L.hid_rm, 1, nullptr}, f));
+    }
+    return c.rng.finish();
+}
+
+int imdbn_rows_logmeanexp(const double* logw, int N, int M, double* out_lme, double* out_ess, imdbn_stream_t stream) {
+    if (N < 1) return fail(IMDBN_E_INVALID, "rows_logmeanexp: N = %d rows", N);
+    if (M < 1) return fail(IMDBN_E_INVALID, "rows_logmeanexp: M = %d chains", M);
+    if (!logw || !out_lme || !out_ess)
+        return fail(IMDBN_E_INVALID, "rows_logmeanexp: null %s", !logw ? "logw" : (!out_lme ? "out_lme" : "out_ess"));
+    hipLaunchKernelGGL(rows_logmeanexp, dim3(cdiv(N, AIS_ROWS)), dim3(64 * AIS_ROWS), 0, S(stream), logw, N, M, out_lme, out_ess);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 // One directed layer of the DBN lower bound: the up propagation's raw logits, bound_entropy_sample_h (h ~ q(h | v) in

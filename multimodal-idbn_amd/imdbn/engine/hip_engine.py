@@ -371,6 +371,47 @@ class HipEngine:
         self._done(rng, r, sched)
         return (logw, vK) if return_state else logw
 
+    def reverse_ais(self, rbm, v_rows, betas, rng, base_vis_bias: Optional[torch.Tensor] = None, return_state: bool = False):
+        """Reverse annealed importance sampling (imdbn_rbm_reverse_ais): one chain per row of ``v_rows`` ``[R, V]`` (0/1; the caller
+        replicates a test row once per chain) runs the AIS transitions of ``ais_groups`` backwards through ``betas``, T_K first.
+        Returns the per-chain log weights, a float64 device tensor ``[R]`` (and the final states u_1 ``[R, V]`` with
+        ``return_state``): ``-log Z_A + logmeanexp`` over a test row's chains is a stochastic lower bound on log p_ann(row), log Z_A
+        as ``ais_groups`` states it.  A row that is not 0/1, or whose softmax group does not hold exactly one 1, gets NaN.  RBMs
+        with softmax groups are accepted.  No host sync."""
+        d = self._desc(rbm, False)
+        if not v_rows.is_cuda or v_rows.dim() != 2 or v_rows.size(1) != d.V:
+            raise N.EngineError(f"reverse_ais needs a HIP tensor v_rows [R, {d.V}]")
+        v = _f32c(v_rows)
+        R_, dev = v.size(0), v.device
+        b = [float(x) for x in (betas.tolist() if hasattr(betas, "tolist") else betas)]
+        K = len(b) - 1
+        arr = (C.c_float * max(1, len(b)))(*b)
+        bA = _on(base_vis_bias, dev, torch.float32)
+        if bA is not None and bA.numel() != d.V:
+            raise N.EngineError(f"reverse_ais: base_vis_bias must have {d.V} elements")
+        logw = torch.empty(max(R_, 1), dtype=torch.float64, device=dev)
+        u1 = torch.empty(max(R_, 1), d.V, device=dev) if return_state else None
+        sched = R.sched_reverse_ais(d.V, d.H, self._groups(rbm), max(K, 1))
+        r, keep = self._rng(rng, sched, max(R_, 1), dev)
+        self._call("imdbn_rbm_reverse_ais", C.byref(d), _ptr(v), v.stride(0), R_, K, arr, _ptr(bA), C.byref(r), _ptr(logw), _ptr(u1), d.V,
+                   *self._ws_tail(dev, d.V, d.H, max(R_, 1)))
+        self._done(rng, r, sched)
+        return (logw, u1) if return_state else logw
+
+    def rows_logmeanexp(self, logw: torch.Tensor, n_chains: int):
+        """``(lme, ess)`` per test row of the chain weights ``logw`` (float64, ``N * n_chains`` elements, row n owns the chains
+        ``n * n_chains ...``; imdbn_rows_logmeanexp): float64 device tensors ``[N]``, ``lme = log mean exp`` and
+        ``ess = (sum w)^2 / sum w^2``.  A NaN stays in its row.  No host sync."""
+        M = int(n_chains)
+        if not logw.is_cuda or logw.dtype != torch.float64 or M < 1 or logw.numel() % M != 0:
+            raise N.EngineError(f"rows_logmeanexp needs a float64 HIP tensor of N * {M} elements")
+        x = logw.contiguous()
+        n, dev = x.numel() // M, x.device
+        lme = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        ess = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        self._call("imdbn_rows_logmeanexp", _ptr(x), n, M, _ptr(lme), _ptr(ess), self._stream(dev))
+        return lme, ess
+
     def label_loglik(self, rbm, z: torch.Tensor, K: int, gt: torch.Tensor):
         """Both label-side values of the joint RBM ``rbm`` per row of the code ``z`` ``[N, Dz]`` (imdbn_rbm_label_loglik; the labels
         sit in the visible columns ``[Dz, Dz + K)``): ``(joint, marg)``, float64 device tensors ``[N]`` with

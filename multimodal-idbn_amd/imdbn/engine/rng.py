@@ -109,6 +109,11 @@ def sched_ais_groups(V: int, H: int, groups: Sequence[Tuple[int, int]], K: int) 
     return sv + (int(K) - 1) * ([("u", H)] + sv)
 
 
+def sched_reverse_ais(V: int, H: int, groups: Sequence[Tuple[int, int]], K: int) -> Schedule:
+    """imdbn_rbm_reverse_ais over K temperatures: one (h, v) transition per temperature, T_K first: K (2 + G) draws for G groups."""
+    return int(K) * ([("u", H)] + sched_sample_visible(V, groups))
+
+
 def sched_bound(H: int) -> Schedule:
     """imdbn_rbm_bound_step: the one draw of h ~ q(h | v)."""
     return [("u", int(H))]

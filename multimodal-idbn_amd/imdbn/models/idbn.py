@@ -161,6 +161,12 @@ class iDBN:
         from imdbn.utils.likelihood import dbn_lower_bound
         return dbn_lower_bound(self, v, log_z_top, **kw)
 
+    def log_likelihood_bound_conservative(self, v: torch.Tensor, **kw) -> torch.Tensor:
+        """The stack's lower bound with the reverse-AIS estimate as its top term, float64 ``[B]``
+        (``imdbn.utils.likelihood.dbn_conservative_bound``; no AIS estimate of log Z enters)."""
+        from imdbn.utils.likelihood import dbn_conservative_bound
+        return dbn_conservative_bound(self, v, **kw)
+
     def save_model(self, path: str):
         """idbn.py:370-372: pickle of {"layers", "params"} (live RBM modules)."""
         model_copy = {"layers": self.layers, "params": self.params}

@@ -162,6 +162,13 @@ class RBM(nn.Module):
         return log_likelihood(self, v, log_z)
 
     @torch.no_grad()
+    def log_likelihood_conservative(self, v: torch.Tensor, **kw) -> dict:
+        """Reverse-AIS lower bound on log p(v) per row under the annealing model: ``{"ll", "ess", "logw"}``
+        (``imdbn.utils.likelihood.reverse_ais_log_likelihood``; no AIS estimate of log Z enters)."""
+        from imdbn.utils.likelihood import reverse_ais_log_likelihood
+        return reverse_ais_log_likelihood(self, v, **kw)
+
+    @torch.no_grad()
     def sample_visible(self, v_prob: torch.Tensor) -> torch.Tensor:
         """Bernoulli over all columns, one categorical per softmax group (rbm.py:125-135)."""
         return self._eng().sample_visible(self, self._in(v_prob), self._rng(v_prob.size(0)))

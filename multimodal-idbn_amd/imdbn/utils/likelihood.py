@@ -41,6 +41,15 @@ values.  ``log Z_joint`` comes from ``estimate_joint_log_partition``: AIS over B
 of ``base_vis_bias`` inside a group as the logits of a categorical (``base_rate_bias_joint``).  The functions of the first two
 paragraphs keep refusing softmax groups.  ``iMDBN_BiModal`` is not covered.
 
+The other side of the sandwich: every number above rests on ONE AIS estimate of log Z, and AIS under-estimates Z in expectation, so
+they are optimistic.  Reverse AIS ("RAISE", Burda, Grosse & Salakhutdinov 2015) reads the forward annealing chain as a generative model
+p_ann (v_1 ~ p_A, then one AIS transition per temperature, the one at beta = 1 included), runs it backwards from each held-out row and
+averages importance weights that only need log Z_A: ``reverse_ais_log_likelihood`` is a stochastic LOWER bound on log p_ann(v) -- of
+the annealing model, which approaches the RBM as the ladder grows, not of the RBM itself.  ``n_chains`` chains per row, ONE
+``HipEngine.reverse_ais`` call per chunk of rows (imdbn_rbm_reverse_ais; ``imdbn.engine.rng.sched_reverse_ais``) and one
+``HipEngine.rows_logmeanexp``.  ``evaluate_log_likelihood_sandwich`` reports both sides and their gap;
+``dbn_conservative_bound`` puts the reverse estimate in place of the top term of ``dbn_lower_bound``.  The iMDBN is not composed.
+
 Data parallelism: the chains are NOT sharded over ranks -- every rank that calls runs all ``n_chains`` chains and gets the same
 estimate (same seed) or an independent one; sharding the chains is a follow-up.
 """
@@ -57,7 +66,8 @@ from imdbn.utils.batches import batches, rows_on_device
 __all__ = ["base_rate_bias", "linear_betas", "estimate_log_partition", "log_likelihood", "evaluate_log_likelihood",
            "dbn_sample_values", "dbn_lower_bound", "dbn_log_likelihood_is", "evaluate_dbn_bound",
            "base_rate_bias_joint", "estimate_joint_log_partition", "imdbn_sample_values", "imdbn_lower_bound",
-           "imdbn_log_likelihood_is", "evaluate_imdbn_bound"]
+           "imdbn_log_likelihood_is", "evaluate_imdbn_bound",
+           "reverse_ais_log_likelihood", "evaluate_log_likelihood_sandwich", "dbn_conservative_bound", "evaluate_dbn_bound_conservative"]
 
 
 def _bottom(model):
@@ -420,4 +430,193 @@ def evaluate_imdbn_bound(model, loader=None, log_z_joint: Optional[float] = None
     if run:
         run.log({"ll/imdbn_" + k: res[k] for k in ("mean_joint_bound", "mean_image_bound", "mean_label_logprob", "log_z_joint", "se",
                                                   "ess", "n_samples") if res[k] is not None})
+    return res
+
+
+# ---- the conservative side: reverse annealed importance sampling ------------------------------------------------------------------
+def _log_z_base(rbm, base_vis_bias, dev) -> torch.Tensor:
+    """log Z_A of the base-rate model of ``rbm`` (float64 scalar on ``dev``): H log 2 + sum_{i outside groups} softplus(b_A,i) +
+    sum_g logsumexp(b_A[g]); no ``base_vis_bias`` = zeros."""
+    V, H = rbm.W.shape
+    bA = torch.zeros(V, dtype=torch.float64, device=dev) if base_vis_bias is None else base_vis_bias.to(dev).double().reshape(-1)
+    if bA.numel() != V:
+        raise ValueError(f"base_vis_bias must have {V} elements")
+    free = torch.ones(V, dtype=torch.bool, device=dev)
+    lzb = torch.full((), H * math.log(2.0), dtype=torch.float64, device=dev)
+    for s, e in (getattr(rbm, "softmax_groups", None) or []):
+        free[int(s):int(e)] = False
+        lzb = lzb + torch.logsumexp(bA[int(s):int(e)], 0)
+    return lzb + torch.nn.functional.softplus(bA[free]).sum()
+
+
+def _reverse_rows(rbm, v, n_chains, betas, base_vis_bias, rng, max_rows):
+    """``(ll [B], ess [B], logw [B, M])`` of ``reverse_ais_log_likelihood`` under the draw source ``rng``, which advances by ONE
+    schedule however many chunks ran: every chunk draws from the same draw numbers, keyed on its global rows."""
+    M = int(n_chains)
+    if M < 1:
+        raise ValueError("n_chains must be >= 1")
+    if int(max_rows) < 1:
+        raise ValueError("max_rows must be >= 1")
+    dev = rbm.W.device
+    if v.size(0) < 1:
+        raise ValueError("reverse_ais_log_likelihood: no rows")
+    v = rows_on_device(v, dev)
+    B = v.size(0)
+    if v.size(1) != rbm.W.shape[0]:
+        raise ValueError(f"reverse_ais_log_likelihood: rows of {v.size(1)} elements, the RBM has {rbm.W.shape[0]} visible units")
+    if base_vis_bias is not None and base_vis_bias.numel() != rbm.W.shape[0]:
+        raise ValueError(f"base_vis_bias must have {rbm.W.shape[0]} elements")
+    eng = _E.get_engine(rbm.W.data)
+    per = max(1, int(max_rows) // M)
+    philox = isinstance(rng, _E.PhiloxRng)
+    if not philox and B > per:
+        raise ValueError("reverse_ais_log_likelihood: more than one chunk of rows needs a PhiloxRng (draws keyed on the global row)")
+    parts, used = [], 0
+    for s in range(0, B, per):
+        rows = v[s:s + per].repeat_interleave(M, 0) if M > 1 else v[s:s + per]
+        r = rng
+        if philox:
+            r = _E.PhiloxRng(rng.seed, row0=rng.row0 + s * M)
+            r.offset, r.device_counter = rng.offset, rng.device_counter
+        parts.append(eng.reverse_ais(rbm, rows, betas, r, base_vis_bias=base_vis_bias))
+        if philox:
+            used = r.offset - rng.offset
+    if philox:
+        rng.advance(used)
+    logw = parts[0] if len(parts) == 1 else torch.cat(parts)
+    lme, ess = eng.rows_logmeanexp(logw, M)
+    return lme - _log_z_base(rbm, base_vis_bias, logw.device), ess, logw.view(B, M)
+
+
+@torch.no_grad()
+def reverse_ais_log_likelihood(rbm, v: torch.Tensor, n_chains: int = 16, n_betas: int = 1000, betas=None,
+                               base_vis_bias: Optional[torch.Tensor] = None, seed: Optional[int] = None, max_rows: int = 4096) -> dict:
+    """Reverse-AIS estimate of log p_ann(v) per row of ``v`` (0/1): ``{"ll": float64 [B], "ess": float64 [B], "logw": float64
+    [B, n_chains]}`` on the device.  ``ll = -log Z_A + logmeanexp(logw)``: exp(ll) is an unbiased estimate of p_ann(v), so ``ll`` is a
+    stochastic LOWER bound on log p_ann(v), the likelihood under the annealing model of the module docstring -- conservative where
+    ``log_likelihood`` with an AIS log Z is optimistic.  ``ess`` = (sum w)^2 / sum w^2 over the row's chains.  RBMs with softmax groups
+    are accepted (``base_vis_bias`` inside a group: the logits of a categorical, as in ``estimate_joint_log_partition``).  A row
+    that is not 0/1 (or a group without exactly one 1) gives NaN in that row.  Rows are processed in chunks of at most
+    ``max_rows // n_chains`` (engine rows = rows x chains); a chunk's draws are keyed on ``first_row * n_chains``, so a row's chains
+    see the same draws whatever the chunking (the same bits while the chunks stay within the same multiple of 64 engine rows, the
+    engine's rule for batch sizes).  ``K (2 + G)`` draw tensors for K temperatures and G groups.  No host sync."""
+    betas = linear_betas(n_betas) if betas is None else betas
+    ll, ess, logw = _reverse_rows(rbm, v, n_chains, betas, base_vis_bias, _draws(seed), max_rows)
+    return {"ll": ll, "ess": ess, "logw": logw}
+
+
+@torch.no_grad()
+def evaluate_log_likelihood_sandwich(model, loader=None, max_batches: Optional[int] = None, **kwargs) -> Optional[dict]:
+    """Both sides of the held-out log-likelihood of an ``RBM`` -- or of the BOTTOM layer of an ``iDBN`` -- over ``loader`` (default
+    ``model.val_loader``; None without one): ``mean_ll_ais`` (``log_likelihood`` with the AIS log Z: optimistic),
+    ``mean_ll_reverse`` (``reverse_ais_log_likelihood``: conservative), ``gap`` = their difference (a long enough ladder closes it),
+    ``n``, ``log_z``, ``se``, ``ess`` (of the AIS estimate) and ``ess_reverse`` (mean over rows).  ``kwargs``: ``n_chains``,
+    ``n_betas``, ``betas``, ``base_vis_bias``, ``seed`` as ``estimate_log_partition`` takes them, and ``n_chains_reverse`` (16),
+    ``max_rows`` for the reverse side, which shares the ladder and the base-rate bias; one draw source carries the AIS run and then
+    every batch.  Binary visibles only (the AIS side).  Everything is accumulated on the device; the host synchronises ONCE, after
+    the last batch.  With a ``wandb_run`` on the model the scalars are logged as ``ll/...``."""
+    rbm = _bottom(model)
+    _check_binary(rbm)
+    loader = loader if loader is not None else getattr(model, "val_loader", None)
+    if loader is None:
+        return None
+    M = int(kwargs.pop("n_chains", 256))
+    Mr = int(kwargs.pop("n_chains_reverse", 16))
+    betas = kwargs.pop("betas", None)
+    betas = linear_betas(kwargs.pop("n_betas", 1000)) if betas is None else betas
+    bA, seed, max_rows = kwargs.pop("base_vis_bias", None), kwargs.pop("seed", None), kwargs.pop("max_rows", 4096)
+    if kwargs:
+        raise TypeError(f"evaluate_log_likelihood_sandwich: unexpected arguments {sorted(kwargs)}")
+    rng = _draws(seed)
+    dev = rbm.W.device
+    logw = _E.get_engine(rbm.W.data).ais(rbm, betas, M, rng, base_vis_bias=bA)
+    lzb = _log_z_base(rbm, bA, logw.device)
+    mx = logw.max()
+    w = torch.exp(logw - mx)
+    mean = w.mean()
+    log_z = lzb + mx + torch.log(mean)
+    ess = w.sum() ** 2 / (w * w).sum()
+    se = (w.std(unbiased=True) if M > 1 else w.new_zeros(())) / (mean * math.sqrt(M))
+    tot = torch.zeros(3, dtype=torch.float64, device=logw.device)
+    n = 0
+    for b, batch in enumerate(batches(loader)):
+        if max_batches is not None and b >= int(max_batches):
+            break
+        v = rows_on_device(_first(batch), dev)
+        ll_r, ess_r, _ = _reverse_rows(rbm, v, Mr, betas, bA, rng, max_rows)
+        ll_a = -rbm.free_energy(v).double().to(log_z.device) - log_z
+        tot += torch.stack([ll_a.sum(), ll_r.sum(), ess_r.sum()])
+        n += v.size(0)
+    host = torch.cat([tot, torch.stack([log_z.reshape(()), se.reshape(()), ess.reshape(())])]).cpu().tolist()
+    d = max(1, n)
+    res = {"mean_ll_ais": host[0] / d, "mean_ll_reverse": host[1] / d, "gap": (host[0] - host[1]) / d, "n": n,
+           "log_z": host[3], "se": host[4], "ess": host[5], "ess_reverse": host[2] / d}
+    run = getattr(model, "wandb_run", None)
+    if run:
+        run.log({"ll/" + k: res[k] for k in ("mean_ll_ais", "mean_ll_reverse", "gap", "log_z", "se", "ess", "ess_reverse")})
+    return res
+
+
+def _conservative_values(layers, v, n_samples, n_chains, betas, base_vis_bias, rng, max_rows):
+    """``(w [B, S], ess [B, S])``: the directed layers as ``_sample_values`` in mode ``entropy``, the top term from reverse AIS on the
+    sampled top-layer states."""
+    S = int(n_samples)
+    if S < 1:
+        raise ValueError("n_samples must be >= 1")
+    top = layers[-1]
+    cur = rows_on_device(v, top.W.device)
+    B = cur.size(0)
+    if S > 1:
+        cur = cur.repeat_interleave(S, 0)
+    acc = None
+    for rbm in layers[:-1]:
+        acc, cur = _E.get_engine(rbm.W.data).bound_step(rbm, cur, rng, acc=acc, mode="entropy")
+    w, ess, _ = _reverse_rows(top, cur, n_chains, betas, base_vis_bias, rng, max_rows)
+    if acc is not None:
+        w = acc.to(w.device) + w
+    return w.view(B, S), ess.view(B, S)
+
+
+@torch.no_grad()
+def dbn_conservative_bound(model, v: torch.Tensor, n_samples: int = 8, n_chains: int = 16, n_betas: int = 1000, betas=None,
+                           base_vis_bias: Optional[torch.Tensor] = None, seed: Optional[int] = None, max_rows: int = 4096) -> torch.Tensor:
+    """``dbn_lower_bound`` without an AIS estimate in it: the directed layers through ``bound_step`` in mode ``entropy``
+    (``n_samples`` draws of the hidden states per row), and in place of ``-F_top - log Z_top`` the reverse-AIS estimate of
+    log p_ann of the top RBM at the sampled top-layer state (``n_chains`` chains each; ``base_vis_bias``: the TOP RBM's base-rate
+    model).  In expectation a lower bound on the variational bound of the stack whose top is the annealing model; float64 ``[B]``
+    on the device, no host sync.  ``model``: an ``iDBN`` or an ``RBM`` (a stack of one: ``reverse_ais_log_likelihood``)."""
+    betas = linear_betas(n_betas) if betas is None else betas
+    return _conservative_values(_stack(model), v, n_samples, n_chains, betas, base_vis_bias, _draws(seed), max_rows)[0].mean(1)
+
+
+@torch.no_grad()
+def evaluate_dbn_bound_conservative(model, loader=None, n_samples: int = 8, n_chains: int = 16, max_batches: Optional[int] = None,
+                                    n_betas: int = 1000, betas=None, base_vis_bias: Optional[torch.Tensor] = None,
+                                    seed: Optional[int] = None, max_rows: int = 4096) -> Optional[dict]:
+    """Mean held-out ``dbn_conservative_bound`` of the stack over ``loader`` (default ``model.val_loader``; None without one):
+    ``mean_bound``, ``sum_bound``, ``n``, ``ess_reverse`` (mean over rows and samples), ``n_samples``, ``n_chains``.  One draw source
+    carries every batch (``seed``: a private one).  Sums on the device, one host sync after the last batch.  With a ``wandb_run`` on
+    the model the scalars are logged as ``ll/dbn_conservative_...``."""
+    layers = _stack(model)
+    loader = loader if loader is not None else getattr(model, "val_loader", None)
+    if loader is None:
+        return None
+    betas = linear_betas(n_betas) if betas is None else betas
+    rng = _draws(seed)
+    tot = None
+    n = 0
+    for b, batch in enumerate(batches(loader)):
+        if max_batches is not None and b >= int(max_batches):
+            break
+        v = _first(batch)
+        w, ess = _conservative_values(layers, v, n_samples, n_chains, betas, base_vis_bias, rng, max_rows)
+        t = torch.stack([w.mean(1).sum(), ess.mean(1).sum()])
+        tot = t if tot is None else tot + t
+        n += v.size(0)
+    t = tot.cpu().tolist() if tot is not None else [0.0, 0.0]
+    d = max(1, n)
+    res = {"mean_bound": t[0] / d, "sum_bound": t[0], "n": n, "ess_reverse": t[1] / d, "n_samples": int(n_samples), "n_chains": int(n_chains)}
+    run = getattr(model, "wandb_run", None)
+    if run:
+        run.log({"ll/dbn_conservative_" + k: res[k] for k in ("mean_bound", "ess_reverse", "n_samples", "n_chains")})
     return res
