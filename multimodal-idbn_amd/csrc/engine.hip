@@ -621,78 +621,120 @@ int imdbn_rbm_free_energy(const imdbn_rbm_desc* d, const float* v, int64_t ldv, 
 // visible bias), and -- but for the last -- the down propagation at T = 1 / beta_k that samples the next visible state.
 // State buffers are scratch that only the softmax-group kernels use otherwise: logits in f_h, the effective bias in f_vp, the
 // fp32 state in f_v[0] (or the caller's out_v) -- imdbn_ws_bytes(V, H, M) covers the call.
-// (the body of imdbn_rbm_ais and imdbn_rbm_ais_groups, after the descriptor checks of either)
-// With softmax groups: the initial state adds one categorical per group (ais_init_v_groups), and the down propagation
-// hands the group columns to finish_groups, which reads and writes fp32 copies of p(v | h) and of the state: the call names its own
-// targets for them (f_v[1], and the state buffer) because prop()'s defaults are f_vp -- the effective bias here -- and f_v[1].
-static int ais_run(const imdbn_rbm_desc* d, int M, int K, const float* betas, const float* base_vis_bias, imdbn_rng* rng, double* logw,
-                   float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
-    if (M < 1) return fail(IMDBN_E_INVALID, "ais: M = %d chains", M);
-    if (K < 1) return fail(IMDBN_E_INVALID, "ais: K = %d temperatures", K);
-    if (!betas || !rng || !logw) return fail(IMDBN_E_INVALID, "ais: null %s", !betas ? "betas" : (!rng ? "rng" : "logw"));
-    if (out_v && ldo < d->V) return fail(IMDBN_E_INVALID, "ais: ldo %lld < V %d", (long long)ldo, d->V);
-    if (betas[0] != 0.0f) return fail(IMDBN_E_INVALID, "ais: betas[0] = %g, must be 0", (double)betas[0]);
-    if (betas[K] != 1.0f) return fail(IMDBN_E_INVALID, "ais: betas[%d] = %g, must be 1", K, (double)betas[K]);
+// With softmax groups: the initial state adds one categorical per group, and the down propagation hands the group
+// columns to finish_groups, which reads and writes fp32 copies of p(v | h) and of the state: the call names its own targets for
+// them (f_v[1], and the state buffer) because prop()'s defaults are f_vp -- the effective bias here -- and f_v[1].
+// Reverse AIS runs the same transitions backwards, T_K first, from the caller's start states.  The anneal_* pieces
+// below are what the two calls share; they differ in their first kernel and their loop.
+
+// the argument checks of either call, in their order; `v`: the start states of the call that takes them (has_v)
+static int anneal_check(const char* name, const imdbn_rbm_desc* d, bool has_v, const float* v, int64_t ldv, int M, int K,
+                        const float* betas, imdbn_rng* rng, double* logw, float* out_v, int64_t ldo) {
+    if (M < 1) return fail(IMDBN_E_INVALID, has_v ? "%s: R = %d rows" : "%s: M = %d chains", name, M);
+    if (K < 1) return fail(IMDBN_E_INVALID, "%s: K = %d temperatures", name, K);
+    if ((has_v && !v) || !betas || !rng || !logw)
+        return fail(IMDBN_E_INVALID, "%s: null %s", name, has_v && !v ? "v" : (!betas ? "betas" : (!rng ? "rng" : "logw")));
+    if (has_v && ldv < d->V) return fail(IMDBN_E_INVALID, "%s: ldv %lld < V %d", name, (long long)ldv, d->V);
+    if (out_v && ldo < d->V) return fail(IMDBN_E_INVALID, "%s: ldo %lld < V %d", name, (long long)ldo, d->V);
+    if (betas[0] != 0.0f) return fail(IMDBN_E_INVALID, "%s: betas[0] = %g, must be 0", name, (double)betas[0]);
+    if (betas[K] != 1.0f) return fail(IMDBN_E_INVALID, "%s: betas[%d] = %g, must be 1", name, K, (double)betas[K]);
     for (int k = 1; k <= K; ++k)
-        if (!(betas[k] > betas[k - 1])) return fail(IMDBN_E_INVALID, "ais: betas[%d] = %g is not above betas[%d] = %g", k, (double)betas[k], k - 1, (double)betas[k - 1]);
-    imdbn_rbm_desc dl = *d;                // local copy: the down half reads the step's effective visible bias through it
-    Ctx c(&dl, rng, S(stream));
-    CHK(setup(c, M, ws, ws_bytes));
-    const Layout& L = c.L;
-    const int G = d->n_groups;
-    if (base_vis_bias) dl.vis_bias = L.f_vp;
-    AisArgs a;
+        if (!(betas[k] > betas[k - 1]))
+            return fail(IMDBN_E_INVALID, "%s: betas[%d] = %g is not above betas[%d] = %g", name, k, (double)betas[k], k - 1, (double)betas[k - 1]);
+    return 0;
+}
+
+struct Anneal {
+    imdbn_rbm_desc dl;      // local copy: the down half reads the step's effective visible bias through it
+    Ctx c;
+    AisArgs a;              // what every kernel of the call is told
+    GroupSpans sp;
+    dim3 grid, block;
+    Anneal(const imdbn_rbm_desc* d, imdbn_rng* rng, imdbn_stream_t stream) : dl(*d), c(&dl, rng, S(stream)) {}
+    Anneal(const Anneal&) = delete;      // c.d points at dl
+};
+
+static int anneal_setup(Anneal& n, const imdbn_rbm_desc* d, int M, const float* base_vis_bias, double* logw, float* out_v, int64_t ldo,
+                        void* ws, size_t ws_bytes) {
+    CHK(setup(n.c, M, ws, ws_bytes));
+    const Layout& L = n.c.L;
+    if (base_vis_bias) n.dl.vis_bias = L.f_vp;
+    AisArgs& a = n.a;
     memset(&a, 0, sizeof(a));
     a.M = M; a.Bp = L.Bp; a.V = L.V; a.H = L.H; a.Vpad = L.Vpad; a.Hpad = L.Hpad;
     a.vis_bias = d->vis_bias; a.base_bias = base_vis_bias; a.eff_bias = L.f_vp;
     a.state = out_v ? out_v : L.f_v[0]; a.lds = out_v ? ldo : L.V;
     a.x = L.f_h; a.ldx = L.H; a.logw = logw;
-    const dim3 grid(L.Bp / AIS_ROWS), block(64 * AIS_ROWS);
+    memset(&n.sp, 0, sizeof(n.sp));
+    n.sp.n_groups = d->n_groups;
+    for (int g = 0; g < d->n_groups; ++g) { n.sp.gs[g] = d->group_start[g]; n.sp.ge[g] = d->group_end[g]; }
+    n.grid = dim3(L.Bp / AIS_ROWS); n.block = dim3(64 * AIS_ROWS);
+    return 0;
+}
+
+// x = c + v W of the current state
+static int anneal_logits(Anneal& n) {
+    const Layout& L = n.c.L;
+    FinishArgs f = new_finish();
+    f.logits_only = 1;
+    f.out_prob = L.f_h; f.ld_prob = L.H;
+    return prop(n.c, true, OpIn{L.vis_rm[0], 1, nullptr}, f);
+}
+
+// The weight step `w` (its k, form and direction are the caller's) on those logits; `sample`: it also draws h for the transition at
+// w.beta_draw and writes that transition's effective visible bias.
+static int anneal_weigh(Anneal& n, AisArgs w, bool sample) {
+    const Layout& L = n.c.L;
+    w.sample = sample ? 1 : 0;
+    if (sample) {
+        w.uni = n.c.rng.floats(w.M, L.H); w.rm = L.hid_rm; w.bits = L.hid_bits;
+        w.eff_scale = (1.0f - w.beta_draw) / w.beta_draw;
+    }
+    hipLaunchKernelGGL(ais_weight_sample_h, n.grid, n.block, 0, n.c.s, w);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the next state from that h: v = 1[sigmoid(beta (b + h W^T) + (1 - beta) b_A) > U]; groups: one category each
+static int anneal_down(Anneal& n, float beta) {
+    Ctx& c = n.c;
+    const Layout& L = c.L;
+    c.hid_bits_ok = true;              // hid_bits describes hid_rm: the down half may read the bit plane
+    FinishArgs f = new_finish();
+    f.T = 1.0f / beta;
+    f.vmode = 1; f.uni = c.rng.floats(n.a.M, L.V);
+    if (n.sp.n_groups > 0) {
+        c.rng.cats(n.a.M, n.sp.n_groups, &f.cat_tape, &f.cat_uni);
+        f.out_prob = L.f_v[1]; f.ld_prob = L.V;
+    }
+    f.out_final = n.a.state; f.ld_final = n.a.lds;
+    f.op.rm = L.vis_rm[0]; f.op.rm_terms = 1; f.rm_src = 2;
+    return prop(c, false, OpIn{L.hid_rm, 1, nullptr}, f);
+}
+
+// (the body of imdbn_rbm_ais and imdbn_rbm_ais_groups, after the descriptor checks of either)
+static int ais_run(const imdbn_rbm_desc* d, int M, int K, const float* betas, const float* base_vis_bias, imdbn_rng* rng, double* logw,
+                   float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(anneal_check("ais", d, false, nullptr, 0, M, K, betas, rng, logw, out_v, ldo));
+    Anneal n(d, rng, stream);
+    CHK(anneal_setup(n, d, M, base_vis_bias, logw, out_v, ldo, ws, ws_bytes));
     {   // v_1 from the base-rate model
-        AisArgs i = a;
-        i.uni = c.rng.floats(M, L.V); i.rm = L.vis_rm[0];
-        if (G > 0) {
-            AisGroupsArgs gi;
-            memset(&gi, 0, sizeof(gi));
-            gi.a = i; gi.n_groups = G;
-            for (int g = 0; g < G; ++g) { gi.gs[g] = d->group_start[g]; gi.ge[g] = d->group_end[g]; }
-            c.rng.cats(M, G, &gi.cat_tape, &gi.cat_uni);
-            hipLaunchKernelGGL(ais_init_v_groups, grid, block, 0, c.s, gi);
-        } else {
-            hipLaunchKernelGGL(ais_init_v, grid, block, 0, c.s, i);
-        }
+        AisGroupsArgs gi;
+        memset(&gi, 0, sizeof(gi));
+        gi.a = n.a; gi.sp = n.sp;
+        gi.a.uni = n.c.rng.floats(M, d->V); gi.a.rm = n.c.L.vis_rm[0];
+        n.c.rng.cats(M, d->n_groups, &gi.cat_tape, &gi.cat_uni);
+        hipLaunchKernelGGL(ais_init_v_groups, n.grid, n.block, 0, n.c.s, gi);
         HIPCHK(hipGetLastError());
     }
     for (int k = 1; k <= K; ++k) {
-        const bool last = k == K;
-        {   // x = c + v_k W
-            FinishArgs f = new_finish();
-            f.logits_only = 1;
-            f.out_prob = L.f_h; f.ld_prob = L.H;
-            CHK(prop(c, true, OpIn{L.vis_rm[0], 1, nullptr}, f));
-        }
-        AisArgs w = a;
-        w.beta_prev = betas[k - 1]; w.beta = betas[k]; w.sample = last ? 0 : 1;
-        if (!last) {
-            w.uni = c.rng.floats(M, L.H); w.rm = L.hid_rm; w.bits = L.hid_bits;
-            w.eff_scale = (1.0f - betas[k]) / betas[k];
-        }
-        hipLaunchKernelGGL(ais_weight_sample_h, grid, block, 0, c.s, w);
-        HIPCHK(hipGetLastError());
-        if (last) break;
-        c.hid_bits_ok = true;              // hid_bits describes hid_rm: the down half may read the bit plane
-        FinishArgs f = new_finish();       // v_{k+1} = 1[sigmoid(beta_k (b + h W^T) + (1 - beta_k) b_A) > U]; groups: one category each
-        f.T = 1.0f / betas[k];
-        f.vmode = 1; f.uni = c.rng.floats(M, L.V);
-        if (G > 0) {
-            c.rng.cats(M, G, &f.cat_tape, &f.cat_uni);
-            f.out_prob = L.f_v[1]; f.ld_prob = L.V;
-        }
-        f.out_final = a.state; f.ld_final = a.lds;
-        f.op.rm = L.vis_rm[0]; f.op.rm_terms = 1; f.rm_src = 2;
-        CHK(prop(c, false, OpIn{L.hid_rm, 1, nullptr}, f));
+        CHK(anneal_logits(n));             // of v_k
+        AisArgs w = n.a;
+        w.beta_prev = betas[k - 1]; w.beta = w.beta_draw = betas[k];
+        CHK(anneal_weigh(n, w, k < K));    // + Delta_k(v_k); the last temperature only weighs
+        if (k < K) CHK(anneal_down(n, betas[k]));
     }
-    return c.rng.finish();
+    return n.c.rng.finish();
 }
 
 int imdbn_rbm_ais(const imdbn_rbm_desc* d, int M, int K, const float* betas, const float* base_vis_bias, imdbn_rng* rng, double* logw,
@@ -709,80 +751,34 @@ int imdbn_rbm_ais_groups(const imdbn_rbm_desc* d, int M, int K, const float* bet
     return ais_run(d, M, K, betas, base_vis_bias, rng, logw, out_v, ldo, ws, ws_bytes, stream);
 }
 
-// Reverse annealed importance sampling: R chains run the AIS transitions backwards, T_K first, from the caller's start
-// states, and logw collects -F(start) - sum_k Delta_k(u_k).  rais_load_v, then K + 1 times the up propagation's raw logits and
-// rais_weight_sample_h, and between two of those the sampling down propagation of ais_run at the temperature the weight kernel drew
-// h for.  Buffers, the local descriptor and the group targets are those of ais_run.
+// Reverse annealed importance sampling: R chains from the caller's start states, and logw collects
+// -F(start) - sum_k Delta_k(u_k).  rais_load_v, then K + 1 weight steps, and between two of them the sampling down propagation at the
+// temperature the weight kernel drew h for.
 int imdbn_rbm_reverse_ais(const imdbn_rbm_desc* d, const float* v, int64_t ldv, int R, int K, const float* betas, const float* base_vis_bias,
                           imdbn_rng* rng, double* logw, float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
     CHK(check_desc(d, false));
-    if (R < 1) return fail(IMDBN_E_INVALID, "reverse_ais: R = %d rows", R);
-    if (K < 1) return fail(IMDBN_E_INVALID, "reverse_ais: K = %d temperatures", K);
-    if (!v || !betas || !rng || !logw)
-        return fail(IMDBN_E_INVALID, "reverse_ais: null %s", !v ? "v" : (!betas ? "betas" : (!rng ? "rng" : "logw")));
-    if (ldv < d->V) return fail(IMDBN_E_INVALID, "reverse_ais: ldv %lld < V %d", (long long)ldv, d->V);
-    if (out_v && ldo < d->V) return fail(IMDBN_E_INVALID, "reverse_ais: ldo %lld < V %d", (long long)ldo, d->V);
-    if (betas[0] != 0.0f) return fail(IMDBN_E_INVALID, "reverse_ais: betas[0] = %g, must be 0", (double)betas[0]);
-    if (betas[K] != 1.0f) return fail(IMDBN_E_INVALID, "reverse_ais: betas[%d] = %g, must be 1", K, (double)betas[K]);
-    for (int k = 1; k <= K; ++k)
-        if (!(betas[k] > betas[k - 1]))
-            return fail(IMDBN_E_INVALID, "reverse_ais: betas[%d] = %g is not above betas[%d] = %g", k, (double)betas[k], k - 1, (double)betas[k - 1]);
-    imdbn_rbm_desc dl = *d;                // local copy: the down half reads the step's effective visible bias through it
-    Ctx c(&dl, rng, S(stream));
-    CHK(setup(c, R, ws, ws_bytes));
-    const Layout& L = c.L;
-    const int G = d->n_groups;
-    if (base_vis_bias) dl.vis_bias = L.f_vp;
-    AisArgs a;
-    memset(&a, 0, sizeof(a));
-    a.M = R; a.Bp = L.Bp; a.V = L.V; a.H = L.H; a.Vpad = L.Vpad; a.Hpad = L.Hpad;
-    a.vis_bias = d->vis_bias; a.base_bias = base_vis_bias; a.eff_bias = L.f_vp;
-    a.state = out_v ? out_v : L.f_v[0]; a.lds = out_v ? ldo : L.V;
-    a.x = L.f_h; a.ldx = L.H; a.logw = logw;
-    const dim3 grid(L.Bp / AIS_ROWS), block(64 * AIS_ROWS);
+    CHK(anneal_check("reverse_ais", d, true, v, ldv, R, K, betas, rng, logw, out_v, ldo));
+    Anneal n(d, rng, stream);
+    CHK(anneal_setup(n, d, R, base_vis_bias, logw, out_v, ldo, ws, ws_bytes));
     {   // u_{K+1} = the caller's rows
         RaisLoadArgs l;
         memset(&l, 0, sizeof(l));
-        l.a = a; l.a.rm = L.vis_rm[0];
-        l.v = v; l.ldv = ldv; l.n_groups = G;
-        for (int g = 0; g < G; ++g) { l.gs[g] = d->group_start[g]; l.ge[g] = d->group_end[g]; }
-        hipLaunchKernelGGL(rais_load_v, grid, block, 0, c.s, l);
+        l.a = n.a; l.a.rm = n.c.L.vis_rm[0]; l.sp = n.sp;
+        l.v = v; l.ldv = ldv;
+        hipLaunchKernelGGL(rais_load_v, n.grid, n.block, 0, n.c.s, l);
         HIPCHK(hipGetLastError());
     }
     for (int k = K + 1; k >= 1; --k) {     // k = K + 1: the start state's softplus term; k <= K: -Delta_k(u_k)
-        const bool first = k == K + 1, last = k == 1;
-        const float bd = first ? betas[K] : betas[k - 1];      // temperature of the transition that follows
-        {   // x = c + u_k W
-            FinishArgs f = new_finish();
-            f.logits_only = 1;
-            f.out_prob = L.f_h; f.ld_prob = L.H;
-            CHK(prop(c, true, OpIn{L.vis_rm[0], 1, nullptr}, f));
-        }
-        RaisArgs w;
-        memset(&w, 0, sizeof(w));
-        w.a = a; w.first = first ? 1 : 0; w.beta_draw = bd;
-        if (!first) { w.a.beta_prev = betas[k - 1]; w.a.beta = betas[k]; }
-        w.a.sample = last ? 0 : 1;
-        if (!last) {
-            w.a.uni = c.rng.floats(R, L.H); w.a.rm = L.hid_rm; w.a.bits = L.hid_bits;
-            w.a.eff_scale = (1.0f - bd) / bd;
-        }
-        hipLaunchKernelGGL(rais_weight_sample_h, grid, block, 0, c.s, w);
-        HIPCHK(hipGetLastError());
-        if (last) break;
-        c.hid_bits_ok = true;              // hid_bits describes hid_rm: the down half may read the bit plane
-        FinishArgs f = new_finish();       // u = 1[sigmoid(bd (b + h W^T) + (1 - bd) b_A) > U]; groups: one category each
-        f.T = 1.0f / bd;
-        f.vmode = 1; f.uni = c.rng.floats(R, L.V);
-        if (G > 0) {
-            c.rng.cats(R, G, &f.cat_tape, &f.cat_uni);
-            f.out_prob = L.f_v[1]; f.ld_prob = L.V;
-        }
-        f.out_final = a.state; f.ld_final = a.lds;
-        f.op.rm = L.vis_rm[0]; f.op.rm_terms = 1; f.rm_src = 2;
-        CHK(prop(c, false, OpIn{L.hid_rm, 1, nullptr}, f));
+        const bool first = k == K + 1;
+        CHK(anneal_logits(n));             // of u_k
+        AisArgs w = n.a;
+        w.reverse = 1; w.first = first ? 1 : 0;
+        if (!first) { w.beta_prev = betas[k - 1]; w.beta = betas[k]; }
+        w.beta_draw = first ? betas[K] : betas[k - 1];      // temperature of the transition that follows
+        CHK(anneal_weigh(n, w, k > 1));    // the last step (k = 1) only weighs
+        if (k > 1) CHK(anneal_down(n, w.beta_draw));
     }
-    return c.rng.finish();
+    return n.c.rng.finish();
 }
 
 int imdbn_rows_logmeanexp(const double* logw, int N, int M, double* out_lme, double* out_ess, imdbn_stream_t stream) {

@@ -34,7 +34,6 @@ __global__ __launch_bounds__(64 * AIS_ROWS) void bound_entropy_sample_h(const Bo
     const bool live = row < a.M;      // wave-uniform
     double e = 0.0;
     const int Hb = (a.H + 63) & ~63;      // whole ballots: the bit plane covers [0, rup(H, 64))
-    const OperandOut ob{nullptr, 0, 0, 0, a.Bp, nullptr, 0, 0, 0, a.bits, 0, 0};
     for (int j = lane; j < Hb; j += 64) {
         bool one = false;
         if (live && j < a.H) {
@@ -45,8 +44,7 @@ __global__ __launch_bounds__(64 * AIS_ROWS) void bound_entropy_sample_h(const Bo
             else e += sp - (one ? xd : 0.0);                       // -(h x - softplus(x))
             a.out_h[(int64_t)row * a.ldh + j] = one ? 1.f : 0.f;
         }
-        if (j < a.Hpad) ais_store_rm(a.rm, a.Bp, row, j, one);
-        store_bits_row(ob, one, j, row, true, 0, 0);
+        ais_store_hidden(a.rm, a.bits, a.Bp, a.Hpad, row, j, one);
     }
     if (!live) return;
     e = wave_sum_f64(e);

@@ -1,14 +1,9 @@
 // kernels_reverse_ais.hpp -- the element-wise half of reverse annealed importance sampling (imdbn_rbm_reverse_ais) and
-// the per-test-row reduction of its weights (imdbn_rows_logmeanexp).
+// the per-test-row reduction of its weights (imdbn_rows_logmeanexp).  The weight-and-draw kernel of the call is ais_weight_sample_h.
 //
 //   rais_load_v            the caller's start states: fp32 state, single-term K16-blocked operand form (padding rows: zeros),
 //                          logw = sum_i b_i v_i in double.  A row holding an element that is not exactly 0 or 1, or a softmax group
 //                          that does not hold exactly one 1, gets logw = NaN -- every later step only adds to it, so the row stays NaN.
-//   rais_weight_sample_h   one pass over the fp32 logits x[R][H] of the current state.  `first`: logw += sum_j sp(x_j) (with
-//                          rais_load_v that is -F of the start state); otherwise logw -= Delta_k, the increment ais_weight_sample_h
-//                          adds.  With `sample` it also draws h = 1[sigmoid(beta_draw x) > U] -- the hidden half of the transition
-//                          that FOLLOWS, beta_K in the first form and beta_{k-1} otherwise -- as the bf16 form and the bit plane,
-//                          and writes that transition's effective visible bias.  The last step (k = 1) only weighs.
 //   rows_logmeanexp        one wave per test row over its M chains: max-shifted sums of w and w^2 in double -> log mean w, ess.
 //
 // Rows, lanes and sums as in kernels_ais.hpp: one wave per row, AIS_ROWS rows per block, rows dealt up to Bp, lane l takes the
@@ -21,7 +16,7 @@ namespace imdbn {
 struct RaisLoadArgs {
     AisArgs a;                                     // M rows; state / lds; rm = vis_rm; vis_bias; logw
     const float* v; int64_t ldv;                   // the caller's start states [M][V]
-    int n_groups; int gs[4]; int ge[4];            // only ever indexed with compile-time constants (see FinishArgs)
+    GroupSpans sp;
 };
 
 __global__ __launch_bounds__(64 * AIS_ROWS) void rais_load_v(const RaisLoadArgs g) {
@@ -45,9 +40,9 @@ __global__ __launch_bounds__(64 * AIS_ROWS) void rais_load_v(const RaisLoadArgs 
     if (!live) return;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        if (q < g.n_groups) {
+        if (q < g.sp.n_groups) {
             int ones = 0;
-            for (int i = g.gs[q] + lane; i < g.ge[q]; i += 64) ones += g.v[(int64_t)row * g.ldv + i] == 1.f ? 1 : 0;
+            for (int i = g.sp.gs[q] + lane; i < g.sp.ge[q]; i += 64) ones += g.v[(int64_t)row * g.ldv + i] == 1.f ? 1 : 0;
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) ones += __shfl_xor(ones, o, 64);
             bad |= ones != 1;
@@ -56,51 +51,6 @@ __global__ __launch_bounds__(64 * AIS_ROWS) void rais_load_v(const RaisLoadArgs 
     const bool any_bad = __ballot(bad) != 0ull;
     const double s = wave_sum_f64(sb);
     if (lane == 0) a.logw[row] = any_bad ? (double)NAN : s;
-}
-
-struct RaisArgs {
-    AisArgs a;            // beta_prev / beta: the step's k; sample, uni, rm, bits, eff_scale: the transition that follows
-    int first;            // the start state's softplus term instead of -Delta_k
-    float beta_draw;      // temperature of the transition that follows
-};
-
-__global__ __launch_bounds__(64 * AIS_ROWS) void rais_weight_sample_h(const RaisArgs r) {
-    const AisArgs& a = r.a;
-    const int lane = threadIdx.x & 63, row = blockIdx.x * AIS_ROWS + (threadIdx.x >> 6);
-    if (a.sample) ais_eff_bias(a);
-    if (row >= a.Bp) return;
-    const bool live = row < a.M;      // wave-uniform
-    // ---- visible term of Delta_k: (beta_k - beta_{k-1}) sum_i (b_i - b_A,i) v_i
-    double sv = 0.0;
-    if (live && !r.first) {
-        const float* v = a.state + (int64_t)row * a.lds;
-        for (int i = lane; i < a.V; i += 64) {
-            const double db = (double)a.vis_bias[i] - (a.base_bias ? (double)a.base_bias[i] : 0.0);
-            sv += db * (double)v[i];
-        }
-    }
-    // ---- hidden term: sum_j sp(x_j), or sum_j sp(beta_k x_j) - sp(beta_{k-1} x_j); h_j = 1[sigmoid(beta_draw x_j) > U]
-    double sh = 0.0;
-    const int Hb = (a.H + 63) & ~63;      // whole ballots: the bit plane covers [0, rup(H, 64))
-    const OperandOut ob{nullptr, 0, 0, 0, a.Bp, nullptr, 0, 0, 0, a.bits, 0, 0};
-    for (int j = lane; j < Hb; j += 64) {
-        const bool in = live && j < a.H;
-        bool one = false;
-        if (in) {
-            const float x = a.x[(int64_t)row * a.ldx + j];
-            sh += r.first ? ais_softplus((double)x)
-                          : ais_softplus((double)a.beta * (double)x) - ais_softplus((double)a.beta_prev * (double)x);
-            if (a.sample) one = sigmoidf_ref(r.beta_draw * x) > draw_uniform(a.uni, row, j);
-        }
-        if (a.sample) {
-            if (j < a.Hpad) ais_store_rm(a.rm, a.Bp, row, j, one);
-            store_bits_row(ob, one, j, row, true, 0, 0);
-        }
-    }
-    if (!live) return;
-    const double tv = wave_sum_f64(sv), th = wave_sum_f64(sh);
-    const double d = r.first ? th : -(((double)a.beta - (double)a.beta_prev) * tv + th);
-    if (lane == 0) a.logw[row] += d;
 }
 
 // Row n owns logw[n M .. n M + M - 1].  out_lme[n] = log((1 / M) sum_m exp(logw)), out_ess[n] = (sum w)^2 / sum w^2 on the weights

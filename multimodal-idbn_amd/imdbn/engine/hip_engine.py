@@ -327,27 +327,33 @@ class HipEngine:
         self._call("imdbn_rbm_free_energy", C.byref(d), _ptr(v), v.stride(0), B, _ptr(out), *self._ws_tail(dev, d.V, d.H, B))
         return out
 
+    def _anneal(self, name: str, rbm, d, sched_fn, n_rows: int, betas, rng, base_vis_bias, return_state: bool, v=None):
+        """The shared body of ``ais``, ``ais_groups`` and ``reverse_ais``: the entry ``imdbn_rbm_<name>`` over ``n_rows`` chains under
+        the draw schedule ``sched_fn(K)``; ``v``: the start states of the call that takes them."""
+        dev = rbm.W.device if v is None else v.device
+        b = [float(x) for x in (betas.tolist() if hasattr(betas, "tolist") else betas)]
+        K, M = len(b) - 1, int(n_rows)
+        arr = (C.c_float * max(1, len(b)))(*b)
+        bA = _on(base_vis_bias, dev, torch.float32)
+        if bA is not None and bA.numel() != d.V:
+            raise N.EngineError(f"{name}: base_vis_bias must have {d.V} elements")
+        logw = torch.empty(max(M, 1), dtype=torch.float64, device=dev)
+        state = torch.empty(max(M, 1), d.V, device=dev) if return_state else None
+        sched = sched_fn(max(K, 1))
+        r, keep = self._rng(rng, sched, max(M, 1), dev)
+        start = () if v is None else (_ptr(v), v.stride(0))
+        self._call("imdbn_rbm_" + name, C.byref(d), *start, M, K, arr, _ptr(bA), C.byref(r), _ptr(logw), _ptr(state), d.V,
+                   *self._ws_tail(dev, d.V, d.H, max(M, 1)))
+        self._done(rng, r, sched)
+        return (logw, state) if return_state else logw
+
     def ais(self, rbm, betas, n_chains: int, rng, base_vis_bias: Optional[torch.Tensor] = None, return_state: bool = False):
         """Annealed importance sampling (imdbn_rbm_ais): ``n_chains`` chains from the base-rate model (visible biases
         ``base_vis_bias``, None = zeros) to ``rbm`` through the temperatures ``betas`` (0 = betas[0] < ... < betas[K] = 1).
         Returns the log importance weights, a float64 device tensor ``[n_chains]`` (and the final states ``[n_chains, V]`` with
         ``return_state``); log Z ~= H log 2 + sum softplus(base_vis_bias) + logmeanexp(logw).  No host sync."""
         d = self._desc(rbm, False)
-        dev = rbm.W.device
-        b = [float(x) for x in (betas.tolist() if hasattr(betas, "tolist") else betas)]
-        K, M = len(b) - 1, int(n_chains)
-        arr = (C.c_float * max(1, len(b)))(*b)
-        bA = _on(base_vis_bias, dev, torch.float32)
-        if bA is not None and bA.numel() != d.V:
-            raise N.EngineError(f"ais: base_vis_bias must have {d.V} elements")
-        logw = torch.empty(max(M, 1), dtype=torch.float64, device=dev)
-        vK = torch.empty(max(M, 1), d.V, device=dev) if return_state else None
-        sched = R.sched_ais(d.V, d.H, max(K, 1))
-        r, keep = self._rng(rng, sched, max(M, 1), dev)
-        self._call("imdbn_rbm_ais", C.byref(d), M, K, arr, _ptr(bA), C.byref(r), _ptr(logw), _ptr(vK), d.V,
-                   *self._ws_tail(dev, d.V, d.H, max(M, 1)))
-        self._done(rng, r, sched)
-        return (logw, vK) if return_state else logw
+        return self._anneal("ais", rbm, d, lambda K: R.sched_ais(d.V, d.H, K), n_chains, betas, rng, base_vis_bias, return_state)
 
     def ais_groups(self, rbm, betas, n_chains: int, rng, base_vis_bias: Optional[torch.Tensor] = None, return_state: bool = False):
         """``ais`` for an RBM whose visible layer has softmax groups (imdbn_rbm_ais_groups): inside a group the columns of
@@ -355,21 +361,8 @@ class HipEngine:
         log Z ~= H log 2 + sum_{i outside groups} softplus(b_A,i) + sum_g logsumexp(b_A[g]) + logmeanexp(logw).  Same returns as
         ``ais``; without groups it is ``ais`` bit for bit.  No host sync."""
         d = self._desc(rbm, False)
-        dev = rbm.W.device
-        b = [float(x) for x in (betas.tolist() if hasattr(betas, "tolist") else betas)]
-        K, M = len(b) - 1, int(n_chains)
-        arr = (C.c_float * max(1, len(b)))(*b)
-        bA = _on(base_vis_bias, dev, torch.float32)
-        if bA is not None and bA.numel() != d.V:
-            raise N.EngineError(f"ais_groups: base_vis_bias must have {d.V} elements")
-        logw = torch.empty(max(M, 1), dtype=torch.float64, device=dev)
-        vK = torch.empty(max(M, 1), d.V, device=dev) if return_state else None
-        sched = R.sched_ais_groups(d.V, d.H, self._groups(rbm), max(K, 1))
-        r, keep = self._rng(rng, sched, max(M, 1), dev)
-        self._call("imdbn_rbm_ais_groups", C.byref(d), M, K, arr, _ptr(bA), C.byref(r), _ptr(logw), _ptr(vK), d.V,
-                   *self._ws_tail(dev, d.V, d.H, max(M, 1)))
-        self._done(rng, r, sched)
-        return (logw, vK) if return_state else logw
+        return self._anneal("ais_groups", rbm, d, lambda K: R.sched_ais_groups(d.V, d.H, self._groups(rbm), K), n_chains, betas, rng,
+                            base_vis_bias, return_state)
 
     def reverse_ais(self, rbm, v_rows, betas, rng, base_vis_bias: Optional[torch.Tensor] = None, return_state: bool = False):
         """Reverse annealed importance sampling (imdbn_rbm_reverse_ais): one chain per row of ``v_rows`` ``[R, V]`` (0/1; the caller
@@ -382,21 +375,8 @@ class HipEngine:
         if not v_rows.is_cuda or v_rows.dim() != 2 or v_rows.size(1) != d.V:
             raise N.EngineError(f"reverse_ais needs a HIP tensor v_rows [R, {d.V}]")
         v = _f32c(v_rows)
-        R_, dev = v.size(0), v.device
-        b = [float(x) for x in (betas.tolist() if hasattr(betas, "tolist") else betas)]
-        K = len(b) - 1
-        arr = (C.c_float * max(1, len(b)))(*b)
-        bA = _on(base_vis_bias, dev, torch.float32)
-        if bA is not None and bA.numel() != d.V:
-            raise N.EngineError(f"reverse_ais: base_vis_bias must have {d.V} elements")
-        logw = torch.empty(max(R_, 1), dtype=torch.float64, device=dev)
-        u1 = torch.empty(max(R_, 1), d.V, device=dev) if return_state else None
-        sched = R.sched_reverse_ais(d.V, d.H, self._groups(rbm), max(K, 1))
-        r, keep = self._rng(rng, sched, max(R_, 1), dev)
-        self._call("imdbn_rbm_reverse_ais", C.byref(d), _ptr(v), v.stride(0), R_, K, arr, _ptr(bA), C.byref(r), _ptr(logw), _ptr(u1), d.V,
-                   *self._ws_tail(dev, d.V, d.H, max(R_, 1)))
-        self._done(rng, r, sched)
-        return (logw, u1) if return_state else logw
+        return self._anneal("reverse_ais", rbm, d, lambda K: R.sched_reverse_ais(d.V, d.H, self._groups(rbm), K), v.size(0), betas, rng,
+                            base_vis_bias, return_state, v=v)
 
     def rows_logmeanexp(self, logw: torch.Tensor, n_chains: int):
         """``(lme, ess)`` per test row of the chain weights ``logw`` (float64, ``N * n_chains`` elements, row n owns the chains

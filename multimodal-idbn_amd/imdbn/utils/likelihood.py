@@ -5,15 +5,14 @@ partition function.  ``estimate_log_partition`` estimates log Z with AIS (Salakh
 analysis of deep belief networks"): ``n_chains`` chains are annealed from the base-rate model A (no weights, visible biases
 ``base_vis_bias``, whose partition function is known: log Z_A = H log 2 + sum_i softplus(b_A,i)) to the RBM through the
 temperatures ``betas``, and log Z ~= log Z_A + logmeanexp(logw).  The whole loop is ONE ``HipEngine.ais`` call
-(imdbn_rbm_ais): per temperature the engine's up propagation, one fused kernel (weight increment in double, hidden
-sample, the step's effective visible bias) and the temperature-scaled sampling down propagation.
+(imdbn_rbm_ais).
 
 Binary visibles without softmax groups only (``ValueError`` otherwise: a softmax group is not a product of Bernoulli units and
 the estimator above does not describe it).
 
-Random draws: ``2 K - 1`` draw tensors per estimate (``imdbn.engine.rng.sched_ais``).  ``seed=None`` consumes the ambient draw
-source; ``seed=int`` runs under a ``PhiloxRng(seed)`` of its own and leaves the caller's draw counter where it was, so estimating
-between epochs does not change training (the rule of ``evaluate_cross_modal``).
+Random draws: ``seed=None`` consumes the ambient draw source; ``seed=int`` runs under a ``PhiloxRng(seed)`` of its own and leaves the
+caller's draw counter where it was, so estimating between epochs does not change training (the rule of ``evaluate_cross_modal``).
+The draw schedules are those of ``imdbn.engine.rng`` (``sched_ais``, ``sched_ais_groups``, ``sched_reverse_ais``, ``sched_bound``).
 
 Stacks: what the project trains is an ``iDBN``, and the RBM likelihood above only speaks about its bottom layer.  The DBN's
 generative model is the top RBM over (h_{L-1}, h_L) with directed layers p(h_{l-1} | h_l) = Bernoulli(sigmoid(b_l + h_l W_l^T))
@@ -24,7 +23,7 @@ below it; with h_l ~ q(h_l | h_{l-1}) = Bernoulli(sigmoid(c_l + h_{l-1} W_l)) dr
 ``E_l`` = the entropy of q(h_l | h_{l-1}) (mode ``entropy``: the mean of w is an unbiased estimate of the variational lower bound
 on log p_DBN(v), ``dbn_lower_bound``) or -log q of the drawn h_l (mode ``logq``: E_q[exp w] = p_DBN(v), and the logmeanexp over
 samples approaches log p(v) from below, ``dbn_log_likelihood_is``).  Each directed layer is ONE ``HipEngine.bound_step`` call
-(imdbn_rbm_bound_step; one draw tensor, ``imdbn.engine.rng.sched_bound``); the top layer is ``free_energy``.
+(imdbn_rbm_bound_step); the top layer is ``free_energy``.
 
 The multimodal model: an ``iMDBN`` is an image stack under a joint RBM whose visible layer is ``[z | one-hot label]``, the label a
 softmax group.  Its generative model, in the DBN reading, is that joint RBM over (z, y, h) with ALL L image layers directed below
@@ -37,17 +36,17 @@ instead; the numbers below are those of the binary-z model, not of that training
 (``imdbn_sample_values``; ``imdbn_lower_bound`` / ``imdbn_log_likelihood_is`` as for the DBN; ``evaluate_imdbn_bound``).  One
 ``bound_step`` per image layer, then ONE ``HipEngine.label_loglik`` call (imdbn_rbm_label_loglik) for both label-side
 values.  ``log Z_joint`` comes from ``estimate_joint_log_partition``: AIS over Bernoulli columns plus softmax groups
-(``HipEngine.ais_groups``, imdbn_rbm_ais_groups; ``imdbn.engine.rng.sched_ais_groups``), whose base-rate model treats the columns
-of ``base_vis_bias`` inside a group as the logits of a categorical (``base_rate_bias_joint``).  The functions of the first two
-paragraphs keep refusing softmax groups.  ``iMDBN_BiModal`` is not covered.
+(``HipEngine.ais_groups``, imdbn_rbm_ais_groups), whose base-rate model treats the columns of ``base_vis_bias`` inside a group as the
+logits of a categorical (``base_rate_bias_joint``).  The functions of the first two paragraphs keep refusing softmax groups.
+``iMDBN_BiModal`` is not covered.
 
 The other side of the sandwich: every number above rests on ONE AIS estimate of log Z, and AIS under-estimates Z in expectation, so
 they are optimistic.  Reverse AIS ("RAISE", Burda, Grosse & Salakhutdinov 2015) reads the forward annealing chain as a generative model
 p_ann (v_1 ~ p_A, then one AIS transition per temperature, the one at beta = 1 included), runs it backwards from each held-out row and
 averages importance weights that only need log Z_A: ``reverse_ais_log_likelihood`` is a stochastic LOWER bound on log p_ann(v) -- of
-the annealing model, which approaches the RBM as the ladder grows, not of the RBM itself.  ``n_chains`` chains per row, ONE
-``HipEngine.reverse_ais`` call per chunk of rows (imdbn_rbm_reverse_ais; ``imdbn.engine.rng.sched_reverse_ais``) and one
-``HipEngine.rows_logmeanexp``.  ``evaluate_log_likelihood_sandwich`` reports both sides and their gap;
+the annealing model, which approaches the RBM as the ladder grows, not of the RBM itself.  ONE ``HipEngine.reverse_ais`` call per
+chunk of rows (imdbn_rbm_reverse_ais) and one ``HipEngine.rows_logmeanexp``.
+``evaluate_log_likelihood_sandwich`` reports both sides and their gap;
 ``dbn_conservative_bound`` puts the reverse estimate in place of the top term of ``dbn_lower_bound``.  The iMDBN is not composed.
 
 Data parallelism: the chains are NOT sharded over ranks -- every rank that calls runs all ``n_chains`` chains and gets the same
@@ -83,6 +82,94 @@ def _check_binary(rbm):
 
 def _first(batch):
     return batch[0] if isinstance(batch, (tuple, list)) else batch
+
+
+def _draws(seed):
+    """The draw source of `seed` (module docstring): the ambient one, or a private PhiloxRng on the caller's row offset."""
+    return _E.get_rng() if seed is None else _E.PhiloxRng(int(seed), row0=int(getattr(_E.get_rng(), "row0", 0)))
+
+
+def _log_z_base(rbm, base_vis_bias, dev) -> torch.Tensor:
+    """log Z_A of the base-rate model of ``rbm`` (float64 scalar on ``dev``): H log 2 + sum_{i outside groups} softplus(b_A,i) +
+    sum_g logsumexp(b_A[g]); no ``base_vis_bias`` = zeros."""
+    V, H = rbm.W.shape
+    bA = torch.zeros(V, dtype=torch.float64, device=dev) if base_vis_bias is None else base_vis_bias.to(dev).double().reshape(-1)
+    if bA.numel() != V:
+        raise ValueError(f"base_vis_bias must have {V} elements")
+    free = torch.ones(V, dtype=torch.bool, device=dev)
+    lzb = torch.full((), H * math.log(2.0), dtype=torch.float64, device=dev)
+    for s, e in (getattr(rbm, "softmax_groups", None) or []):
+        free[int(s):int(e)] = False
+        lzb = lzb + torch.logsumexp(bA[int(s):int(e)], 0)
+    return lzb + torch.nn.functional.softplus(bA[free]).sum()
+
+
+def _weight_stats_device(logw: torch.Tensor, lzb: torch.Tensor) -> torch.Tensor:
+    """``[log_z, log_z_base, ess, se]`` of the AIS weights ``logw`` (``estimate_log_partition``) as one float64 device vector."""
+    M = logw.numel()
+    mx = logw.max()
+    w = torch.exp(logw - mx)
+    mean = w.mean()
+    log_z = lzb + mx + torch.log(mean)
+    ess = w.sum() ** 2 / (w * w).sum()
+    se = (w.std(unbiased=True) if M > 1 else w.new_zeros(())) / (mean * math.sqrt(M))
+    return torch.stack([log_z.reshape(()), lzb.reshape(()), ess.reshape(()), se.reshape(())])
+
+
+def _weight_stats(logw: torch.Tensor, lzb: torch.Tensor) -> dict:
+    """The result dict of ``estimate_log_partition``, with its one device-to-host copy."""
+    host = _weight_stats_device(logw, lzb).cpu().tolist()
+    return {"log_z": host[0], "log_z_base": host[1], "logw": logw, "ess": host[2], "se": host[3]}
+
+
+def _known_or_estimated(log_z, estimate, rbm, ais_kwargs):
+    """``(log_z, se, ess)``: the caller's ``log_z`` (se and ess None), or those of ``estimate(rbm, **ais_kwargs)``."""
+    if log_z is not None:
+        return log_z, None, None
+    est = estimate(rbm, **ais_kwargs)
+    return est["log_z"], est["se"], est["ess"]
+
+
+def _sum_batches(loader, max_batches, batch_sums, width: int, extra: Optional[torch.Tensor] = None):
+    """``(sums, n)`` over the batches of ``loader``, at most ``max_batches`` of them: ``batch_sums(batch)`` gives a float64 device
+    vector of ``width`` sums over the batch's rows, they are added up on the device and come to the host in ONE copy after the last
+    batch, as a list; ``n`` counts the rows.  ``extra``: a device vector that rides along with that copy, appended to the list."""
+    tot, n = None, 0
+    for b, batch in enumerate(batches(loader)):
+        if max_batches is not None and b >= int(max_batches):
+            break
+        t = batch_sums(batch)
+        tot = t if tot is None else tot + t
+        n += _first(batch).size(0)
+    parts = [t for t in (tot, extra) if t is not None]
+    host = torch.cat(parts).cpu().tolist() if parts else []
+    return ([0.0] * width if tot is None else []) + host, n
+
+
+def _log_scalars(model, prefix: str, res: dict, keys):
+    run = getattr(model, "wandb_run", None)
+    if run:
+        run.log({prefix + k: res[k] for k in keys if res[k] is not None})
+
+
+def _directed(layers, v, dev, n_samples, mode, rng):
+    """The directed layers ``layers`` (binary, bottom first) above the rows ``v``: every row ``n_samples`` times (row b's samples are
+    the engine rows b S .. b S + S - 1), one ``bound_step`` per layer.  ``(acc, top state, B, S)``; ``acc`` None without layers."""
+    if mode not in ("entropy", "logq"):
+        raise ValueError("mode must be 'entropy' or 'logq'")
+    S = int(n_samples)
+    if S < 1:
+        raise ValueError("n_samples must be >= 1")
+    for rbm in layers:
+        _check_binary(rbm)
+    cur = rows_on_device(v, dev)
+    B = cur.size(0)
+    if S > 1:
+        cur = cur.repeat_interleave(S, 0)
+    acc = None
+    for rbm in layers:
+        acc, cur = _E.get_engine(rbm.W.data).bound_step(rbm, cur, rng, acc=acc, mode=mode)
+    return acc, cur, B, S
 
 
 @torch.no_grad()
@@ -124,25 +211,8 @@ def estimate_log_partition(rbm, n_chains: int = 256, n_betas: int = 1000, betas=
     the ``n_betas`` evenly spaced temperatures.  One device-to-host copy.  See the module docstring for ``seed``."""
     _check_binary(rbm)
     betas = linear_betas(n_betas) if betas is None else betas
-    eng = _E.get_engine(rbm.W.data)
-    M = int(n_chains)
-    if seed is None:
-        logw = eng.ais(rbm, betas, M, _E.get_rng(), base_vis_bias=base_vis_bias)
-    else:
-        logw = eng.ais(rbm, betas, M, _E.PhiloxRng(int(seed), row0=int(getattr(_E.get_rng(), "row0", 0))), base_vis_bias=base_vis_bias)
-    V, H = rbm.W.shape
-    if base_vis_bias is None:                      # zeros: softplus(0) = log 2 per visible unit
-        lzb = logw.new_full((1,), (V + H) * math.log(2.0))
-    else:
-        lzb = H * math.log(2.0) + torch.nn.functional.softplus(base_vis_bias.to(logw.device).double()).sum().reshape(1)
-    mx = logw.max()
-    w = torch.exp(logw - mx)
-    mean = w.mean()
-    log_z = lzb + mx + torch.log(mean)
-    ess = w.sum() ** 2 / (w * w).sum()
-    se = (w.std(unbiased=True) if M > 1 else w.new_zeros(())) / (mean * math.sqrt(M))
-    host = torch.stack([log_z.reshape(()), lzb.reshape(()), ess.reshape(()), se.reshape(())]).cpu().tolist()
-    return {"log_z": host[0], "log_z_base": host[1], "logw": logw, "ess": host[2], "se": host[3]}
+    logw = _E.get_engine(rbm.W.data).ais(rbm, betas, int(n_chains), _draws(seed), base_vis_bias=base_vis_bias)
+    return _weight_stats(logw, _log_z_base(rbm, base_vis_bias, logw.device))
 
 
 @torch.no_grad()
@@ -164,24 +234,11 @@ def evaluate_log_likelihood(model, loader=None, log_z: Optional[float] = None, m
     loader = loader if loader is not None else getattr(model, "val_loader", None)
     if loader is None:
         return None
-    se = ess = None
-    if log_z is None:
-        est = estimate_log_partition(rbm, **ais_kwargs)
-        log_z, se, ess = est["log_z"], est["se"], est["ess"]
-    dev = rbm.W.device
-    tot = torch.zeros((), dtype=torch.float64, device=dev)
-    n = 0
-    for b, batch in enumerate(batches(loader)):
-        if max_batches is not None and b >= int(max_batches):
-            break
-        v = rows_on_device(_first(batch), dev)
-        tot += log_likelihood(rbm, v, log_z).sum()
-        n += v.size(0)
-    s = float(tot)
+    log_z, se, ess = _known_or_estimated(log_z, estimate_log_partition, rbm, ais_kwargs)
+    (s,), n = _sum_batches(loader, max_batches,
+                           lambda batch: log_likelihood(rbm, rows_on_device(_first(batch), rbm.W.device), log_z).sum().reshape(1), 1)
     res = {"mean_ll": s / max(1, n), "sum_ll": s, "n": n, "log_z": float(log_z), "se": se, "ess": ess}
-    run = getattr(model, "wandb_run", None)
-    if run:
-        run.log({"ll/" + k: res[k] for k in ("mean_ll", "log_z", "se", "ess") if res[k] is not None})
+    _log_scalars(model, "ll/", res, ("mean_ll", "log_z", "se", "ess"))
     return res
 
 
@@ -195,25 +252,9 @@ def _stack(model):
     return layers
 
 
-def _draws(seed):
-    """The draw source of `seed` (module docstring): the ambient one, or a private PhiloxRng on the caller's row offset."""
-    return _E.get_rng() if seed is None else _E.PhiloxRng(int(seed), row0=int(getattr(_E.get_rng(), "row0", 0)))
-
-
 def _sample_values(layers, v, log_z_top, n_samples, mode, rng) -> torch.Tensor:
-    if mode not in ("entropy", "logq"):
-        raise ValueError("mode must be 'entropy' or 'logq'")
-    S = int(n_samples)
-    if S < 1:
-        raise ValueError("n_samples must be >= 1")
     top = layers[-1]
-    cur = rows_on_device(v, top.W.device)
-    B = cur.size(0)
-    if S > 1:
-        cur = cur.repeat_interleave(S, 0)
-    acc = None
-    for rbm in layers[:-1]:
-        acc, cur = _E.get_engine(rbm.W.data).bound_step(rbm, cur, rng, acc=acc, mode=mode)
+    acc, cur, B, S = _directed(layers[:-1], v, top.W.device, n_samples, mode, rng)
     w = -top.free_energy(cur).double() - log_z_top
     if acc is not None:
         w = acc + w
@@ -262,26 +303,16 @@ def evaluate_dbn_bound(model, loader=None, log_z_top: Optional[float] = None, n_
     loader = loader if loader is not None else getattr(model, "val_loader", None)
     if loader is None:
         return None
-    se = ess = None
-    if log_z_top is None:
-        est = estimate_log_partition(layers[-1], **ais_kwargs)
-        log_z_top, se, ess = est["log_z"], est["se"], est["ess"]
+    log_z_top, se, ess = _known_or_estimated(log_z_top, estimate_log_partition, layers[-1], ais_kwargs)
     rng = _draws(ais_kwargs.get("seed"))
-    dev = layers[-1].W.device
-    tot = torch.zeros((), dtype=torch.float64, device=dev)
-    n = 0
-    for b, batch in enumerate(batches(loader)):
-        if max_batches is not None and b >= int(max_batches):
-            break
-        v = _first(batch)
-        w = _sample_values(layers, v, log_z_top, n_samples, "logq" if importance else "entropy", rng)
-        tot += (_logmeanexp_rows(w) if importance else w.mean(1)).sum()
-        n += v.size(0)
-    s = float(tot)
+
+    def sums(batch):
+        w = _sample_values(layers, _first(batch), log_z_top, n_samples, "logq" if importance else "entropy", rng)
+        return (_logmeanexp_rows(w) if importance else w.mean(1)).sum().reshape(1)
+
+    (s,), n = _sum_batches(loader, max_batches, sums, 1)
     res = {"mean_bound": s / max(1, n), "sum_bound": s, "n": n, "log_z_top": float(log_z_top), "se": se, "ess": ess, "n_samples": int(n_samples)}
-    run = getattr(model, "wandb_run", None)
-    if run:
-        run.log({"ll/dbn_" + k: res[k] for k in ("mean_bound", "log_z_top", "se", "ess", "n_samples") if res[k] is not None})
+    _log_scalars(model, "ll/dbn_", res, ("mean_bound", "log_z_top", "se", "ess", "n_samples"))
     return res
 
 
@@ -322,47 +353,18 @@ def estimate_joint_log_partition(rbm, n_chains: int = 256, n_betas: int = 1000, 
     ``HipEngine.ais_groups``, with ``log_z_base`` = H log 2 + sum_{i outside groups} softplus(b_A,i) + sum_g logsumexp(b_A[g])
     (no ``base_vis_bias``: zeros, i.e. log 2 per Bernoulli column and log(width) per group).  One device-to-host copy."""
     betas = linear_betas(n_betas) if betas is None else betas
-    eng = _E.get_engine(rbm.W.data)
-    M = int(n_chains)
-    logw = eng.ais_groups(rbm, betas, M, _draws(seed), base_vis_bias=base_vis_bias)
-    V, H = rbm.W.shape
-    groups = [(int(s), int(e)) for s, e in (getattr(rbm, "softmax_groups", None) or [])]
-    bA = logw.new_zeros(V) if base_vis_bias is None else base_vis_bias.to(logw.device).double().reshape(-1)
-    free = torch.ones(V, dtype=torch.bool, device=logw.device)
-    lzb = logw.new_full((1,), H * math.log(2.0))
-    for s, e in groups:
-        free[s:e] = False
-        lzb = lzb + torch.logsumexp(bA[s:e], 0)
-    lzb = lzb + torch.nn.functional.softplus(bA[free]).sum()
-    mx = logw.max()
-    w = torch.exp(logw - mx)
-    mean = w.mean()
-    log_z = lzb + mx + torch.log(mean)
-    ess = w.sum() ** 2 / (w * w).sum()
-    se = (w.std(unbiased=True) if M > 1 else w.new_zeros(())) / (mean * math.sqrt(M))
-    host = torch.stack([log_z.reshape(()), lzb.reshape(()), ess.reshape(()), se.reshape(())]).cpu().tolist()
-    return {"log_z": host[0], "log_z_base": host[1], "logw": logw, "ess": host[2], "se": host[3]}
+    logw = _E.get_engine(rbm.W.data).ais_groups(rbm, betas, int(n_chains), _draws(seed), base_vis_bias=base_vis_bias)
+    return _weight_stats(logw, _log_z_base(rbm, base_vis_bias, logw.device))
 
 
 def _imdbn_values(model, img, y, log_z_joint, n_samples, mode, rng):
-    if mode not in ("entropy", "logq"):
-        raise ValueError("mode must be 'entropy' or 'logq'")
-    S = int(n_samples)
-    if S < 1:
-        raise ValueError("n_samples must be >= 1")
-    layers = list(model.image_idbn.layers)
-    for rbm in layers:
-        _check_binary(rbm)
     jr = model.joint_rbm
     dev = jr.W.device
-    cur = rows_on_device(img, dev)
+    # ALL image layers are directed: the joint RBM sits above the top one
+    acc, cur, B, S = _directed(list(model.image_idbn.layers), img, dev, n_samples, mode, rng)
     gt = _label_index(y.to(dev)).to(torch.int32)
-    B = cur.size(0)
     if S > 1:
-        cur, gt = cur.repeat_interleave(S, 0), gt.repeat_interleave(S, 0)
-    acc = None
-    for rbm in layers:                                    # ALL image layers are directed: the joint RBM sits above the top one
-        acc, cur = _E.get_engine(rbm.W.data).bound_step(rbm, cur, rng, acc=acc, mode=mode)
+        gt = gt.repeat_interleave(S, 0)
     joint, marg = _E.get_engine(jr.W.data).label_loglik(jr, cur, int(model.num_labels), gt)
     return (acc + joint - log_z_joint).view(B, S), (acc + marg - log_z_joint).view(B, S)
 
@@ -409,46 +411,23 @@ def evaluate_imdbn_bound(model, loader=None, log_z_joint: Optional[float] = None
     loader = loader if loader is not None else getattr(model, "val_loader", None)
     if loader is None:
         return None
-    se = ess = None
-    if log_z_joint is None:
-        est = estimate_joint_log_partition(model.joint_rbm, **ais_kwargs)
-        log_z_joint, se, ess = est["log_z"], est["se"], est["ess"]
+    log_z_joint, se, ess = _known_or_estimated(log_z_joint, estimate_joint_log_partition, model.joint_rbm, ais_kwargs)
     rng = _draws(ais_kwargs.get("seed"))
-    tot = torch.zeros(3, dtype=torch.float64, device=model.joint_rbm.W.device)
-    n = 0
-    for b, (img, y) in enumerate(batches(loader)):
-        if max_batches is not None and b >= int(max_batches):
-            break
-        j, m = _imdbn_values(model, img, y, log_z_joint, n_samples, "entropy", rng)
-        tot += torch.stack([j.mean(1).sum(), m.mean(1).sum(), (j - m).mean(1).sum()])
-        n += j.size(0)
-    t = tot.cpu().tolist()
+
+    def sums(batch):
+        j, m = _imdbn_values(model, batch[0], batch[1], log_z_joint, n_samples, "entropy", rng)
+        return torch.stack([j.mean(1).sum(), m.mean(1).sum(), (j - m).mean(1).sum()])
+
+    t, n = _sum_batches(loader, max_batches, sums, 3)
     d = max(1, n)
     res = {"mean_joint_bound": t[0] / d, "mean_image_bound": t[1] / d, "mean_label_logprob": t[2] / d, "n": n,
            "log_z_joint": float(log_z_joint), "se": se, "ess": ess, "n_samples": int(n_samples)}
-    run = getattr(model, "wandb_run", None)
-    if run:
-        run.log({"ll/imdbn_" + k: res[k] for k in ("mean_joint_bound", "mean_image_bound", "mean_label_logprob", "log_z_joint", "se",
-                                                  "ess", "n_samples") if res[k] is not None})
+    _log_scalars(model, "ll/imdbn_", res, ("mean_joint_bound", "mean_image_bound", "mean_label_logprob", "log_z_joint", "se", "ess",
+                                            "n_samples"))
     return res
 
 
 # ---- the conservative side: reverse annealed importance sampling ------------------------------------------------------------------
-def _log_z_base(rbm, base_vis_bias, dev) -> torch.Tensor:
-    """log Z_A of the base-rate model of ``rbm`` (float64 scalar on ``dev``): H log 2 + sum_{i outside groups} softplus(b_A,i) +
-    sum_g logsumexp(b_A[g]); no ``base_vis_bias`` = zeros."""
-    V, H = rbm.W.shape
-    bA = torch.zeros(V, dtype=torch.float64, device=dev) if base_vis_bias is None else base_vis_bias.to(dev).double().reshape(-1)
-    if bA.numel() != V:
-        raise ValueError(f"base_vis_bias must have {V} elements")
-    free = torch.ones(V, dtype=torch.bool, device=dev)
-    lzb = torch.full((), H * math.log(2.0), dtype=torch.float64, device=dev)
-    for s, e in (getattr(rbm, "softmax_groups", None) or []):
-        free[int(s):int(e)] = False
-        lzb = lzb + torch.logsumexp(bA[int(s):int(e)], 0)
-    return lzb + torch.nn.functional.softplus(bA[free]).sum()
-
-
 def _reverse_rows(rbm, v, n_chains, betas, base_vis_bias, rng, max_rows):
     """``(ll [B], ess [B], logw [B, M])`` of ``reverse_ais_log_likelihood`` under the draw source ``rng``, which advances by ONE
     schedule however many chunks ran: every chunk draws from the same draw numbers, keyed on its global rows."""
@@ -528,49 +507,29 @@ def evaluate_log_likelihood_sandwich(model, loader=None, max_batches: Optional[i
     if kwargs:
         raise TypeError(f"evaluate_log_likelihood_sandwich: unexpected arguments {sorted(kwargs)}")
     rng = _draws(seed)
-    dev = rbm.W.device
     logw = _E.get_engine(rbm.W.data).ais(rbm, betas, M, rng, base_vis_bias=bA)
-    lzb = _log_z_base(rbm, bA, logw.device)
-    mx = logw.max()
-    w = torch.exp(logw - mx)
-    mean = w.mean()
-    log_z = lzb + mx + torch.log(mean)
-    ess = w.sum() ** 2 / (w * w).sum()
-    se = (w.std(unbiased=True) if M > 1 else w.new_zeros(())) / (mean * math.sqrt(M))
-    tot = torch.zeros(3, dtype=torch.float64, device=logw.device)
-    n = 0
-    for b, batch in enumerate(batches(loader)):
-        if max_batches is not None and b >= int(max_batches):
-            break
-        v = rows_on_device(_first(batch), dev)
+    stats = _weight_stats_device(logw, _log_z_base(rbm, bA, logw.device))      # log_z, log_z_base, ess, se
+    log_z = stats[0]
+
+    def sums(batch):
+        v = rows_on_device(_first(batch), rbm.W.device)
         ll_r, ess_r, _ = _reverse_rows(rbm, v, Mr, betas, bA, rng, max_rows)
         ll_a = -rbm.free_energy(v).double().to(log_z.device) - log_z
-        tot += torch.stack([ll_a.sum(), ll_r.sum(), ess_r.sum()])
-        n += v.size(0)
-    host = torch.cat([tot, torch.stack([log_z.reshape(()), se.reshape(()), ess.reshape(())])]).cpu().tolist()
+        return torch.stack([ll_a.sum(), ll_r.sum(), ess_r.sum()])
+
+    host, n = _sum_batches(loader, max_batches, sums, 3, extra=stats)
     d = max(1, n)
     res = {"mean_ll_ais": host[0] / d, "mean_ll_reverse": host[1] / d, "gap": (host[0] - host[1]) / d, "n": n,
-           "log_z": host[3], "se": host[4], "ess": host[5], "ess_reverse": host[2] / d}
-    run = getattr(model, "wandb_run", None)
-    if run:
-        run.log({"ll/" + k: res[k] for k in ("mean_ll_ais", "mean_ll_reverse", "gap", "log_z", "se", "ess", "ess_reverse")})
+           "log_z": host[3], "se": host[6], "ess": host[5], "ess_reverse": host[2] / d}
+    _log_scalars(model, "ll/", res, ("mean_ll_ais", "mean_ll_reverse", "gap", "log_z", "se", "ess", "ess_reverse"))
     return res
 
 
 def _conservative_values(layers, v, n_samples, n_chains, betas, base_vis_bias, rng, max_rows):
     """``(w [B, S], ess [B, S])``: the directed layers as ``_sample_values`` in mode ``entropy``, the top term from reverse AIS on the
     sampled top-layer states."""
-    S = int(n_samples)
-    if S < 1:
-        raise ValueError("n_samples must be >= 1")
     top = layers[-1]
-    cur = rows_on_device(v, top.W.device)
-    B = cur.size(0)
-    if S > 1:
-        cur = cur.repeat_interleave(S, 0)
-    acc = None
-    for rbm in layers[:-1]:
-        acc, cur = _E.get_engine(rbm.W.data).bound_step(rbm, cur, rng, acc=acc, mode="entropy")
+    acc, cur, B, S = _directed(layers[:-1], v, top.W.device, n_samples, "entropy", rng)
     w, ess, _ = _reverse_rows(top, cur, n_chains, betas, base_vis_bias, rng, max_rows)
     if acc is not None:
         w = acc.to(w.device) + w
@@ -603,20 +562,13 @@ def evaluate_dbn_bound_conservative(model, loader=None, n_samples: int = 8, n_ch
         return None
     betas = linear_betas(n_betas) if betas is None else betas
     rng = _draws(seed)
-    tot = None
-    n = 0
-    for b, batch in enumerate(batches(loader)):
-        if max_batches is not None and b >= int(max_batches):
-            break
-        v = _first(batch)
-        w, ess = _conservative_values(layers, v, n_samples, n_chains, betas, base_vis_bias, rng, max_rows)
-        t = torch.stack([w.mean(1).sum(), ess.mean(1).sum()])
-        tot = t if tot is None else tot + t
-        n += v.size(0)
-    t = tot.cpu().tolist() if tot is not None else [0.0, 0.0]
+
+    def sums(batch):
+        w, ess = _conservative_values(layers, _first(batch), n_samples, n_chains, betas, base_vis_bias, rng, max_rows)
+        return torch.stack([w.mean(1).sum(), ess.mean(1).sum()])
+
+    t, n = _sum_batches(loader, max_batches, sums, 2)
     d = max(1, n)
     res = {"mean_bound": t[0] / d, "sum_bound": t[0], "n": n, "ess_reverse": t[1] / d, "n_samples": int(n_samples), "n_chains": int(n_chains)}
-    run = getattr(model, "wandb_run", None)
-    if run:
-        run.log({"ll/dbn_conservative_" + k: res[k] for k in ("mean_bound", "ess_reverse", "n_samples", "n_chains")})
+    _log_scalars(model, "ll/dbn_conservative_", res, ("mean_bound", "ess_reverse", "n_samples", "n_chains"))
     return res

@@ -167,6 +167,17 @@ def test_an_rbm_without_groups_gets_the_binary_estimate(double):
     assert torch.equal(a["logw"], b["logw"]) and a["log_z"] == pytest.approx(b["log_z"], rel=1e-12)
 
 
+@pytest.mark.parametrize("with_bA", [False, True])
+def test_without_groups_both_estimates_are_one_computation(double, with_bA):
+    """Same weights, same statistics, same log Z_A: the dicts are equal, not merely close."""
+    c = Cs.parity_case("plain")
+    r = _rbm(c)
+    kw = dict(n_chains=c["M"], betas=c["betas"], base_vis_bias=torch.from_numpy(c["bA"]) if with_bA else None, seed=3)
+    a, b = LK.estimate_joint_log_partition(r, **kw), LK.estimate_log_partition(r, **kw)
+    assert set(a) == set(b) == {"log_z", "log_z_base", "logw", "ess", "se"}
+    assert torch.equal(a["logw"], b["logw"]) and all(a[k] == b[k] for k in ("log_z", "log_z_base", "ess", "se"))
+
+
 # ---- 3. ABI -----------------------------------------------------------------------------------------------------------
 def test_exports_are_declared_bound_and_present():
     src = open(os.path.join(ROOT, "include", "imdbn_engine.h")).read()

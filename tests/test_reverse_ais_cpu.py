@@ -259,6 +259,17 @@ def test_sandwich_over_a_ragged_loader_on_the_golden_stack(double):
         LK.evaluate_log_likelihood_sandwich(m, loader=loader, chains=3)
 
 
+def test_sandwich_reports_the_statistics_of_estimate_log_partition(double):
+    """The AIS side of the sandwich under a seed IS estimate_log_partition under that seed: equal scalars, not merely close."""
+    c = Cs.parity_case("tiny_bA")
+    r = _rbm(c)
+    for M in (1, 5):                                                    # one chain: se = 0
+        kw = dict(n_chains=M, betas=c["betas"], base_vis_bias=_bA(c), seed=4)
+        res = LK.evaluate_log_likelihood_sandwich(r, loader=[torch.from_numpy(c["x"])], n_chains_reverse=2, **kw)
+        est = LK.estimate_log_partition(r, **kw)
+        assert all(res[k] == est[k] for k in ("log_z", "se", "ess")) and np.isfinite([res["log_z"], res["se"], res["ess"]]).all()
+
+
 def test_conservative_bound_on_the_golden_stack(double):
     layers = _golden_stack()
     X = torch.from_numpy(Cs.start_rows(7, 100, 6, p=0.25))

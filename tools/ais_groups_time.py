@@ -2,7 +2,8 @@
 
 Both forms run on the same parameters in the same process, alternating in rounds; each round times one whole chain of `--temps`
 temperatures between two device events and divides by the number of temperatures.  Prints the median time per temperature of either
-form and their ratio.  No GPU: an error, never a CPU number."""
+form and their ratio.  ``--reverse`` times HipEngine.reverse_ais instead, one chain per start state and `--chains` of
+them at the same shape; the engine form only.  No GPU: an error, never a CPU number."""
 import argparse
 import os
 import statistics
@@ -44,6 +45,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--shape", default="532x256")
     ap.add_argument("--labels", type=int, default=32)
+    ap.add_argument("--reverse", action="store_true")
     args = ap.parse_args()
     import __graft_entry__ as ge
     ge.build()
@@ -66,13 +68,18 @@ def main():
     rng = E.PhiloxRng(1)
     forms = {"engine": lambda: eng.ais_groups(r, betas, args.chains, rng, base_vis_bias=bA),
              "torch": lambda: torch_chain(Wc, b, c, bA, s, e, bl, args.chains)}
+    if args.reverse:
+        x = (torch.rand(args.chains, V, device=dev) < 0.5).float()
+        x[:, s:e] = 0
+        x[torch.arange(args.chains), s + torch.randint(0, e - s, (args.chains,), device=dev)] = 1
+        forms = {"engine": lambda: eng.reverse_ais(r, x, betas, rng, base_vis_bias=bA)}
     out = {}
     for k, fn in forms.items():                        # warm-up: code objects, workspaces, GEMM algorithm choice
         out[k] = fn()
     torch.cuda.synchronize()
     lme = {k: float(torch.logsumexp(w, 0)) - float(torch.log(torch.tensor(float(args.chains)))) for k, w in out.items()}
-    print(f"{V}x{H} group ({s},{e}) chains {args.chains} temps {args.temps}: logmeanexp(logw) engine {lme['engine']:.3f}, torch {lme['torch']:.3f} "
-          f"(other draws)", flush=True)
+    print(f"{V}x{H} group ({s},{e}) chains {args.chains} temps {args.temps}: logmeanexp(logw) "
+          + ", ".join(f"{k} {v:.3f}" for k, v in lme.items()) + " (other draws)", flush=True)
     ms = {k: [] for k in forms}
     for _ in range(args.rounds):
         for k, fn in forms.items():
@@ -82,7 +89,12 @@ def main():
             t1.record()
             torch.cuda.synchronize()
             ms[k].append(1e3 * t0.elapsed_time(t1) / args.temps)
-    me, mt = statistics.median(ms["engine"]), statistics.median(ms["torch"])
+    me = statistics.median(ms["engine"])
+    if args.reverse:
+        print(f"{V}x{H} chains {args.chains}: reverse_ais {me:.1f} us per temperature (min {min(ms['engine']):.1f}, max {max(ms['engine']):.1f})",
+              flush=True)
+        return
+    mt = statistics.median(ms["torch"])
     print(f"{V}x{H} chains {args.chains}: ais_groups {me:.1f} us per temperature (min {min(ms['engine']):.1f}, max {max(ms['engine']):.1f}); "
           f"torch {mt:.1f} us (min {min(ms['torch']):.1f}, max {max(ms['torch']):.1f}); torch / ais_groups {mt / me:.2f}", flush=True)
 
