@@ -6,7 +6,7 @@ logits) must take every decision as the twin does; the TRUTH seeds are ones at w
 standard errors of the enumerated values (test_dbn_bound_cpu.py states what the other seeds gave)."""
 import numpy as np
 
-from ais_cases import MARGIN, params  # noqa: F401
+from anneal_cases import MARGIN, params  # noqa: F401
 
 F32 = np.float32
 

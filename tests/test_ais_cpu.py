@@ -3,7 +3,7 @@ imdbn/utils/likelihood.py on a test double of the engine, and the export's decla
 
 Twin against enumeration: V = 20, H = 12, W ~ N(0, 1), biases ~ N(0, 0.5), K = 200 linear temperatures, M = 64 chains, with and
 without a base-rate bias; |log Z_hat - exact| <= 3 se.  Over the Philox seeds 1..8 the largest error of this setup was 2.4 se with
-se <= 0.051 (both variants passed on every seed); seed 1 is pinned (ais_cases.TRUTH_SEED): 0.08 se and -0.18 se."""
+se <= 0.051 (both variants passed on every seed); seed 1 is pinned (anneal_cases.TRUTH_SEED): 0.08 se and -0.18 se."""
 import os
 import re
 
@@ -11,39 +11,23 @@ import numpy as np
 import pytest
 import torch
 
-import ais_cases as Cs
-import ais_oracle as A
+import anneal_cases as Cs
+import anneal_oracle as A
+from bound_oracle import double, host_rbm  # noqa: F401  (the fixture, by name)
 from imdbn import engine as E
 from imdbn.engine import native, rng as R
-from imdbn.models import RBM
 from imdbn.utils import likelihood as LK
 from oracle.draws import PhiloxStream
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture()
-def double():
-    eng = A.AisOracleEngine()
-    E.set_engine_for_testing(eng)
-    yield eng
-    E.set_engine_for_testing(None)
-
-
-def _rbm(c, groups=None):
-    r = RBM(c["V"], c["H"], 0.1, 0.0, 0.5, softmax_groups=groups).to("cpu")
-    r.W.data = torch.from_numpy(c["W"].copy())
-    r.vis_bias.data = torch.from_numpy(c["b"].copy())
-    r.hid_bias.data = torch.from_numpy(c["c"].copy())
-    return r
-
-
 # ---- 1. the twin against enumeration ----------------------------------------------------------------------------------
 @pytest.mark.parametrize("with_bA", [False, True])
 def test_twin_estimate_is_within_three_standard_errors_of_the_enumerated_log_z(with_bA):
-    c = Cs.truth_case(with_bA)
+    c = Cs.forward_truth(with_bA)
     exact = A.exact_log_z(c["W"], c["b"], c["c"])
-    logw, v, _ = A.ais_logw(c["W"], c["b"], c["c"], c["bA"], c["betas"], c["M"], PhiloxStream(c["seed"]))
+    logw, v, _, _ = A.ais_logw(c["W"], c["b"], c["c"], c["bA"], c["betas"], c["M"], PhiloxStream(c["seed"]))
     lme, se, ess = A.weight_stats(logw)
     log_z = A.log_z_base(c["V"], c["H"], c["bA"]) + lme
     print(f"b_A {with_bA}: log Z_hat {log_z:.4f}, exact {exact:.4f}, error {(log_z - exact) / se:+.2f} se, se {se:.4f}, ess {ess:.1f} of {c['M']}")
@@ -65,7 +49,7 @@ def test_one_temperature_is_plain_importance_sampling_from_the_base():
     """K = 1: no transition, one draw, logw = -F(v_1) + F_A(v_1) up to the constants in log Z_A."""
     W, b, c, bA = Cs.params(9, 4, 5, 1.0)
     ps = PhiloxStream(3)
-    logw, v, _ = A.ais_logw(W, b, c, bA, np.array([0, 1], np.float32), 6, ps)
+    logw, v, _, _ = A.ais_logw(W, b, c, bA, np.array([0, 1], np.float32), 6, ps)
     assert ps.log == [("u", (6, 9))]
     x = (v @ W + c).astype(np.float64)
     want = v.astype(np.float64) @ (b.astype(np.float64) - bA) + (A.softplus(x) - np.log(2.0)).sum(1)
@@ -74,8 +58,8 @@ def test_one_temperature_is_plain_importance_sampling_from_the_base():
 
 # ---- 2. host logic of imdbn/utils/likelihood.py on the test double ----------------------------------------------------
 def test_schedule_is_what_the_double_consumed(double):
-    c = Cs.parity_case("tiny_bA")
-    r = _rbm(c)
+    c = Cs.case(Cs.FORWARD, "tiny_bA")
+    r = host_rbm(c)
     rng = E.PhiloxRng(5)
     double.ais(r, c["betas"], c["M"], rng, base_vis_bias=torch.from_numpy(c["bA"]))
     sched = R.sched_ais(c["V"], c["H"], c["K"])
@@ -84,14 +68,14 @@ def test_schedule_is_what_the_double_consumed(double):
 
 
 def test_estimate_matches_the_twin_and_a_seed_leaves_the_ambient_counter_alone(double):
-    c = Cs.parity_case("tiny_bA")
-    r = _rbm(c)
+    c = Cs.case(Cs.FORWARD, "tiny_bA")
+    r = host_rbm(c)
     bA = torch.from_numpy(c["bA"])
     E.manual_seed(77)
     E.get_rng().advance(3)
     est = LK.estimate_log_partition(r, n_chains=c["M"], betas=c["betas"], base_vis_bias=bA, seed=c["seed"])
     assert E.get_rng().offset == 3 and E.get_rng().seed == 77
-    logw, _, _ = A.ais_logw(c["W"], c["b"], c["c"], c["bA"], c["betas"], c["M"], PhiloxStream(c["seed"]))
+    logw, _, _, _ = A.ais_logw(c["W"], c["b"], c["c"], c["bA"], c["betas"], c["M"], PhiloxStream(c["seed"]))
     lme, se, ess = A.weight_stats(logw)
     assert np.array_equal(est["logw"].numpy(), logw) and est["logw"].dtype == torch.float64
     assert est["log_z_base"] == pytest.approx(A.log_z_base(c["V"], c["H"], c["bA"]), rel=1e-12)
@@ -100,7 +84,7 @@ def test_estimate_matches_the_twin_and_a_seed_leaves_the_ambient_counter_alone(d
     # seed=None draws from the ambient source, from where it stands
     est2 = r.log_partition(n_chains=c["M"], betas=c["betas"])
     assert E.get_rng().offset == 3 + 2 * c["K"] - 1
-    logw2, _, _ = A.ais_logw(c["W"], c["b"], c["c"], None, c["betas"], c["M"], PhiloxStream(77, 3))
+    logw2, _, _, _ = A.ais_logw(c["W"], c["b"], c["c"], None, c["betas"], c["M"], PhiloxStream(77, 3))
     assert np.array_equal(est2["logw"].numpy(), logw2)
     assert est2["log_z_base"] == pytest.approx((c["V"] + c["H"]) * np.log(2.0), rel=1e-12)
     # n_betas: evenly spaced temperatures
@@ -108,8 +92,8 @@ def test_estimate_matches_the_twin_and_a_seed_leaves_the_ambient_counter_alone(d
 
 
 def test_softmax_groups_raise_value_error(double):
-    c = Cs.parity_case("tiny")
-    r = _rbm(c, groups=[(15, 20)])
+    c = Cs.case(Cs.FORWARD, "tiny")
+    r = host_rbm(c, groups=[(15, 20)])
     with pytest.raises(ValueError):
         LK.estimate_log_partition(r, n_chains=4, n_betas=3, seed=1)
     with pytest.raises(ValueError):
@@ -119,8 +103,8 @@ def test_softmax_groups_raise_value_error(double):
 
 
 def test_log_likelihood_is_minus_free_energy_minus_log_z(double):
-    c = Cs.parity_case("tiny")
-    r = _rbm(c)
+    c = Cs.case(Cs.FORWARD, "tiny")
+    r = host_rbm(c)
     g = np.random.Generator(np.random.PCG64(4))
     v = torch.from_numpy((g.random((6, c["V"])) > 0.5).astype(np.float32))
     ll = r.log_likelihood(v, 12.5)
@@ -128,7 +112,7 @@ def test_log_likelihood_is_minus_free_energy_minus_log_z(double):
     assert torch.equal(ll, -r.free_energy(v).double() - 12.5)
     # the probabilities of all 2^V states sum to one under the exact log Z (V = 7)
     W, b, cc, _ = Cs.params(7, 5, 3, 1.0)
-    r7 = _rbm(dict(V=7, H=5, W=W, b=b, c=cc))
+    r7 = host_rbm((W, b, cc))
     vs = torch.from_numpy(((np.arange(1 << 7)[:, None] >> np.arange(7)[None, :]) & 1).astype(np.float32))
     total = float(torch.exp(LK.log_likelihood(r7, vs, A.exact_log_z(W, b, cc))).sum())
     assert total == pytest.approx(1.0, abs=1e-5)        # F in fp32
@@ -140,8 +124,8 @@ class _Run:
 
 
 def test_evaluate_over_a_ragged_loader_equals_the_one_shot_mean(double):
-    c = Cs.parity_case("tiny")
-    r = _rbm(c)
+    c = Cs.case(Cs.FORWARD, "tiny")
+    r = host_rbm(c)
     g = np.random.Generator(np.random.PCG64(9))
     X = torch.from_numpy((g.random((11, c["V"])) > 0.4).astype(np.float32))
     loader = torch.utils.data.DataLoader(torch.utils.data.TensorDataset(X, torch.zeros(11)), batch_size=4)      # 4 + 4 + 3 rows

@@ -14,39 +14,23 @@ import numpy as np
 import pytest
 import torch
 
-import ais_oracle as A
+import anneal_oracle as A
 import bound_cases as Cs
 import bound_oracle as B
+from bound_oracle import double, host_rbm  # noqa: F401  (the fixture, by name)
 from imdbn import engine as E
 from imdbn.engine import native, rng as R
-from imdbn.models import RBM
 from imdbn.utils import likelihood as LK
 from oracle.draws import PhiloxStream
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture()
-def double():
-    eng = B.BoundOracleEngine()
-    E.set_engine_for_testing(eng)
-    yield eng
-    E.set_engine_for_testing(None)
-
-
-def _rbm(W, b, c, groups=None):
-    r = RBM(W.shape[0], W.shape[1], 0.1, 0.0, 0.5, softmax_groups=groups).to("cpu")
-    r.W.data = torch.from_numpy(W.copy())
-    r.vis_bias.data = torch.from_numpy(b.copy())
-    r.hid_bias.data = torch.from_numpy(c.copy())
-    return r
-
-
 class _Stack:
     """What the dbn_* functions need of an iDBN: layers (+ val_loader, wandb_run)."""
 
     def __init__(self, layers, **kw):
-        self.layers = [_rbm(*l) for l in layers]
+        self.layers = [host_rbm(l) for l in layers]
         self.__dict__.update(kw)
 
 
@@ -111,7 +95,7 @@ def test_both_modes_share_the_decisions_and_differ_by_log_q_plus_entropy():
 # ---- 2. host logic of imdbn/utils/likelihood.py on the test double ----------------------------------------------------
 def test_a_stack_of_one_is_log_likelihood_bit_for_bit(double):
     W, b, c = Cs.stack("s3")[0]
-    r = _rbm(W, b, c)
+    r = host_rbm((W, b, c))
     v = torch.from_numpy(Cs.inputs(6, 10, 5, False))
     E.manual_seed(9)
     want = LK.log_likelihood(r, v, 3.25)
@@ -159,7 +143,7 @@ def test_bad_arguments_raise_value_error(double):
     with pytest.raises(ValueError):
         LK.dbn_sample_values(_Stack(L), v, 0.0, n_samples=0)
     grouped = _Stack(L)
-    grouped.layers[1] = _rbm(*L[1], groups=[(2, 6)])                  # softmax groups anywhere in the stack
+    grouped.layers[1] = host_rbm(L[1], groups=[(2, 6)])                  # softmax groups anywhere in the stack
     for fn in (LK.dbn_sample_values, LK.dbn_lower_bound, LK.dbn_log_likelihood_is):
         with pytest.raises(ValueError):
             fn(grouped, v, 0.0)
@@ -205,7 +189,7 @@ def test_idbn_method_is_the_lower_bound(double):
     from imdbn.models.idbn import iDBN
     L = Cs.stack("s3")
     m = iDBN.__new__(iDBN)                                             # the method needs the layers only
-    m.layers = [_rbm(*l) for l in L]
+    m.layers = [host_rbm(l) for l in L]
     v = torch.from_numpy(Cs.inputs(3, 10, 2, False))
     got = m.log_likelihood_bound(v, 0.75, n_samples=4, seed=2)
     assert torch.equal(got, LK.dbn_lower_bound(m, v, 0.75, n_samples=4, seed=2)) and got.shape == (3,)
@@ -224,7 +208,7 @@ def test_existing_entry_points_keep_their_behaviour(double):
 # ---- 3. draws and ABI -------------------------------------------------------------------------------------------------
 def test_schedule_is_what_the_double_consumed(double):
     c = Cs.parity_case("tiny")
-    r = _rbm(c["W"], c["b"], c["c"])
+    r = host_rbm(c)
     rng = E.PhiloxRng(5)
     acc, h = double.bound_step(r, torch.from_numpy(c["v"]), rng)
     assert double.last_log == R.sched_bound(c["H"]) == [("u", c["H"])] and rng.offset == 1

@@ -14,73 +14,32 @@ import numpy as np
 import pytest
 import torch
 
-import ais_oracle as A
+import anneal_oracle as A
 import bound_cases as Cs
 import bound_oracle as B
+from likelihood_gpu import DEV, _native, close, dev, device_rbm, eng, twin  # noqa: F401  (the fixtures, by name)
 from oracle.draws import DrawStream, PhiloxStream
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 REPLAY_SEED = 11
 MODES = ["entropy", "logq"]
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _native():
-    import __graft_entry__ as ge
-    ge.build()
-    from imdbn import engine as E
-    E.set_engine_for_testing(None)
-    yield E.get_hip_engine()
-
-
-@pytest.fixture(scope="module")
-def eng(_native):
-    return _native
-
-
-def _rbm(W, b, c, pitch=None, groups=None):
-    """An RBM on the device; `pitch`: weight rows `pitch` floats apart (None: the constructor's padded pitch)."""
-    from imdbn.models import RBM
-    r = RBM(W.shape[0], W.shape[1], 0.1, 0.0, 0.5, softmax_groups=groups).to(DEV)
-    if pitch is not None:
-        r.W.data = torch.empty(W.shape[0], pitch, device=DEV)[:, :W.shape[1]]
-    r.W.data.copy_(torch.from_numpy(W))
-    r.vis_bias.data.copy_(torch.from_numpy(b))
-    r.hid_bias.data.copy_(torch.from_numpy(c))
-    return r
-
-
-def _case_rbm(c, groups=None):
-    return _rbm(c["W"], c["b"], c["c"], c["pitch"], groups)
-
-
 class _Stack:
     def __init__(self, layers):
-        self.layers = [_rbm(*l) for l in layers]
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-_TWIN = {}
+        self.layers = [device_rbm(l) for l in layers]
 
 
 def _twin(name, mode):
-    """(case, acc, h, margin) of a parity case under its pinned Philox seed, computed once."""
-    if (name, mode) not in _TWIN:
+    """(case, acc, h, margin) of a parity case under its pinned Philox seed."""
+    def run():
         c = Cs.parity_case(name)
-        _TWIN[name, mode] = (c,) + B.bound_step(c["W"], c["b"], c["c"], c["v"], mode, PhiloxStream(c["seed"]))
-    return _TWIN[name, mode]
+        return (c,) + B.bound_step(c["W"], c["b"], c["c"], c["v"], mode, PhiloxStream(c["seed"]))
+    return twin(("bound_step", name, mode), run)
 
 
 def _close(got, want, n_units, what, extra=0.0):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    tol = n_units * 1e-5 + 1e-9 * np.abs(want) + extra
-    err = np.abs(got - want)
-    print(f"{what}: max |acc - twin| {err.max():.3g} (tolerance {tol.min():.3g})")
-    assert (err <= tol).all(), f"{what}: {err.max():.3g}"
+    close(got, want, n_units * 1e-5 + 1e-9 * np.abs(want) + extra, what)
 
 
 # ---- 1. parity with the twin ------------------------------------------------------------------------------------------
@@ -91,9 +50,9 @@ def test_parity_with_the_twin(eng, name, mode):
     c, acc, h, margin = _twin(name, mode)
     print(f"{name}: twin margin {margin:.3g}")
     assert margin >= Cs.MARGIN
-    r = _case_rbm(c)
+    r = device_rbm(c)
     rng = E.PhiloxRng(c["seed"])
-    a, hd = eng.bound_step(r, _dev(c["v"]), rng, mode=mode)
+    a, hd = eng.bound_step(r, dev(c["v"]), rng, mode=mode)
     torch.cuda.synchronize()
     assert a.dtype == torch.float64 and tuple(a.shape) == (c["M"],) and tuple(hd.shape) == (c["M"], c["H"]) and rng.offset == 1
     bad = np.nonzero(hd.cpu().numpy() != h)
@@ -107,11 +66,11 @@ def test_h_is_the_sample_of_prop_up_and_draws_are_row_keyed(eng, name):
     from imdbn import engine as E
     from imdbn.engine import rng as R
     c = Cs.parity_case(name)
-    r = _case_rbm(c)
+    r = device_rbm(c)
     x9 = Cs.inputs(9, c["V"], 3, False)
     margin = B.bound_step(c["W"], c["b"], c["c"], x9, "logq", PhiloxStream(c["seed"]))[2]
     assert margin >= Cs.MARGIN          # the two up propagations sum their logits in different orders
-    v9 = _dev(x9)
+    v9 = dev(x9)
     rng = E.PhiloxRng(c["seed"])
     a9, h9 = eng.bound_step(r, v9, rng, mode="logq")
     _, hs = eng.prop_up(r, v9, sample=True, rng=E.PhiloxRng(c["seed"]))
@@ -137,7 +96,7 @@ def test_replay_tape_matches_the_twin_fed_the_same_tape(eng):
     want, h, margin = B.bound_step(c["W"], c["b"], c["c"], c["v"], "logq", DrawStream(REPLAY_SEED))
     print(f"replay: twin margin {margin:.3g}")
     assert margin >= Cs.MARGIN
-    a, hd = eng.bound_step(_case_rbm(c), _dev(c["v"]), E.ReplayRng(DrawStream(REPLAY_SEED)), mode="logq")
+    a, hd = eng.bound_step(device_rbm(c), dev(c["v"]), E.ReplayRng(DrawStream(REPLAY_SEED)), mode="logq")
     assert np.array_equal(hd.cpu().numpy(), h)
     _close(a.cpu().numpy(), want, c["V"] + c["H"], "replay")
 
@@ -147,7 +106,7 @@ def test_the_call_adds_to_a_non_zero_acc(eng):
     c, acc, _, margin = _twin("mid", "entropy")
     assert margin >= Cs.MARGIN
     start = torch.arange(c["M"], dtype=torch.float64, device=DEV) - 3.5
-    a, _ = eng.bound_step(_case_rbm(c), _dev(c["v"]), E.PhiloxRng(c["seed"]), acc=start, mode="entropy")
+    a, _ = eng.bound_step(device_rbm(c), dev(c["v"]), E.PhiloxRng(c["seed"]), acc=start, mode="entropy")
     assert a is start
     _close(a.cpu().numpy(), acc + np.arange(c["M"]) - 3.5, c["V"] + c["H"], "accumulate")
 
@@ -169,7 +128,7 @@ def test_sample_values_of_a_stack_match_the_twin(eng, name, mode):
     want, margin, mag = B.dbn_values(L, v, S, mode, PhiloxStream(seed), 1.25)
     print(f"{name}: twin margin {margin:.3g}")
     assert margin >= Cs.MARGIN
-    got = LK.dbn_sample_values(_Stack(L), _dev(v), 1.25, n_samples=S, mode=mode, seed=seed)
+    got = LK.dbn_sample_values(_Stack(L), dev(v), 1.25, n_samples=S, mode=mode, seed=seed)
     assert got.dtype == torch.float64 and tuple(got.shape) == (Cs.PATH["B"], S) and got.is_cuda
     units, extra = _path_tol(L, mag)
     _close(got.cpu().numpy(), want, units, f"{name} {mode}", extra)
@@ -178,8 +137,8 @@ def test_sample_values_of_a_stack_match_the_twin(eng, name, mode):
 def test_a_stack_of_one_is_log_likelihood_bit_for_bit(eng):
     from imdbn.utils import likelihood as LK
     c = Cs.parity_case("mid")
-    r = _case_rbm(c)
-    v = _dev(c["v"])
+    r = device_rbm(c)
+    v = dev(c["v"])
     assert torch.equal(LK.dbn_sample_values(r, v, 2.5)[:, 0], LK.log_likelihood(r, v, 2.5))
 
 
@@ -196,12 +155,12 @@ def test_estimates_against_the_enumerated_bound_and_likelihood(eng, name):
     m.layers = _Stack(L).layers
     tw, _, _ = B.dbn_values(L, v, S, "entropy", PhiloxStream(seed), lz)
     t_se = tw.std(1, ddof=1) / np.sqrt(S)
-    got = m.log_likelihood_bound(_dev(v), lz, n_samples=S, seed=seed).cpu().numpy()
+    got = m.log_likelihood_bound(dev(v), lz, n_samples=S, seed=seed).cpu().numpy()
     print(f"{name}: bound errors {((got - lb) / t_se).round(2)} twin se")
     assert (np.abs(got - lb) <= 5 * t_se).all()
     tq, _, _ = B.dbn_values(L, v[:1], S2, "logq", PhiloxStream(seed), lz)
     _, q_se, _ = A.weight_stats(tq[0])
-    est = float(LK.dbn_log_likelihood_is(m, _dev(v[:1]), lz, n_samples=S2, seed=seed)[0])
+    est = float(LK.dbn_log_likelihood_is(m, dev(v[:1]), lz, n_samples=S2, seed=seed)[0])
     print(f"{name}: log p_hat {est:.4f}, exact {lp[0]:.4f}, error {(est - lp[0]) / q_se:+.2f} twin se")
     assert abs(est - lp[0]) <= 5 * q_se
 
@@ -229,8 +188,8 @@ def _raw(eng, r, v, M, mode=0, short=0):
 @pytest.mark.parametrize("what,code", [("groups", -5), ("M0", -1), ("mode", -1), ("short", -2)])
 def test_invalid_arguments_launch_nothing(eng, what, code):
     c = Cs.parity_case("tiny")
-    v = _dev(c["v"])
-    r = _case_rbm(c, groups=[(15, 20)] if what == "groups" else None)
+    v = dev(c["v"])
+    r = device_rbm(c, groups=[(15, 20)] if what == "groups" else None)
     msg, acc = _raw(eng, r, v, 0 if what == "M0" else 5, mode=7 if what == "mode" else 0, short=1 if what == "short" else 0)
     print(what, "->", msg)
     assert msg is not None and f"rc={code})" in msg
@@ -238,7 +197,7 @@ def test_invalid_arguments_launch_nothing(eng, what, code):
     if what == "mode":
         assert "7" in msg                                              # the offending value is named
     # the same workspace still serves a good call
-    msg, acc = _raw(eng, _case_rbm(c), v, 5)
+    msg, acc = _raw(eng, device_rbm(c), v, 5)
     assert msg is None and torch.isfinite(acc).all() and not (acc == -7.25).any()
 
 
@@ -246,9 +205,9 @@ def test_python_entry_raises_engine_error(eng):
     from imdbn import engine as E
     c = Cs.parity_case("tiny")
     with pytest.raises(E.EngineError):
-        eng.bound_step(_case_rbm(c), _dev(c["v"]), E.PhiloxRng(1), mode="mean")
+        eng.bound_step(device_rbm(c), dev(c["v"]), E.PhiloxRng(1), mode="mean")
     with pytest.raises(E.EngineError):
-        eng.bound_step(_case_rbm(c, groups=[(15, 20)]), _dev(c["v"]), E.PhiloxRng(1))
+        eng.bound_step(device_rbm(c, groups=[(15, 20)]), dev(c["v"]), E.PhiloxRng(1))
 
 
 # ---- 6. nothing else moved --------------------------------------------------------------------------------------------
@@ -256,10 +215,10 @@ def test_python_entry_raises_engine_error(eng):
 def test_free_energy_and_weights_are_untouched(eng, name):
     from imdbn import engine as E
     c = Cs.parity_case(name)
-    r = _case_rbm(c)
-    v = _dev(c["v"])
+    r = device_rbm(c)
+    v = dev(c["v"])
     g = np.random.Generator(np.random.PCG64(2))
-    x = _dev((g.random((c["M"], c["V"])) > 0.5).astype(np.float32))    # M rows: the workspace of the bound_step call
+    x = dev((g.random((c["M"], c["V"])) > 0.5).astype(np.float32))    # M rows: the workspace of the bound_step call
     W0, b0, c0, v0 = r.W.data.clone(), r.vis_bias.data.clone(), r.hid_bias.data.clone(), v.clone()
     F0 = eng.free_energy(r, x)
     eng.bound_step(r, v, E.PhiloxRng(c["seed"]))

@@ -1,7 +1,7 @@
-"""CPU-only: the iMDBN likelihood functions of imdbn/utils/likelihood.py -- the numpy twins (tests/joint_ais_oracle.py) against
+"""CPU-only: the iMDBN likelihood functions of imdbn/utils/likelihood.py -- the numpy twins (tests/bound_oracle.py) against
 enumeration, and the host logic on a test double of the engine.
 
-Tiny iMDBN (joint_ais_cases.TINY): image stack 8-5-4, joint RBM (4 + 3) <-> 4, W ~ N(0, 0.5).  Exact log p(img, y) and log p(img) by
+Tiny iMDBN (anneal_cases.TINY): image stack 8-5-4, joint RBM (4 + 3) <-> 4, W ~ N(0, 0.5).  Exact log p(img, y) and log p(img) by
 enumerating the hidden states of both directed layers and of the joint RBM.  Twin against them on 6 rows: ENTROPY with S = 256, every
 row's mean within 3 of its own standard errors of the exact bound; LOGQ with S = 2048, every row's logmeanexp within 3 se of the exact
 log p; both for the joint and for the image-marginal value.  Worst row of the twelve (6 rows x joint / marginal) over the Philox seeds
@@ -11,48 +11,33 @@ log p; both for the joint and for the image-marginal value.  Worst row of the tw
 Seeds 3 (one marginal value, 3.12) and 5 (row 0: 3.91 / 4.00) miss the ENTROPY bound, each by ONE row whose joint and marginal values
 share their samples.  A bias of the twin would show at any sample size: at S = 65536 (seed 99) the worst row is 2.12 se off with an
 absolute error below 0.01 nat, so these are the tails of 256-sample means (se itself estimated from the sample), not an error of the
-twin.  Seed 1 is pinned (joint_ais_cases.TINY_SEED)."""
+twin.  Seed 1 is pinned (anneal_cases.TINY_SEED)."""
 import numpy as np
 import pytest
 import torch
 
-import joint_ais_cases as Cs
-import joint_ais_oracle as J
+import anneal_cases as Cs
+import anneal_oracle as A
+import bound_oracle as B
+from bound_oracle import double, host_rbm  # noqa: F401  (the fixture, by name)
 from imdbn import engine as E
-from imdbn.models import RBM
 from imdbn.models.imdbn import iMDBN
 from imdbn.utils import likelihood as LK
 from oracle.draws import PhiloxStream
-
-
-@pytest.fixture()
-def double():
-    eng = J.JointOracleEngine()
-    E.set_engine_for_testing(eng)
-    yield eng
-    E.set_engine_for_testing(None)
 
 
 @pytest.fixture(scope="module")
 def tiny():
     layers, joint = Cs.imdbn(Cs.TINY)
     K = Cs.TINY["K"]
-    top_joint, top_marg = J.joint_top_values(joint, K)
+    top_joint, top_marg = B.joint_top_values(joint, K)
     return dict(layers=layers, joint=joint, K=K, Dz=Cs.TINY["sizes"][-1], top_joint=top_joint, top_marg=top_marg,
-                log_z=J.exact_log_z_groups(*joint, [(Cs.TINY["sizes"][-1], Cs.TINY["sizes"][-1] + K)]))
-
-
-def _rbm(W, b, c, groups=None):
-    r = RBM(W.shape[0], W.shape[1], 0.1, 0.0, 0.5, softmax_groups=groups).to("cpu")
-    r.W.data = torch.from_numpy(W.copy())
-    r.vis_bias.data = torch.from_numpy(b.copy())
-    r.hid_bias.data = torch.from_numpy(c.copy())
-    return r
+                log_z=A.exact_log_z(*joint, [(Cs.TINY["sizes"][-1], Cs.TINY["sizes"][-1] + K)]))
 
 
 class _Stack:
     def __init__(self, layers):
-        self.layers = [_rbm(*l) for l in layers]
+        self.layers = [host_rbm(l) for l in layers]
 
     def represent(self, x):
         for r in self.layers:
@@ -65,21 +50,21 @@ class _Model:
 
     def __init__(self, layers, joint, K):
         Dz = joint[0].shape[0] - K
-        self.image_idbn, self.joint_rbm, self.num_labels = _Stack(layers), _rbm(*joint, groups=[(Dz, Dz + K)]), K
+        self.image_idbn, self.joint_rbm, self.num_labels = _Stack(layers), host_rbm(joint, groups=[(Dz, Dz + K)]), K
         self.val_loader = self.dataloader = self.wandb_run = None
 
 
 # ---- 1. enumeration ---------------------------------------------------------------------------------------------------
 def test_exact_bound_is_below_exact_log_p_and_the_labels_sum_out(tiny):
     vs = ((np.arange(256)[:, None] >> np.arange(8)[None, :]) & 1).astype(np.float64)
-    lp_y = np.stack([J.exact_log_p(tiny["layers"], vs, tiny["top_joint"][:, k]) for k in range(tiny["K"])], 1)       # [256, 3]
-    bd_y = np.stack([J.exact_bound(tiny["layers"], vs, tiny["top_joint"][:, k]) for k in range(tiny["K"])], 1)
-    lp, bd = J.exact_log_p(tiny["layers"], vs, tiny["top_marg"]), J.exact_bound(tiny["layers"], vs, tiny["top_marg"])
+    lp_y = np.stack([B.exact_log_p(tiny["layers"], vs, tiny["top_joint"][:, k]) for k in range(tiny["K"])], 1)       # [256, 3]
+    bd_y = np.stack([B.exact_bound(tiny["layers"], vs, tiny["top_joint"][:, k]) for k in range(tiny["K"])], 1)
+    lp, bd = B.exact_log_p(tiny["layers"], vs, tiny["top_marg"]), B.exact_bound(tiny["layers"], vs, tiny["top_marg"])
     assert (bd_y <= lp_y + 1e-12).all() and (bd <= lp + 1e-12).all()
     assert (lp_y - bd_y).min() > 1e-3                                    # the bound is not tight on this model
-    assert np.allclose(J._lse(lp_y, 1), lp, rtol=0, atol=1e-12)          # sum_y p(img, y) = p(img)
+    assert np.allclose(A._lse(lp_y, 1), lp, rtol=0, atol=1e-12)          # sum_y p(img, y) = p(img)
     assert abs(np.exp(lp).sum() - 1.0) <= 1e-12 and abs(np.exp(lp_y).sum() - 1.0) <= 1e-12
-    assert np.allclose(J._lse(tiny["top_joint"], 1), tiny["top_marg"], rtol=0, atol=1e-12)
+    assert np.allclose(A._lse(tiny["top_joint"], 1), tiny["top_marg"], rtol=0, atol=1e-12)
 
 
 def _truth_inputs(tiny):
@@ -87,15 +72,15 @@ def _truth_inputs(tiny):
     img, gt = Cs.inputs(T["B"], Cs.TINY["sizes"][0], tiny["K"], T["in_seed"])
     rows = range(T["B"])
     pick = lambda f, top: np.array([f(tiny["layers"], img[i:i + 1], top[:, gt[i]])[0] for i in rows])
-    exact = dict(bound_joint=pick(J.exact_bound, tiny["top_joint"]), bound_marg=J.exact_bound(tiny["layers"], img, tiny["top_marg"]),
-                 lp_joint=pick(J.exact_log_p, tiny["top_joint"]), lp_marg=J.exact_log_p(tiny["layers"], img, tiny["top_marg"]))
+    exact = dict(bound_joint=pick(B.exact_bound, tiny["top_joint"]), bound_marg=B.exact_bound(tiny["layers"], img, tiny["top_marg"]),
+                 lp_joint=pick(B.exact_log_p, tiny["top_joint"]), lp_marg=B.exact_log_p(tiny["layers"], img, tiny["top_marg"]))
     return img, gt, exact
 
 
 def test_twin_entropy_mean_is_within_three_standard_errors_of_the_exact_bound(tiny):
     img, gt, ex = _truth_inputs(tiny)
     S = Cs.TINY_TRUTH["S_entropy"]
-    wj, wm, _, _ = J.imdbn_values(tiny["layers"], tiny["joint"], tiny["K"], img, gt, S, "entropy", PhiloxStream(Cs.TINY_SEED), tiny["log_z"])
+    wj, wm, _, _ = B.imdbn_values(tiny["layers"], tiny["joint"], tiny["K"], img, gt, S, "entropy", PhiloxStream(Cs.TINY_SEED), tiny["log_z"])
     for what, w, want in (("joint", wj, ex["bound_joint"]), ("image", wm, ex["bound_marg"])):
         se = w.std(1, ddof=1) / np.sqrt(S)
         err = (w.mean(1) - want) / se
@@ -106,10 +91,10 @@ def test_twin_entropy_mean_is_within_three_standard_errors_of_the_exact_bound(ti
 def test_twin_logq_logmeanexp_is_within_three_standard_errors_of_the_exact_log_p(tiny):
     img, gt, ex = _truth_inputs(tiny)
     S = Cs.TINY_TRUTH["S_logq"]
-    wj, wm, _, _ = J.imdbn_values(tiny["layers"], tiny["joint"], tiny["K"], img, gt, S, "logq", PhiloxStream(Cs.TINY_SEED), tiny["log_z"])
+    wj, wm, _, _ = B.imdbn_values(tiny["layers"], tiny["joint"], tiny["K"], img, gt, S, "logq", PhiloxStream(Cs.TINY_SEED), tiny["log_z"])
     for what, w, want in (("joint", wj, ex["lp_joint"]), ("image", wm, ex["lp_marg"])):
         for r in range(w.shape[0]):
-            lme, se, ess = J.weight_stats(w[r])
+            lme, se, ess = A.weight_stats(w[r])
             print(f"LOGQ {what} row {r}: {lme:.4f} vs {want[r]:.4f}, error {(lme - want[r]) / se:+.2f} se, se {se:.4f}, ess {ess:.0f}")
             assert abs(lme - want[r]) <= 3 * se and 0 < se <= 0.09
 
@@ -119,10 +104,10 @@ def test_label_loglik_twin_is_the_free_energy_of_the_joint_state(tiny):
     Dz, K = tiny["Dz"], tiny["K"]
     zs = ((np.arange(16)[:, None] >> np.arange(4)[None, :]) & 1).astype(np.float32)
     gt = np.arange(16) % K
-    j, m = J.label_loglik(W, b, c, zs, Dz, K, gt)
+    j, m = B.label_loglik(W, b, c, zs, Dz, K, gt)
     assert np.allclose(j - tiny["log_z"], tiny["top_joint"][np.arange(16), gt], rtol=0, atol=1e-5)      # base in fp32
     assert np.allclose(m - tiny["log_z"], tiny["top_marg"], rtol=0, atol=1e-5)
-    j2, m2 = J.label_loglik(W, b, c, zs, Dz, K, np.where(np.arange(16) == 3, -1, gt))
+    j2, m2 = B.label_loglik(W, b, c, zs, Dz, K, np.where(np.arange(16) == 3, -1, gt))
     assert np.isnan(j2[3]) and np.array_equal(np.delete(j2, 3), np.delete(j, 3)) and np.array_equal(m2, m)
 
 
@@ -135,23 +120,23 @@ def test_sample_values_match_the_twin_and_a_seed_leaves_the_ambient_counter_alon
     E.get_rng().advance(3)
     for mode in ("entropy", "logq"):
         wj, wm = LK.imdbn_sample_values(m, torch.from_numpy(img), y, 1.5, n_samples=3, mode=mode, seed=4)
-        tj, tm, _, _ = J.imdbn_values(tiny["layers"], tiny["joint"], tiny["K"], img, gt, 3, mode, PhiloxStream(4), 1.5)
+        tj, tm, _, _ = B.imdbn_values(tiny["layers"], tiny["joint"], tiny["K"], img, gt, 3, mode, PhiloxStream(4), 1.5)
         assert wj.dtype == wm.dtype == torch.float64 and tuple(wj.shape) == tuple(wm.shape) == (5, 3)
         assert np.array_equal(wj.numpy(), tj) and np.array_equal(wm.numpy(), tm)
     assert E.get_rng().offset == 3 and E.get_rng().seed == 77
     # class indices instead of one-hot rows; the ambient source: one draw tensor per image layer
     wj2, _ = LK.imdbn_sample_values(m, torch.from_numpy(img), torch.from_numpy(gt), 1.5, n_samples=3, mode="entropy")
     assert E.get_rng().offset == 3 + len(tiny["layers"])
-    assert np.array_equal(wj2.numpy(), J.imdbn_values(tiny["layers"], tiny["joint"], tiny["K"], img, gt, 3, "entropy", PhiloxStream(77, 3), 1.5)[0])
+    assert np.array_equal(wj2.numpy(), B.imdbn_values(tiny["layers"], tiny["joint"], tiny["K"], img, gt, 3, "entropy", PhiloxStream(77, 3), 1.5)[0])
     # the two reductions, and the thin method
     lbj, lbm = LK.imdbn_lower_bound(m, torch.from_numpy(img), y, 1.5, n_samples=3, seed=4)
-    tj, tm, _, _ = J.imdbn_values(tiny["layers"], tiny["joint"], tiny["K"], img, gt, 3, "entropy", PhiloxStream(4), 1.5)
+    tj, tm, _, _ = B.imdbn_values(tiny["layers"], tiny["joint"], tiny["K"], img, gt, 3, "entropy", PhiloxStream(4), 1.5)
     assert np.allclose(lbj.numpy(), tj.mean(1), rtol=1e-13) and np.allclose(lbm.numpy(), tm.mean(1), rtol=1e-13)
     mj, mm = iMDBN.log_likelihood_bound(m, torch.from_numpy(img), y, 1.5, n_samples=3, seed=4)
     assert torch.equal(mj, lbj) and torch.equal(mm, lbm)
     isj, ism = LK.imdbn_log_likelihood_is(m, torch.from_numpy(img), y, 1.5, n_samples=3, seed=4)
-    tj, tm, _, _ = J.imdbn_values(tiny["layers"], tiny["joint"], tiny["K"], img, gt, 3, "logq", PhiloxStream(4), 1.5)
-    assert np.allclose(isj.numpy(), [J.logmeanexp(r) for r in tj], rtol=1e-13) and np.allclose(ism.numpy(), [J.logmeanexp(r) for r in tm], rtol=1e-13)
+    tj, tm, _, _ = B.imdbn_values(tiny["layers"], tiny["joint"], tiny["K"], img, gt, 3, "logq", PhiloxStream(4), 1.5)
+    assert np.allclose(isj.numpy(), [A.logmeanexp(r) for r in tj], rtol=1e-13) and np.allclose(ism.numpy(), [A.logmeanexp(r) for r in tm], rtol=1e-13)
     assert (ism >= isj).all()                                              # summing the label out cannot lose mass
     with pytest.raises(ValueError):
         LK.imdbn_sample_values(m, torch.from_numpy(img), y, 0.0, mode="mean")
@@ -175,7 +160,7 @@ def test_evaluate_over_a_ragged_loader_equals_the_one_shot_mean(double, tiny):
     assert E.get_rng().offset == 0
     # one private draw source over all batches: the batches' draws follow each other
     ps = PhiloxStream(6)
-    parts = [J.imdbn_values(tiny["layers"], tiny["joint"], tiny["K"], img[s:s + 4], gt[s:s + 4], 3, "entropy", ps, 2.0)[:2] for s in (0, 4, 8)]
+    parts = [B.imdbn_values(tiny["layers"], tiny["joint"], tiny["K"], img[s:s + 4], gt[s:s + 4], 3, "entropy", ps, 2.0)[:2] for s in (0, 4, 8)]
     wj, wm = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
     assert res["n"] == 11 and res["log_z_joint"] == 2.0 and res["se"] is None and res["ess"] is None and res["n_samples"] == 3
     assert res["mean_joint_bound"] == pytest.approx(wj.mean(), rel=1e-12) and res["mean_image_bound"] == pytest.approx(wm.mean(), rel=1e-12)

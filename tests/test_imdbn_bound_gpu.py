@@ -1,7 +1,7 @@
 """GPU: imdbn_sample_values / imdbn_lower_bound / imdbn_log_likelihood_is / evaluate_imdbn_bound of imdbn/utils/likelihood.py on the
-engine against the numpy twin (tests/joint_ais_oracle.py).
+engine against the numpy twin (tests/bound_oracle.py).
 
-Stack 100-40-20 under the joint RBM (20 + 4) <-> 16 (joint_ais_cases.PATH), 5 rows x 3 samples.  The seed was chosen on the CPU so that
+Stack 100-40-20 under the joint RBM (20 + 4) <-> 16 (anneal_cases.PATH), 5 rows x 3 samples.  The seed was chosen on the CPU so that
 the twin's smallest Bernoulli margin |p - u| is >= 1e-5 in both modes (asserted first), so the sampled code z must be the twin's
 exactly.  The values are held to the sum of the per-layer bounds of test_dbn_bound_gpu.py, (V_l + H_l) * 1e-5 per image layer, plus the
 label_loglik bound H_joint * 1e-5 of test_joint_ais_gpu.py, plus 1e-9 |value|."""
@@ -9,35 +9,17 @@ import numpy as np
 import pytest
 import torch
 
-import joint_ais_cases as Cs
-import joint_ais_oracle as J
+import anneal_cases as Cs
+import bound_oracle as B
+from likelihood_gpu import DEV, _native, close, device_rbm  # noqa: F401  (the fixture, by name)
 from oracle.draws import PhiloxStream
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _native():
-    import __graft_entry__ as ge
-    ge.build()
-    from imdbn import engine as E
-    E.set_engine_for_testing(None)
-    yield E.get_hip_engine()
-
-
-def _rbm(W, b, c, groups=None):
-    from imdbn.models import RBM
-    r = RBM(W.shape[0], W.shape[1], 0.1, 0.0, 0.5, softmax_groups=groups).to(DEV)
-    r.W.data.copy_(torch.from_numpy(W))
-    r.vis_bias.data.copy_(torch.from_numpy(b))
-    r.hid_bias.data.copy_(torch.from_numpy(c))
-    return r
 
 
 class _Stack:
     def __init__(self, layers):
-        self.layers = [_rbm(*l) for l in layers]
+        self.layers = [device_rbm(l) for l in layers]
 
 
 class _Model:
@@ -45,7 +27,7 @@ class _Model:
 
     def __init__(self, layers, joint, K):
         Dz = joint[0].shape[0] - K
-        self.image_idbn, self.joint_rbm, self.num_labels = _Stack(layers), _rbm(*joint, groups=[(Dz, Dz + K)]), K
+        self.image_idbn, self.joint_rbm, self.num_labels = _Stack(layers), device_rbm(joint, groups=[(Dz, Dz + K)]), K
         self.val_loader = self.dataloader = self.wandb_run = None
 
 
@@ -63,7 +45,7 @@ def test_sample_values_and_the_sampled_code_match_the_twin(path, mode):
     from imdbn import engine as E
     from imdbn.utils import likelihood as LK
     p = path
-    tj, tm, margin, z = J.imdbn_values(p["layers"], p["joint"], p["K"], p["img"], p["gt"], p["S"], mode, PhiloxStream(Cs.PATH_SEED), 3.25)
+    tj, tm, margin, z = B.imdbn_values(p["layers"], p["joint"], p["K"], p["img"], p["gt"], p["S"], mode, PhiloxStream(Cs.PATH_SEED), 3.25)
     print(f"{mode}: twin margin {margin:.3g}")
     assert margin >= Cs.MARGIN
     img, y = torch.from_numpy(p["img"]).to(DEV), torch.from_numpy(p["gt"]).to(DEV)
@@ -77,9 +59,7 @@ def test_sample_values_and_the_sampled_code_match_the_twin(path, mode):
         acc, cur = E.get_hip_engine().bound_step(r, cur, rng, acc=acc, mode=mode)
     assert np.array_equal(cur.cpu().numpy(), z)
     for what, got, want in (("joint", wj, tj), ("image", wm, tm)):
-        err = np.abs(got.cpu().numpy() - want)
-        print(f"{mode} {what}: max |device - twin| {err.max():.3g} (tolerance {p['tol']:.3g})")
-        assert (err <= p["tol"] + 1e-9 * np.abs(want)).all()
+        close(got.cpu().numpy(), want, p["tol"] + 1e-9 * np.abs(want), f"{mode} {what}")
     # the two values of a sample differ by the exact log p(y | z) of its code
     jj, mm = E.get_hip_engine().label_loglik(p["model"].joint_rbm, cur, p["K"], y.repeat_interleave(p["S"], 0))
     assert torch.allclose((wj - wm).reshape(-1), jj - mm, rtol=0, atol=1e-9) and (jj <= mm).all()

@@ -1,5 +1,5 @@
 """GPU: imdbn_rbm_ais_groups / HipEngine.ais_groups and imdbn_rbm_label_loglik / HipEngine.label_loglik against the numpy twins
-(tests/joint_ais_oracle.py) and the enumerated partition function.
+(tests/anneal_oracle.py, tests/bound_oracle.py) and the enumerated partition function.
 
 AIS parity: every case's seed was chosen on the CPU so that the twin's smallest Bernoulli margin |p - u| outside the softmax groups AND
 its smallest categorical-CDF margin are >= 1e-5 (asserted first; test_joint_ais_cpu.py holds the same), so every decision of the device
@@ -14,66 +14,31 @@ import numpy as np
 import pytest
 import torch
 
-import joint_ais_cases as Cs
-import joint_ais_oracle as J
+import anneal_cases as Cs
+import anneal_oracle as A
+import bound_oracle as B
+from likelihood_gpu import DEV, _native, base_bias, close, device_rbm, eng  # noqa: F401  (the fixtures, by name)
 from oracle.draws import DrawStream, PhiloxStream
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _native():
-    import __graft_entry__ as ge
-    ge.build()
-    from imdbn import engine as E
-    E.set_engine_for_testing(None)
-    yield E.get_hip_engine()
-
-
-@pytest.fixture(scope="module")
-def eng(_native):
-    return _native
-
-
-def _rbm(c, groups="case"):
-    """The case's RBM on the device; the case's `pitch`: weight rows that many floats apart (None: the constructor's padded pitch)."""
-    from imdbn.models import RBM
-    V, H = c["W"].shape
-    g = c.get("groups") if groups == "case" else groups
-    r = RBM(V, H, 0.1, 0.0, 0.5, softmax_groups=g or None).to(DEV)
-    if c.get("pitch") is not None:
-        r.W.data = torch.empty(V, c["pitch"], device=DEV)[:, :H]
-    r.W.data.copy_(torch.from_numpy(c["W"]))
-    r.vis_bias.data.copy_(torch.from_numpy(c["b"]))
-    r.hid_bias.data.copy_(torch.from_numpy(c["c"]))
-    return r
-
-
-def _bA(c):
-    return None if c["bA"] is None else torch.from_numpy(c["bA"]).to(DEV)
 
 
 def _close(got, want, H, what):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    tol = H * 1e-5 + 1e-9 * np.abs(want)
-    err = np.abs(got - want)
-    print(f"{what}: max |device - twin| {np.nanmax(err):.3g} (tolerance {tol.min():.3g})")
-    assert (err <= tol).all(), f"{what}: {np.nanmax(err):.3g}"
+    close(got, want, H * 1e-5 + 1e-9 * np.abs(want), what)
 
 
 # ---- 1. AIS parity with the twin ----------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(Cs.PARITY))
+@pytest.mark.parametrize("name", list(Cs.GROUPS))
 def test_parity_with_the_twin(eng, name):
     from imdbn import engine as E
     from imdbn.engine import rng as R
-    c = Cs.parity_case(name)
-    logw, vK, margin, cat_margin = J.ais_groups_logw(c["W"], c["b"], c["c"], c["bA"], c["groups"], c["betas"], c["M"], PhiloxStream(c["seed"]))
+    c = Cs.case(Cs.GROUPS, name)
+    logw, vK, margin, cat_margin = A.ais_logw(c["W"], c["b"], c["c"], c["bA"], c["betas"], c["M"], PhiloxStream(c["seed"]), c["groups"])
     print(f"{name}: twin margins {margin:.3g} (Bernoulli), {cat_margin:.3g} (categorical)")
     assert margin >= Cs.MARGIN and cat_margin >= Cs.MARGIN
-    r = _rbm(c)
+    r = device_rbm(c)
     rng = E.PhiloxRng(c["seed"])
-    lw, v = eng.ais_groups(r, c["betas"], c["M"], rng, base_vis_bias=_bA(c), return_state=True)
+    lw, v = eng.ais_groups(r, c["betas"], c["M"], rng, base_vis_bias=base_bias(c), return_state=True)
     torch.cuda.synchronize()
     G = len(c["groups"])
     assert lw.dtype == torch.float64 and tuple(lw.shape) == (c["M"],) and tuple(v.shape) == (c["M"], c["V"])
@@ -87,40 +52,40 @@ def test_parity_with_the_twin(eng, name):
     if G > 0 and c["K"] > 1:
         assert route["finish_groups"], route
     if G == 0:                                                          # n_groups = 0: imdbn_rbm_ais bit for bit
-        lw0, v0 = eng.ais(r, c["betas"], c["M"], E.PhiloxRng(c["seed"]), base_vis_bias=_bA(c), return_state=True)
+        lw0, v0 = eng.ais(r, c["betas"], c["M"], E.PhiloxRng(c["seed"]), base_vis_bias=base_bias(c), return_state=True)
         assert torch.equal(lw, lw0) and torch.equal(v, v0)
     else:                                                               # deterministic, and the Philox key is the row
-        lw2 = eng.ais_groups(r, c["betas"], c["M"], E.PhiloxRng(c["seed"]), base_vis_bias=_bA(c))
+        lw2 = eng.ais_groups(r, c["betas"], c["M"], E.PhiloxRng(c["seed"]), base_vis_bias=base_bias(c))
         assert torch.equal(lw, lw2)
         if c["M"] <= 64:
-            few = eng.ais_groups(r, c["betas"], min(3, c["M"]), E.PhiloxRng(c["seed"]), base_vis_bias=_bA(c))
+            few = eng.ais_groups(r, c["betas"], min(3, c["M"]), E.PhiloxRng(c["seed"]), base_vis_bias=base_bias(c))
             assert torch.equal(few, lw[:few.numel()])
 
 
 def test_estimate_against_the_enumerated_log_z(eng):
     from imdbn.utils import likelihood as LK
-    c = Cs.truth_case(True)
-    exact = J.exact_log_z_groups(c["W"], c["b"], c["c"], c["groups"])
-    t_logw = J.ais_groups_logw(c["W"], c["b"], c["c"], c["bA"], c["groups"], c["betas"], c["M"], PhiloxStream(c["seed"]))[0]
-    _, t_se, _ = J.weight_stats(t_logw)
-    est = LK.estimate_joint_log_partition(_rbm(c), n_chains=c["M"], betas=c["betas"], base_vis_bias=_bA(c), seed=c["seed"])
+    c = Cs.groups_truth(True)
+    exact = A.exact_log_z(c["W"], c["b"], c["c"], c["groups"])
+    t_logw = A.ais_logw(c["W"], c["b"], c["c"], c["bA"], c["betas"], c["M"], PhiloxStream(c["seed"]), c["groups"])[0]
+    _, t_se, _ = A.weight_stats(t_logw)
+    est = LK.estimate_joint_log_partition(device_rbm(c), n_chains=c["M"], betas=c["betas"], base_vis_bias=base_bias(c), seed=c["seed"])
     print(f"device log Z {est['log_z']:.4f}, exact {exact:.4f}, error {(est['log_z'] - exact) / t_se:+.2f} twin se; se {est['se']:.4f} (twin {t_se:.4f})")
     assert abs(est["log_z"] - exact) <= 5 * t_se and est["se"] <= 2 * t_se          # the rule of test_ais_gpu.py
-    assert est["log_z_base"] == pytest.approx(J.log_z_base(c["V"], c["H"], c["bA"], c["groups"]), rel=1e-6)
+    assert est["log_z_base"] == pytest.approx(A.log_z_base(c["V"], c["H"], c["bA"], c["groups"]), rel=1e-6)
 
 
 # ---- 2. replay ----------------------------------------------------------------------------------------------------------
 def test_replay_tape_with_cat_tape_matches_philox_fed_the_same_decisions(eng):
     """A replay tape (uniforms AND categorical indices) against the twin fed the same tape."""
     from imdbn import engine as E
-    c = Cs.parity_case("two")
+    c = Cs.case(Cs.GROUPS, "two")
     M, G = 9, len(c["groups"])
     g = np.random.Generator(np.random.PCG64(5))
     cats = [g.integers(0, e - s, M) for _ in range(c["K"]) for s, e in c["groups"]]
-    want, vK, margin, _ = J.ais_groups_logw(c["W"], c["b"], c["c"], c["bA"], c["groups"], c["betas"], M, DrawStream(11, cat=cats))
+    want, vK, margin, _ = A.ais_logw(c["W"], c["b"], c["c"], c["bA"], c["betas"], M, DrawStream(11, cat=cats), c["groups"])
     assert margin >= Cs.MARGIN
     src = DrawStream(11, cat=cats)
-    lw, v = eng.ais_groups(_rbm(c), c["betas"], M, E.ReplayRng(src), base_vis_bias=_bA(c), return_state=True)
+    lw, v = eng.ais_groups(device_rbm(c), c["betas"], M, E.ReplayRng(src), base_vis_bias=base_bias(c), return_state=True)
     assert src.exhausted_cat() and len(cats) == c["K"] * G
     vd = v.cpu().numpy()
     assert np.array_equal(vd, vK)
@@ -153,8 +118,8 @@ def _raw(eng, r, betas, M, short=0, n_groups=None):
 
 @pytest.mark.parametrize("what,code", [("K0", -1), ("flat", -1), ("first", -1), ("last", -1), ("M0", -1), ("short", -2), ("groups5", -5)])
 def test_invalid_arguments_launch_nothing(eng, what, code):
-    c = Cs.parity_case("odd")
-    r = _rbm(c)
+    c = Cs.case(Cs.GROUPS, "odd")
+    r = device_rbm(c)
     betas = {"flat": [0, 0.5, 0.5, 1], "first": [0.1, 0.5, 1], "last": [0, 0.5, 0.9], "K0": [0.0]}.get(what, [0, 0.25, 0.5, 1])
     msg, logw = _raw(eng, r, betas, 0 if what == "M0" else 5, short=1 if what == "short" else 0, n_groups=5 if what == "groups5" else None)
     print(what, "->", msg)
@@ -171,12 +136,12 @@ def test_invalid_arguments_launch_nothing(eng, what, code):
 
 def test_the_binary_call_still_refuses_groups_and_parameters_are_untouched(eng):
     from imdbn import engine as E
-    c = Cs.parity_case("odd")
-    r = _rbm(c)
+    c = Cs.case(Cs.GROUPS, "odd")
+    r = device_rbm(c)
     W0, b0, c0 = r.W.data.clone(), r.vis_bias.data.clone(), r.hid_bias.data.clone()
     with pytest.raises(E.EngineError):
         eng.ais(r, c["betas"], 5, E.PhiloxRng(1))
-    eng.ais_groups(r, c["betas"], 5, E.PhiloxRng(1), base_vis_bias=_bA(c))
+    eng.ais_groups(r, c["betas"], 5, E.PhiloxRng(1), base_vis_bias=base_bias(c))
     assert torch.equal(r.W.data, W0) and torch.equal(r.vis_bias.data, b0) and torch.equal(r.hid_bias.data, c0)
 
 
@@ -189,8 +154,8 @@ def test_label_loglik_against_the_twin(eng, name, N, real, pad):
     gt[1] = -1                                                            # one label out of range: NaN joint, finite marg, no fault
     if N > 64:
         gt[65] = K
-    wj, wm = J.label_loglik(c["W"], c["b"], c["c"], c["z"], Dz, K, gt)
-    r = _rbm(c, groups=[(Dz, Dz + K)])
+    wj, wm = B.label_loglik(c["W"], c["b"], c["c"], c["z"], Dz, K, gt)
+    r = device_rbm(c, groups=[(Dz, Dz + K)])
     zbuf = torch.full((N, Dz + pad), 7.0, device=DEV)                     # ldz > Dz: the columns behind the code are not read
     zbuf[:, :Dz] = torch.from_numpy(c["z"]).to(DEV)
     z = zbuf[:, :Dz]
@@ -223,7 +188,7 @@ def test_label_loglik_invalid_arguments_name_the_value(eng, what):
     from imdbn.engine import native as N
     c = Cs.label_case("small", 5, False)
     Dz, K = c["Dz"], c["K"]
-    r = _rbm(c, groups=[(Dz, Dz + K)])
+    r = device_rbm(c, groups=[(Dz, Dz + K)])
     d = eng._desc(r, False)
     z = torch.from_numpy(c["z"]).to(DEV)
     gt = torch.from_numpy(c["gt"]).to(DEV)

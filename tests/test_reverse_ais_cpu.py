@@ -1,11 +1,11 @@
-"""CPU-only: the numpy twin of imdbn_rbm_reverse_ais (tests/reverse_ais_oracle.py) against the enumerated annealing model, the host
+"""CPU-only: the numpy twin of imdbn_rbm_reverse_ais (tests/anneal_oracle.py) against the enumerated annealing model, the host
 logic of the reverse-AIS functions of imdbn/utils/likelihood.py on a test double of the engine, the draw schedule and the exports'
 declaration and binding.
 
 Twin against enumeration: V = 10, H = 6, W ~ N(0, 1), biases ~ N(0, 0.5), K = 20 linear temperatures, N = 4 rows drawn from the
 enumerated annealing model x M = 256 chains, with and without a base-rate bias; every row's estimate within 3 of its own standard
 errors of log p_ann(x).  Over the Philox seeds 1..8 all eight pass with and without b_A; the largest error was 2.05 se, se
-0.028..0.045, ess 170..213 of 256.  Seed 1 is pinned (reverse_ais_cases.TRUTH_SEED): at most 1.02 se."""
+0.028..0.045, ess 170..213 of 256.  Seed 1 is pinned (anneal_cases.TRUTH_SEED): at most 1.02 se."""
 import os
 import pickle
 import re
@@ -14,31 +14,15 @@ import numpy as np
 import pytest
 import torch
 
-import reverse_ais_cases as Cs
-import reverse_ais_oracle as RA
+import anneal_cases as Cs
+import anneal_oracle as A
+from bound_oracle import double, host_rbm  # noqa: F401  (the fixture, by name)
 from imdbn import engine as E
 from imdbn.engine import native, rng as R
-from imdbn.models import RBM
 from imdbn.utils import likelihood as LK
 from oracle.draws import PhiloxStream
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture()
-def double():
-    eng = RA.ReverseAisOracleEngine()
-    E.set_engine_for_testing(eng)
-    yield eng
-    E.set_engine_for_testing(None)
-
-
-def _rbm(c, groups=None):
-    r = RBM(c["V"], c["H"], 0.1, 0.0, 0.5, softmax_groups=groups or None).to("cpu")
-    r.W.data = torch.from_numpy(c["W"].copy())
-    r.vis_bias.data = torch.from_numpy(c["b"].copy())
-    r.hid_bias.data = torch.from_numpy(c["c"].copy())
-    return r
 
 
 def _bA(c):
@@ -51,8 +35,8 @@ _TRUTH = {}
 def _truth(with_bA):
     """(case, rows [N, V], exact log p_ann of the rows [N]), enumerated once."""
     if with_bA not in _TRUTH:
-        c = Cs.truth_params(with_bA)
-        lp, st = RA.annealing_model(c["W"], c["b"], c["c"], c["bA"], c["betas"])
+        c = Cs.reverse_truth(with_bA)
+        lp, st = A.annealing_model(c["W"], c["b"], c["c"], c["bA"], c["betas"])
         _TRUTH[with_bA] = (c,) + Cs.truth_rows(lp, st)
     return _TRUTH[with_bA]
 
@@ -61,9 +45,9 @@ def _truth(with_bA):
 @pytest.mark.parametrize("with_bA", [False, True])
 def test_twin_estimate_is_within_three_standard_errors_of_the_enumerated_annealing_model(with_bA):
     c, x, want = _truth(with_bA)
-    logw, u1, _, _ = RA.reverse_ais_logw(c["W"], c["b"], c["c"], c["bA"], [], c["betas"], np.repeat(x, c["M"], 0), PhiloxStream(c["seed"]))
-    lme, se, ess = RA.row_stats(logw, c["M"])
-    got = lme - RA.log_z_base(c["V"], c["H"], c["bA"], [])
+    logw, u1, _, _ = A.reverse_ais_logw(c["W"], c["b"], c["c"], c["bA"], [], c["betas"], np.repeat(x, c["M"], 0), PhiloxStream(c["seed"]))
+    lme, se, ess = A.row_stats(logw, c["M"])
+    got = lme - A.log_z_base(c["V"], c["H"], c["bA"], [])
     print(f"b_A {with_bA}: log p_hat {got.round(4)}, exact {want.round(4)}, errors {((got - want) / se).round(2)} se, se {se.round(4)}, ess {ess.round(0)}")
     assert u1.shape == (c["N"] * c["M"], c["V"]) and set(np.unique(u1)) <= {0.0, 1.0}
     assert (se > 0).all() and (se <= 0.06).all()
@@ -74,11 +58,11 @@ def test_the_enumerated_annealing_model_approaches_the_rbm_as_the_ladder_grows()
     """p_ann is a distribution for every K, and its distance from the RBM shrinks with K (what the estimator bounds is p_ann)."""
     W, b, c, bA = Cs.params(6, 4, 3, 1.0)
     vs = ((np.arange(1 << 6)[:, None] >> np.arange(6)[None, :]) & 1).astype(np.float64)
-    t = vs @ b.astype(np.float64) + RA.softplus(vs @ W.astype(np.float64) + c).sum(1)
+    t = vs @ b.astype(np.float64) + A.softplus(vs @ W.astype(np.float64) + c).sum(1)
     log_p = t - (t.max() + np.log(np.exp(t - t.max()).sum()))
     kl = []
     for K in (1, 10, 100):
-        lp, _ = RA.annealing_model(W, b, c, bA, Cs.linear(K))
+        lp, _ = A.annealing_model(W, b, c, bA, Cs.linear(K))
         assert np.exp(lp).sum() == pytest.approx(1.0, abs=1e-12)
         kl.append(float((np.exp(lp) * (lp - log_p)).sum()))
     print("KL(p_ann || p_RBM) for K = 1, 10, 100:", np.round(kl, 5))
@@ -90,34 +74,34 @@ def test_one_temperature_is_one_gibbs_step_from_the_start_state():
     W, b, c, bA = Cs.params(9, 4, 5, 1.0)
     x = Cs.start_rows(6, 9, 1)
     ps = PhiloxStream(3)
-    logw, u1, _, _ = RA.reverse_ais_logw(W, b, c, bA, [], np.array([0, 1], np.float32), x, ps)
+    logw, u1, _, _ = A.reverse_ais_logw(W, b, c, bA, [], np.array([0, 1], np.float32), x, ps)
     assert ps.log == [("u", (6, 4)), ("u", (6, 9))]
     q = PhiloxStream(3)
-    h = (RA.sigmoid((x @ W + c).astype(np.float64)) > q.uniform((6, 4))).astype(np.float32)
-    want_u = (RA.sigmoid((h @ W.T + b).astype(np.float64)) > q.uniform((6, 9))).astype(np.float32)
+    h = (A.sigmoid((x @ W + c).astype(np.float64)) > q.uniform((6, 4))).astype(np.float32)
+    want_u = (A.sigmoid((h @ W.T + b).astype(np.float64)) > q.uniform((6, 9))).astype(np.float32)
     assert np.array_equal(u1, want_u)
-    nf = x.astype(np.float64) @ b + RA.softplus((x @ W + c).astype(np.float64)).sum(1)
-    d1 = u1.astype(np.float64) @ (b.astype(np.float64) - bA) + (RA.softplus((u1 @ W + c).astype(np.float64)) - np.log(2.0)).sum(1)
+    nf = x.astype(np.float64) @ b + A.softplus((x @ W + c).astype(np.float64)).sum(1)
+    d1 = u1.astype(np.float64) @ (b.astype(np.float64) - bA) + (A.softplus((u1 @ W + c).astype(np.float64)) - np.log(2.0)).sum(1)
     assert np.allclose(logw, nf - d1, rtol=1e-12, atol=1e-5)          # two fp32 summation orders in the logits
 
 
 def test_rows_that_are_not_states_are_nan_and_only_they():
-    c = Cs.parity_case("group")
+    c = Cs.case(Cs.REVERSE, "group")
     x = c["x"].copy()
     x[1, 3] = 0.5
     x[4, 20:25] = 0.0
     x[4, 21] = x[4, 23] = 1.0
-    logw, _, _, _ = RA.reverse_ais_logw(c["W"], c["b"], c["c"], c["bA"], c["groups"], c["betas"], x, PhiloxStream(1))
+    logw, _, _, _ = A.reverse_ais_logw(c["W"], c["b"], c["c"], c["bA"], c["groups"], c["betas"], x, PhiloxStream(1))
     assert np.isnan(logw[[1, 4]]).all() and np.isfinite(np.delete(logw, [1, 4])).all()
-    lme, ess = RA.rows_logmeanexp(logw, 2)
+    lme, ess = A.rows_logmeanexp(logw, 2)
     assert np.isnan(lme[[0, 2]]).all() and np.isfinite(lme[1]) and np.isnan(ess[[0, 2]]).all() and np.isfinite(ess[1])
 
 
 # ---- 2. host logic of imdbn/utils/likelihood.py on the test double ----------------------------------------------------
 @pytest.mark.parametrize("name", ["tiny_bA", "group", "one"])
 def test_schedule_is_what_the_double_consumed(double, name):
-    c = Cs.parity_case(name)
-    r = _rbm(c, c["groups"])
+    c = Cs.case(Cs.REVERSE, name)
+    r = host_rbm(c)
     rng = E.PhiloxRng(5)
     lw, u1 = double.reverse_ais(r, torch.from_numpy(c["x"]), c["betas"], rng, base_vis_bias=_bA(c), return_state=True)
     sched = R.sched_reverse_ais(c["V"], c["H"], c["groups"], c["K"])
@@ -131,8 +115,8 @@ def test_schedule_is_what_the_double_consumed(double, name):
 
 
 def test_function_matches_the_twin_keys_and_the_seed_rule(double):
-    c = Cs.parity_case("tiny_bA")
-    r = _rbm(c)
+    c = Cs.case(Cs.REVERSE, "tiny_bA")
+    r = host_rbm(c)
     x, M = c["x"], 3
     E.manual_seed(77)
     E.get_rng().advance(3)
@@ -141,25 +125,25 @@ def test_function_matches_the_twin_keys_and_the_seed_rule(double):
     assert set(res) == {"ll", "ess", "logw"}
     assert res["ll"].dtype == res["ess"].dtype == res["logw"].dtype == torch.float64
     assert res["ll"].shape == res["ess"].shape == (c["R"],) and res["logw"].shape == (c["R"], M)
-    logw, _, _, _ = RA.reverse_ais_logw(c["W"], c["b"], c["c"], c["bA"], [], c["betas"], np.repeat(x, M, 0), PhiloxStream(9))
-    lme, ess = RA.rows_logmeanexp(logw, M)
+    logw, _, _, _ = A.reverse_ais_logw(c["W"], c["b"], c["c"], c["bA"], [], c["betas"], np.repeat(x, M, 0), PhiloxStream(9))
+    lme, ess = A.rows_logmeanexp(logw, M)
     assert np.array_equal(res["logw"].numpy().reshape(-1), logw)       # row b's chains are the engine rows b M .. b M + M - 1
-    assert np.allclose(res["ll"].numpy(), lme - RA.log_z_base(c["V"], c["H"], c["bA"], []), rtol=1e-12, atol=1e-12)
+    assert np.allclose(res["ll"].numpy(), lme - A.log_z_base(c["V"], c["H"], c["bA"], []), rtol=1e-12, atol=1e-12)
     assert np.allclose(res["ess"].numpy(), ess, rtol=1e-12)
     # seed=None draws from the ambient source, from where it stands, and advances it by one schedule
     res2 = r.log_likelihood_conservative(torch.from_numpy(x), n_chains=M, n_betas=c["K"])
     assert E.get_rng().offset == 3 + 2 * c["K"]
-    logw2, _, _, _ = RA.reverse_ais_logw(c["W"], c["b"], c["c"], None, [], Cs.linear(c["K"]), np.repeat(x, M, 0), PhiloxStream(77, 3))
+    logw2, _, _, _ = A.reverse_ais_logw(c["W"], c["b"], c["c"], None, [], Cs.linear(c["K"]), np.repeat(x, M, 0), PhiloxStream(77, 3))
     assert np.array_equal(res2["logw"].numpy().reshape(-1), logw2)
-    assert np.allclose(res2["ll"].numpy(), RA.rows_logmeanexp(logw2, M)[0] - (c["V"] + c["H"]) * np.log(2.0), rtol=1e-12, atol=1e-12)
+    assert np.allclose(res2["ll"].numpy(), A.rows_logmeanexp(logw2, M)[0] - (c["V"] + c["H"]) * np.log(2.0), rtol=1e-12, atol=1e-12)
 
 
 @pytest.mark.parametrize("name", ["tiny_bA", "group"])
 def test_chunking_changes_no_bit(double, name):
     """max_rows 16 against 4096: 4 chains per row, so chunks of 4 test rows against one chunk; a chunk's draws carry its first
     global engine row."""
-    c = Cs.parity_case(name)
-    r = _rbm(c, c["groups"])
+    c = Cs.case(Cs.REVERSE, name)
+    r = host_rbm(c)
     x = torch.from_numpy(Cs.start_rows(11, c["V"], 8, c["groups"]))
     kw = dict(n_chains=4, betas=c["betas"], base_vis_bias=_bA(c), seed=6)
     one = LK.reverse_ais_log_likelihood(r, x, max_rows=4096, **kw)
@@ -179,8 +163,8 @@ def test_chunking_changes_no_bit(double, name):
 
 
 def test_bad_arguments_raise_value_error(double):
-    c = Cs.parity_case("tiny")
-    r = _rbm(c)
+    c = Cs.case(Cs.REVERSE, "tiny")
+    r = host_rbm(c)
     x = torch.from_numpy(c["x"])
     with pytest.raises(ValueError):
         LK.reverse_ais_log_likelihood(r, x, n_chains=0, n_betas=3)
@@ -197,7 +181,7 @@ def test_bad_arguments_raise_value_error(double):
     with pytest.raises(ValueError):                                     # a replay tape cannot be keyed on the global row
         with E.use_rng(E.ReplayRng(PhiloxStream(1))):
             LK.reverse_ais_log_likelihood(r, x, n_chains=2, n_betas=3, max_rows=4)
-    grouped = _rbm(c, [(15, 20)])                                       # the AIS side of the sandwich stays binary-only
+    grouped = host_rbm(c, [(15, 20)])                                       # the AIS side of the sandwich stays binary-only
     with pytest.raises(ValueError):
         LK.evaluate_log_likelihood_sandwich(grouped, loader=[x], n_chains=4, n_betas=3)
     with pytest.raises(ValueError):
@@ -261,8 +245,8 @@ def test_sandwich_over_a_ragged_loader_on_the_golden_stack(double):
 
 def test_sandwich_reports_the_statistics_of_estimate_log_partition(double):
     """The AIS side of the sandwich under a seed IS estimate_log_partition under that seed: equal scalars, not merely close."""
-    c = Cs.parity_case("tiny_bA")
-    r = _rbm(c)
+    c = Cs.case(Cs.REVERSE, "tiny_bA")
+    r = host_rbm(c)
     for M in (1, 5):                                                    # one chain: se = 0
         kw = dict(n_chains=M, betas=c["betas"], base_vis_bias=_bA(c), seed=4)
         res = LK.evaluate_log_likelihood_sandwich(r, loader=[torch.from_numpy(c["x"])], n_chains_reverse=2, **kw)
@@ -319,8 +303,8 @@ def test_evaluate_conservative_bound_over_a_ragged_loader(double):
 
 def test_existing_entry_points_keep_their_results(double):
     """The functions that were there return what they returned: the double's ais / bound_step are the parents' own."""
-    c = Cs.parity_case("tiny_bA")
-    r = _rbm(c)
+    c = Cs.case(Cs.REVERSE, "tiny_bA")
+    r = host_rbm(c)
     a = LK.estimate_log_partition(r, n_chains=5, betas=c["betas"], base_vis_bias=_bA(c), seed=1)
     LK.reverse_ais_log_likelihood(r, torch.from_numpy(c["x"]), n_chains=2, betas=c["betas"], seed=1)
     b = LK.estimate_log_partition(r, n_chains=5, betas=c["betas"], base_vis_bias=_bA(c), seed=1)

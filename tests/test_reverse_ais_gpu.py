@@ -1,5 +1,5 @@
 """GPU: imdbn_rbm_reverse_ais / imdbn_rows_logmeanexp and the reverse-AIS functions of imdbn/utils/likelihood.py against the numpy
-twin (tests/reverse_ais_oracle.py) and the enumerated annealing model.
+twin (tests/anneal_oracle.py) and the enumerated annealing model.
 
 Parity: every case's seed was chosen on the CPU so that the twin's smallest Bernoulli margin |p - u| is >= 1e-5 and its smallest
 categorical margin >= 1e-6 (asserted first), so every decision of the device must be the twin's: the final states u_1 are compared
@@ -13,66 +13,24 @@ import numpy as np
 import pytest
 import torch
 
-import reverse_ais_cases as Cs
-import reverse_ais_oracle as RA
+import anneal_cases as Cs
+import anneal_oracle as A
+from likelihood_gpu import DEV, _native, base_bias, close, dev, device_rbm, eng, twin  # noqa: F401  (the fixtures, by name)
 from oracle.draws import DrawStream, PhiloxStream
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _native():
-    import __graft_entry__ as ge
-    ge.build()
-    from imdbn import engine as E
-    E.set_engine_for_testing(None)
-    yield E.get_hip_engine()
-
-
-@pytest.fixture(scope="module")
-def eng(_native):
-    return _native
-
-
-def _rbm(c, pitch=None, groups=None):
-    """The case's RBM on the device; `pitch`: weight rows `pitch` floats apart (None: the constructor's padded pitch)."""
-    from imdbn.models import RBM
-    groups = c.get("groups") if groups is None else groups
-    r = RBM(c["V"], c["H"], 0.1, 0.0, 0.5, softmax_groups=groups or None).to(DEV)
-    if pitch is not None:
-        r.W.data = torch.empty(c["V"], pitch, device=DEV)[:, :c["H"]]
-    r.W.data.copy_(torch.from_numpy(c["W"]))
-    r.vis_bias.data.copy_(torch.from_numpy(c["b"]))
-    r.hid_bias.data.copy_(torch.from_numpy(c["c"]))
-    return r
-
-
-def _bA(c):
-    return None if c["bA"] is None else torch.from_numpy(c["bA"]).to(DEV)
-
-
-def _x(c):
-    return torch.from_numpy(c["x"]).to(DEV)
-
-
-_TWIN = {}
 
 
 def _twin(name):
-    """(case, logw, u_1, margin, categorical margin) of a parity case under its pinned Philox seed, computed once."""
-    if name not in _TWIN:
-        c = Cs.parity_case(name)
-        _TWIN[name] = (c,) + RA.reverse_ais_logw(c["W"], c["b"], c["c"], c["bA"], c["groups"], c["betas"], c["x"], PhiloxStream(c["seed"]))
-    return _TWIN[name]
+    """(case, logw, u_1, margin, categorical margin) of a parity case under its pinned Philox seed."""
+    def run():
+        c = Cs.case(Cs.REVERSE, name)
+        return (c,) + A.reverse_ais_logw(c["W"], c["b"], c["c"], c["bA"], c["groups"], c["betas"], c["x"], PhiloxStream(c["seed"]))
+    return twin(("reverse_ais", name), run)
 
 
 def _close(got, want, H, what):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    tol = 2 * H * 1e-5 + 1e-9 * np.abs(want)
-    err = np.abs(got - want)
-    print(f"{what}: max |logw - twin| {err.max():.3g} (tolerance {tol.min():.3g})")
-    assert (err <= tol).all(), f"{what}: {err.max():.3g}"
+    close(got, want, 2 * H * 1e-5 + 1e-9 * np.abs(want), what)
 
 
 # ---- 1. parity with the twin ------------------------------------------------------------------------------------------
@@ -86,9 +44,9 @@ def test_parity_with_the_twin(eng, name, pitch):
     c, logw, u1, margin, cat_margin = _twin(name)
     print(f"{name}: twin margin {margin:.3g}, categorical margin {cat_margin:.3g}")
     assert margin >= Cs.MARGIN and cat_margin >= Cs.CAT_MARGIN
-    r = _rbm(c, pitch)
+    r = device_rbm(c, pitch)
     rng = E.PhiloxRng(c["seed"])
-    lw, u = eng.reverse_ais(r, _x(c), c["betas"], rng, base_vis_bias=_bA(c), return_state=True)
+    lw, u = eng.reverse_ais(r, dev(c["x"]), c["betas"], rng, base_vis_bias=base_bias(c), return_state=True)
     torch.cuda.synchronize()
     assert lw.dtype == torch.float64 and tuple(lw.shape) == (c["R"],) and tuple(u.shape) == (c["R"], c["V"])
     assert rng.offset == c["K"] * (2 + len(c["groups"])) == len(R.sched_reverse_ais(c["V"], c["H"], c["groups"], c["K"]))
@@ -99,11 +57,11 @@ def test_parity_with_the_twin(eng, name, pitch):
 
 def test_replay_tape_matches_the_twin_fed_the_same_tape(eng):
     from imdbn import engine as E
-    c = Cs.parity_case(Cs.REPLAY_CASE)
-    want, u1, margin, _ = RA.reverse_ais_logw(c["W"], c["b"], c["c"], c["bA"], [], c["betas"], c["x"], DrawStream(Cs.REPLAY_SEED))
+    c = Cs.case(Cs.REVERSE, Cs.REPLAY_CASE)
+    want, u1, margin, _ = A.reverse_ais_logw(c["W"], c["b"], c["c"], c["bA"], [], c["betas"], c["x"], DrawStream(Cs.REPLAY_SEED))
     print(f"replay: twin margin {margin:.3g}")
     assert margin >= Cs.MARGIN
-    lw, u = eng.reverse_ais(_rbm(c), _x(c), c["betas"], E.ReplayRng(DrawStream(Cs.REPLAY_SEED)), base_vis_bias=_bA(c), return_state=True)
+    lw, u = eng.reverse_ais(device_rbm(c), dev(c["x"]), c["betas"], E.ReplayRng(DrawStream(Cs.REPLAY_SEED)), base_vis_bias=base_bias(c), return_state=True)
     assert np.array_equal(u.cpu().numpy(), u1)
     _close(lw.cpu().numpy(), want, c["H"], "replay")
 
@@ -112,21 +70,21 @@ def test_replay_tape_matches_the_twin_fed_the_same_tape(eng):
 @pytest.mark.parametrize("with_bA", [False, True])
 def test_estimate_against_the_enumerated_annealing_model(eng, with_bA):
     from imdbn.utils import likelihood as LK
-    c = Cs.truth_params(with_bA)
-    lp, st = RA.annealing_model(c["W"], c["b"], c["c"], c["bA"], c["betas"])
+    c = Cs.reverse_truth(with_bA)
+    lp, st = A.annealing_model(c["W"], c["b"], c["c"], c["bA"], c["betas"])
     x, want = Cs.truth_rows(lp, st)
-    t_logw, _, _, _ = RA.reverse_ais_logw(c["W"], c["b"], c["c"], c["bA"], [], c["betas"], np.repeat(x, c["M"], 0), PhiloxStream(c["seed"]))
-    _, t_se, _ = RA.row_stats(t_logw, c["M"])
-    res = LK.reverse_ais_log_likelihood(_rbm(c), torch.from_numpy(x).to(DEV), n_chains=c["M"], betas=c["betas"], base_vis_bias=_bA(c),
+    t_logw, _, _, _ = A.reverse_ais_logw(c["W"], c["b"], c["c"], c["bA"], [], c["betas"], np.repeat(x, c["M"], 0), PhiloxStream(c["seed"]))
+    _, t_se, _ = A.row_stats(t_logw, c["M"])
+    res = LK.reverse_ais_log_likelihood(device_rbm(c), torch.from_numpy(x).to(DEV), n_chains=c["M"], betas=c["betas"], base_vis_bias=base_bias(c),
                                         seed=c["seed"])
     got = res["ll"].cpu().numpy()
-    lme, se, ess = RA.row_stats(res["logw"].cpu().numpy(), c["M"])
+    lme, se, ess = A.row_stats(res["logw"].cpu().numpy(), c["M"])
     print(f"b_A {with_bA}: device {got.round(4)}, exact {want.round(4)}, errors {((got - want) / t_se).round(2)} twin se; "
           f"se {se.round(4)} (twin {t_se.round(4)}), ess {ess.round(1)}")
     assert res["ll"].dtype == torch.float64 and got.shape == (c["N"],) and tuple(res["logw"].shape) == (c["N"], c["M"])
     assert (np.abs(got - want) <= 5 * t_se).all()
     assert (se <= 2 * t_se).all()
-    assert np.allclose(got, lme - RA.log_z_base(c["V"], c["H"], c["bA"], []), rtol=1e-12, atol=1e-12)
+    assert np.allclose(got, lme - A.log_z_base(c["V"], c["H"], c["bA"], []), rtol=1e-12, atol=1e-12)
     assert np.allclose(res["ess"].cpu().numpy(), ess, rtol=1e-12)
 
 
@@ -135,13 +93,13 @@ def test_estimate_against_the_enumerated_annealing_model(eng, with_bA):
 def test_determinism_draw_count_and_row_keyed_draws(eng, name):
     from imdbn import engine as E
     from imdbn.engine import rng as R
-    c = Cs.parity_case(name)
-    r = _rbm(c)
-    bA = _bA(c)
+    c = Cs.case(Cs.REVERSE, name)
+    r = device_rbm(c)
+    bA = base_bias(c)
     sched = R.sched_reverse_ais(c["V"], c["H"], c["groups"], c["K"])
     rng = E.PhiloxRng(c["seed"])
-    a = eng.reverse_ais(r, _x(c), c["betas"], rng, base_vis_bias=bA)
-    b = eng.reverse_ais(r, _x(c), c["betas"], E.PhiloxRng(c["seed"]), base_vis_bias=bA)
+    a = eng.reverse_ais(r, dev(c["x"]), c["betas"], rng, base_vis_bias=bA)
+    b = eng.reverse_ais(r, dev(c["x"]), c["betas"], E.PhiloxRng(c["seed"]), base_vis_bias=bA)
     assert torch.equal(a, b)
     assert rng.offset == len(sched)
     # the next call draws what it would after skipping the schedule
@@ -164,10 +122,10 @@ def test_python_function_is_chunk_invariant(eng, name):
     """11 test rows x 4 chains: one chunk of 44 engine rows against chunks of 16, 16 and 12 (all within one 64-row multiple)."""
     from imdbn import engine as E
     from imdbn.utils import likelihood as LK
-    c = Cs.parity_case(name)
-    r = _rbm(c)
+    c = Cs.case(Cs.REVERSE, name)
+    r = device_rbm(c)
     x = torch.from_numpy(Cs.start_rows(11, c["V"], 8, c["groups"])).to(DEV)
-    kw = dict(n_chains=4, betas=c["betas"], base_vis_bias=_bA(c), seed=6)
+    kw = dict(n_chains=4, betas=c["betas"], base_vis_bias=base_bias(c), seed=6)
     one = LK.reverse_ais_log_likelihood(r, x, max_rows=4096, **kw)
     many = LK.reverse_ais_log_likelihood(r, x, max_rows=16, **kw)
     for k in ("ll", "ess", "logw"):
@@ -187,7 +145,7 @@ def test_rows_logmeanexp_against_numpy(eng, N, M):
     lme, ess = eng.rows_logmeanexp(torch.from_numpy(x).to(DEV), M)
     torch.cuda.synchronize()
     lme, ess = lme.cpu().numpy(), ess.cpu().numpy()
-    want_l, want_e = RA.rows_logmeanexp(x, M)
+    want_l, want_e = A.rows_logmeanexp(x, M)
     keep = np.arange(N) != 1
     assert lme.dtype == np.float64 and lme.shape == ess.shape == (N,)
     assert np.isnan(lme[1]) and np.isnan(ess[1]) and np.isfinite(lme[keep]).all() and np.isfinite(ess[keep]).all()
@@ -226,9 +184,9 @@ def _raw(eng, r, x, betas, R_=None, K=None, short=0, ldv=None, null=None):
 @pytest.mark.parametrize("what,code", [("R0", -1), ("K0", -1), ("flat", -1), ("first", -1), ("last", -1), ("null_v", -1), ("null_betas", -1),
                                        ("null_rng", -1), ("ldv", -1), ("short", -2)])
 def test_invalid_arguments_launch_nothing(eng, what, code):
-    c = Cs.parity_case("tiny")
-    r = _rbm(c)
-    x = _x(c)
+    c = Cs.case(Cs.REVERSE, "tiny")
+    r = device_rbm(c)
+    x = dev(c["x"])
     betas = {"flat": [0, 0.5, 0.5, 1], "first": [0.1, 0.5, 1], "last": [0, 0.5, 0.9], "K0": [0.0]}.get(what, [0, 0.25, 0.5, 1])
     msg, logw = _raw(eng, r, x, betas, R_=0 if what == "R0" else None, short=1 if what == "short" else 0,
                      ldv=c["V"] - 1 if what == "ldv" else None, null=what[5:] if what.startswith("null_") else None)
@@ -246,33 +204,33 @@ def test_invalid_arguments_launch_nothing(eng, what, code):
 
 def test_null_logw_and_python_entry_raise_engine_error(eng):
     from imdbn import engine as E
-    c = Cs.parity_case("tiny")
-    msg, _ = _raw(eng, _rbm(c), _x(c), [0, 0.5, 1], null="logw")
+    c = Cs.case(Cs.REVERSE, "tiny")
+    msg, _ = _raw(eng, device_rbm(c), dev(c["x"]), [0, 0.5, 1], null="logw")
     assert msg is not None and "rc=-1)" in msg and "logw" in msg
     with pytest.raises(E.EngineError):
-        eng.reverse_ais(_rbm(c), _x(c), [0, 0.6, 0.4, 1], E.PhiloxRng(1))
+        eng.reverse_ais(device_rbm(c), dev(c["x"]), [0, 0.6, 0.4, 1], E.PhiloxRng(1))
     with pytest.raises(E.EngineError):
-        eng.reverse_ais(_rbm(c), _x(c)[:, :7], [0, 1], E.PhiloxRng(1))
+        eng.reverse_ais(device_rbm(c), dev(c["x"])[:, :7], [0, 1], E.PhiloxRng(1))
 
 
 def test_rows_that_are_not_states_are_nan_and_only_they(eng):
     from imdbn import engine as E
-    c = Cs.parity_case("group")
-    r = _rbm(c)
+    c = Cs.case(Cs.REVERSE, "group")
+    r = device_rbm(c)
     x = c["x"].copy()
     x[1, 3] = 0.5
     x[4, 20:25] = 0.0
     x[4, 21] = x[4, 23] = 1.0
-    lw = eng.reverse_ais(r, torch.from_numpy(x).to(DEV), c["betas"], E.PhiloxRng(c["seed"]), base_vis_bias=_bA(c)).cpu().numpy()
+    lw = eng.reverse_ais(r, torch.from_numpy(x).to(DEV), c["betas"], E.PhiloxRng(c["seed"]), base_vis_bias=base_bias(c)).cpu().numpy()
     assert np.isnan(lw[[1, 4]]).all() and np.isfinite(np.delete(lw, [1, 4])).all()
     # the good rows are the rows of the clean run: a bad row disturbs nobody
     _, logw, _, _, _ = _twin("group")
     _close(np.delete(lw, [1, 4]), np.delete(logw, [1, 4]), c["H"], "good rows next to NaN rows")
     # a Bernoulli-only RBM: the 0/1 check alone
-    c = Cs.parity_case("tiny")
+    c = Cs.case(Cs.REVERSE, "tiny")
     x = c["x"].copy()
     x[2, 19] = 0.5
-    lw = eng.reverse_ais(_rbm(c), torch.from_numpy(x).to(DEV), c["betas"], E.PhiloxRng(1)).cpu().numpy()
+    lw = eng.reverse_ais(device_rbm(c), torch.from_numpy(x).to(DEV), c["betas"], E.PhiloxRng(1)).cpu().numpy()
     assert np.isnan(lw[2]) and np.isfinite(np.delete(lw, 2)).all()
 
 
@@ -280,15 +238,15 @@ def test_rows_that_are_not_states_are_nan_and_only_they(eng):
 @pytest.mark.parametrize("name", ["mid_bA", "wide_bA"])
 def test_parameters_free_energy_and_ais_are_untouched(eng, name):
     from imdbn import engine as E
-    c = Cs.parity_case(name)
-    r = _rbm(c)
-    x = _x(c)                                                          # R rows: the workspace of the reverse call
+    c = Cs.case(Cs.REVERSE, name)
+    r = device_rbm(c)
+    x = dev(c["x"])                                                          # R rows: the workspace of the reverse call
     W0, b0, c0 = r.W.data.clone(), r.vis_bias.data.clone(), r.hid_bias.data.clone()
     F0 = eng.free_energy(r, x)
-    A0 = eng.ais(r, c["betas"], c["R"], E.PhiloxRng(3), base_vis_bias=_bA(c))
-    eng.reverse_ais(r, x, c["betas"], E.PhiloxRng(c["seed"]), base_vis_bias=_bA(c))
+    A0 = eng.ais(r, c["betas"], c["R"], E.PhiloxRng(3), base_vis_bias=base_bias(c))
+    eng.reverse_ais(r, x, c["betas"], E.PhiloxRng(c["seed"]), base_vis_bias=base_bias(c))
     F1 = eng.free_energy(r, x)
-    A1 = eng.ais(r, c["betas"], c["R"], E.PhiloxRng(3), base_vis_bias=_bA(c))
+    A1 = eng.ais(r, c["betas"], c["R"], E.PhiloxRng(3), base_vis_bias=base_bias(c))
     assert torch.equal(F0, F1) and torch.equal(A0, A1)
     assert torch.equal(r.W.data, W0) and torch.equal(r.vis_bias.data, b0) and torch.equal(r.hid_bias.data, c0)
     assert torch.equal(x.cpu(), torch.from_numpy(c["x"]))              # the caller's rows are only read

@@ -20,9 +20,7 @@ def main():
     import __graft_entry__ as ge
     ge.build()
     import torch
-    import ais_cases as A
-    import joint_ais_cases as J
-    import reverse_ais_cases as Rv
+    import anneal_cases as Cs
     from imdbn import engine as E
     from imdbn.models import RBM
     if not torch.cuda.is_available():
@@ -43,14 +41,14 @@ def main():
         return dict(betas=torch.from_numpy(c["betas"]), rng=E.PhiloxRng(c["seed"]), return_state=True,
                     base_vis_bias=None if c["bA"] is None else torch.from_numpy(c["bA"]).to(dev))
 
-    for name in A.PARITY:
-        c = A.parity_case(name)
+    for name in Cs.FORWARD:
+        c = Cs.case(Cs.FORWARD, name)
         print("ais", name, digest(*eng.ais(rbm(c), n_chains=c["M"], **ladder(c))), flush=True)
-    for name in J.PARITY:
-        c = J.parity_case(name)
+    for name in Cs.GROUPS:
+        c = Cs.case(Cs.GROUPS, name)
         print("ais_groups", name, digest(*eng.ais_groups(rbm(c), n_chains=c["M"], **ladder(c))), flush=True)
-    for name in Rv.PARITY:
-        c = Rv.parity_case(name)
+    for name in Cs.REVERSE:
+        c = Cs.case(Cs.REVERSE, name)
         x = torch.from_numpy(c["x"]).to(dev)
         print("reverse_ais", name, digest(*eng.reverse_ais(rbm(c), x, **ladder(c))), flush=True)
         for mode in () if c["groups"] else ("entropy", "logq"):      # bound_step takes no softmax groups
