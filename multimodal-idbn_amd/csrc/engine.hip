@@ -167,6 +167,44 @@ int setup(Ctx& c, int B, void* ws, size_t ws_bytes) {
 #include "host_prop.hpp"
 #include "host_update.hpp"
 
+// The caller's fp32 rows x (visible rows when `up`, hidden rows otherwise) into the row-major operand form of their side, then the
+// propagation from it with `f`.
+int prep_prop(Ctx& c, bool up, const float* x, int64_t ldx, const FinishArgs& f) {
+    const Layout& L = c.L;
+    bf16_t* rm = up ? L.vis_rm[0] : L.hid_rm;
+    int* flags = up ? L.flags : L.flags_h;
+    CHK(prep(c, x, ldx, up ? c.d->V : c.d->H, rm, up ? L.Vpad : L.Hpad, nullptr, flags));
+    return prop(c, up, OpIn{rm, c.nw == 1 ? 1 : 0, flags}, f);
+}
+
+// What imdbn_energy_trace and imdbn_rbm_label_loglik start from: a joint RBM over [z | y | ...] with the code in the first Dz visible
+// columns and K labels behind it.  check() opens either call (`name`, for the messages), the call's own checks follow it, then
+// propagate() leaves base = z W[:Dz] + c -- the logits path of prop_up on the descriptor cut to its first Dz weight rows -- in the
+// workspace.
+struct LabelSide {
+    imdbn_rbm_desc dz;      // the cut descriptor
+    Ctx c;
+    const float *base, *bz, *by, *Wy;      // base [N][H] of pitch H; biases of the code and label columns; the labels' weight rows
+    static int check(const char* name, const imdbn_rbm_desc* d, int Dz, int K) {
+        if (K < 2 || K > LABEL_KMAX) return fail(IMDBN_E_INVALID, "%s: K = %d outside [2, %d]", name, K, LABEL_KMAX);
+        if (Dz < 1 || (int64_t)Dz + K > d->V) return fail(IMDBN_E_INVALID, "%s: Dz = %d, K = %d do not fit V = %d", name, Dz, K, d->V);
+        return 0;
+    }
+    LabelSide(const imdbn_rbm_desc* d, int Dz, hipStream_t stream) : dz(*d), c(&dz, nullptr, stream) {
+        dz.V = Dz; dz.n_groups = 0;
+        bz = d->vis_bias; by = d->vis_bias + Dz; Wy = d->W + (int64_t)Dz * d->ldw;
+    }
+    LabelSide(const LabelSide&) = delete;      // c.d points at dz
+    int propagate(const float* z, int64_t ldz, int N, void* ws, size_t ws_bytes) {
+        CHK(setup(c, N, ws, ws_bytes));
+        FinishArgs f = new_finish();
+        f.logits_only = 1;
+        f.out_prob = c.L.f_h; f.ld_prob = c.L.H;
+        base = c.L.f_h;
+        return prep_prop(c, true, z, ldz, f);
+    }
+};
+
 // rbm.py:199-209: positive phase, CD-k Gibbs, statistics left in the workspace operand buffers.
 int cd_phases(Ctx& c, const float* data, int64_t ldd, const imdbn_cd_opts* o, const PrepArgs* next = nullptr) {
     const Layout& L = c.L;
@@ -445,8 +483,8 @@ hipStream_t S(imdbn_stream_t s) { return (hipStream_t)s; }
 // the label kernel of imdbn_energy_trace (kernels_energy.hpp): Wy in LDS or global, base / h rows in LDS or global
 template <bool WLDS, bool HLDS>
 int launch_energy(const EnergyArgs& a, hipStream_t st) {
-    const size_t lds = (WLDS ? sizeof(float) * (size_t)a.K * a.H : 0) + (HLDS ? sizeof(float) * 2 * ENERGY_ROWS * (size_t)a.H : 0);
-    hipLaunchKernelGGL((energy_trace_rows<WLDS, HLDS>), dim3(cdiv(a.N, ENERGY_ROWS)), dim3(64 * ENERGY_ROWS), lds, st, a);
+    const size_t lds = (WLDS ? sizeof(float) * (size_t)a.K * a.H : 0) + (HLDS ? sizeof(float) * 2 * ROW_WAVES * (size_t)a.H : 0);
+    hipLaunchKernelGGL((energy_trace_rows<WLDS, HLDS>), dim3(cdiv(a.N, ROW_WAVES)), dim3(64 * ROW_WAVES), lds, st, a);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -571,7 +609,6 @@ int imdbn_rbm_prop_up(const imdbn_rbm_desc* d, const float* v, int64_t ldv, int 
     if (!v || !out_prob || ldv < d->V || ldo < d->H) return fail(IMDBN_E_INVALID, "prop_up: bad tensor argument");
     Ctx c(d, rng, S(stream));
     CHK(setup(c, B, ws, ws_bytes));
-    CHK(prep(c, v, ldv, d->V, c.L.vis_rm[0], c.L.Vpad, nullptr, c.L.flags));
     FinishArgs f = new_finish();
     f.T = T;
     f.out_prob = out_prob; f.ld_prob = ldo;
@@ -579,7 +616,7 @@ int imdbn_rbm_prop_up(const imdbn_rbm_desc* d, const float* v, int64_t ldv, int 
         if (lds < d->H) return fail(IMDBN_E_INVALID, "prop_up: bad sample ld");
         f.vmode = 1; f.uni = c.rng.floats(B, d->H); f.out_final = out_sample; f.ld_final = lds;
     }
-    CHK(prop(c, true, OpIn{c.L.vis_rm[0], c.nw == 1 ? 1 : 0, c.L.flags}, f));
+    CHK(prep_prop(c, true, v, ldv, f));
     return c.rng.finish();
 }
 
@@ -606,11 +643,10 @@ int imdbn_rbm_free_energy(const imdbn_rbm_desc* d, const float* v, int64_t ldv, 
     if (!v || !out_F || ldv < d->V) return fail(IMDBN_E_INVALID, "free_energy: bad tensor argument");
     Ctx c(d, nullptr, S(stream));
     CHK(setup(c, B, ws, ws_bytes));
-    CHK(prep(c, v, ldv, d->V, c.L.vis_rm[0], c.L.Vpad, nullptr, c.L.flags));
     FinishArgs f = new_finish();
     f.logits_only = 1;                                     // x = v W + c
     f.out_prob = c.L.f_h; f.ld_prob = d->H;
-    CHK(prop(c, true, OpIn{c.L.vis_rm[0], c.nw == 1 ? 1 : 0, c.L.flags}, f));
+    CHK(prep_prop(c, true, v, ldv, f));
     hipLaunchKernelGGL(free_energy_rows, dim3(B), dim3(256), 0, c.s, v, ldv, d->vis_bias, d->V, c.L.f_h, (int64_t)d->H, d->H, out_F);
     HIPCHK(hipGetLastError());
     return 0;
@@ -668,7 +704,7 @@ static int anneal_setup(Anneal& n, const imdbn_rbm_desc* d, int M, const float* 
     memset(&n.sp, 0, sizeof(n.sp));
     n.sp.n_groups = d->n_groups;
     for (int g = 0; g < d->n_groups; ++g) { n.sp.gs[g] = d->group_start[g]; n.sp.ge[g] = d->group_end[g]; }
-    n.grid = dim3(L.Bp / AIS_ROWS); n.block = dim3(64 * AIS_ROWS);
+    n.grid = dim3(L.Bp / ROW_WAVES); n.block = dim3(64 * ROW_WAVES);
     return 0;
 }
 
@@ -786,7 +822,7 @@ int imdbn_rows_logmeanexp(const double* logw, int N, int M, double* out_lme, dou
     if (M < 1) return fail(IMDBN_E_INVALID, "rows_logmeanexp: M = %d chains", M);
     if (!logw || !out_lme || !out_ess)
         return fail(IMDBN_E_INVALID, "rows_logmeanexp: null %s", !logw ? "logw" : (!out_lme ? "out_lme" : "out_ess"));
-    hipLaunchKernelGGL(rows_logmeanexp, dim3(cdiv(N, AIS_ROWS)), dim3(64 * AIS_ROWS), 0, S(stream), logw, N, M, out_lme, out_ess);
+    hipLaunchKernelGGL(rows_logmeanexp, dim3(cdiv(N, ROW_WAVES)), dim3(64 * ROW_WAVES), 0, S(stream), logw, N, M, out_lme, out_ess);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -813,14 +849,13 @@ int imdbn_rbm_bound_step(const imdbn_rbm_desc* d, const float* v, int64_t ldv, i
     a.out_h = out_h; a.ldh = ldh; a.rm = L.hid_rm; a.bits = L.hid_bits; a.acc = acc;
     a.uni = c.rng.floats(M, L.H);
     if (c.rng.bad) return c.rng.finish();      // a short replay tape is an error like the others: before the first launch
-    CHK(prep(c, v, ldv, d->V, L.vis_rm[0], L.Vpad, nullptr, L.flags));
     {   // x = c + v W
         FinishArgs f = new_finish();
         f.logits_only = 1;
         f.out_prob = L.f_h; f.ld_prob = L.H;
-        CHK(prop(c, true, OpIn{L.vis_rm[0], c.nw == 1 ? 1 : 0, L.flags}, f));
+        CHK(prep_prop(c, true, v, ldv, f));
     }
-    const dim3 grid(L.Bp / AIS_ROWS), block(64 * AIS_ROWS);
+    const dim3 grid(L.Bp / ROW_WAVES), block(64 * ROW_WAVES);
     hipLaunchKernelGGL(bound_entropy_sample_h, grid, block, 0, c.s, a);
     HIPCHK(hipGetLastError());
     c.hid_bits_ok = true;                      // hid_bits describes hid_rm: the down half may read the bit plane
@@ -841,11 +876,10 @@ int imdbn_rbm_prop_down(const imdbn_rbm_desc* d, const float* h, int64_t ldh, in
     if (!h || !out_prob || ldh < d->H || ldo < d->V) return fail(IMDBN_E_INVALID, "prop_down: bad tensor argument");
     Ctx c(d, nullptr, S(stream));
     CHK(setup(c, B, ws, ws_bytes));
-    CHK(prep(c, h, ldh, d->H, c.L.hid_rm, c.L.Hpad, nullptr, c.L.flags_h));
     FinishArgs f = new_finish();
     f.T = T; f.logits_only = logits_only;
     f.out_prob = out_prob; f.ld_prob = ldo;
-    CHK(prop(c, false, OpIn{c.L.hid_rm, c.nw == 1 ? 1 : 0, c.L.flags_h}, f));
+    CHK(prep_prop(c, false, h, ldh, f));
     return 0;
 }
 
@@ -1260,10 +1294,10 @@ int imdbn_rbm_chain_traced_vh(const imdbn_rbm_desc* d, int B, const imdbn_chain_
 int imdbn_trace_label_scan(const float* trace, int64_t step_stride, int64_t ld_row, int T, int B, int K, const int32_t* gt,
                            double eps_l1, int stable_steps, double gap_thresh, float* p_top1, float* p_top2, int32_t* k1, int32_t* k2,
                            float* p_gt, float* l1, int32_t* steps, int32_t* pred, imdbn_stream_t stream) {
-    if (!trace || T < 1 || B < 1 || K < 2 || K > TRACE_KMAX || ld_row < K || step_stride < (int64_t)B * ld_row || !p_top1 || !p_top2 ||
+    if (!trace || T < 1 || B < 1 || K < 2 || K > LABEL_KMAX || ld_row < K || step_stride < (int64_t)B * ld_row || !p_top1 || !p_top2 ||
         !k1 || !k2 || !l1 || !steps || !pred || (gt && !p_gt))
         return fail(IMDBN_E_INVALID, "trace_label_scan: bad argument (T=%d B=%d K=%d)", T, B, K);
-    hipLaunchKernelGGL(trace_label_scan, dim3(cdiv(B, 4)), dim3(256), 0, S(stream), trace, step_stride, ld_row, T, B, K, gt, eps_l1,
+    hipLaunchKernelGGL(trace_label_scan, dim3(cdiv(B, ROW_WAVES)), dim3(64 * ROW_WAVES), 0, S(stream), trace, step_stride, ld_row, T, B, K, gt, eps_l1,
                        stable_steps, gap_thresh, p_top1, p_top2, k1, k2, gt ? p_gt : nullptr, l1, steps, pred);
     HIPCHK(hipGetLastError());
     return 0;
@@ -1273,7 +1307,7 @@ int imdbn_trace_code_scan(const float* trace, int64_t step_stride, int64_t ld_ro
                           int64_t ld_init, float ema_beta, float* z_new, float* dz, imdbn_stream_t stream) {
     if (!trace || !z_init || !z_new || !dz || T < 1 || B < 1 || Dz < 1 || ld_row < Dz || ld_init < Dz || step_stride < (int64_t)B * ld_row)
         return fail(IMDBN_E_INVALID, "trace_code_scan: bad argument (T=%d B=%d Dz=%d)", T, B, Dz);
-    hipLaunchKernelGGL(trace_code_scan, dim3(cdiv(B, 4)), dim3(256), 0, S(stream), trace, step_stride, ld_row, T, B, Dz, z_init, ld_init,
+    hipLaunchKernelGGL(trace_code_scan, dim3(cdiv(B, ROW_WAVES)), dim3(64 * ROW_WAVES), 0, S(stream), trace, step_stride, ld_row, T, B, Dz, z_init, ld_init,
                        ema_beta, z_new, dz);
     HIPCHK(hipGetLastError());
     return 0;
@@ -1296,10 +1330,9 @@ int imdbn_rbm_prop_down_sqerr(const imdbn_rbm_desc* d, const float* h, int64_t l
     Ctx c(d, nullptr, S(stream));
     CHK(setup(c, B, ws, ws_bytes));
     // imdbn_rbm_prop_down at T = 1 into the workspace's [Bp][V] fp32 buffer, then the per-row error in a fixed order
-    CHK(prep(c, h, ldh, d->H, c.L.hid_rm, c.L.Hpad, nullptr, c.L.flags_h));
     FinishArgs f = new_finish();
     f.out_prob = c.L.f_vp; f.ld_prob = d->V;
-    CHK(prop(c, false, OpIn{c.L.hid_rm, c.nw == 1 ? 1 : 0, c.L.flags_h}, f));
+    CHK(prep_prop(c, false, h, ldh, f));
     hipLaunchKernelGGL(row_sqerr, dim3(B), dim3(256), 0, S(stream), c.L.f_vp, (int64_t)d->V, B, d->V, ref, ldr, ref_row, out_mse);
     HIPCHK(hipGetLastError());
     return 0;
@@ -1308,7 +1341,7 @@ int imdbn_rbm_prop_down_sqerr(const imdbn_rbm_desc* d, const float* h, int64_t l
 // ---- latent nearest-neighbour search (imdbn/utils/imdbn_logging.py; kernels_knn.hpp) ----------------------------------------
 int imdbn_row_stats(const float* x, int64_t ldx, int N, int D, float* out_sum, float* out_sumsq, imdbn_stream_t stream) {
     if (!x || N < 1 || D < 1 || ldx < D || (!out_sum && !out_sumsq)) return fail(IMDBN_E_INVALID, "row_stats: bad argument (N=%d D=%d)", N, D);
-    hipLaunchKernelGGL(knn_row_stats, dim3(cdiv(N, 4)), dim3(256), 0, S(stream), x, ldx, N, D, out_sum, out_sumsq);
+    hipLaunchKernelGGL(knn_row_stats, dim3(cdiv(N, ROW_WAVES)), dim3(64 * ROW_WAVES), 0, S(stream), x, ldx, N, D, out_sum, out_sumsq);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1341,10 +1374,10 @@ int imdbn_latent_topk(const float* bank, int64_t ldb, int N, int D, const float*
     int32_t* part_i = (int32_t*)(p + knn_align(sizeof(float) * (size_t)Q * k) * chunks);
     const hipStream_t st = S(stream);
     if (norms) {
-        hipLaunchKernelGGL(knn_row_stats, dim3(cdiv(Q, 4)), dim3(256), 0, st, queries, ldq, Q, D, nullptr, qss);
+        hipLaunchKernelGGL(knn_row_stats, dim3(cdiv(Q, ROW_WAVES)), dim3(64 * ROW_WAVES), 0, st, queries, ldq, Q, D, nullptr, qss);
         HIPCHK(hipGetLastError());
         if (own_bss) {
-            hipLaunchKernelGGL(knn_row_stats, dim3(cdiv(N, 4)), dim3(256), 0, st, bank, ldb, N, D, nullptr, (float*)bss);
+            hipLaunchKernelGGL(knn_row_stats, dim3(cdiv(N, ROW_WAVES)), dim3(64 * ROW_WAVES), 0, st, bank, ldb, N, D, nullptr, (float*)bss);
             HIPCHK(hipGetLastError());
         }
     }
@@ -1367,29 +1400,22 @@ int imdbn_energy_trace(const imdbn_rbm_desc* d, const float* z, int64_t ldz, int
                        const float* y_start, int64_t ldy, double eps_l1, int stable_steps, double gap_thresh,
                        const imdbn_energy_out* out, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
     CHK(check_desc(d, false));
-    if (K < 2 || K > TRACE_KMAX) return fail(IMDBN_E_INVALID, "energy_trace: K = %d outside [2, %d]", K, TRACE_KMAX);
-    if (Dz < 1 || (int64_t)Dz + K > d->V) return fail(IMDBN_E_INVALID, "energy_trace: Dz = %d, K = %d do not fit V = %d", Dz, K, d->V);
+    CHK(LabelSide::check("energy_trace", d, Dz, K));
     if (steps < 1 || N < 1) return fail(IMDBN_E_INVALID, "energy_trace: steps = %d, N = %d (both must be >= 1)", steps, N);
     if (!z || ldz < Dz || (y_start && ldy < K)) return fail(IMDBN_E_INVALID, "energy_trace: bad tensor argument (ldz=%lld ldy=%lld)", (long long)ldz, (long long)ldy);
     if (!out || !out->p_top1 || !out->p_top2 || !out->deltaF_pred || !out->l1 || !out->k1 || !out->steps_to_converge || !out->kstar ||
         !out->predT || !out->margin_energy || !out->fe_top1 || !out->fe_gap || !out->F || (gt && !out->p_gt))
         return fail(IMDBN_E_INVALID, "energy_trace: null output");
-    // phase A: base = z W[:Dz] + c -- the logits path of prop_up on the descriptor cut to its first Dz weight rows
-    imdbn_rbm_desc dz = *d;
-    dz.V = Dz; dz.n_groups = 0;
-    Ctx c(&dz, nullptr, S(stream));
-    CHK(setup(c, N, ws, ws_bytes));
-    CHK(prep(c, z, ldz, Dz, c.L.vis_rm[0], c.L.Vpad, nullptr, c.L.flags));
-    FinishArgs f = new_finish();
-    f.logits_only = 1;
-    f.out_prob = c.L.f_h; f.ld_prob = d->H;
-    CHK(prop(c, true, OpIn{c.L.vis_rm[0], c.nw == 1 ? 1 : 0, c.L.flags}, f));
+    // phase A: base = z W[:Dz] + c
+    LabelSide s(d, Dz, S(stream));
+    CHK(s.propagate(z, ldz, N, ws, ws_bytes));
+    const Ctx& c = s.c;
     // phase B: everything else, one wave per row
     EnergyArgs a{};
-    a.base = c.L.f_h; a.ldb = d->H;
+    a.base = s.base; a.ldb = d->H;
     a.z = z; a.ldz = ldz;
-    a.bz = d->vis_bias; a.by = d->vis_bias + Dz;
-    a.Wy = d->W + (int64_t)Dz * d->ldw; a.ldw = d->ldw;
+    a.bz = s.bz; a.by = s.by;
+    a.Wy = s.Wy; a.ldw = d->ldw;
     a.N = N; a.Dz = Dz; a.K = K; a.H = d->H; a.steps = steps;
     a.gt = gt; a.y0 = y_start; a.ldy0 = ldy;
     a.eps_l1 = eps_l1; a.stable_steps = stable_steps; a.gap_thresh = gap_thresh;
@@ -1406,30 +1432,22 @@ int imdbn_energy_trace(const imdbn_rbm_desc* d, const float* z, int64_t ldz, int
 int imdbn_rbm_label_loglik(const imdbn_rbm_desc* d, const float* z, int64_t ldz, int N, int Dz, int K, const int32_t* gt,
                            double* out_joint, double* out_marg, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
     CHK(check_desc(d, false));
-    if (K < 2 || K > JOINT_KMAX) return fail(IMDBN_E_INVALID, "label_loglik: K = %d outside [2, %d]", K, JOINT_KMAX);
-    if (Dz < 1 || (int64_t)Dz + K > d->V) return fail(IMDBN_E_INVALID, "label_loglik: Dz = %d, K = %d do not fit V = %d", Dz, K, d->V);
+    CHK(LabelSide::check("label_loglik", d, Dz, K));
     if (N < 1) return fail(IMDBN_E_INVALID, "label_loglik: N = %d rows", N);
     if (ldz < Dz) return fail(IMDBN_E_INVALID, "label_loglik: ldz %lld < Dz %d", (long long)ldz, Dz);
     if (!z || !gt || !out_joint || !out_marg)
         return fail(IMDBN_E_INVALID, "label_loglik: null %s", !z ? "z" : (!gt ? "gt" : (!out_joint ? "out_joint" : "out_marg")));
-    // base = z W[:Dz] + c: the logits path of prop_up on the descriptor cut to its first Dz weight rows (as imdbn_energy_trace)
-    imdbn_rbm_desc dz = *d;
-    dz.V = Dz; dz.n_groups = 0;
-    Ctx c(&dz, nullptr, S(stream));
-    CHK(setup(c, N, ws, ws_bytes));
-    CHK(prep(c, z, ldz, Dz, c.L.vis_rm[0], c.L.Vpad, nullptr, c.L.flags));
-    FinishArgs f = new_finish();
-    f.logits_only = 1;
-    f.out_prob = c.L.f_h; f.ld_prob = d->H;
-    CHK(prop(c, true, OpIn{c.L.vis_rm[0], c.nw == 1 ? 1 : 0, c.L.flags}, f));
+    LabelSide s(d, Dz, S(stream));
+    CHK(s.propagate(z, ldz, N, ws, ws_bytes));
+    const Ctx& c = s.c;
     JointArgs a{};
-    a.base = c.L.f_h; a.ldb = d->H;
+    a.base = s.base; a.ldb = d->H;
     a.z = z; a.ldz = ldz;
-    a.bz = d->vis_bias; a.by = d->vis_bias + Dz;
-    a.Wy = d->W + (int64_t)Dz * d->ldw; a.ldw = d->ldw;
+    a.bz = s.bz; a.by = s.by;
+    a.Wy = s.Wy; a.ldw = d->ldw;
     a.gt = gt; a.N = N; a.Dz = Dz; a.K = K; a.H = d->H;
     a.joint = out_joint; a.marg = out_marg;
-    hipLaunchKernelGGL(joint_label_loglik, dim3(c.L.Bp / AIS_ROWS), dim3(64 * AIS_ROWS), 0, c.s, a);
+    hipLaunchKernelGGL(joint_label_loglik, dim3(c.L.Bp / ROW_WAVES), dim3(64 * ROW_WAVES), 0, c.s, a);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1437,7 +1455,7 @@ int imdbn_rbm_label_loglik(const imdbn_rbm_desc* d, const float* z, int64_t ldz,
 // ---- cross-modal label metrics (imdbn/utils/cross_eval.py; kernels_metrics.hpp) ---------------------------------------------
 int imdbn_cross_metrics(const float* p, int64_t ldp, int B, int K, const float* y, int64_t ldy, const int32_t* gt, const float* row_mse,
                         int npix, int topk, const imdbn_cross_metrics_out* out, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
-    if (K < 2 || K > TRACE_KMAX) return fail(IMDBN_E_INVALID, "cross_metrics: K = %d outside [2, %d]", K, TRACE_KMAX);
+    if (K < 2 || K > LABEL_KMAX) return fail(IMDBN_E_INVALID, "cross_metrics: K = %d outside [2, %d]", K, LABEL_KMAX);
     if (B < 1) return fail(IMDBN_E_INVALID, "cross_metrics: B = %d (must be >= 1)", B);
     if (topk < 1) return fail(IMDBN_E_INVALID, "cross_metrics: topk = %d (must be >= 1)", topk);
     if (npix < 1) return fail(IMDBN_E_INVALID, "cross_metrics: npix = %d (must be >= 1)", npix);
@@ -1447,19 +1465,19 @@ int imdbn_cross_metrics(const float* p, int64_t ldp, int B, int K, const float* 
     if (y && ldy < K) return fail(IMDBN_E_INVALID, "cross_metrics: ldy = %lld < K = %d", (long long)ldy, K);
     if (!out || !out->acc) return fail(IMDBN_E_INVALID, "cross_metrics: null accumulator acc");
     // workspace: the per-row codes [B], then one partial record per wave of cross_metrics_rows
-    const size_t code_bytes = knn_align(sizeof(int32_t) * (size_t)B), need = code_bytes + sizeof(CmPartial) * 4 * CM_MAX_BLOCKS;
+    const size_t code_bytes = knn_align(sizeof(int32_t) * (size_t)B), need = code_bytes + sizeof(CmPartial) * ROW_WAVES * CM_MAX_BLOCKS;
     if (!ws || ((uintptr_t)ws & 255) != 0 || ws_bytes < need)
         return fail(IMDBN_E_WORKSPACE, "cross_metrics: workspace %zu < %zu bytes (or null / not 256-byte aligned)", ws_bytes, need);
-    const int nb = std::min(cdiv(B, 4), CM_MAX_BLOCKS);
+    const int nb = std::min(cdiv(B, ROW_WAVES), CM_MAX_BLOCKS);
     CmArgs a{};
     a.p = p; a.ldp = ldp; a.y = y; a.ldy = ldy; a.gt = gt; a.row_mse = row_mse;
     a.B = B; a.K = K; a.npix = npix; a.topk = topk;
     a.pred = out->pred; a.gt_out = out->gt; a.rank = out->rank; a.p_pred = out->p_pred; a.p_true = out->p_true;
     a.confusion = (unsigned long long*)out->confusion;
     a.code = (int32_t*)ws; a.part = (CmPartial*)((char*)ws + code_bytes);
-    hipLaunchKernelGGL(cross_metrics_rows, dim3(nb), dim3(256), 0, S(stream), a);
+    hipLaunchKernelGGL(cross_metrics_rows, dim3(nb), dim3(64 * ROW_WAVES), 0, S(stream), a);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(cross_metrics_combine, dim3(1 + (out->class_sums ? K : 0)), dim3(64), 0, S(stream), a.part, 4 * nb, a.code, row_mse,
+    hipLaunchKernelGGL(cross_metrics_combine, dim3(1 + (out->class_sums ? K : 0)), dim3(64), 0, S(stream), a.part, ROW_WAVES * nb, a.code, row_mse,
                        B, out->acc, out->class_sums);
     HIPCHK(hipGetLastError());
     return 0;

@@ -14,22 +14,16 @@
 //
 // One wave per chain (row), four rows per block, rows dealt up to Bp (the padded rows write zeros into the operand forms and touch
 // nothing else), so M is free.  Lane l of a row's wave takes the elements l, l + 64, ... in ascending order and the 64 lane sums
-// meet in a fixed butterfly: the order of every sum depends on (V, H) only.  Lane 0 owns logw[row]; no atomics, no LDS, no scratch.
+// meet in the fixed butterfly (wave_sum_all): the order of every sum depends on (V, H) only.  Lane 0 owns logw[row]; no atomics, no
+// LDS, no scratch.
 #pragma once
 #include "kernels_ew.hpp"
+#include "kernels_rows.hpp"
 
 namespace imdbn {
 
-constexpr int AIS_ROWS = 4;      // rows (waves) per block
-
 // softplus in double, stable form
 __device__ __forceinline__ double ais_softplus(double t) { return fmax(t, 0.0) + log1p(exp(-fabs(t))); }
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);      // fixed butterfly order: deterministic, every lane ends with the sum
-    return v;
-}
 
 struct AisArgs {
     int M, Bp, V, H, Vpad, Hpad;
@@ -103,9 +97,9 @@ __device__ __forceinline__ int ais_pick_category(const AisGroupsArgs& g, int q, 
     return idx;
 }
 
-__global__ __launch_bounds__(64 * AIS_ROWS) void ais_init_v_groups(const AisGroupsArgs g) {
+__global__ __launch_bounds__(64 * ROW_WAVES) void ais_init_v_groups(const AisGroupsArgs g) {
     const AisArgs& a = g.a;
-    const int lane = threadIdx.x & 63, row = blockIdx.x * AIS_ROWS + (threadIdx.x >> 6);
+    const int lane = wave_lane(), row = wave_row();
     if (row >= a.Bp) return;
     const bool live = row < a.M;      // wave-uniform
     int pick[4] = {-1, -1, -1, -1};
@@ -135,8 +129,8 @@ __global__ __launch_bounds__(64 * AIS_ROWS) void ais_init_v_groups(const AisGrou
     if (live && lane == 0) a.logw[row] = 0.0;
 }
 
-__global__ __launch_bounds__(64 * AIS_ROWS) void ais_weight_sample_h(const AisArgs a) {
-    const int lane = threadIdx.x & 63, row = blockIdx.x * AIS_ROWS + (threadIdx.x >> 6);
+__global__ __launch_bounds__(64 * ROW_WAVES) void ais_weight_sample_h(const AisArgs a) {
+    const int lane = wave_lane(), row = wave_row();
     if (a.sample) ais_eff_bias(a);
     if (row >= a.Bp) return;
     const bool live = row < a.M;      // wave-uniform
@@ -164,7 +158,7 @@ __global__ __launch_bounds__(64 * AIS_ROWS) void ais_weight_sample_h(const AisAr
         if (a.sample) ais_store_hidden(a.rm, a.bits, a.Bp, a.Hpad, row, j, one);
     }
     if (!live) return;
-    const double tv = wave_sum_f64(sv), th = wave_sum_f64(sh);
+    const double tv = wave_sum_all(sv), th = wave_sum_all(sh);
     const double delta = ((double)a.beta - (double)a.beta_prev) * tv + th;
     if (lane == 0) a.logw[row] += a.first ? th : (a.reverse ? -delta : delta);
 }

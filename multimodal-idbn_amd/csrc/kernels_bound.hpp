@@ -28,8 +28,8 @@ struct BoundArgs {
     double* acc;
 };
 
-__global__ __launch_bounds__(64 * AIS_ROWS) void bound_entropy_sample_h(const BoundArgs a) {
-    const int lane = threadIdx.x & 63, row = blockIdx.x * AIS_ROWS + (threadIdx.x >> 6);
+__global__ __launch_bounds__(64 * ROW_WAVES) void bound_entropy_sample_h(const BoundArgs a) {
+    const int lane = wave_lane(), row = wave_row();
     if (row >= a.Bp) return;
     const bool live = row < a.M;      // wave-uniform
     double e = 0.0;
@@ -47,12 +47,12 @@ __global__ __launch_bounds__(64 * AIS_ROWS) void bound_entropy_sample_h(const Bo
         ais_store_hidden(a.rm, a.bits, a.Bp, a.Hpad, row, j, one);
     }
     if (!live) return;
-    e = wave_sum_f64(e);
+    e = wave_sum_all(e);
     if (lane == 0) a.acc[row] += e;
 }
 
-__global__ __launch_bounds__(64 * AIS_ROWS) void bound_loglik_rows(const BoundArgs a) {
-    const int lane = threadIdx.x & 63, row = blockIdx.x * AIS_ROWS + (threadIdx.x >> 6);
+__global__ __launch_bounds__(64 * ROW_WAVES) void bound_loglik_rows(const BoundArgs a) {
+    const int lane = wave_lane(), row = wave_row();
     if (row >= a.M) return;           // wave-uniform
     const float* lg = a.a + (int64_t)row * a.lda;
     const float* v = a.v + (int64_t)row * a.ldv;
@@ -61,7 +61,7 @@ __global__ __launch_bounds__(64 * AIS_ROWS) void bound_loglik_rows(const BoundAr
         const double t = (double)lg[i];
         s += (double)v[i] * t - ais_softplus(t);
     }
-    s = wave_sum_f64(s);
+    s = wave_sum_all(s);
     if (lane == 0) a.acc[row] += s;
 }
 

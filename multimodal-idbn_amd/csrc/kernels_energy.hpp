@@ -16,18 +16,17 @@
 //   WLDS: Wy [K][H] staged once per block in LDS (K H 4 <= ENERGY_WY_LDS bytes), else read from global (L2-resident).
 //   HLDS: base and h of the wave's row live in LDS (H <= ENERGY_H_LDS), else base is re-read from global and h goes through a
 //         global scratch row; each lane only reads back what it wrote itself.
-// Label values sit in registers, label k in lane k & 63, slot k >> 6 (K <= TRACE_KMAX = 256).
+// Label values sit in registers, label k in lane k & 63, slot k >> 6 (kernels_rows.hpp; K <= LABEL_KMAX = 256).
 #pragma once
 #include <type_traits>
 
 #include "common.hpp"
-#include "kernels_trace.hpp"
+#include "kernels_rows.hpp"
 
 namespace imdbn {
 
-constexpr int ENERGY_ROWS = 4;                   // rows (waves) per block
 constexpr int ENERGY_WY_LDS = 32 * 1024;         // bytes of Wy staged in LDS (32 x 256 fp32 fits exactly)
-constexpr int ENERGY_H_LDS = 1024;               // widest H whose base / h rows are kept in LDS (2 x 4 rows x 4 KB)
+constexpr int ENERGY_H_LDS = 1024;               // widest H whose base / h rows are kept in LDS (2 x ROW_WAVES rows x 4 KB)
 
 struct EnergyArgs {
     const float* base; int64_t ldb;              // [N][H] hidden pre-activations of the clamped code
@@ -47,48 +46,21 @@ struct EnergyArgs {
     float* y_out;                                // [N][K] nullable: y after the last step
 };
 
-__device__ __forceinline__ float en_wave_sum(float v) {
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 __device__ __forceinline__ float en_lane(float v, int lane) {      // lane is wave-uniform
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
 __device__ __forceinline__ float en_softplus(float t) { return t > 20.0f ? t : log1pf(expf(t)); }      // as torch
 
-// top-2 of the per-lane label slots under tr_better (every lane ends with the result)
-struct EnTop2 { float v1, v2; int i1, i2; };
-__device__ __forceinline__ EnTop2 en_top2(const float (&y)[4], int l, int K) {
-    float v1 = -INFINITY, v2 = -INFINITY; int i1 = 0x7fffffff, i2 = 0x7fffffff;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int c = l + 64 * q;
-        const float yq = y[q];
-        if (c < K) {
-            if (tr_better(yq, c, v1, i1)) { v2 = v1; i2 = i1; v1 = yq; i1 = c; }
-            else if (tr_better(yq, c, v2, i2)) { v2 = yq; i2 = c; }
-        }
-    }
-    for (int o = 32; o >= 1; o >>= 1) {
-        const float w1 = __shfl_xor(v1, o), w2 = __shfl_xor(v2, o);
-        const int j1 = __shfl_xor(i1, o), j2 = __shfl_xor(i2, o);
-        if (tr_better(v1, i1, w1, j1)) {
-            if (tr_better(w1, j1, v2, i2)) { v2 = w1; i2 = j1; }
-        } else {
-            if (tr_better(v1, i1, w2, j2)) { v2 = v1; i2 = i1; } else { v2 = w2; i2 = j2; }
-            v1 = w1; i1 = j1;
-        }
-    }
-    return EnTop2{v1, v2, i1, i2};
-}
-
-// the value of label k out of the per-lane slots, in every lane (the owner's value plus 63 zeros: exact)
+// The value of label k out of the label slots, in every lane, as the owner's value plus 63 zeros (exact; 0 for a k no lane owns).  Not
+// slots_pick: its shuffle costs this kernel two to four VGPRs, and <true, false> sits at 64 of them, the last step of 8 waves per SIMD.
+// For the same reason the kernel spells out its row and its two slot loads below: with wave_row() and slots_load the compiler allots
+// its registers otherwise and a row's chain of steps measured 2 to 3 % slower.
 __device__ __forceinline__ float en_pick(const float (&y)[4], int l, int k) {
     float v = 0.f;
 #pragma unroll
     for (int q = 0; q < 4; ++q)
         if (l + 64 * q == k) v = y[q];
-    return en_wave_sum(v);
+    return wave_sum_all(v);
 }
 
 // body(q) for the four label slots with q a compile-time constant (the slots are registers: no dynamic index)
@@ -99,14 +71,14 @@ __device__ __forceinline__ void en_slots(Fn&& body) {
 }
 
 template <bool WLDS, bool HLDS>
-__global__ __launch_bounds__(64 * ENERGY_ROWS) void energy_trace_rows(const EnergyArgs a) {
+__global__ __launch_bounds__(64 * ROW_WAVES) void energy_trace_rows(const EnergyArgs a) {
     extern __shared__ float en_lds[];
-    const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, b = blockIdx.x * ENERGY_ROWS + wv;
+    const int l = wave_lane(), wv = threadIdx.x >> 6, b = blockIdx.x * ROW_WAVES + wv;      // = wave_row()
     const int K = a.K, H = a.H;
     const float* W = a.Wy;
     int64_t ldw = a.ldw;
     if (WLDS) {
-        for (int i = threadIdx.x; i < K * H; i += 64 * ENERGY_ROWS) {
+        for (int i = threadIdx.x; i < K * H; i += 64 * ROW_WAVES) {
             const int k = i / H, j = i - k * H;
             en_lds[i] = a.Wy[(int64_t)k * a.ldw + j];
         }
@@ -127,11 +99,11 @@ __global__ __launch_bounds__(64 * ENERGY_ROWS) void energy_trace_rows(const Ener
     // ---- z . bz
     float zb = 0.f;
     for (int c = l; c < a.Dz; c += 64) zb = fmaf(a.z[(int64_t)b * a.ldz + c], a.bz[c], zb);
-    zb = en_wave_sum(zb);
+    zb = wave_sum_all(zb);
     // ---- class free energies; nF = -F in the label slots
     float nF[4] = {0.f, 0.f, 0.f, 0.f}, by[4], y[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
+    for (int q = 0; q < 4; ++q) {                                          // slots_load of by and of y0, or the uniform start
         const int c = l + 64 * q;
         by[q] = c < K ? a.by[c] : 0.f;
         y[q] = c < K ? (a.y0 ? a.y0[(int64_t)b * a.ldy0 + c] : 1.0f / (float)K) : 0.f;
@@ -143,11 +115,11 @@ __global__ __launch_bounds__(64 * ENERGY_ROWS) void energy_trace_rows(const Ener
             const float* wr = W + (int64_t)(64 * q + kk) * ldw;
             float s = 0.f;
             for (int j = l; j < H; j += 64) s += en_softplus(bs[j] + wr[j]);
-            s = en_wave_sum(s);
+            s = wave_sum_all(s);
             if (l == kk) nF[q] = (zb + by[q]) + s;                         // F_k = -(z.bz + by_k) - sum softplus
         }
     });
-    const EnTop2 tf = en_top2(nF, l, K);                                   // largest -F first, the lower index on ties (torch.min)
+    const Top2 tf = slots_top2(nF, l, K);                                   // largest -F first, the lower index on ties (torch.min)
     const float f1 = tf.v1, f2 = tf.v2, Fmin = -tf.v1;
     const int kstar = tf.i1;
     {
@@ -157,7 +129,7 @@ __global__ __launch_bounds__(64 * ENERGY_ROWS) void energy_trace_rows(const Ener
             const int c = l + 64 * q;
             if (c < K) { e += expf(nF[q] - f1); a.F[(int64_t)b * K + c] = -nF[q]; }
         }
-        e = en_wave_sum(e);
+        e = wave_sum_all(e);
         if (l == 0) {
             a.kstar[b] = kstar;
             a.margin[b] = K > 1 ? (-f2) - (-f1) : 0.f;                     // F(2) - F(1)
@@ -167,7 +139,7 @@ __global__ __launch_bounds__(64 * ENERGY_ROWS) void energy_trace_rows(const Ener
     }
     // ---- the label chain
     const int g = a.gt ? a.gt[b] : -1;
-    int pred = en_top2(y, l, K).i1, streak = 0, conv = a.steps + 1;      // argmax of the start (0 for the uniform start)
+    int pred = slots_top2(y, l, K).i1, streak = 0, conv = a.steps + 1;      // argmax of the start (0 for the uniform start)
     for (int t = 1; t <= a.steps; ++t) {
         // h = sigmoid(base + y Wy): per column base first, then k ascending
         for (int j = l; j < H; j += 64) {
@@ -188,7 +160,7 @@ __global__ __launch_bounds__(64 * ENERGY_ROWS) void energy_trace_rows(const Ener
                 const float* wr = W + (int64_t)(64 * q + kk) * ldw;
                 float s = 0.f;
                 for (int j = l; j < H; j += 64) s = fmaf(hs[j], wr[j], s);
-                s = en_wave_sum(s);
+                s = wave_sum_all(s);
                 if (l == kk) x[q] = s;
             }
         });
@@ -198,14 +170,14 @@ __global__ __launch_bounds__(64 * ENERGY_ROWS) void energy_trace_rows(const Ener
             x[q] = sigmoidf_ref(x[q] + by[q]);
             if (l + 64 * q < K) mx = fmaxf(mx, x[q]);
         }
-        for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+        mx = wave_max_all(mx);
         float den = 0.f;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             x[q] = l + 64 * q < K ? expf(x[q] - mx) : 0.f;
             den += x[q];
         }
-        den = en_wave_sum(den);
+        den = wave_sum_all(den);
         float l1 = 0.f;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -213,8 +185,8 @@ __global__ __launch_bounds__(64 * ENERGY_ROWS) void energy_trace_rows(const Ener
             l1 += fabsf(yn - y[q]);                                        // slots past K hold 0 on both sides
             y[q] = yn;
         }
-        l1 = en_wave_sum(l1);
-        const EnTop2 ty = en_top2(y, l, K);
+        l1 = wave_sum_all(l1);
+        const Top2 ty = slots_top2(y, l, K);
         const float v1 = ty.v1, v2 = ty.v2;
         const int i1 = ty.i1;
         streak = (i1 == pred) ? streak + 1 : 1;

@@ -7,15 +7,13 @@
 //                         all in double, the fp32 operands widened.
 //
 // One wave per row, four rows per block.  Lane l takes j = l, l + 64, ... in ascending order and the 64 lane sums meet in the fixed
-// butterfly of wave_sum_f64, so every sum is a function of (Dz, K, H) only and a row gives the same bits alone and inside a batch.
-// The K class values are computed in index order and parked in registers, value k in lane k & 63, slot k >> 6 (K <= 256); the
-// logsumexp is shifted by their maximum and its K terms are added in index order.  No atomics, no LDS, no scratch.
+// butterfly of wave_sum_all, so every sum is a function of (Dz, K, H) only and a row gives the same bits alone and inside a batch.
+// The K class values are computed in index order and parked in the label slots of kernels_rows.hpp (in double, an empty slot holds
+// -inf); the logsumexp is shifted by their maximum and its K terms are added in index order.  No atomics, no LDS, no scratch.
 #pragma once
 #include "kernels_ais.hpp"
 
 namespace imdbn {
-
-constexpr int JOINT_KMAX = 256;      // 4 register slots of 64 lanes
 
 struct JointArgs {
     const float* base; int64_t ldb;        // [N][H] fp32
@@ -27,14 +25,14 @@ struct JointArgs {
     double* joint; double* marg;           // [N]
 };
 
-__global__ __launch_bounds__(64 * AIS_ROWS) void joint_label_loglik(const JointArgs a) {
-    const int lane = threadIdx.x & 63, row = blockIdx.x * AIS_ROWS + (threadIdx.x >> 6);
+__global__ __launch_bounds__(64 * ROW_WAVES) void joint_label_loglik(const JointArgs a) {
+    const int lane = wave_lane(), row = wave_row();
     if (row >= a.N) return;      // wave-uniform
     const float* z = a.z + (int64_t)row * a.ldz;
     const float* base = a.base + (int64_t)row * a.ldb;
     double zb = 0.0;
     for (int i = lane; i < a.Dz; i += 64) zb += (double)z[i] * (double)a.bz[i];
-    zb = wave_sum_f64(zb);
+    zb = wave_sum_all(zb);
     double val[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -44,13 +42,11 @@ __global__ __launch_bounds__(64 * AIS_ROWS) void joint_label_loglik(const JointA
             const float* w = a.Wy + (int64_t)k * a.ldw;
             double sh = 0.0;
             for (int j = lane; j < a.H; j += 64) sh += ais_softplus((double)base[j] + (double)w[j]);
-            const double ak = zb + (double)a.by[k] + wave_sum_f64(sh);
+            const double ak = zb + (double)a.by[k] + wave_sum_all(sh);
             if (lane == kk) val[s] = ak;
         }
     }
-    double mx = fmax(fmax(val[0], val[1]), fmax(val[2], val[3]));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+    const double mx = wave_max_all(fmax(fmax(val[0], val[1]), fmax(val[2], val[3])));
     double sum = 0.0;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -61,9 +57,7 @@ __global__ __launch_bounds__(64 * AIS_ROWS) void joint_label_loglik(const JointA
         }
     }
     const int g = a.gt[row];
-    const int gs = g >> 6;
-    const double mine = gs == 0 ? val[0] : (gs == 1 ? val[1] : (gs == 2 ? val[2] : val[3]));
-    const double at = __shfl(mine, g & 63, 64);
+    const double at = slots_pick(val, g);
     if (lane == 0) {
         a.joint[row] = (g >= 0 && g < a.K) ? at : (double)NAN;
         a.marg[row] = mx + log(sum);

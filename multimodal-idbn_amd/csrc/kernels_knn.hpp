@@ -17,7 +17,7 @@
 // ranks higher than that.  The result does not depend on the order of the offers, so the per-chunk lists (the chunk's top-k
 // keys by per-key maximum) merge to the global answer exactly.  No score matrix reaches HBM.
 #pragma once
-#include "common.hpp"
+#include "kernels_rows.hpp"
 
 namespace imdbn {
 
@@ -34,11 +34,11 @@ constexpr int KNN_STP = KNN_BT + 1;        // padded row pitch of the score tile
 inline size_t knn_chunk_lds(int k) { return sizeof(float) * (2 * KNN_QT * KNN_LDP + KNN_QT * KNN_STP + 4 * KNN_QT * k); }
 inline size_t knn_merge_lds(int k) { return sizeof(float) * 4 * KNN_QT * k; }
 
-// block of 256 threads = 4 waves = 4 rows; lane l sums columns l, l+64, ... in order, then a fixed xor butterfly
-__global__ __launch_bounds__(256) void knn_row_stats(const float* __restrict__ x, int64_t ldx, int N, int D, float* __restrict__ out_sum,
-                                                     float* __restrict__ out_sumsq) {
-    const int l = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+// one wave per row: lane l sums columns l, l+64, ... in order, then the fixed xor butterfly
+__global__ __launch_bounds__(64 * ROW_WAVES) void knn_row_stats(const float* __restrict__ x, int64_t ldx, int N, int D,
+                                                               float* __restrict__ out_sum, float* __restrict__ out_sumsq) {
+    const int l = wave_lane();
+    const int64_t r = wave_row();
     if (r >= N) return;                                                    // wave-uniform
     const float* row = x + r * ldx;
     float a = 0.f, b = 0.f;
@@ -47,17 +47,13 @@ __global__ __launch_bounds__(256) void knn_row_stats(const float* __restrict__ x
         a += v;
         b += v * v;
     }
-    for (int o = 32; o >= 1; o >>= 1) {
-        a += __shfl_xor(a, o);
-        b += __shfl_xor(b, o);
-    }
+    a = wave_sum_all(a);
+    b = wave_sum_all(b);
     if (l == 0) {
         if (out_sum) out_sum[r] = a;
         if (out_sumsq) out_sumsq[r] = b;
     }
 }
-
-__device__ __forceinline__ bool knn_better(float s, int i, float t, int j) { return s > t || (s == t && i < j); }
 
 // the lists of the 64 owners of a block, entry e of owner t at [e * KNN_QT + t] (consecutive owners in consecutive banks)
 struct KnnList {
@@ -82,7 +78,7 @@ __device__ int knn_offer(const KnnList& L, int t, int n, int k, float s, int b, 
     if (keyed) {
         for (int e = 0; e < n; ++e) {
             if (L.k0[e * KNN_QT + t] == a && L.k1[e * KNN_QT + t] == c) {
-                if (!knn_better(s, b, L.s[e * KNN_QT + t], L.i[e * KNN_QT + t])) return n;
+                if (!vi_better(s, b, L.s[e * KNN_QT + t], L.i[e * KNN_QT + t])) return n;
                 p = e;
                 break;
             }
@@ -92,11 +88,11 @@ __device__ int knn_offer(const KnnList& L, int t, int n, int k, float s, int b, 
         if (n < k) {
             ++n;
         } else {
-            if (!knn_better(s, b, L.s[(k - 1) * KNN_QT + t], L.i[(k - 1) * KNN_QT + t])) return n;
+            if (!vi_better(s, b, L.s[(k - 1) * KNN_QT + t], L.i[(k - 1) * KNN_QT + t])) return n;
             p = k - 1;                                                     // the last entry drops out
         }
     }
-    while (p > 0 && knn_better(s, b, L.s[(p - 1) * KNN_QT + t], L.i[(p - 1) * KNN_QT + t])) {
+    while (p > 0 && vi_better(s, b, L.s[(p - 1) * KNN_QT + t], L.i[(p - 1) * KNN_QT + t])) {
         const int e = p - 1;
         L.at(p, t, L.s[e * KNN_QT + t], L.i[e * KNN_QT + t], L.k0[e * KNN_QT + t], L.k1[e * KNN_QT + t]);
         p = e;
@@ -184,7 +180,7 @@ __global__ __launch_bounds__(256) void knn_topk_chunk(const KnnArgs a) {
                 const float s = St[l * KNN_STP + j];
                 const int b = bb + j;
                 if (!(s == s) || b == ex) continue;                        // NaN scores are never candidates
-                if (n == a.k && !knn_better(s, b, L.s[(a.k - 1) * KNN_QT + l], L.i[(a.k - 1) * KNN_QT + l])) continue;
+                if (n == a.k && !vi_better(s, b, L.s[(a.k - 1) * KNN_QT + l], L.i[(a.k - 1) * KNN_QT + l])) continue;
                 float ka = 0.f, kb = 0.f;
                 if (a.key) { ka = a.key[2 * (int64_t)b]; kb = a.key[2 * (int64_t)b + 1]; }
                 n = knn_offer(L, l, n, a.k, s, b, a.key != nullptr, ka, kb);
@@ -217,7 +213,7 @@ __global__ __launch_bounds__(64) void knn_topk_merge(const float* __restrict__ p
             if (b < 0) break;                                              // padding: the chunk's list ends
             const float s = part_s[o + e];
             // a chunk's list is sorted: once an entry cannot enter a full list, none after it can
-            if (n == k && !knn_better(s, b, L.s[(k - 1) * KNN_QT + t], L.i[(k - 1) * KNN_QT + t])) break;
+            if (n == k && !vi_better(s, b, L.s[(k - 1) * KNN_QT + t], L.i[(k - 1) * KNN_QT + t])) break;
             float ka = 0.f, kb = 0.f;
             if (key) { ka = key[2 * (int64_t)b]; kb = key[2 * (int64_t)b + 1]; }
             n = knn_offer(L, t, n, k, s, b, key != nullptr, ka, kb);

@@ -15,8 +15,7 @@
 // rows l, l + 64, .. ascending, then the butterfly) and adds to class_sums[k].  Every order depends on (B, K) alone, so the same
 // batches leave the same bits; the accumulators are read, added to and written back by one lane each (calls on one stream are ordered).
 #pragma once
-#include "common.hpp"
-#include "kernels_trace.hpp"
+#include "kernels_rows.hpp"
 
 namespace imdbn {
 
@@ -37,66 +36,26 @@ struct CmArgs {
     CmPartial* part;                             // workspace [4 nb]
 };
 
-__device__ __forceinline__ double cm_wave_sum(double v) {
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ int cm_wave_sum(int v) {
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// first maximum of the wave's row (lower index on ties; NaN never wins; an all-NaN row gives 0), the same in every lane
-__device__ __forceinline__ int cm_argmax(const float (&v)[4], int l, int K, float& best) {
-    best = -INFINITY; int bi = 0x7fffffff;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int c = l + 64 * q;
-        if (c < K && tr_better(v[q], c, best, bi)) { best = v[q]; bi = c; }
-    }
-    for (int o = 32; o >= 1; o >>= 1) {
-        const float w = __shfl_xor(best, o); const int j = __shfl_xor(bi, o);
-        if (tr_better(w, j, best, bi)) { best = w; bi = j; }
-    }
-    return bi < K ? bi : 0;
-}
-
-// the value of label k (wave-uniform, in [0, K)) out of the per-lane slots, in every lane
-__device__ __forceinline__ float cm_pick(const float (&v)[4], int k) {
-    const int q = k >> 6;
-    const float sel = q == 0 ? v[0] : q == 1 ? v[1] : q == 2 ? v[2] : v[3];
-    return __shfl(sel, k & 63);
-}
-
-__global__ __launch_bounds__(256) void cross_metrics_rows(const CmArgs a) {
-    const int l = threadIdx.x & 63, wave = blockIdx.x * 4 + (threadIdx.x >> 6), stride = gridDim.x * 4;
+__global__ __launch_bounds__(64 * ROW_WAVES) void cross_metrics_rows(const CmArgs a) {
+    const int l = wave_lane(), wave = wave_row(), stride = gridDim.x * ROW_WAVES;
     const int K = a.K, kk = min(a.topk, K);
     const float lo = 1e-6f, hi = (float)(1.0 - 1e-6);
     double ce = 0.0, mse = 0.0;
     int n = 0, top1 = 0, topk = 0, skipped = 0;
     for (int r = wave; r < a.B; r += stride) {                             // wave-uniform
         float p[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int c = l + 64 * q;
-            p[q] = c < K ? a.p[(int64_t)r * a.ldp + c] : 0.f;
-        }
-        float pmax;
-        const int pred = cm_argmax(p, l, K, pmax);
+        slots_load(p, a.p + (int64_t)r * a.ldp, l, K);
+        const int pred = slots_argmax(p, l, K, 0);                         // an all-NaN row gives 0
         int g;
         if (a.y) {
-            float yv[4], ymax;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int c = l + 64 * q;
-                yv[q] = c < K ? a.y[(int64_t)r * a.ldy + c] : 0.f;
-            }
-            g = cm_argmax(yv, l, K, ymax);
+            float yv[4];
+            slots_load(yv, a.y + (int64_t)r * a.ldy, l, K);
+            g = slots_argmax(yv, l, K, 0);
         } else {
             g = a.gt[r];
         }
         const bool ok = g >= 0 && g < K;
-        const float ppred = cm_pick(p, pred);
+        const float ppred = slots_pick(p, pred);
         if (l == 0) {
             if (a.pred) a.pred[r] = pred;
             if (a.gt_out) a.gt_out[r] = g;
@@ -111,7 +70,7 @@ __global__ __launch_bounds__(256) void cross_metrics_rows(const CmArgs a) {
             }
             continue;
         }
-        const float pg = cm_pick(p, g);
+        const float pg = slots_pick(p, g);
         int above = 0;
         double s = 0.0;
 #pragma unroll
@@ -123,8 +82,8 @@ __global__ __launch_bounds__(256) void cross_metrics_rows(const CmArgs a) {
                 s += (double)(c == g ? logf(pt) : logf(1.0f - pt));
             }
         }
-        above = cm_wave_sum(above);
-        s = cm_wave_sum(s);
+        above = wave_sum_all(above);
+        s = wave_sum_all(s);
         ++n;
         top1 += pred == g ? 1 : 0;
         topk += above < kk ? 1 : 0;
@@ -156,8 +115,8 @@ __global__ __launch_bounds__(64) void cross_metrics_combine(const CmPartial* __r
             const CmPartial q = part[i];
             ce += q.ce; mse += q.mse; n += q.n; top1 += q.top1; topk += q.topk; skipped += q.skipped;
         }
-        ce = cm_wave_sum(ce); mse = cm_wave_sum(mse);
-        n = cm_wave_sum(n); top1 = cm_wave_sum(top1); topk = cm_wave_sum(topk); skipped = cm_wave_sum(skipped);
+        ce = wave_sum_all(ce); mse = wave_sum_all(mse);
+        n = wave_sum_all(n); top1 = wave_sum_all(top1); topk = wave_sum_all(topk); skipped = wave_sum_all(skipped);
         if (l == 0) {
             acc[0] += (double)n; acc[1] += (double)top1; acc[2] += (double)topk;
             acc[3] += ce; acc[4] += mse; acc[5] += (double)skipped;
@@ -175,7 +134,7 @@ __global__ __launch_bounds__(64) void cross_metrics_combine(const CmPartial* __r
             if (row_mse) s += (double)row_mse[r];
         }
     }
-    n = cm_wave_sum(n); hit = cm_wave_sum(hit); s = cm_wave_sum(s);
+    n = wave_sum_all(n); hit = wave_sum_all(hit); s = wave_sum_all(s);
     if (l == 0) {
         class_sums[3 * k] += (double)n; class_sums[3 * k + 1] += (double)hit; class_sums[3 * k + 2] += s;
     }

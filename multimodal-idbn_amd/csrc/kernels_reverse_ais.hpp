@@ -6,7 +6,7 @@
 //                          that does not hold exactly one 1, gets logw = NaN -- every later step only adds to it, so the row stays NaN.
 //   rows_logmeanexp        one wave per test row over its M chains: max-shifted sums of w and w^2 in double -> log mean w, ess.
 //
-// Rows, lanes and sums as in kernels_ais.hpp: one wave per row, AIS_ROWS rows per block, rows dealt up to Bp, lane l takes the
+// Rows, lanes and sums as in kernels_ais.hpp: one wave per row, ROW_WAVES rows per block, rows dealt up to Bp, lane l takes the
 // elements l, l + 64, ... in ascending order, the 64 lane sums meet in the fixed butterfly.  No atomics, no LDS, no scratch.
 #pragma once
 #include "kernels_ais.hpp"
@@ -19,9 +19,9 @@ struct RaisLoadArgs {
     GroupSpans sp;
 };
 
-__global__ __launch_bounds__(64 * AIS_ROWS) void rais_load_v(const RaisLoadArgs g) {
+__global__ __launch_bounds__(64 * ROW_WAVES) void rais_load_v(const RaisLoadArgs g) {
     const AisArgs& a = g.a;
-    const int lane = threadIdx.x & 63, row = blockIdx.x * AIS_ROWS + (threadIdx.x >> 6);
+    const int lane = wave_lane(), row = wave_row();
     if (row >= a.Bp) return;
     const bool live = row < a.M;      // wave-uniform
     double sb = 0.0;
@@ -43,21 +43,19 @@ __global__ __launch_bounds__(64 * AIS_ROWS) void rais_load_v(const RaisLoadArgs 
         if (q < g.sp.n_groups) {
             int ones = 0;
             for (int i = g.sp.gs[q] + lane; i < g.sp.ge[q]; i += 64) ones += g.v[(int64_t)row * g.ldv + i] == 1.f ? 1 : 0;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) ones += __shfl_xor(ones, o, 64);
-            bad |= ones != 1;
+            bad |= wave_sum_all(ones) != 1;
         }
     }
     const bool any_bad = __ballot(bad) != 0ull;
-    const double s = wave_sum_f64(sb);
+    const double s = wave_sum_all(sb);
     if (lane == 0) a.logw[row] = any_bad ? (double)NAN : s;
 }
 
 // Row n owns logw[n M .. n M + M - 1].  out_lme[n] = log((1 / M) sum_m exp(logw)), out_ess[n] = (sum w)^2 / sum w^2 on the weights
 // shifted by the row's maximum.  A NaN anywhere in the row makes both outputs of that row NaN, and of that row only.
-__global__ __launch_bounds__(64 * AIS_ROWS) void rows_logmeanexp(const double* __restrict__ logw, int N, int M,
+__global__ __launch_bounds__(64 * ROW_WAVES) void rows_logmeanexp(const double* __restrict__ logw, int N, int M,
                                                                  double* __restrict__ out_lme, double* __restrict__ out_ess) {
-    const int lane = threadIdx.x & 63, row = blockIdx.x * AIS_ROWS + (threadIdx.x >> 6);
+    const int lane = wave_lane(), row = wave_row();
     if (row >= N) return;
     const double* x = logw + (int64_t)row * M;
     double mx = -INFINITY;
@@ -67,8 +65,7 @@ __global__ __launch_bounds__(64 * AIS_ROWS) void rows_logmeanexp(const double* _
         nan |= t != t;
         mx = fmax(mx, t);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+    mx = wave_max_all(mx);
     const bool any_nan = __ballot(nan) != 0ull;
     const double shift = mx == -INFINITY ? 0.0 : mx;      // a row of zero weights: log mean = -inf, not NaN
     double s1 = 0.0, s2 = 0.0;
@@ -77,8 +74,8 @@ __global__ __launch_bounds__(64 * AIS_ROWS) void rows_logmeanexp(const double* _
         s1 += w;
         s2 += w * w;
     }
-    s1 = wave_sum_f64(s1);
-    s2 = wave_sum_f64(s2);
+    s1 = wave_sum_all(s1);
+    s2 = wave_sum_all(s2);
     if (lane == 0) {
         out_lme[row] = any_nan ? (double)NAN : shift + log(s1 / (double)M);
         out_ess[row] = any_nan ? (double)NAN : s1 * s1 / s2;

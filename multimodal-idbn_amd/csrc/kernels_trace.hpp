@@ -10,69 +10,40 @@
 // The scans are sequential over steps per row: one wave per row (lanes over the columns), one thread per row for the
 // patience rule (two scalars per step).  Decisions compare in double, as the reference does with Python floats.
 #pragma once
-#include "common.hpp"
+#include "kernels_rows.hpp"
 
 namespace imdbn {
 
-constexpr int TRACE_KMAX = 256;                  // label window <= GROUP_WMAX: at most 4 values per lane
-
-// (value, index) ordering of torch.argmax / topk: larger value first, the lower index on ties
-__device__ __forceinline__ bool tr_better(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
-
-// block of 256 threads = 4 waves = 4 rows
-__global__ __launch_bounds__(256) void trace_label_scan(const float* __restrict__ tr, int64_t ss, int64_t ld, int T, int B, int K,
-                                                        const int32_t* __restrict__ gt, double eps_l1, int stable_steps, double gap_thresh,
-                                                        float* __restrict__ p1o, float* __restrict__ p2o, int32_t* __restrict__ k1o,
-                                                        int32_t* __restrict__ k2o, float* __restrict__ pgo, float* __restrict__ l1o,
-                                                        int32_t* __restrict__ steps_o, int32_t* __restrict__ pred_o) {
-    const int l = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+__global__ __launch_bounds__(64 * ROW_WAVES) void trace_label_scan(const float* __restrict__ tr, int64_t ss, int64_t ld, int T, int B,
+                                                                  int K, const int32_t* __restrict__ gt, double eps_l1, int stable_steps,
+                                                                  double gap_thresh, float* __restrict__ p1o, float* __restrict__ p2o,
+                                                                  int32_t* __restrict__ k1o, int32_t* __restrict__ k2o,
+                                                                  float* __restrict__ pgo, float* __restrict__ l1o,
+                                                                  int32_t* __restrict__ steps_o, int32_t* __restrict__ pred_o) {
+    const int l = wave_lane(), b = wave_row();
     if (b >= B) return;                                                    // wave-uniform
     const int g = gt ? gt[b] : -1;
     // slot 0 = baseline p(v | p(h | v0)): its argmax starts the streak, its values are y_prev of step 1
-    float prev[4];
-    float best = -INFINITY; int bi = 0x7fffffff;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int c = l + 64 * q;
-        prev[q] = c < K ? tr[(int64_t)b * ld + c] : 0.f;
-        if (c < K && tr_better(prev[q], c, best, bi)) { best = prev[q]; bi = c; }
-    }
-    for (int o = 32; o >= 1; o >>= 1) {
-        const float w = __shfl_xor(best, o); const int j = __shfl_xor(bi, o);
-        if (tr_better(w, j, best, bi)) { best = w; bi = j; }
-    }
-    int pred = bi, streak = 0, conv = T + 1;
+    float prev[4], y[4];
+    slots_load(prev, tr + (int64_t)b * ld, l, K);
+    int pred = slots_argmax(prev, l, K), streak = 0, conv = T + 1;
     for (int t = 1; t <= T; ++t) {
-        const float* row = tr + (int64_t)t * ss + (int64_t)b * ld;
-        float v1 = -INFINITY, v2 = -INFINITY; int i1 = 0x7fffffff, i2 = 0x7fffffff;
-        float l1 = 0.f, pg = 0.f;
+        slots_load(y, tr + (int64_t)t * ss + (int64_t)b * ld, l, K);
+        float l1 = 0.f;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const int c = l + 64 * q;
-            if (c >= K) break;
-            const float y = row[c];
-            l1 += fabsf(y - prev[q]);
-            prev[q] = y;
-            if (c == g) pg = y;
-            if (tr_better(y, c, v1, i1)) { v2 = v1; i2 = i1; v1 = y; i1 = c; }
-            else if (tr_better(y, c, v2, i2)) { v2 = y; i2 = c; }
+            l1 += fabsf(y[q] - prev[q]);                                   // slots past K hold 0 on both sides
+            prev[q] = y[q];
         }
-        for (int o = 32; o >= 1; o >>= 1) {                               // merge of two sorted top-2 lists (butterfly: every lane ends with the result)
-            const float w1 = __shfl_xor(v1, o), w2 = __shfl_xor(v2, o);
-            const int j1 = __shfl_xor(i1, o), j2 = __shfl_xor(i2, o);
-            l1 += __shfl_xor(l1, o);
-            pg += __shfl_xor(pg, o);
-            if (tr_better(v1, i1, w1, j1)) {
-                if (tr_better(w1, j1, v2, i2)) { v2 = w1; i2 = j1; }
-            } else {
-                if (tr_better(v1, i1, w2, j2)) { v2 = v1; i2 = i1; } else { v2 = w2; i2 = j2; }
-                v1 = w1; i1 = j1;
-            }
-        }
+        l1 = wave_sum_all(l1);
+        const Top2 ty = slots_top2(y, l, K);
+        const float v1 = ty.v1, v2 = ty.v2;
+        const int i1 = ty.i1, i2 = ty.i2;
+        const float pg = g >= 0 && g < K ? slots_pick(y, g) : 0.f;         // wave-uniform: every lane shuffles
         if (l == 0) {
             const int64_t o = (int64_t)b * T + (t - 1);
             p1o[o] = v1; p2o[o] = v2; k1o[o] = i1; k2o[o] = i2; l1o[o] = l1;
-            if (pgo) pgo[o] = g >= 0 ? pg : 0.f;
+            if (pgo) pgo[o] = pg;
         }
         streak = (i1 == pred) ? streak + 1 : 1;
         pred = i1;
@@ -88,10 +59,10 @@ __global__ __launch_bounds__(256) void trace_label_scan(const float* __restrict_
 }
 
 // z trace [T][B] rows of Dz (slot t at tr + t*ss + b*ld) -> z_new [T][B][Dz] (EMA when beta > 0), dz [B][T] = ||z_new_t - z_new_{t-1}||_2
-__global__ __launch_bounds__(256) void trace_code_scan(const float* __restrict__ tr, int64_t ss, int64_t ld, int T, int B, int Dz,
-                                                       const float* __restrict__ z0, int64_t ldz0, float beta,
-                                                       float* __restrict__ zn, float* __restrict__ dzo) {
-    const int l = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+__global__ __launch_bounds__(64 * ROW_WAVES) void trace_code_scan(const float* __restrict__ tr, int64_t ss, int64_t ld, int T, int B,
+                                                                 int Dz, const float* __restrict__ z0, int64_t ldz0, float beta,
+                                                                 float* __restrict__ zn, float* __restrict__ dzo) {
+    const int l = wave_lane(), b = wave_row();
     if (b >= B) return;
     const float* zp = z0 + (int64_t)b * ldz0;
     for (int t = 0; t < T; ++t) {
@@ -105,7 +76,7 @@ __global__ __launch_bounds__(256) void trace_code_scan(const float* __restrict__
             acc += d * d;
             zo[c] = z;
         }
-        for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+        acc = wave_sum_all(acc);
         if (l == 0) dzo[(int64_t)b * T + t] = sqrtf(acc);
         zp = zo;
     }

@@ -151,18 +151,23 @@ def truth_rows(log_p, states):
     return states[idx].astype(F32), log_p[idx]
 
 
-# ---- imdbn_rbm_label_loglik.  name -> (Dz, K, H, extra visible columns behind the labels, w_scale)
-LABEL = {"small": (12, 3, 7, 0, 0.5), "paper": (500, 32, 256, 0, 0.05)}
+# ---- imdbn_rbm_label_loglik.  name -> (Dz, K, H, extra visible columns behind the labels, w_scale, labels of the rows 0, 2, 3, 4 or
+# None: drawn like the rest).  "slots": K = 130 fills two label slots of the kernel and two lanes of a third; the first and last label
+# of every slot are somebody's truth (row 1 is left out: the test gives it a label out of range)
+LABEL = {"small": (12, 3, 7, 0, 0.5, None), "paper": (500, 32, 256, 0, 0.05, None), "slots": (20, 130, 70, 0, 0.2, (0, 63, 64, 129))}
 
 
 def label_case(name, N, real, gen_seed=0):
     """A joint RBM [Dz | K] x H and N code rows (0/1, or uniform in [0, 1)), labels in [0, K)."""
-    Dz, K, H, extra, ws = LABEL[name]
+    Dz, K, H, extra, ws, first = LABEL[name]
     W, b, c, _ = params(Dz + K + extra, H, 700 + Dz, ws)
     g = np.random.Generator(np.random.PCG64(800 + N + gen_seed))
     u = g.random((N, Dz))
     z = u.astype(F32) if real else (u > 0.5).astype(F32)
-    return dict(Dz=Dz, K=K, H=H, W=W, b=b, c=c, z=z, gt=g.integers(0, K, N).astype(np.int32))
+    gt = g.integers(0, K, N).astype(np.int32)
+    if first is not None:
+        gt[[0, 2, 3, 4]] = first
+    return dict(Dz=Dz, K=K, H=H, W=W, b=b, c=c, z=z, gt=gt)
 
 
 # ---- a tiny iMDBN for enumeration: image stack 8-5-4, joint RBM (4 + 3) <-> 4, W ~ N(0, 0.5)

@@ -198,6 +198,50 @@ def test_batched_rows_equal_the_b1_calls(fx, small):
             _close(b[k][0].cpu(), t2i[k][i].cpu(), 1e-6, f"row {i} {k}", rel=(k != "z_l2"))
 
 
+def _slot_trace(K, B=5, T=6):
+    """A label trace [T + 1, B, K] on the grid 2^-10 -- every fp32 sum of it is exact in any order -- and the truth labels, with, where K
+    allows: row 0 constant with a lone maximum at gt = K - 1 (converges); row 1 the maximum tied between columns 0 and 64 (one lane, two
+    slots), the rest changing; row 2 constant with the maximum tied between columns 63 and 64 (never a gap); row 3 a lone maximum and
+    second place tied between columns 5 and K - 2, constant from step 3 on; row 4 (alone in the second block) changing throughout."""
+    g = np.random.Generator(np.random.PCG64(40 + K))
+    tr = g.integers(0, 512, (T + 1, B, K)).astype(np.float32) / 1024          # [0, 0.5)
+    gt = g.integers(0, K, B).astype(np.int32)
+    tr[:, 0] = tr[0, 0]; tr[:, 0, K - 1] = 0.875; gt[0] = K - 1
+    if K > 64:
+        tr[:, 1, 0] = tr[:, 1, 64] = 0.75
+        tr[:, 2] = tr[0, 2]; tr[:, 2, 63] = tr[:, 2, 64] = 0.75
+    if K > 2:
+        tr[3:, 3] = tr[3, 3]
+        tr[:, 3, 1] = 0.875; tr[:, 3, 5] = tr[:, 3, K - 2] = 0.625
+    return tr, gt
+
+
+@pytest.mark.parametrize("K", [2, 64, 65, 256])
+def test_label_scan_slots_against_the_oracle(K):
+    """imdbn_trace_label_scan alone, across the label slots (K = 2; one full slot; one label in the second; all four full), every
+    output equal to the numpy oracle's.  The thresholds are dyadic like the trace, so no decision is a matter of rounding."""
+    from imdbn import engine as E
+    T, thr = 6, dict(eps_l1=2.0 ** -4, stable_steps=3, gap_thresh=0.25)
+    tr, gt = _slot_trace(K, T=T)
+    ys = tr[1:].astype(np.float64)
+    r, steps, pred, _ = TO.label_scan(tr[0].astype(np.float64), ys, gt=gt, **thr)
+    # the planted cases are there
+    p1, p2 = r["p1"][None], r["p2"][None]                                   # [1, B, T] against ys [K, B, T]
+    yk = ys.transpose(2, 1, 0)
+    assert (steps <= T).any() and (steps == T + 1).any() and steps[0] <= T and gt[0] == K - 1
+    if K > 64:
+        at_k1 = np.arange(K)[:, None, None] == r["k1"][None]
+        assert (np.roll(at_k1, 64, 0) & (yk == p1))[64:].any(), "no maximum tied across two slots of one lane"
+        assert ((r["k1"] == 63) & (r["k2"] == 64) & (r["p1"] == r["p2"])).any(), "no maximum tied between columns 63 and 64"
+    if K > 2:
+        assert (((yk == p2).sum(0) >= 2) & (r["p2"] < r["p1"])).any(), "no tie for second place"
+    o = E.get_hip_engine().label_scan(torch.from_numpy(tr).to(DEV), torch.from_numpy(gt).to(DEV), **thr)
+    for k, ref in (("p_top1", r["p1"]), ("p_top2", r["p2"]), ("k1", r["k1"]), ("k2", r["k2"]), ("p_gt", r["p_gt"]), ("l1", r["l1"]),
+                   ("steps", steps), ("pred", pred)):
+        got = o[k].cpu().numpy()
+        assert got.shape == ref.shape and np.array_equal(got.astype(np.float64), ref.astype(np.float64)), (K, k, got, ref)
+
+
 def test_tracing_only_observes_the_chain(small):
     """chain_traced vs chain_pair with Philox and sampled steps, on the chain kernel and one launch per half step."""
     from imdbn import engine as E

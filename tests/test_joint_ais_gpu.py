@@ -146,7 +146,8 @@ def test_the_binary_call_still_refuses_groups_and_parameters_are_untouched(eng):
 
 
 # ---- 4. label_loglik ----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name,N,real,pad", [("small", 5, False, 0), ("small", 70, True, 3), ("paper", 5, True, 0), ("paper", 70, False, 12)])
+@pytest.mark.parametrize("name,N,real,pad", [("small", 5, False, 0), ("small", 70, True, 3), ("paper", 5, True, 0), ("paper", 70, False, 12),
+                                             ("slots", 5, False, 0), ("slots", 70, True, 3)])
 def test_label_loglik_against_the_twin(eng, name, N, real, pad):
     c = Cs.label_case(name, N, real)
     Dz, K, H = c["Dz"], c["K"], c["H"]
