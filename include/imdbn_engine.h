@@ -283,6 +283,24 @@ int imdbn_rows_logmeanexp(const double* logw, int N, int M, double* out_lme, dou
 int imdbn_rbm_label_loglik(const imdbn_rbm_desc* d, const float* z, int64_t ldz, int N, int Dz, int K, const int32_t* gt,
                            double* out_joint, double* out_marg, void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- exact pseudo-log-likelihood (imdbn/utils/likelihood.py: pseudo_log_likelihood) -----------------------------
+ * PLL(v) = sum over sites of log p(v_site | v_rest), a site being every visible column outside the softmax groups and every group
+ * as a whole.  No reference counterpart; built over the free energy above: with x = hid_bias + v W, sigma = sigmoid(x), s_i = 1 - 2 v_i,
+ *   Bernoulli column i:  g_i = s_i b_i + sum_j log1p(sigma_j expm1(s_i W_ij)) = F(v) - F(v with bit i flipped);   term = -softplus(g_i)
+ *   group, observed t:   g_k = (b_k - b_t) + sum_j log1p(sigma_j expm1(W_kj - W_tj));   term = -log sum_{k in group} exp(g_k)
+ *   out_pll[N] (device, double) = the sum of the row's terms.
+ *   out_site[N][V] (nullable, fp32, row stride lds): the term of column i; a group's term sits at its observed column and the
+ *   group's other columns hold 0, so a row of out_site sums to out_pll.
+ * v [N][V] is 0/1 with one-hot groups, row stride ldv; 0 <= n_groups <= IMDBN_MAX_GROUPS.  A row holding an element that is not
+ * exactly 0 or 1, or a group without exactly one 1, gets out_pll = NaN and a NaN row in out_site, that row only (checked on the
+ * device).  The logits are those of the propagations; the j sums run in fp32 over chunks of 128 hidden units and in double across
+ * the chunks, every other sum in double, all in an order fixed by (V, H, groups): a row gives the same bits alone and inside any
+ * batch; no floating-point atomics.  No draws.
+ * IMDBN_E_INVALID (naming the value): N < 1, null v / out_pll, ldv < V, out_site with lds < V.  Nothing is launched and no output
+ * is touched on any error.  Workspace: imdbn_ws_bytes(V, H, N).  The caller's parameters are only read. */
+int imdbn_rbm_pseudo_loglik(const imdbn_rbm_desc* d, const float* v, int64_t ldv, int N, double* out_pll, float* out_site, int64_t lds,
+                            void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- one directed layer of the DBN lower bound (imdbn/utils/likelihood.py: dbn_sample_values; the same paper, §4) -----------------
  * For every row of v [M][V] (0/1 or real in [0, 1], row stride ldv), x = hid_bias + v W, sp = softplus in double:
  *   h = 1[sigmoid(x) > U]                         -> out_h [M][H] fp32 0/1, row stride ldh (the decision of imdbn_rbm_prop_up's sample)

@@ -32,6 +32,7 @@
 #include "kernels_reverse_ais.hpp"
 #include "kernels_bound.hpp"
 #include "kernels_joint.hpp"
+#include "kernels_pll.hpp"
 
 using namespace imdbn;
 
@@ -1448,6 +1449,43 @@ int imdbn_rbm_label_loglik(const imdbn_rbm_desc* d, const float* z, int64_t ldz,
     a.gt = gt; a.N = N; a.Dz = Dz; a.K = K; a.H = d->H;
     a.joint = out_joint; a.marg = out_marg;
     hipLaunchKernelGGL(joint_label_loglik, dim3(c.L.Bp / ROW_WAVES), dim3(64 * ROW_WAVES), 0, c.s, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ---- exact pseudo-log-likelihood (imdbn/utils/likelihood.py; kernels_pll.hpp) ------------------------------------------
+// The up propagation's raw logits (f_h), pll_rows_sigmoid (sigma in place, NaN rows for invalid input), pll_sites (every column as
+// a Bernoulli site, into the caller's out_site or f_vp) and pll_rows_finish (group terms, row totals).
+int imdbn_rbm_pseudo_loglik(const imdbn_rbm_desc* d, const float* v, int64_t ldv, int N, double* out_pll, float* out_site, int64_t lds,
+                            void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(check_desc(d, false));
+    if (N < 1) return fail(IMDBN_E_INVALID, "pseudo_loglik: N = %d rows", N);
+    if (!v || !out_pll) return fail(IMDBN_E_INVALID, "pseudo_loglik: null %s", !v ? "v" : "out_pll");
+    if (ldv < d->V) return fail(IMDBN_E_INVALID, "pseudo_loglik: ldv %lld < V %d", (long long)ldv, d->V);
+    if (out_site && lds < d->V) return fail(IMDBN_E_INVALID, "pseudo_loglik: lds %lld < V %d", (long long)lds, d->V);
+    Ctx c(d, nullptr, S(stream));
+    CHK(setup(c, N, ws, ws_bytes));
+    const Layout& L = c.L;
+    {   // x = c + v W
+        FinishArgs f = new_finish();
+        f.logits_only = 1;
+        f.out_prob = L.f_h; f.ld_prob = L.H;
+        CHK(prep_prop(c, true, v, ldv, f));
+    }
+    PllArgs a;
+    memset(&a, 0, sizeof(a));
+    a.v = v; a.ldv = ldv; a.sig = L.f_h; a.ldx = L.H;
+    a.W = d->W; a.ldw = d->ldw; a.vis_bias = d->vis_bias;
+    a.site = out_site ? out_site : L.f_vp; a.lds = out_site ? lds : L.V;
+    a.pll = out_pll; a.N = N; a.V = d->V; a.H = d->H;
+    a.sp.n_groups = d->n_groups;
+    for (int g = 0; g < d->n_groups; ++g) { a.sp.gs[g] = d->group_start[g]; a.sp.ge[g] = d->group_end[g]; }
+    const dim3 rows(cdiv(N, ROW_WAVES)), rblock(64 * ROW_WAVES);
+    hipLaunchKernelGGL(pll_rows_sigmoid, rows, rblock, 0, c.s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(pll_sites, dim3(cdiv(d->V, PLL_TI), cdiv(N, PLL_TR)), dim3(256), 0, c.s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(pll_rows_finish, rows, rblock, 0, c.s, a);
     HIPCHK(hipGetLastError());
     return 0;
 }

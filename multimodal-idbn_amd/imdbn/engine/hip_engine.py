@@ -412,6 +412,22 @@ class HipEngine:
                    *self._ws_tail(dev, Dz, d.H, max(n, 1)))       # the propagation is (Dz, H, N): its workspace, not (V, H, N)
         return joint, marg
 
+    def pseudo_loglik(self, rbm, v: torch.Tensor, return_sites: bool = False):
+        """Exact pseudo-log-likelihood per row of ``v`` ``[N, V]`` (0/1, one-hot softmax groups; imdbn_rbm_pseudo_loglik):
+        ``PLL = sum_sites log p(v_site | v_rest)``, a float64 device tensor ``[N]``; with ``return_sites`` also the per-column terms,
+        fp32 ``[N, V]`` (a group's term at its observed column, 0 in the group's other columns).  A row that is not 0/1, or a group
+        without exactly one 1, is NaN in both.  One up propagation and three kernels, no draws, no host sync."""
+        d = self._desc(rbm, False)
+        if not v.is_cuda or v.dim() != 2 or v.size(1) != d.V:
+            raise N.EngineError(f"pseudo_loglik needs a HIP tensor v [N, {d.V}]")
+        v = _f32c(v)
+        n, dev = v.size(0), v.device
+        pll = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        site = torch.empty(max(n, 1), d.V, device=dev) if return_sites else None
+        self._call("imdbn_rbm_pseudo_loglik", C.byref(d), _ptr(v), v.stride(0), n, _ptr(pll), _ptr(site), d.V,
+                   *self._ws_tail(dev, d.V, d.H, max(n, 1)))
+        return (pll, site) if return_sites else pll
+
     def bound_step(self, rbm, v, rng, acc: Optional[torch.Tensor] = None, mode: str = "entropy"):
         """One directed layer of the DBN lower bound (imdbn_rbm_bound_step): draws ``h ~ q(h | v)`` and adds
         ``log p(v | h)`` plus the entropy of q (``mode="entropy"``) or ``-log q(h | v)`` (``mode="logq"``) to ``acc``, a float64

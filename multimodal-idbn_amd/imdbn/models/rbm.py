@@ -156,6 +156,13 @@ class RBM(nn.Module):
         return estimate_log_partition(self, **kw)
 
     @torch.no_grad()
+    def pseudo_log_likelihood(self, v: torch.Tensor, return_sites: bool = False):
+        """Exact pseudo-log-likelihood sum_sites log p(v_site | v_rest) per row, float64 ``[B]``
+        (``imdbn.utils.likelihood.pseudo_log_likelihood``; softmax groups accepted, no partition function, no draws)."""
+        from imdbn.utils.likelihood import pseudo_log_likelihood
+        return pseudo_log_likelihood(self, v, return_sites=return_sites)
+
+    @torch.no_grad()
     def log_likelihood(self, v: torch.Tensor, log_z) -> torch.Tensor:
         """log p(v) = -F(v) - log Z per row, float64 ``[B]`` (``imdbn.utils.likelihood.log_likelihood``)."""
         from imdbn.utils.likelihood import log_likelihood

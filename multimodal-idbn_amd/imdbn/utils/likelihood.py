@@ -49,6 +49,15 @@ chunk of rows (imdbn_rbm_reverse_ais) and one ``HipEngine.rows_logm
 ``evaluate_log_likelihood_sandwich`` reports both sides and their gap;
 ``dbn_conservative_bound`` puts the reverse estimate in place of the top term of ``dbn_lower_bound``.  The iMDBN is not composed.
 
+The cheap monitor: everything above costs hundreds to thousands of annealing steps per estimate.  The pseudo-log-likelihood
+PLL(v) = sum_sites log p(v_site | v_rest) needs no partition function, no chain and no draw, and the engine computes the EXACT sum over
+all sites -- every visible column outside the softmax groups, every group as one site -- in about the time of one propagation
+(``pseudo_log_likelihood``, ONE ``HipEngine.pseudo_loglik`` call, imdbn_rbm_pseudo_loglik; the toolkits' estimate from one
+random bit per row is not offered).  Softmax groups are accepted; rows must be 0/1 with one-hot groups (NaN otherwise, that row only).
+``evaluate_pseudo_likelihood`` is the per-epoch monitor over a loader; ``imdbn_pseudo_log_likelihood`` evaluates the joint RBM of an
+``iMDBN`` on ``[z | one-hot y]`` with z drawn as the bounds above draw it, and its group term is log p(y | z), the classification
+log-loss, without a chain.  It is a training monitor, not a likelihood: PLL is not comparable with the numbers above.
+
 Data parallelism: the chains are NOT sharded over ranks -- every rank that calls runs all ``n_chains`` chains and gets the same
 estimate (same seed) or an independent one; sharding the chains is a follow-up.
 """
@@ -66,7 +75,8 @@ __all__ = ["base_rate_bias", "linear_betas", "estimate_log_partition", "log_like
            "dbn_sample_values", "dbn_lower_bound", "dbn_log_likelihood_is", "evaluate_dbn_bound",
            "base_rate_bias_joint", "estimate_joint_log_partition", "imdbn_sample_values", "imdbn_lower_bound",
            "imdbn_log_likelihood_is", "evaluate_imdbn_bound",
-           "reverse_ais_log_likelihood", "evaluate_log_likelihood_sandwich", "dbn_conservative_bound", "evaluate_dbn_bound_conservative"]
+           "reverse_ais_log_likelihood", "evaluate_log_likelihood_sandwich", "dbn_conservative_bound", "evaluate_dbn_bound_conservative",
+           "pseudo_log_likelihood", "evaluate_pseudo_likelihood", "imdbn_pseudo_log_likelihood"]
 
 
 def _bottom(model):
@@ -572,3 +582,66 @@ def evaluate_dbn_bound_conservative(model, loader=None, n_samples: int = 8, n_ch
     res = {"mean_bound": t[0] / d, "sum_bound": t[0], "n": n, "ess_reverse": t[1] / d, "n_samples": int(n_samples), "n_chains": int(n_chains)}
     _log_scalars(model, "ll/dbn_conservative_", res, ("mean_bound", "ess_reverse", "n_samples", "n_chains"))
     return res
+
+
+# ---- the cheap monitor: exact pseudo-log-likelihood --------------------------------------------------------------------------------
+def _n_sites(rbm) -> int:
+    """Sites of a row: the visible columns outside the softmax groups, plus one per group."""
+    groups = getattr(rbm, "softmax_groups", None) or []
+    return int(rbm.W.shape[0]) - sum(int(e) - int(s) for s, e in groups) + len(groups)
+
+
+@torch.no_grad()
+def pseudo_log_likelihood(model, v: torch.Tensor, return_sites: bool = False):
+    """Exact PLL(v) = sum_sites log p(v_site | v_rest) per row of ``v`` (0/1, one-hot softmax groups) under an ``RBM`` -- or the BOTTOM
+    layer of an ``iDBN``: float64 ``[B]`` on the device; with ``return_sites`` also the per-column terms, fp32 ``[B, V]`` (a group's
+    term at its observed column, 0 in the group's other columns; a row sums to its PLL).  A row that is not 0/1, or a group without
+    exactly one 1, is NaN.  One ``HipEngine.pseudo_loglik`` call; no draws, no host sync."""
+    rbm = _bottom(model)
+    return _E.get_engine(rbm.W.data).pseudo_loglik(rbm, rows_on_device(v, rbm.W.device), return_sites=return_sites)
+
+
+@torch.no_grad()
+def evaluate_pseudo_likelihood(model, loader=None, max_batches: Optional[int] = None) -> Optional[dict]:
+    """Mean held-out ``pseudo_log_likelihood`` of an ``RBM`` -- or of the BOTTOM layer of an ``iDBN`` -- over ``loader`` (default
+    ``model.val_loader``; None without one): ``mean_pll``, ``sum_pll``, ``n`` (the valid rows), ``mean_site`` = mean_pll / number of
+    sites (the mean log-probability of one site given the rest) and ``n_invalid``: the NaN rows, which are counted and left out of
+    the sums.  Sums on the device, ONE host copy after the last batch.  A ragged last batch is fine; ``max_batches`` stops early.
+    With a ``wandb_run`` on the model the scalars are logged as ``ll/pll_...``."""
+    rbm = _bottom(model)
+    loader = loader if loader is not None else getattr(model, "val_loader", None)
+    if loader is None:
+        return None
+
+    def sums(batch):
+        pll = pseudo_log_likelihood(rbm, _first(batch))
+        bad = torch.isnan(pll)
+        return torch.stack([torch.where(bad, torch.zeros_like(pll), pll).sum(), bad.sum().double()])
+
+    (s, bad), rows = _sum_batches(loader, max_batches, sums, 2)
+    n = rows - int(bad)
+    mean = s / max(1, n)
+    res = {"mean_pll": mean, "sum_pll": s, "n": n, "mean_site": mean / _n_sites(rbm), "n_invalid": int(bad)}
+    _log_scalars(model, "ll/pll_", res, ("mean_pll", "mean_site", "n", "n_invalid"))
+    return res
+
+
+@torch.no_grad()
+def imdbn_pseudo_log_likelihood(model, img: torch.Tensor, y: torch.Tensor, seed: Optional[int] = None):
+    """``(pll_joint [B], log_p_y_given_z [B])``, float64 on the device: the pseudo-log-likelihood of ``model.joint_rbm`` at the rows
+    ``[z | one-hot y]``, z the binary code drawn from the image layers as ``imdbn_sample_values`` draws it (one sample per row, one
+    ``bound_step`` per image layer), and the label group's site term, which is the exact log p(y | z) of the joint RBM -- the
+    classification log-loss, without a chain.  ``y``: one-hot ``[B, K]`` or class indices ``[B]``; a label outside ``[0, K)`` leaves
+    the group empty and makes both outputs of that row NaN.  See the module docstring for ``seed``.  No host sync."""
+    jr = model.joint_rbm
+    dev = jr.W.device
+    _, z, B, _ = _directed(list(model.image_idbn.layers), img, dev, 1, "entropy", _draws(seed))
+    K = int(model.num_labels)
+    Dz = z.size(1)
+    gt = _label_index(y.to(dev)).long()
+    rows = torch.zeros(B, Dz + K, device=dev)
+    rows[:, :Dz] = z
+    ok = (gt >= 0) & (gt < K)
+    rows[:, Dz:] = torch.nn.functional.one_hot(torch.where(ok, gt, torch.zeros_like(gt)), K).float() * ok.unsqueeze(1).float()
+    pll, sites = _E.get_engine(jr.W.data).pseudo_loglik(jr, rows, return_sites=True)
+    return pll, sites[:, Dz:].double().sum(1)
