@@ -283,6 +283,30 @@ int imdbn_rows_logmeanexp(const double* logw, int N, int M, double* out_lme, dou
 int imdbn_rbm_label_loglik(const imdbn_rbm_desc* d, const float* z, int64_t ldz, int N, int Dz, int K, const int32_t* gt,
                            double* out_joint, double* out_marg, void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- one ascent step on log p(y | z) of the joint RBM (imdbn/models/rbm.py: train_epoch_labels) ------------------
+ * d: the joint RBM with its momentum buffers, visible = [code (Dz) | labels (K)], Dz + K == V.  No reference counterpart (its w_sup is
+ * unused); the exact gradient of the hybrid objective of Larochelle & Bengio (2008).  With base and a_k as above, U = W[Dz:],
+ * o_kj = base_j + U_kj, s = sigmoid(o), t = gt[row]:
+ *   out_logp[row] = a_t - logsumexp_k a_k       double [N]; the bits of out_joint - out_marg of imdbn_rbm_label_loglik on the parameters
+ *                                               on entry; NaN when t is outside [0, K)
+ *   p_k = exp(a_k - logsumexp a),  r_k = 1[k = t] - p_k,  hpos_j = s_tj,  hneg_j = sum_k p_k s_kj
+ *   G_W[:Dz] = z^T hpos - z^T hneg,  G_W[Dz + k][j] = sum_n r_nk s_nkj,  G_c = sum_n (hpos - hneg),  G_b[Dz + k] = sum_n r_nk,  G_b[:Dz] = 0
+ * and the update of imdbn_rbm_cd_step (rbm.py:212-224) with (pos - neg) replaced by G, the divisor N and no sparsity term, on every
+ * parameter:  W_m = momentum W_m + lr (G_W / N - weight_decay W), W += W_m;  hb_m = momentum hb_m + lr G_c / N, hid_bias += hb_m;
+ * vb_m = momentum vb_m + lr G_b / N, vis_bias += vb_m (the code columns get their momentum only).  Of o only lr, momentum and
+ * weight_decay are read.  All gradients come from the parameters on entry.  A row whose label is outside [0, K) enters no sum (the
+ * divisor stays N) and nothing is read through its label.
+ * The class values are summed in double as in imdbn_rbm_label_loglik; s, p_k and r_k are fp32, hneg and the sums over n of the label
+ * side are single fp32 fma chains in index order, the code side runs the update kernel's exact products: every sum has an order fixed
+ * by (Dz, K, H, N), no floating-point atomics, the same call on the same state gives the same bits.
+ * scratch: N (K + 2 H) floats of the caller's (device; r, hpos, hneg between the launches; contents on return unspecified).  The
+ * workspace is that of the propagation on the first Dz weight rows, which has no room sized by K.
+ * IMDBN_E_INVALID (naming the value) before the first launch, no parameter and no output touched: a null momentum buffer, K outside
+ * [2, 256], Dz < 1, Dz + K != V, N < 1, ldz < Dz, a null z / gt / o / out_logp / scratch.  Workspace: imdbn_ws_bytes(Dz, H, N).
+ * No draws, no host synchronisation, plain launches on `stream`. */
+int imdbn_rbm_label_step(const imdbn_rbm_desc* d, const float* z, int64_t ldz, int N, int Dz, int K, const int32_t* gt,
+                         const imdbn_cd_opts* o, double* out_logp, float* scratch, void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- exact pseudo-log-likelihood (imdbn/utils/likelihood.py: pseudo_log_likelihood) -----------------------------
  * PLL(v) = sum over sites of log p(v_site | v_rest), a site being every visible column outside the softmax groups and every group
  * as a whole.  No reference counterpart; built over the free energy above: with x = hid_bias + v W, sigma = sigmoid(x), s_i = 1 - 2 v_i,

@@ -32,6 +32,7 @@
 #include "kernels_reverse_ais.hpp"
 #include "kernels_bound.hpp"
 #include "kernels_joint.hpp"
+#include "kernels_labelgrad.hpp"
 #include "kernels_pll.hpp"
 
 using namespace imdbn;
@@ -1604,16 +1605,10 @@ int imdbn_rbm_clamped_stats(const imdbn_rbm_desc* d, const float* v_known, const
 
 
 // ---- K3 alone: rbm.py:209-224 from caller-supplied phase tensors ------------------------------------------------------
-int imdbn_rbm_assoc_update(const imdbn_rbm_desc* d, const float* vpos, int64_t ldvp, const float* hpos, int64_t ldhp,
-                           const float* vneg, int64_t ldvn, const float* hneg, int64_t ldhn, int B, const imdbn_cd_opts* o,
-                           void* ws, size_t ws_bytes, imdbn_stream_t stream) {
-    CHK(check_desc(d, true));
-    if (!vpos || !hpos || !vneg || !hneg || !o || ldvp < d->V || ldvn < d->V || ldhp < d->H || ldhn < d->H)
-        return fail(IMDBN_E_INVALID, "assoc_update: bad tensor argument");
-    Ctx c(d, nullptr, S(stream));
-    CHK(setup(c, B, ws, ws_bytes));
+// operand planes + column sums of the four tensors (exact three-term planes wherever a value is not exactly bf16), then the update
+static int assoc_from_tensors(Ctx& c, const float* vpos, int64_t ldvp, const float* hpos, int64_t ldhp, const float* vneg, int64_t ldvn,
+                              const float* hneg, int64_t ldhn, const imdbn_cd_opts* o, bool sparsity) {
     const Layout& L = c.L;
-    // operand planes + column sums of the four tensors (exact three-term planes wherever a value is not exactly bf16)
     CHK(prep(c, vpos, ldvp, L.V, nullptr, L.Vpad, L.vis_tr[0], L.flags, L.cs_vpos, c.rt));
     CHK(prep(c, vneg, ldvn, L.V, nullptr, L.Vpad, L.vis_tr[1], nullptr, L.cs_vneg, c.rt));
     CHK(prep(c, hpos, ldhp, L.H, nullptr, L.Hpad, L.hid_tr[0], L.flags_h, L.cs_hpos, c.ht));
@@ -1626,10 +1621,62 @@ int imdbn_rbm_assoc_update(const imdbn_rbm_desc* d, const float* vpos, int64_t l
         hipLaunchKernelGGL(prep_operand, dim3(cdiv(L.Hpad, 64), L.P), dim3(256), 0, c.s, p);
         HIPCHK(hipGetLastError());
     }
-    BiasArgs bias = make_bias(c, o, o->sparsity != 0, (float)B, nullptr);
+    BiasArgs bias = make_bias(c, o, sparsity, (float)L.B, nullptr);
     bias.loss_part = nullptr; bias.n_loss = 0;
-    CHK(launch_assoc(c, 0, o, c.nw == 1 ? 1 : 0, L.flags, c.rt, (float)B, nullptr, &bias));
+    CHK(launch_assoc(c, 0, o, c.nw == 1 ? 1 : 0, L.flags, c.rt, (float)L.B, nullptr, &bias));
     return 0;
+}
+
+int imdbn_rbm_assoc_update(const imdbn_rbm_desc* d, const float* vpos, int64_t ldvp, const float* hpos, int64_t ldhp,
+                           const float* vneg, int64_t ldvn, const float* hneg, int64_t ldhn, int B, const imdbn_cd_opts* o,
+                           void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(check_desc(d, true));
+    if (!vpos || !hpos || !vneg || !hneg || !o || ldvp < d->V || ldvn < d->V || ldhp < d->H || ldhn < d->H)
+        return fail(IMDBN_E_INVALID, "assoc_update: bad tensor argument");
+    Ctx c(d, nullptr, S(stream));
+    CHK(setup(c, B, ws, ws_bytes));
+    return assoc_from_tensors(c, vpos, ldvp, hpos, ldhp, vneg, ldvn, hneg, ldhn, o, o->sparsity != 0);
+}
+
+// ---- one ascent step on log p(y | z) of the joint RBM (imdbn/models/rbm.py: train_epoch_labels; kernels_labelgrad.hpp) ---
+// base = z W[:Dz] + c as imdbn_rbm_label_loglik leaves it (f_h); label_grad_rows (logp, r, hpos, hneg into the caller's scratch);
+// label_grad_update (the label rows of W / W_m and the label entries of the visible bias and its momentum, from base and the old
+// label rows); then the update path of imdbn_rbm_assoc_update on the descriptor cut to its first Dz rows with vpos = vneg = z:
+// W[:Dz] gets z^T hpos - z^T hneg, hid_bias the column sums of hpos - hneg, the code columns of vis_bias their momentum.
+// Its operand preparation writes vis_tr / hid_tr / flags / column sums: f_h and the scratch are out of its way, and the label kernel
+// has read base and the label rows before the update kernel starts (one stream), so both halves see the parameters on entry.
+int imdbn_rbm_label_step(const imdbn_rbm_desc* d, const float* z, int64_t ldz, int N, int Dz, int K, const int32_t* gt,
+                         const imdbn_cd_opts* o, double* out_logp, float* scratch, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(check_desc(d, true));
+    CHK(LabelSide::check("label_step", d, Dz, K));
+    if (Dz + K != d->V) return fail(IMDBN_E_INVALID, "label_step: Dz + K = %d is not V = %d", Dz + K, d->V);
+    if (N < 1) return fail(IMDBN_E_INVALID, "label_step: N = %d rows", N);
+    if (ldz < Dz) return fail(IMDBN_E_INVALID, "label_step: ldz %lld < Dz %d", (long long)ldz, Dz);
+    if (!z || !gt || !o || !out_logp || !scratch)
+        return fail(IMDBN_E_INVALID, "label_step: null %s", !z ? "z" : (!gt ? "gt" : (!o ? "opts" : (!out_logp ? "out_logp" : "scratch"))));
+    LabelSide s(d, Dz, S(stream));
+    CHK(s.propagate(z, ldz, N, ws, ws_bytes));
+    Ctx& c = s.c;
+    const int H = d->H;
+    LabelGradArgs g{};
+    g.j.base = s.base; g.j.ldb = H;
+    g.j.z = z; g.j.ldz = ldz;
+    g.j.bz = s.bz; g.j.by = s.by;
+    g.j.Wy = s.Wy; g.j.ldw = d->ldw;
+    g.j.gt = gt; g.j.N = N; g.j.Dz = Dz; g.j.K = K; g.j.H = H;
+    g.logp = out_logp;
+    g.r = scratch; g.hpos = scratch + (size_t)N * K; g.hneg = g.hpos + (size_t)N * H;
+    hipLaunchKernelGGL(label_grad_rows, dim3(cdiv(N, ROW_WAVES)), dim3(64 * ROW_WAVES), 0, c.s, g);
+    HIPCHK(hipGetLastError());
+    LabelUpdateArgs u{};
+    u.base = s.base; u.ldb = H; u.r = g.r;
+    u.U = d->W + (int64_t)Dz * d->ldw; u.Um = d->W_m + (int64_t)Dz * d->ldw; u.ldw = d->ldw;
+    u.by = d->vis_bias + Dz; u.bym = d->vb_m + Dz;
+    u.N = N; u.K = K; u.H = H;
+    u.lr = o->lr; u.mom = o->momentum; u.wd = o->weight_decay; u.n = (float)N;
+    hipLaunchKernelGGL(label_grad_update, dim3((unsigned)(((int64_t)K * H + K + 255) / 256)), dim3(256), 0, c.s, u);
+    HIPCHK(hipGetLastError());
+    return assoc_from_tensors(c, z, ldz, g.hpos, H, z, ldz, g.hneg, H, o, false);
 }
 
 // ---- C1: collectives over RCCL for callers that do not go through torch.distributed ------------------------------------

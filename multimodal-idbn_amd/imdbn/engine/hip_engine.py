@@ -412,6 +412,30 @@ class HipEngine:
                    *self._ws_tail(dev, Dz, d.H, max(n, 1)))       # the propagation is (Dz, H, N): its workspace, not (V, H, N)
         return joint, marg
 
+    def label_step(self, rbm, z: torch.Tensor, K: int, gt: torch.Tensor, lr: float, mom: float) -> torch.Tensor:
+        """One ascent step on ``mean log p(gt | z)`` of the joint RBM ``rbm`` over ``[z (Dz) | labels (K)]`` (imdbn_rbm_label_step):
+        every parameter and momentum buffer is updated in place with learning rate ``lr``, momentum ``mom`` and the RBM's weight
+        decay.  Returns ``log p(gt | z)`` under the parameters on entry, a float64 device tensor ``[N]`` (NaN where ``gt`` is
+        outside ``[0, K)``; such a row enters no gradient).  One up propagation, two kernels and the update path, no draws, no
+        host sync."""
+        d = self._desc(rbm, True)
+        if not z.is_cuda or z.dim() != 2:
+            raise N.EngineError("label_step needs a HIP tensor z [N, Dz]")
+        z = _f32c(z)
+        n, Dz = z.shape
+        dev = z.device
+        g = _on(gt, dev, torch.int32)
+        if g is None or g.numel() != n:
+            raise N.EngineError("label_step: gt must hold one label per row of z")
+        K = int(K)
+        o = self._opts(rbm, lr, mom, 1)
+        logp = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        need = max(n, 1) * (max(K, 0) + 2 * d.H)
+        scratch = self._buffer(("label_step", dev, torch.cuda.current_stream(dev).cuda_stream), lambda: _f32(dev, need), need)
+        self._call("imdbn_rbm_label_step", C.byref(d), _ptr(z), z.stride(0), n, Dz, K, _ptr(g), C.byref(o), _ptr(logp), _ptr(scratch),
+                   *self._ws_tail(dev, Dz, d.H, max(n, 1)))       # the propagation and the update are (Dz, H, N), as label_loglik
+        return logp
+
     def pseudo_loglik(self, rbm, v: torch.Tensor, return_sites: bool = False):
         """Exact pseudo-log-likelihood per row of ``v`` ``[N, V]`` (0/1, one-hot softmax groups; imdbn_rbm_pseudo_loglik):
         ``PLL = sum_sites log p(v_site | v_rest)``, a float64 device tensor ``[N]``; with ``return_sites`` also the per-column terms,

@@ -261,6 +261,20 @@ class iMDBN(nn.Module):
         last.lr = old_lr
         print("[finetune_image_last_layer] done")
 
+    def finetune_joint_labels(self, epochs: int = 0, lr_scale: float = 0.3):
+        """The supervised analogue of ``finetune_image_last_layer`` (extension): ``epochs`` passes over the training
+        loader of ``RBM.train_epoch_labels`` on the joint RBM, at ``lr_scale`` times its learning rate.  Returns the mean
+        ``-log p(y | z)`` per epoch (also kept as ``self.finetune_sup_nll``); one host sync per epoch."""
+        self.finetune_sup_nll = []
+        for ep in range(max(0, int(epochs))):
+            nll = []
+            for img, y in batches(self.dataloader):
+                z = self.image_idbn.represent(rows_on_device(img, self.device))
+                nll.append(self.joint_rbm.train_epoch_labels(z, y.to(self.device).argmax(dim=1), ep, int(epochs), self.num_labels,
+                                                             lr_mult=float(lr_scale)))
+            self.finetune_sup_nll.append(float(torch.stack(nll).mean()) if nll else float("nan"))
+        return self.finetune_sup_nll
+
     # ---- cross-modal inference (imdbn.py:386-488) -------------------------------------------------
     @torch.no_grad()
     def _cross_reconstruct(self, z_img: torch.Tensor, y_onehot: torch.Tensor,
@@ -352,9 +366,16 @@ class iMDBN(nn.Module):
         """Warm-up (epochs < 8): 2x label-clamped CD per batch; then free CD + label-clamped CD
         (+ image-clamped CD every 50th batch); `_cross_reconstruct` metrics on EVERY batch.
 
+        ``w_sup > 0`` (extension; the reference carries the argument unused): after a batch's generative updates, one exact
+        ascent step on ``log p(y | z_img)`` at ``w_sup`` times the scheduled learning rate (``RBM.train_epoch_labels``, the hybrid
+        objective of Larochelle & Bengio 2008); the epoch record gains ``"sup_nll"``.  ``w_sup == 0`` changes nothing.
+
         Metric accumulators stay on the device and are fetched once per epoch
         (``self.joint_history``); the reference syncs 4x per batch (imdbn.py:635-638).
         """
+        w_sup = float(w_sup)
+        if w_sup > 0 and _E.dp.active():
+            raise NotImplementedError("train_joint(w_sup > 0) has no data-parallel split; run w_sup on a single rank")
         print("[iMDBN] joint training (with warmup y-clamp)")
         self.init_joint_bias_from_data(n_batches=10)
         jr = self.joint_rbm
@@ -365,7 +386,7 @@ class iMDBN(nn.Module):
         # numbers; one event each way per batch.  JOINT_METRICS_OVERLAP=False runs it in line.
         ov = _MetricsOverlap(self) if (bool(self.params.get("JOINT_METRICS_OVERLAP", True)) and jr.W.is_cuda) else None
         for epoch in range(int(epochs)):
-            cd_losses = []
+            cd_losses, sup_nll = [], []
             acc = torch.zeros(5, device=self.device, dtype=torch.float64)   # n, top1, top3, ce_sum, mse_sum
             npix, n_rows = None, 0
             for b_idx, (img, y) in enumerate(batches(self.dataloader)):
@@ -396,6 +417,8 @@ class iMDBN(nn.Module):
                         jr.train_epoch_clamped(vk, km, epoch, epochs, CD=1, cond_init_steps=aux_cond_steps,
                                                sample_h=False, sample_v=False, reclamp_negative=False,
                                                aux_lr_mult=0.3, use_noisy_init=True)
+                if w_sup > 0:
+                    sup_nll.append(jr.train_epoch_labels(z_img, y.argmax(dim=1), epoch, epochs, K, lr_mult=w_sup))
                 npix = img.size(1)
                 n_rows += B
                 if ov is not None:
@@ -407,16 +430,21 @@ class iMDBN(nn.Module):
             acc[0] = float(n_rows)
             if _E.dp.active():                      # each rank accumulated its shard: sums over rows
                 _E.dp.all_reduce_sum(acc)
-            a = acc.cpu()
+            sup = torch.stack(sup_nll).mean().reshape(1) if sup_nll else None       # rides on the epoch's one fetch
+            a = (acc if sup is None else torch.cat([acc, sup.to(acc.dtype)])).cpu()
             n = max(1.0, float(a[0]))
             rec = {"epoch": epoch, "n": int(a[0]), "text_top1": float(a[1]) / n, "text_top3": float(a[2]) / n,
                    "text_ce": float(a[3]) / n, "image_mse": float(a[4]) / max(1.0, n * max(1, npix or 1)),
                    "cd_loss": float(torch.stack(cd_losses).mean()) if cd_losses else None,
                    "cd_losses": torch.stack(cd_losses).cpu() if cd_losses else None}
+            if w_sup > 0:
+                rec["sup_nll"] = float(a[5]) if sup is not None else None
             self.joint_history.append(rec)
             if self.wandb_run:
                 if rec["cd_loss"] is not None:
                     self.wandb_run.log({"joint/cd_loss": rec["cd_loss"], "epoch": epoch})
+                if rec.get("sup_nll") is not None:
+                    self.wandb_run.log({"joint/sup_nll": rec["sup_nll"], "epoch": epoch})
                 self.wandb_run.log({"cross_modality/text_top1": rec["text_top1"], "cross_modality/text_top3": rec["text_top3"],
                                     "cross_modality/text_ce": rec["text_ce"], "cross_modality/image_mse": rec["image_mse"],
                                     "epoch": epoch})

@@ -261,6 +261,21 @@ class RBM(nn.Module):
         loss = eng.cd_step(self, x, lr, mom, CD, rng, next_data=next_data, **kw)
         return (loss, self.forward(data)) if return_forward else loss
 
+    # ---- supervised step on the labels (extension) ---------------------------------------
+    @torch.no_grad()
+    def train_epoch_labels(self, z: torch.Tensor, gt: torch.Tensor, epoch: int, max_epochs: int, num_labels: int,
+                           lr_mult: float = 1.0):
+        """One ascent step on ``mean log p(gt | z)`` of a joint RBM over ``[z | one-hot label]`` (the last ``num_labels`` visible
+        columns): the exact gradient of the hybrid objective of Larochelle & Bengio (2008), applied to every parameter with the
+        learning rate (times ``lr_mult``) and momentum schedule of ``train_epoch``.  ``gt``: integer labels ``[B]``; a label
+        outside ``[0, num_labels)`` takes no part.  Returns the 0-d device scalar ``-nanmean(log p(gt | z))`` (float64) under the
+        parameters before the step.  No reference counterpart (its ``w_sup`` is unused); no draws."""
+        if _E.dp.active():
+            raise NotImplementedError("train_epoch_labels (w_sup) has no data-parallel split")
+        lr, mom = self._lr_mom(epoch)
+        logp = self._eng().label_step(self, self._in(z), int(num_labels), gt, float(lr_mult) * lr, mom)
+        return -torch.nanmean(logp)
+
     # ---- schedules (rbm.py:229-238) -------------------------------------------------------------
     def _lin_schedule(self, t, t_max, start, end):
         if t_max <= 1:
