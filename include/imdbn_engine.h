@@ -368,6 +368,53 @@ int imdbn_rbm_cd_step(const imdbn_rbm_desc* d, const float* data, int64_t ldd, i
  * float4 fused K2 carries the prefetch blocks), else 0 -- then next_data is ignored and nothing may be assumed prefetched. */
 int imdbn_rbm_prefetch_ok(const imdbn_rbm_desc* d, int B);
 
+/* ---- persistent contrastive divergence (imdbn/models/rbm.py: train_epoch_persistent; Tieleman 2008) -------------
+ * The update of imdbn_rbm_cd_step (rbm.py:199-226) with the negative phase taken from caller-owned chains instead of from the data.
+ * particles [B][V]: fp32, 0/1, one-hot inside softmax groups, row stride ldp >= V; READ AND OVERWRITTEN.
+ *   pos_h = sigmoid(data W + c);   pos_assoc = data^T pos_h
+ *   v = particles;  o->cd_k times (cd_k >= 0; 0: the particles as they are):
+ *       h = 1[sigmoid(v W + c) > U];   v = sample_visible(visible_probs(h))              ("u", H), ("u", V), ("c", w_g) per group
+ *   h_neg = sigmoid(v W + c) (probabilities, no draw);   neg_assoc = v^T h_neg
+ *   the update of rbm.py:212-224 with (h_prob, v) := (h_neg, v), divisor B, the sparsity term from pos_h when o->sparsity
+ *   particles := v
+ * draws_used = cd_k (2 + G); rng may be NULL when cd_k = 0.
+ * loss_out (device float[1], nullable): mean((data - v_rec)^2) with v_rec = visible_probs(pos_h) at T = 1, the mean-field
+ * reconstruction error -- one more down propagation (a persistent chain does not reconstruct the batch, so the v_prob of
+ * imdbn_rbm_cd_step does not exist here); NULL: that propagation is not launched.
+ * o->data_binary as in imdbn_rbm_cd_step; the prefetch fields (next_data, next_slot, data_slot, next_binary) and fwd_out must be zero.
+ * Every sum has the order imdbn_rbm_cd_step gives it; the same call on the same state gives the same bits.
+ * IMDBN_E_INVALID (naming the value) before the first launch, nothing touched: a null momentum buffer, null data / particles / o,
+ * ldd < V, ldp < V, B < 1, cd_k < 0, a null rng with cd_k > 0, a non-zero prefetch field or fwd_out; IMDBN_E_RNG: a replay tape
+ * shorter than the draws.  Workspace: imdbn_ws_bytes(V, H, B); the reconstruction needs no more. */
+int imdbn_rbm_pcd_step(const imdbn_rbm_desc* d, const float* data, int64_t ldd, int B, float* particles, int64_t ldp,
+                       const imdbn_cd_opts* o, imdbn_rng* rng, float* loss_out, void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
+/* ---- parallel tempering over persistent chains (Desjardins et al. 2010; Cho, Raiko & Ilin 2010) -----------------
+ * state [R M][V]: fp32, 0/1, one-hot inside softmax groups, row stride lds >= V, IN PLACE; replica r owns the rows [r M, (r + 1) M)
+ * and samples p_beta(v) ~ exp(beta b.v + S(beta, v)), S(beta, v) = sum_j softplus(beta x_j(v)), x(v) = c + v W, at beta = betas[r].
+ * betas: HOST array of R floats, 0 < betas[0] < ... < betas[R - 1] = 1.  swap_try / swap_acc: device int64 [max(R - 1, 1)], ADDED
+ * to (the caller zeroes them): proposals and acceptances of the pair (r, r + 1) at index r.
+ * Sweep s = 0 .. n_sweeps - 1:
+ *   1. one Gibbs step per replica at T = 1 / betas[r]: h = 1[sigmoid(beta x(v)) > U], v = sample_visible(visible_probs(h, T)) -- the
+ *      propagations of imdbn_rbm_gibbs_step(sample_h = 1, sample_v = 1) on the replica's rows.  The draw tensors span all R M rows:
+ *      ("u", H), ("u", V), ("c", w_g) per group, and Philox is keyed on the row within them.
+ *   2. only when R >= 2: for every pair (r, r + 1) with r = s (mod 2), r + 1 < R, and every chain m, with u / u' the states of
+ *      chain m in the replicas r / r + 1:
+ *        Delta = (beta_{r+1} - beta_r) (b.u - b.u') + S(beta_r, u') + S(beta_{r+1}, u) - S(beta_r, u) - S(beta_{r+1}, u')
+ *        the two rows are swapped  iff  log(U) < Delta,     U: ("u", 1) over all R M rows, read at the LOWER replica's row
+ *      -- the Metropolis ratio of the two tempered marginals; a one-hot group is part of the state and needs nothing extra.  The
+ *      ("u", 1) tensor is consumed every sweep, also when no pair has the sweep's parity.  The logits are those of one logits-only
+ *      up propagation over all rows; the softplus sums run in fp32 over chunks of 128 hidden units and in double across the
+ *      chunks, b.u - b.u' in double, the comparison in double: every order is fixed by (V, H); the counters are integer atomics,
+ *      there are no floating-point atomics.  A row outside every pair of the sweep is not touched by the exchange.
+ * draws_used = n_sweeps (2 + G + [R >= 2]).  R = 1 is n_sweeps Gibbs steps at T = 1: the bits of imdbn_rbm_gibbs_step on the same draws.
+ * IMDBN_E_INVALID (naming the value), nothing launched: null state / betas / rng / swap_try / swap_acc, lds < V, R < 1, M < 1,
+ * n_sweeps < 0, betas[0] <= 0, betas[R - 1] != 1, betas not increasing; IMDBN_E_UNSUPPORTED: R > 64; a REPLAY tape with R >= 2 and
+ * more than one softmax group; IMDBN_E_RNG: a replay tape shorter than the draws.
+ * Workspace: imdbn_ws_bytes(V, H, R M), and no less than imdbn_ws_bytes(V, H, M) (the replicas' steps; checked).  Parameters are only read. */
+int imdbn_rbm_pt_sweep(const imdbn_rbm_desc* d, float* state, int64_t lds, int R, int M, const float* betas, int n_sweeps, imdbn_rng* rng,
+                       int64_t* swap_try, int64_t* swap_acc, void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- data-parallel split of the same update ------------------------------ */
 /* packed layout (floats): [dW V*H][dc H][db V][sum P+ H][sq-err sum 1][pad to 4] */
 size_t imdbn_packed_delta_floats(int V, int H);

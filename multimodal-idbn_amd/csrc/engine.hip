@@ -34,6 +34,7 @@
 #include "kernels_joint.hpp"
 #include "kernels_labelgrad.hpp"
 #include "kernels_pll.hpp"
+#include "kernels_pt.hpp"
 
 using namespace imdbn;
 
@@ -1603,6 +1604,176 @@ int imdbn_rbm_clamped_stats(const imdbn_rbm_desc* d, const float* v_known, const
     return 0;
 }
 
+
+// ---- persistent chains (imdbn/models/rbm.py: train_epoch_persistent; kernels_pt.hpp) -----------------------------------
+// a REPLAY tape must hold what the call will draw: checked before the first launch, so that an error leaves nothing touched
+static int tape_room(const char* name, const imdbn_rng* rng, int64_t floats, int64_t cats) {
+    if (!rng || rng->mode != IMDBN_RNG_REPLAY) return 0;
+    if ((floats > 0 && (!rng->tape || rng->tape_len < floats)) || (cats > 0 && (!rng->cat_tape || rng->cat_len < cats)))
+        return fail(IMDBN_E_RNG, "%s: the replay tape holds %lld floats / %lld indices, the call draws %lld / %lld", name,
+                    (long long)rng->tape_len, (long long)rng->cat_len, (long long)floats, (long long)cats);
+    return 0;
+}
+
+// rbm.py:199-209 with the negative phase taken from the caller's particles: cd_k Gibbs steps on them (written back in place), H- from
+// where they end, then the positive phase of the data -- it draws nothing, so it may come last, and with `recon` its probabilities
+// stay in hid_rm for one more down propagation, the mean-field reconstruction whose squared error is the loss.  That K2 is the last
+// of the call: its block count is what n_loss_used() reports.  Leaves the statistics operands in the workspace exactly as cd_phases does.
+static int pcd_phases(Ctx& c, const float* data, int64_t ldd, float* particles, int64_t ldp, const imdbn_cd_opts* o, bool recon) {
+    const Layout& L = c.L;
+    const int B = L.B;
+    const bool vbits = c.r.vbits;      // (Route: the visible state travels as a bit plane too, as the negative phase of cd_phases)
+    // v = particles: a 0/1 state is one bf16 term; with cd_k = 0 they are the negative statistics as they are
+    CHK(prep(c, particles, ldp, L.V, L.vis_rm[1], L.Vpad, L.vis_tr[1], nullptr, L.cs_vneg, 1, vbits ? L.vis_bits[1] : nullptr));
+    const OpIn vneg{L.vis_rm[1], 1, nullptr, vbits ? L.vis_bits[1] : nullptr, 1};
+    for (int it = 0; it < o->cd_k; ++it) {
+        {   // h = 1[up(v) > U]
+            FinishArgs f = new_finish();
+            f.vmode = 1; f.uni = c.rng.floats(B, L.H);
+            f.op.rm = L.hid_rm; f.op.rm_terms = 1; f.rm_src = 2;
+            CHK(prop(c, true, vneg, f));
+        }
+        {   // v = sampleV(down(h)), into the particles
+            FinishArgs f = new_finish();
+            f.vmode = 1; f.uni = c.rng.floats(B, L.V);
+            c.rng.cats(B, c.d->n_groups, &f.cat_tape, &f.cat_uni);
+            if (c.r.neg_rm) { f.op.rm = L.vis_rm[1]; f.op.rm_terms = 1; f.rm_src = 2; }      // (only a K1 that cannot read the bit plane needs it)
+            f.op.tr = L.vis_tr[1]; f.op.tr_terms = 1; f.tr_src = 2;
+            f.colsum_part = L.cs_vneg; f.colsum_src = 2;
+            if (vbits) f.op.bits = L.vis_bits[1];
+            f.out_final = particles; f.ld_final = ldp;
+            CHK(prop(c, false, OpIn{L.hid_rm, 1, nullptr}, f));
+        }
+    }
+    {   // H- = up(v): probabilities, no draw
+        FinishArgs f = new_finish();
+        f.op.tr = L.hid_tr[1]; f.op.tr_terms = c.ht; f.tr_src = 1; f.op.tr_negate = 1;
+        f.colsum_part = L.cs_hneg; f.colsum_src = 1;
+        CHK(prop(c, true, vneg, f));
+    }
+    // positive phase: P+ = up(data)
+    CHK(prep(c, data, ldd, L.V, L.vis_rm[0], L.Vpad, L.vis_tr[0], L.flags, L.cs_vpos, 3, L.vis_bits[0]));
+    {
+        FinishArgs f = new_finish();
+        if (recon) { f.op.rm = L.hid_rm; f.op.rm_terms = c.rt; f.rm_src = 1; }
+        f.op.tr = L.hid_tr[0]; f.op.tr_terms = c.ht; f.tr_src = 1;
+        f.colsum_part = L.cs_hpos; f.colsum_src = 1;
+        CHK(prop(c, true, OpIn{L.vis_rm[0], c.nw == 1 ? 1 : 0, L.flags, L.vis_bits[0], data_operand_kind(o->data_binary)}, f));
+    }
+    if (recon) {   // v_rec = down(P+) at T = 1; its squared error against the data
+        FinishArgs f = new_finish();
+        f.loss_ref = data; f.ld_ref = ldd; f.loss_src = 1; f.loss_part = L.loss_part;
+        CHK(prop(c, false, OpIn{L.hid_rm, c.rt, nullptr}, f));
+    }
+    return 0;
+}
+
+int imdbn_rbm_pcd_step(const imdbn_rbm_desc* d, const float* data, int64_t ldd, int B, float* particles, int64_t ldp,
+                       const imdbn_cd_opts* o, imdbn_rng* rng, float* loss_out, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(check_desc(d, true));
+    if (!data || !particles || !o) return fail(IMDBN_E_INVALID, "pcd_step: null %s", !data ? "data" : (!particles ? "particles" : "opts"));
+    if (ldd < d->V) return fail(IMDBN_E_INVALID, "pcd_step: ldd %lld < V %d", (long long)ldd, d->V);
+    if (ldp < d->V) return fail(IMDBN_E_INVALID, "pcd_step: ldp %lld < V %d", (long long)ldp, d->V);
+    if (B < 1) return fail(IMDBN_E_INVALID, "pcd_step: B = %d rows", B);
+    if (o->cd_k < 0) return fail(IMDBN_E_INVALID, "pcd_step: cd_k = %d", o->cd_k);
+    if (o->cd_k > 0 && !rng) return fail(IMDBN_E_INVALID, "pcd_step: null rng with cd_k = %d", o->cd_k);
+    if (o->data_binary < 0 || o->data_binary > 2) return fail(IMDBN_E_INVALID, "pcd_step: data_binary %d outside 0..2", o->data_binary);
+    if (o->next_data || o->next_slot || o->data_slot || o->next_binary || o->fwd_out)
+        return fail(IMDBN_E_INVALID, "pcd_step: the prefetch fields and fwd_out must be zero (next_data %p, next_slot %d, data_slot %d, next_binary %d, fwd_out %p)",
+                    (const void*)o->next_data, o->next_slot, o->data_slot, o->next_binary, (const void*)o->fwd_out);
+    const int G = d->n_groups;
+    CHK(tape_room("pcd_step", rng, (int64_t)o->cd_k * B * ((int64_t)d->H + d->V), (int64_t)o->cd_k * G * B));
+    Ctx c(d, rng, S(stream));
+    CHK(setup(c, B, ws, ws_bytes));
+    CHK(pcd_phases(c, data, ldd, particles, ldp, o, loss_out != nullptr));
+    CHK(c.rng.finish());
+    BiasArgs bias = make_bias(c, o, o->sparsity != 0, (float)B, loss_out);
+    if (!loss_out) { bias.loss_part = nullptr; bias.n_loss = 0; }
+    CHK(launch_assoc(c, 0, o, c.nw == 1 ? 1 : 0, c.L.flags, 1, (float)B, nullptr, &bias));
+    return 0;
+}
+
+// rows [row, row + ...) of a draw tensor that spans more rows than the launch it feeds
+static DrawSrc draw_rows(DrawSrc s, int64_t row, int N) {
+    s.row0 += row;
+    if (s.tape) s.tape += row * N;
+    return s;
+}
+
+int imdbn_rbm_pt_sweep(const imdbn_rbm_desc* d, float* state, int64_t lds, int R, int M, const float* betas, int n_sweeps, imdbn_rng* rng,
+                       int64_t* swap_try, int64_t* swap_acc, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(check_desc(d, false));
+    if (!state || !betas || !rng || !swap_try || !swap_acc)
+        return fail(IMDBN_E_INVALID, "pt_sweep: null %s", !state ? "state" : (!betas ? "betas" : (!rng ? "rng" : (!swap_try ? "swap_try" : "swap_acc"))));
+    if (lds < d->V) return fail(IMDBN_E_INVALID, "pt_sweep: lds %lld < V %d", (long long)lds, d->V);
+    if (R < 1) return fail(IMDBN_E_INVALID, "pt_sweep: R = %d replicas", R);
+    if (M < 1) return fail(IMDBN_E_INVALID, "pt_sweep: M = %d chains", M);
+    if (n_sweeps < 0) return fail(IMDBN_E_INVALID, "pt_sweep: n_sweeps = %d", n_sweeps);
+    if (R > PT_RMAX) return fail(IMDBN_E_UNSUPPORTED, "pt_sweep: R = %d replicas; at most %d supported", R, PT_RMAX);
+    if ((int64_t)R * M > (int64_t)INT_MAX / 2) return fail(IMDBN_E_INVALID, "pt_sweep: R M = %lld rows", (long long)R * M);
+    if (!(betas[0] > 0.0f)) return fail(IMDBN_E_INVALID, "pt_sweep: betas[0] = %g, must be above 0", (double)betas[0]);
+    if (betas[R - 1] != 1.0f) return fail(IMDBN_E_INVALID, "pt_sweep: betas[%d] = %g, must be 1", R - 1, (double)betas[R - 1]);
+    for (int r = 1; r < R; ++r)
+        if (!(betas[r] > betas[r - 1]))
+            return fail(IMDBN_E_INVALID, "pt_sweep: betas[%d] = %g is not above betas[%d] = %g", r, (double)betas[r], r - 1, (double)betas[r - 1]);
+    const int G = d->n_groups, RM = R * M, V = d->V, H = d->H;
+    // finish_groups finds group g's indices at cat_tape + g B, B the rows of its launch: a replica's rows of a tape over R M rows
+    // are there for one group only
+    if (rng->mode == IMDBN_RNG_REPLAY && R >= 2 && G >= 2)
+        return fail(IMDBN_E_UNSUPPORTED, "pt_sweep: a replay tape serves R >= 2 replicas with at most one softmax group (n_groups = %d)", G);
+    CHK(tape_room("pt_sweep", rng, (int64_t)n_sweeps * RM * ((int64_t)H + V + (R >= 2 ? 1 : 0)), (int64_t)n_sweeps * G * RM));
+    Ctx call(d, rng, S(stream));       // all R M rows: the draw cursor, the logits of the exchange
+    CHK(setup(call, RM, ws, ws_bytes));
+    Ctx rep(d, nullptr, S(stream));    // one replica's rows: its Gibbs step (the same workspace, one launch after the other)
+    CHK(setup(rep, M, ws, ws_bytes));
+    PtArgs x;
+    memset(&x, 0, sizeof(x));
+    x.state = state; x.lds = lds; x.x = call.L.f_h; x.ldx = H; x.vis_bias = d->vis_bias;
+    x.R = R; x.M = M; x.V = V; x.H = H;
+    x.swap_try = (unsigned long long*)swap_try; x.swap_acc = (unsigned long long*)swap_acc;
+    for (int r = 0; r < R; ++r) x.beta[r] = betas[r];
+    for (int s = 0; s < n_sweeps; ++s) {
+        // part 1: one Gibbs step per replica at T = 1 / beta_r -- imdbn_rbm_gibbs_step(sample_h, sample_v) on the replica's rows
+        const DrawSrc uh = call.rng.floats(RM, H), uv = call.rng.floats(RM, V);
+        const int32_t* ct; DrawSrc cu;
+        call.rng.cats(RM, G, &ct, &cu);
+        for (int r = 0; r < R; ++r) {
+            const int64_t row = (int64_t)r * M;
+            float* rows = state + row * lds;
+            const Layout& L = rep.L;
+            CHK(prep(rep, rows, lds, V, L.vis_rm[0], L.Vpad, nullptr, L.flags));
+            {
+                FinishArgs f = new_finish();
+                f.T = 1.0f / betas[r];
+                f.vmode = 1; f.uni = draw_rows(uh, row, H);
+                f.op.rm = L.hid_rm; f.op.rm_terms = 1; f.rm_src = 2;
+                CHK(prop(rep, true, OpIn{L.vis_rm[0], rep.nw == 1 ? 1 : 0, L.flags}, f));
+            }
+            {
+                FinishArgs f = new_finish();
+                f.T = 1.0f / betas[r];
+                f.vmode = 1; f.uni = draw_rows(uv, row, V);
+                f.cat_tape = ct ? ct + row : nullptr; f.cat_uni = draw_rows(cu, row, 1);
+                f.out_final = rows; f.ld_final = lds;
+                CHK(prop(rep, false, OpIn{L.hid_rm, 1, nullptr}, f));
+            }
+        }
+        if (R < 2) continue;
+        // part 2: exchange between the pairs (r, r + 1), r = s mod 2, s mod 2 + 2, ...; the draw is consumed with or without a pair
+        x.uni = call.rng.floats(RM, 1);
+        x.parity = s & 1; x.n_pairs = (R - x.parity) / 2;
+        if (x.n_pairs == 0) continue;
+        {   // x = c + v W of every row
+            FinishArgs f = new_finish();
+            f.logits_only = 1;
+            f.out_prob = call.L.f_h; f.ld_prob = H;
+            CHK(prep_prop(call, true, state, lds, f));
+        }
+        hipLaunchKernelGGL(pt_exchange_rows, dim3(cdiv(x.n_pairs * M, ROW_WAVES)), dim3(64 * ROW_WAVES), 0, call.s, x);
+        HIPCHK(hipGetLastError());
+    }
+    return call.rng.finish();
+}
 
 // ---- K3 alone: rbm.py:209-224 from caller-supplied phase tensors ------------------------------------------------------
 // operand planes + column sums of the four tensors (exact three-term planes wherever a value is not exactly bf16), then the update

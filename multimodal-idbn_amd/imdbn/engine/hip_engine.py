@@ -568,19 +568,22 @@ class HipEngine:
             o.next_binary = self.binary_hint(next_data)
         return key, nxt
 
-    def _cd(self, name: str, rbm, d, data, o, rng, data_binary, *outs, next_data=None, prefetch: bool = True):
-        """The CD pass behind cd_step / cd_stats / cd_factors / cd_factors_wire: entry `name`(desc, batch, ld, B, opts, rng,
-        *outs, workspace tail).  `d` is the caller's descriptor (each method asks for its own ``need_momentum``), `o` its
-        options.  With `prefetch` (cd_factors has none) this is the one place that consumes and records the next-batch state: the
-        record of this shape is popped before the call, the new one stored only after the call and its draw count came out right."""
+    def _cd(self, name: str, rbm, d, data, o, rng, data_binary, *outs, next_data=None, prefetch: bool = True, particles=None):
+        """The CD pass behind cd_step / cd_stats / cd_factors / cd_factors_wire / pcd_step: entry `name`(desc, batch, ld, B,
+        [particles, ld,] opts, rng, *outs, workspace tail).  `d` is the caller's descriptor (each method asks for its own
+        ``need_momentum``), `o` its options.  With `prefetch` (cd_factors and pcd_step have none) this is the one place that consumes
+        and records the next-batch state: the record of this shape is popped before the call, the new one stored only after the
+        call and its draw count came out right.  `particles`: the persistent chains of pcd_step, whose draws are theirs alone."""
         x = _f32c(data)
         B, dev = x.size(0), x.device
         o.data_binary = self._hint(data, data_binary)       # the caller's tensor: a fp32 copy `x` has lost the tag
-        sched = R.sched_cd(d.V, d.H, self._groups(rbm), o.cd_k)
+        groups = self._groups(rbm)
+        sched = R.sched_cd(d.V, d.H, groups, o.cd_k) if particles is None else R.sched_pcd(d.V, d.H, groups, o.cd_k)
         r, keep = self._rng(rng, sched, B, dev)
         tail = self._ws_tail(dev, d.V, d.H, B)
         key, nxt = self._prefetch_opts(o, d, x, next_data) if prefetch else (None, None)
-        self._call(name, C.byref(d), _ptr(x), x.stride(0), B, C.byref(o), C.byref(r), *outs, *tail)
+        chains = () if particles is None else (_ptr(particles), particles.stride(0))
+        self._call(name, C.byref(d), _ptr(x), x.stride(0), B, *chains, C.byref(o), C.byref(r), *outs, *tail)
         self._done(rng, r, sched)
         if nxt is not None:                      # the strong reference keeps the address from being recycled
             self._pf[key] = (self._ident(nxt), int(o.next_slot), nxt)
@@ -602,6 +605,61 @@ class HipEngine:
         if forward:
             return loss.reshape(()), fwd
         return loss.reshape(())
+
+    @staticmethod
+    def _chains(who: str, t: torch.Tensor, V: int) -> torch.Tensor:
+        """Persistent chains are updated IN PLACE: the caller's tensor goes to the engine as it is, never as a copy."""
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.size(1) == V
+                and t.size(0) >= 1 and t.stride(1) == 1 and t.stride(0) >= V):
+            raise N.EngineError(f"{who} needs its chains as an fp32 HIP tensor [rows, {V}] with unit inner stride (updated in place)")
+        return t
+
+    def pcd_step(self, rbm, data, particles, lr, mom, cd_k, rng, data_binary=None, monitor: bool = True):
+        """One persistent-CD update (imdbn_rbm_pcd_step): the update of ``cd_step`` with the negative phase run for ``cd_k`` Gibbs
+        steps (0: none) on ``particles`` ``[B, V]`` (fp32 0/1, updated in place) instead of from the data.  Returns the mean-field
+        reconstruction error ``mean((data - visible_probs(forward(data)))^2)`` as a 0-d device tensor, or None with
+        ``monitor=False`` (that propagation is then not launched).  No host sync."""
+        d = self._desc(rbm, True)
+        p = self._chains("pcd_step", particles, d.V)
+        if p.size(0) != data.size(0) or p.device != data.device:
+            raise N.EngineError(f"pcd_step: {p.size(0)} chains on {p.device} for a batch of {data.size(0)} rows on {data.device}")
+        o = self._opts(rbm, lr, mom, cd_k, sparsity=getattr(rbm, "sparsity", False))
+        loss = torch.empty(1, device=data.device) if monitor else None
+        self._cd("imdbn_rbm_pcd_step", rbm, d, data, o, rng, data_binary, _ptr(loss), prefetch=False, particles=p)
+        return loss.reshape(()) if monitor else None
+
+    def pt_sweep(self, rbm, state, betas, n_sweeps: int, rng, swap_try: Optional[torch.Tensor] = None,
+                 swap_acc: Optional[torch.Tensor] = None):
+        """``n_sweeps`` parallel-tempering sweeps (imdbn_rbm_pt_sweep) over ``state`` ``[R M, V]`` (fp32 0/1, updated in place), R =
+        ``len(betas)`` replicas of M chains, replica r in the rows ``[r M, (r + 1) M)`` at inverse temperature ``betas[r]``
+        (0 < betas[0] < ... < betas[R - 1] = 1): per sweep one Gibbs step of every replica at its temperature, then the exchange
+        between the neighbouring replicas of the sweep's parity.  Returns ``(swap_try, swap_acc)``, int64 device tensors
+        ``[max(R - 1, 1)]`` the call ADDS its proposals and acceptances per pair to (created zeroed when None).  No host sync."""
+        d = self._desc(rbm, False)
+        x = self._chains("pt_sweep", state, d.V)
+        b = [float(t) for t in (betas.tolist() if hasattr(betas, "tolist") else betas)]
+        Rn, dev = len(b), x.device
+        if Rn < 1 or x.size(0) % Rn != 0:
+            raise N.EngineError(f"pt_sweep: {x.size(0)} rows do not divide into {Rn} replicas")
+        M = x.size(0) // Rn
+        arr = (C.c_float * Rn)(*b)
+        cnt = []
+        for nm, t in (("swap_try", swap_try), ("swap_acc", swap_acc)):
+            if t is None:
+                t = torch.zeros(max(Rn - 1, 1), dtype=torch.int64, device=dev)
+            elif t.dtype != torch.int64 or t.device != dev or t.numel() != max(Rn - 1, 1) or not t.is_contiguous():
+                raise N.EngineError(f"pt_sweep: {nm} must be a contiguous int64 [{max(Rn - 1, 1)}] tensor on {dev}")
+            cnt.append(t)
+        sched = R.sched_pt(d.V, d.H, self._groups(rbm), Rn, n_sweeps)
+        r, keep = self._rng(rng, sched, Rn * M, dev)
+        # the replicas' steps run on M rows, the exchange on all of them: one workspace that serves both layouts
+        need = max(int(self._lib.imdbn_ws_bytes(d.V, d.H, Rn * M)), int(self._lib.imdbn_ws_bytes(d.V, d.H, M)))
+        ws = self._buffer(("pt_sweep", dev, d.V, d.H, torch.cuda.current_stream(dev).cuda_stream),
+                          lambda: torch.empty(need, dtype=torch.uint8, device=dev), need)
+        self._call("imdbn_rbm_pt_sweep", C.byref(d), _ptr(x), x.stride(0), Rn, M, arr, int(n_sweeps), C.byref(r), _ptr(cnt[0]), _ptr(cnt[1]),
+                   _ptr(ws), ws.numel(), self._stream(dev))
+        self._done(rng, r, sched)
+        return cnt[0], cnt[1]
 
     def assoc_update(self, rbm, vpos, hpos, vneg, hneg, lr, mom):
         """The weight / bias update alone (rbm.py:209-224) from the four phase tensors (imdbn_rbm_assoc_update)."""

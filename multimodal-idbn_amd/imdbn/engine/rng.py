@@ -73,6 +73,16 @@ def sched_cd(V: int, H: int, groups, cd_k: int) -> Schedule:
     return s
 
 
+def sched_pcd(V: int, H: int, groups, cd_k: int) -> Schedule:
+    """imdbn_rbm_pcd_step: cd_k Gibbs steps on the particles, nothing else draws: cd_k (2 + G) draws for G groups."""
+    return int(cd_k) * ([("u", H)] + sched_sample_visible(V, groups))
+
+
+def sched_pt(V: int, H: int, groups, n_replicas: int, n_sweeps: int) -> Schedule:
+    """imdbn_rbm_pt_sweep, every tensor over all R M rows: per sweep one Gibbs step and, with R >= 2, the ("u", 1) of the exchange."""
+    return int(n_sweeps) * ([("u", H)] + sched_sample_visible(V, groups) + ([("u", 1)] if int(n_replicas) >= 2 else []))
+
+
 def sched_chain(V: int, H: int, groups, steps, init_uniform: bool) -> Schedule:
     s: Schedule = [("u", V)] if init_uniform else []
     for st in steps:

@@ -18,6 +18,12 @@ from imdbn.models.rbm import RBM
 from imdbn.utils import batches, rows_on_device
 
 
+def binary_input(v: torch.Tensor) -> bool:
+    """Whether a layer's input can seed persistent chains: anything but the probabilities an engine propagation returned (those
+    carry ``_imdbn_binary = False``, RBM.forward)."""
+    return getattr(v, "_imdbn_binary", None) is not False
+
+
 class iDBN:
     def __init__(
         self,
@@ -101,6 +107,10 @@ class iDBN:
         (values identical).  ``self.loss_history`` keeps them.
         """
         self.loss_history = []
+        # extension (DESIGN §23), off by default: params["PERSISTENT"] trains the layers whose input is binary -- a batch of the
+        # loader, never another layer's probabilities -- with persistent chains (RBM.train_epoch_persistent: PCD-k, or parallel
+        # tempering over params["PT_BETAS"]); every other layer keeps CD-k
+        persistent, pt_betas = bool(self.params.get("PERSISTENT", False)), self.params.get("PT_BETAS")
         for epoch in range(int(epochs)):
             losses = []
             # one batch of lookahead: the first layer prepares the operand forms of the following batch during its
@@ -115,7 +125,11 @@ class iDBN:
                 for li, rbm in enumerate(self.layers):
                     # update + forward of the same batch as one engine call; the top layer's forward (computed and
                     # dropped by the reference, idbn.py:203) has no side effect and is not run
-                    if li < last:
+                    if persistent and binary_input(v):
+                        loss = rbm.train_epoch_persistent(v, epoch, epochs, CD=self.cd_k, betas=pt_betas)
+                        if li < last:
+                            v = rbm.forward(v)
+                    elif li < last:
                         loss, v = rbm.train_epoch(v, epoch, epochs, CD=self.cd_k, next_data=nxt if li == 0 else None, return_forward=True)
                     else:
                         loss = rbm.train_epoch(v, epoch, epochs, CD=self.cd_k, next_data=nxt if li == 0 else None)

@@ -23,7 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from imdbn import engine as _E
-from imdbn.models.idbn import iDBN
+from imdbn.models.idbn import binary_input, iDBN
 from imdbn.models.rbm import RBM
 from imdbn.utils import batches, rows_on_device
 from imdbn.utils import cross_eval as _CE
@@ -249,13 +249,17 @@ class iMDBN(nn.Module):
         use_cd = int(cd_k) if cd_k is not None else int(self.image_idbn.cd_k)
         print(f"[finetune_image_last_layer] epochs={epochs}, lr={last.lr:.4g}, CD={use_cd}")
         self.finetune_losses = []
+        persistent = bool(self.params.get("PERSISTENT", False))      # extension, as iDBN.train reads it
         for ep in range(int(epochs)):
             losses = []
             for img, _ in batches(self.dataloader):
                 v = rows_on_device(img, self.device)
                 for rbm in self.image_idbn.layers[:-1]:
                     v = rbm.forward(v)
-                losses.append(last.train_epoch(v, ep, epochs, CD=use_cd))
+                if persistent and binary_input(v):      # (a one-layer stack: the last layer reads the images themselves)
+                    losses.append(last.train_epoch_persistent(v, ep, epochs, CD=use_cd, betas=self.params.get("PT_BETAS")))
+                else:
+                    losses.append(last.train_epoch(v, ep, epochs, CD=use_cd))
             if losses:
                 self.finetune_losses.append(torch.stack(losses).cpu())
         last.lr = old_lr

@@ -89,6 +89,8 @@ class RBM(nn.Module):
         the reference class -- or this one -- expects to unpickle."""
         state = self.__dict__.copy()
         state.pop("_imdbn_desc", None)                 # the engine's cached native descriptor (raw addresses): never part of the state
+        for k in ("_pcd", "_pcd_replicas", "_pt_try", "_pt_acc"):      # persistent chains and their swap counters: a loaded model restarts its chains
+            state.pop(k, None)
         params = state["_parameters"].copy()
         W = params.get("W")
         if W is not None and not W.is_contiguous():
@@ -260,6 +262,60 @@ class RBM(nn.Module):
             return loss, h
         loss = eng.cd_step(self, x, lr, mom, CD, rng, next_data=next_data, **kw)
         return (loss, self.forward(data)) if return_forward else loss
+
+    # ---- persistent chains: PCD-k and parallel tempering (extension) --------------------
+    @torch.no_grad()
+    def train_epoch_persistent(self, data: torch.Tensor, epoch: int, max_epochs: int, CD: int = 1, betas=None, monitor: bool = True):
+        """One persistent-CD update on one mini-batch (Tieleman 2008): ``train_epoch`` with the negative phase run on chains that
+        live across calls instead of restarting from the data.  Learning rate and momentum follow ``train_epoch``'s schedule.
+
+        The chains are ``self._pcd``, ``[R * B, V]`` 0/1 with replica r in the rows ``[r B, (r + 1) B)``: created on first use as
+        ``sample_visible(data)`` per replica (and again when a batch outgrows them or the number of replicas changes), never
+        pickled.  A batch shorter than the chains uses and advances the first rows of every replica only.
+
+        ``betas=None``: ``CD`` Gibbs steps on the chains, then the update (PCD-k).  ``betas`` (R >= 2 inverse temperatures,
+        ``0 < betas[0] < ... < betas[R - 1] = 1``): ``CD`` parallel-tempering sweeps over all replicas -- a Gibbs step each at its
+        temperature, then Metropolis exchanges between neighbours (Desjardins et al. 2010) -- and the update from the ``beta = 1``
+        replica as it stands.  ``pt_swap_rates()`` reports the exchanges.
+
+        Returns the 0-d mean-field reconstruction error ``mean((data - visible_probs(forward(data)))^2)`` (a persistent chain does
+        not reconstruct the batch), or None with ``monitor=False`` -- the reconstruction is then not computed.  No reference
+        counterpart; no data-parallel split."""
+        if _E.dp.active():
+            raise NotImplementedError("train_epoch_persistent has no data-parallel split")
+        lr, mom = self._lr_mom(epoch)
+        eng, x = self._eng(), self._in(data)
+        b, V = x.size(0), self.num_visible
+        bl = None if betas is None else [float(t) for t in (betas.tolist() if hasattr(betas, "tolist") else betas)]
+        if bl is not None and len(bl) < 2:
+            raise ValueError("train_epoch_persistent: betas needs at least two inverse temperatures (None: plain PCD)")
+        Rn = 1 if bl is None else len(bl)
+        chains = self.__dict__.get("_pcd")
+        if (chains is None or chains.device != x.device or chains.size(1) != V or chains.size(0) % Rn != 0
+                or chains.size(0) // Rn < b or getattr(self, "_pcd_replicas", Rn) != Rn):
+            chains = self._pcd = torch.cat([self.sample_visible(x) for _ in range(Rn)], 0).contiguous()
+            self._pcd_replicas = Rn
+            self._pt_try = self._pt_acc = None
+        Bc = chains.size(0) // Rn
+        kw = {"data_binary": eng.binary_hint(data)} if hasattr(eng, "binary_hint") else {}
+        if bl is None:
+            return eng.pcd_step(self, x, chains[:b], lr, mom, CD, self._rng(b), monitor=monitor, **kw)
+        # a short batch: the first b rows of every replica, as one [R b, V] tensor of their own for the sweep
+        short = b < Bc
+        state = chains.view(Rn, Bc, V)[:, :b].reshape(Rn * b, V) if short else chains
+        self._pt_try, self._pt_acc = eng.pt_sweep(self, state, bl, CD, self._rng(Rn * b), self._pt_try, self._pt_acc)
+        if short:
+            chains.view(Rn, Bc, V)[:, :b] = state.view(Rn, b, V)
+        return eng.pcd_step(self, x, chains[(Rn - 1) * Bc:(Rn - 1) * Bc + b], lr, mom, 0, self._rng(b), monitor=monitor, **kw)
+
+    def pt_swap_rates(self):
+        """Accepted / proposed exchanges per neighbouring pair of replicas since the chains were created: a float64 CPU tensor
+        ``[R - 1]`` (NaN for a pair never proposed; None before the first tempered update).  ONE host read, on request only."""
+        t, a = self.__dict__.get("_pt_try"), self.__dict__.get("_pt_acc")
+        if t is None or a is None:
+            return None
+        ta = torch.stack([t, a]).cpu().double()
+        return torch.where(ta[0] > 0, ta[1] / ta[0].clamp(min=1.0), torch.full_like(ta[0], float("nan")))
 
     # ---- supervised step on the labels (extension; DESIGN §22) ---------------------------------------
     @torch.no_grad()
