@@ -389,6 +389,39 @@ int imdbn_rbm_prefetch_ok(const imdbn_rbm_desc* d, int B);
 int imdbn_rbm_pcd_step(const imdbn_rbm_desc* d, const float* data, int64_t ldd, int B, float* particles, int64_t ldp,
                        const imdbn_cd_opts* o, imdbn_rng* rng, float* loss_out, void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- centered update: the centering trick / enhanced gradient (imdbn/models/rbm.py: train_epoch_centered; Montavon & Mueller 2012;
+ * Cho, Raiko & Ilin 2011; Melchior, Fischer & Wiskott 2016) -------------------------------------------------------
+ * A centered RBM with offsets mu (visible) and lam (hidden) is the normal RBM with the biases b - W lam and c - W^T mu: the NORMAL
+ * parameters stay stored and only the gradient changes.  mu [V], lam [H]: device fp32, READ AND OVERWRITTEN.
+ * Phases, unchanged: particles == NULL: those of imdbn_rbm_cd_step (cd_k >= 1; draws ("u", H), then cd_k times ("u", V), ("c", w_g)
+ * per group, ("u", H): draws_used = 1 + cd_k (2 + G)); loss = mean((data - v_prob)^2).  particles != NULL ([B][V], row stride
+ * ldp >= V, advanced IN PLACE): those of imdbn_rbm_pcd_step (cd_k >= 0, draws_used = cd_k (2 + G), rng may be NULL when cd_k = 0);
+ * loss = the mean-field reconstruction error, and with loss_out == NULL that propagation is not launched.  loss_out is nullable
+ * in both cases.  With n = B, the column sums sv+ / sv- / sh+ / sh- of the positive / negative visible and hidden operands
+ * (sh+ = sum P+), dW = V+^T H+ - V-^T H-, dv = (sv+ - sv-) / n, dh = (sh+ - sh-) / n:
+ *   1. mode 0 (data):  mv = sv+ / n, mh = sh+ / n;     mode 1 (enhanced):  mv = (sv+ + sv-) / (2 n), mh = (sh+ + sh-) / (2 n)
+ *   2. mu' = (1 - slide) mu + slide mv,   lam' = (1 - slide) lam + slide mh          (the model does not depend on the offsets:
+ *      moving them transforms no parameter)
+ *   3. gW = dW / n - mu' dh^T - dv lam'^T,   gb = dv - gW lam',   gc = dh - gW^T mu'
+ *   4. W_m = mom W_m + lr (gW - wd W), W += W_m;   hb_m = mom hb_m + lr gc [- lr (sh+ / n - target) when o->sparsity],
+ *      hid_bias += hb_m;   vb_m = mom vb_m + lr gb, vis_bias += vb_m
+ *   5. mu := mu', lam := lam'
+ * With mu = lam = 0 and slide = 0 this is the update of imdbn_rbm_cd_step / imdbn_rbm_pcd_step.
+ * Launches, plain, on `stream`, no host sync: the phases, the statistics pass of the update kernel into `scratch`, centered_apply,
+ * centered_finish.  No floating-point atomics; every sum has an order fixed by (V, H) and the grid, the grid depends on (V, H) and
+ * the device's CU count only: the same call on the same state gives the same bits.  The row padding of W / W_m is neither read
+ * nor written.  o->data_binary as in imdbn_rbm_cd_step; the prefetch fields and fwd_out must be zero.
+ * scratch: device, imdbn_centered_scratch_floats(V, H) floats (the V H statistics, then the column and row partials of the bias
+ * gradients), 16-byte aligned for the float4 kernels; contents unspecified on return.  Workspace: imdbn_ws_bytes(V, H, B).
+ * IMDBN_E_INVALID (naming the value) before the first launch, nothing touched: a null momentum buffer, null data / o / mu / lam /
+ * scratch, ldd < V, ldp < V with particles, B < 1, cd_k < 1 without particles or < 0 with them, a null rng where draws are needed,
+ * slide outside [0, 1] or NaN, mode outside {0, 1}, a non-zero prefetch field or fwd_out; IMDBN_E_RNG: a replay tape shorter than
+ * the draws. */
+size_t imdbn_centered_scratch_floats(int V, int H);
+int imdbn_rbm_centered_step(const imdbn_rbm_desc* d, const float* data, int64_t ldd, int B, float* particles, int64_t ldp,
+                            const imdbn_cd_opts* o, imdbn_rng* rng, float* mu, float* lam, float slide, int mode,
+                            float* loss_out, float* scratch, void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- parallel tempering over persistent chains (Desjardins et al. 2010; Cho, Raiko & Ilin 2010) -----------------
  * state [R M][V]: fp32, 0/1, one-hot inside softmax groups, row stride lds >= V, IN PLACE; replica r owns the rows [r M, (r + 1) M)
  * and samples p_beta(v) ~ exp(beta b.v + S(beta, v)), S(beta, v) = sum_j softplus(beta x_j(v)), x(v) = c + v W, at beta = betas[r].

@@ -35,6 +35,7 @@
 #include "kernels_labelgrad.hpp"
 #include "kernels_pll.hpp"
 #include "kernels_pt.hpp"
+#include "kernels_centered.hpp"
 
 using namespace imdbn;
 
@@ -1690,6 +1691,83 @@ int imdbn_rbm_pcd_step(const imdbn_rbm_desc* d, const float* data, int64_t ldd, 
     BiasArgs bias = make_bias(c, o, o->sparsity != 0, (float)B, loss_out);
     if (!loss_out) { bias.loss_part = nullptr; bias.n_loss = 0; }
     CHK(launch_assoc(c, 0, o, c.nw == 1 ? 1 : 0, c.L.flags, 1, (float)B, nullptr, &bias));
+    return 0;
+}
+
+// ---- centered update (imdbn/models/rbm.py: train_epoch_centered; kernels_centered.hpp) ---------------------------------
+// The grid of centered_apply: column tiles of `tw` columns (64 E per wave step, at most CTR_CS steps, the steps spread evenly over
+// the tiles) times row stripes of `rps` <= CTR_ROWS rows, about two blocks per CU.  A function of (V, H) and the CU count alone.
+struct CenteredPlan { int tw, ctiles, rps, nstripes; };
+static CenteredPlan centered_plan(int V, int H, bool vec4) {
+    const int unit = 64 * (vec4 ? 4 : 1), nunits = cdiv(H, unit);
+    CenteredPlan p;
+    p.tw = cdiv(nunits, cdiv(nunits, CTR_CS)) * unit;
+    p.ctiles = cdiv(H, p.tw);
+    const int want = std::max(cdiv(V, CTR_ROWS), std::min(V, cdiv(2 * std::max(cu_count(), 1), p.ctiles)));
+    p.rps = cdiv(V, want);
+    p.nstripes = cdiv(V, p.rps);
+    return p;
+}
+// scratch = [dW V H | pad to 4 | col_part nstripes H | row_part ctiles V]; sized for whichever of the two plans has more partials
+static size_t centered_dw_floats(int V, int H) { return ((size_t)V * H + 3) / 4 * 4; }
+size_t imdbn_centered_scratch_floats(int V, int H) {
+    if (V <= 0 || H <= 0) return 0;
+    size_t tail = 0;
+    for (int v4 = 0; v4 < 2; ++v4) {
+        const CenteredPlan p = centered_plan(V, H, v4 != 0);
+        tail = std::max(tail, (size_t)p.nstripes * H + (size_t)p.ctiles * V);
+    }
+    return centered_dw_floats(V, H) + (tail + 3) / 4 * 4;
+}
+
+int imdbn_rbm_centered_step(const imdbn_rbm_desc* d, const float* data, int64_t ldd, int B, float* particles, int64_t ldp,
+                            const imdbn_cd_opts* o, imdbn_rng* rng, float* mu, float* lam, float slide, int mode,
+                            float* loss_out, float* scratch, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(check_desc(d, true));
+    if (!data || !o || !mu || !lam || !scratch)
+        return fail(IMDBN_E_INVALID, "centered_step: null %s", !data ? "data" : (!o ? "opts" : (!mu ? "mu" : (!lam ? "lam" : "scratch"))));
+    if (ldd < d->V) return fail(IMDBN_E_INVALID, "centered_step: ldd %lld < V %d", (long long)ldd, d->V);
+    if (particles && ldp < d->V) return fail(IMDBN_E_INVALID, "centered_step: ldp %lld < V %d", (long long)ldp, d->V);
+    if (B < 1) return fail(IMDBN_E_INVALID, "centered_step: B = %d rows", B);
+    if (o->cd_k < (particles ? 0 : 1))
+        return fail(IMDBN_E_INVALID, "centered_step: cd_k = %d (%s)", o->cd_k, particles ? "particles need cd_k >= 0" : "CD from the data needs cd_k >= 1");
+    const bool draws = !particles || o->cd_k > 0;
+    if (draws && !rng) return fail(IMDBN_E_INVALID, "centered_step: null rng with cd_k = %d", o->cd_k);
+    if (!(slide >= 0.0f && slide <= 1.0f)) return fail(IMDBN_E_INVALID, "centered_step: slide = %g outside [0, 1]", (double)slide);
+    if (mode != 0 && mode != 1) return fail(IMDBN_E_INVALID, "centered_step: mode = %d outside {0, 1}", mode);
+    if (o->data_binary < 0 || o->data_binary > 2) return fail(IMDBN_E_INVALID, "centered_step: data_binary %d outside 0..2", o->data_binary);
+    if (o->next_data || o->next_slot || o->data_slot || o->next_binary || o->fwd_out)
+        return fail(IMDBN_E_INVALID, "centered_step: the prefetch fields and fwd_out must be zero (next_data %p, next_slot %d, data_slot %d, next_binary %d, fwd_out %p)",
+                    (const void*)o->next_data, o->next_slot, o->data_slot, o->next_binary, (const void*)o->fwd_out);
+    const int G = d->n_groups, V = d->V, H = d->H;
+    if (particles) CHK(tape_room("centered_step", rng, (int64_t)o->cd_k * B * ((int64_t)H + V), (int64_t)o->cd_k * G * B));
+    else CHK(tape_room("centered_step", rng, (int64_t)B * H + (int64_t)o->cd_k * B * ((int64_t)H + V), (int64_t)o->cd_k * G * B));
+    Ctx c(d, rng, S(stream));
+    CHK(setup(c, B, ws, ws_bytes));
+    if (particles) CHK(pcd_phases(c, data, ldd, particles, ldp, o, loss_out != nullptr));
+    else CHK(cd_phases(c, data, ldd, o));
+    CHK(c.rng.finish());
+    CHK(launch_assoc(c, 1, o, c.nw == 1 ? 1 : 0, c.L.flags, 1, 1.0f, scratch));
+    const Layout& L = c.L;
+    const bool vec4 = c.r.vec4 && (((uintptr_t)c.d->W_m | (uintptr_t)scratch) & 15) == 0;
+    const CenteredPlan p = centered_plan(V, H, vec4);
+    CenteredArgs a;
+    memset(&a, 0, sizeof(a));
+    a.W = d->W; a.Wm = d->W_m; a.ldw = d->ldw; a.V = V; a.H = H; a.dW = scratch;
+    a.hpos = L.cs_hpos; a.hneg = L.cs_hneg; a.vpos = L.cs_vpos; a.vneg = L.cs_vneg; a.P = L.P;
+    a.mu = mu; a.lam = lam;
+    a.lr = o->lr; a.mom = o->momentum; a.wd = o->weight_decay; a.n = (float)B; a.slide = slide; a.mode = mode;
+    a.rps = p.rps; a.tw = p.tw; a.nstripes = p.nstripes; a.ctiles = p.ctiles;
+    a.col_part = scratch + centered_dw_floats(V, H); a.row_part = a.col_part + (size_t)p.nstripes * H;
+    a.hid_bias = d->hid_bias; a.hb_m = d->hb_m; a.vis_bias = d->vis_bias; a.vb_m = d->vb_m;
+    a.sparsity = o->sparsity != 0; a.target = o->sparsity_target;
+    a.loss_part = L.loss_part; a.n_loss = n_loss_used(c); a.loss_den = (float)B * (float)V;
+    a.loss_out = loss_out;
+    if (vec4) hipLaunchKernelGGL(centered_apply<true>, dim3(p.ctiles, p.nstripes), dim3(256), 0, c.s, a);
+    else      hipLaunchKernelGGL(centered_apply<false>, dim3(p.ctiles, p.nstripes), dim3(256), 0, c.s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(centered_finish, dim3(cdiv(std::max(V, H), 256) + 1), dim3(256), 0, c.s, a);
+    HIPCHK(hipGetLastError());
     return 0;
 }
 

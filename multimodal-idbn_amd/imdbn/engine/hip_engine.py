@@ -568,12 +568,14 @@ class HipEngine:
             o.next_binary = self.binary_hint(next_data)
         return key, nxt
 
-    def _cd(self, name: str, rbm, d, data, o, rng, data_binary, *outs, next_data=None, prefetch: bool = True, particles=None):
-        """The CD pass behind cd_step / cd_stats / cd_factors / cd_factors_wire / pcd_step: entry `name`(desc, batch, ld, B,
-        [particles, ld,] opts, rng, *outs, workspace tail).  `d` is the caller's descriptor (each method asks for its own
-        ``need_momentum``), `o` its options.  With `prefetch` (cd_factors and pcd_step have none) this is the one place that consumes
-        and records the next-batch state: the record of this shape is popped before the call, the new one stored only after the
-        call and its draw count came out right.  `particles`: the persistent chains of pcd_step, whose draws are theirs alone."""
+    def _cd(self, name: str, rbm, d, data, o, rng, data_binary, *outs, next_data=None, prefetch: bool = True, particles=None,
+            nullable_chains: bool = False):
+        """The CD pass behind cd_step / cd_stats / cd_factors / cd_factors_wire / pcd_step / centered_step: entry `name`(desc,
+        batch, ld, B, [particles, ld,] opts, rng, *outs, workspace tail).  `d` is the caller's descriptor (each method asks for its
+        own ``need_momentum``), `o` its options.  With `prefetch` (cd_factors, pcd_step and centered_step have none) this is the one
+        place that consumes and records the next-batch state: the record of this shape is popped before the call, the new one
+        stored only after the call and its draw count came out right.  `particles`: the persistent chains of pcd_step /
+        centered_step, whose draws are theirs alone; `nullable_chains`: the entry takes the pair also when there are none (NULL, 0)."""
         x = _f32c(data)
         B, dev = x.size(0), x.device
         o.data_binary = self._hint(data, data_binary)       # the caller's tensor: a fp32 copy `x` has lost the tag
@@ -582,7 +584,7 @@ class HipEngine:
         r, keep = self._rng(rng, sched, B, dev)
         tail = self._ws_tail(dev, d.V, d.H, B)
         key, nxt = self._prefetch_opts(o, d, x, next_data) if prefetch else (None, None)
-        chains = () if particles is None else (_ptr(particles), particles.stride(0))
+        chains = ((None, 0) if nullable_chains else ()) if particles is None else (_ptr(particles), particles.stride(0))
         self._call(name, C.byref(d), _ptr(x), x.stride(0), B, *chains, C.byref(o), C.byref(r), *outs, *tail)
         self._done(rng, r, sched)
         if nxt is not None:                      # the strong reference keeps the address from being recycled
@@ -626,6 +628,37 @@ class HipEngine:
         o = self._opts(rbm, lr, mom, cd_k, sparsity=getattr(rbm, "sparsity", False))
         loss = torch.empty(1, device=data.device) if monitor else None
         self._cd("imdbn_rbm_pcd_step", rbm, d, data, o, rng, data_binary, _ptr(loss), prefetch=False, particles=p)
+        return loss.reshape(()) if monitor else None
+
+    @staticmethod
+    def _offsets(who: str, t: torch.Tensor, n: int, dev) -> torch.Tensor:
+        """Centering offsets are updated IN PLACE, as the chains are."""
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32 and t.dim() == 1 and t.numel() == n
+                and t.is_contiguous()):
+            raise N.EngineError(f"{who} must be a contiguous fp32 [{n}] tensor on {dev} (updated in place)")
+        return t
+
+    def centered_step(self, rbm, data, particles, lr, mom, cd_k, rng, mu, lam, slide, mode, data_binary=None, monitor: bool = True):
+        """One centered update (imdbn_rbm_centered_step): the phases of ``cd_step`` (``particles=None``, CD-``cd_k``
+        from the data) or of ``pcd_step`` (``particles`` ``[B, V]``, advanced in place by ``cd_k`` >= 0 Gibbs steps), then the
+        update with the centered gradient around the offsets ``mu`` ``[V]`` / ``lam`` ``[H]`` (fp32, updated in place: they first
+        slide by ``slide`` in [0, 1] towards the batch means -- ``mode`` 0: of the data, 1: of data and model).  Returns the loss
+        of the phases' call as a 0-d device tensor, or None with ``monitor=False``.  No host sync."""
+        d = self._desc(rbm, True)
+        dev = data.device
+        p = None
+        if particles is not None:
+            p = self._chains("centered_step", particles, d.V)
+            if p.size(0) != data.size(0) or p.device != dev:
+                raise N.EngineError(f"centered_step: {p.size(0)} chains on {p.device} for a batch of {data.size(0)} rows on {dev}")
+        mu, lam = self._offsets("centered_step: mu", mu, d.V, dev), self._offsets("centered_step: lam", lam, d.H, dev)
+        o = self._opts(rbm, lr, mom, cd_k, sparsity=getattr(rbm, "sparsity", False))
+        loss = torch.empty(1, device=dev) if monitor else None
+        need = int(self._lib.imdbn_centered_scratch_floats(d.V, d.H))
+        scratch = self._buffer(("centered", dev, d.V, d.H, torch.cuda.current_stream(dev).cuda_stream),
+                               lambda: torch.empty(need, dtype=torch.float32, device=dev), need)
+        self._cd("imdbn_rbm_centered_step", rbm, d, data, o, rng, data_binary, _ptr(mu), _ptr(lam), float(slide), int(mode), _ptr(loss),
+                 _ptr(scratch), prefetch=False, particles=p, nullable_chains=True)
         return loss.reshape(()) if monitor else None
 
     def pt_sweep(self, rbm, state, betas, n_sweeps: int, rng, swap_try: Optional[torch.Tensor] = None,

@@ -111,6 +111,12 @@ class iDBN:
         # loader, never another layer's probabilities -- with persistent chains (RBM.train_epoch_persistent: PCD-k, or parallel
         # tempering over params["PT_BETAS"]); every other layer keeps CD-k
         persistent, pt_betas = bool(self.params.get("PERSISTENT", False)), self.params.get("PT_BETAS")
+        # extension, off by default: params["CENTERED"] (True: slide 0.01; a float: the slide) routes every layer's
+        # update through RBM.train_epoch_centered with the offsets of params["CENTERED_OFFSETS"] ("data" / "enhanced"); persistent
+        # chains keep the gate above
+        centered = self.params.get("CENTERED", False)
+        centered = None if centered is None or centered is False else (0.01 if centered is True else float(centered))
+        ctr_offsets = self.params.get("CENTERED_OFFSETS", "data")
         for epoch in range(int(epochs)):
             losses = []
             # one batch of lookahead: the first layer prepares the operand forms of the following batch during its
@@ -125,7 +131,13 @@ class iDBN:
                 for li, rbm in enumerate(self.layers):
                     # update + forward of the same batch as one engine call; the top layer's forward (computed and
                     # dropped by the reference, idbn.py:203) has no side effect and is not run
-                    if persistent and binary_input(v):
+                    if centered is not None:
+                        chains = persistent and binary_input(v)
+                        loss = rbm.train_epoch_centered(v, epoch, epochs, CD=self.cd_k, persistent=chains, betas=pt_betas if chains else None,
+                                                        slide=centered, offsets=ctr_offsets)
+                        if li < last:
+                            v = rbm.forward(v)
+                    elif persistent and binary_input(v):
                         loss = rbm.train_epoch_persistent(v, epoch, epochs, CD=self.cd_k, betas=pt_betas)
                         if li < last:
                             v = rbm.forward(v)

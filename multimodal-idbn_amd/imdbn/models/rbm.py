@@ -89,7 +89,8 @@ class RBM(nn.Module):
         the reference class -- or this one -- expects to unpickle."""
         state = self.__dict__.copy()
         state.pop("_imdbn_desc", None)                 # the engine's cached native descriptor (raw addresses): never part of the state
-        for k in ("_pcd", "_pcd_replicas", "_pt_try", "_pt_acc"):      # persistent chains and their swap counters: a loaded model restarts its chains
+        # persistent chains, their swap counters and the centering offsets: a loaded model restarts its chains and re-initialises its offsets
+        for k in ("_pcd", "_pcd_replicas", "_pt_try", "_pt_acc", "_ctr_mu", "_ctr_lam"):
             state.pop(k, None)
         params = state["_parameters"].copy()
         W = params.get("W")
@@ -285,10 +286,19 @@ class RBM(nn.Module):
             raise NotImplementedError("train_epoch_persistent has no data-parallel split")
         lr, mom = self._lr_mom(epoch)
         eng, x = self._eng(), self._in(data)
+        particles, k = self._negative_chains(eng, x, betas, CD, "train_epoch_persistent")
+        kw = {"data_binary": eng.binary_hint(data)} if hasattr(eng, "binary_hint") else {}
+        return eng.pcd_step(self, x, particles, lr, mom, k, self._rng(x.size(0)), monitor=monitor, **kw)
+
+    def _negative_chains(self, eng, x: torch.Tensor, betas, CD: int, who: str):
+        """The persistent chains behind one update on the batch ``x`` (train_epoch_persistent, train_epoch_centered): creates
+        ``self._pcd`` where needed and returns ``(particles, k)``, the ``[b, V]`` view of the chains the update's negative phase
+        runs on and the Gibbs steps it still has to make on them -- ``CD`` without ``betas``; with them the ``CD`` tempering
+        sweeps run here and the ``beta = 1`` replica is used as it stands (``k = 0``)."""
         b, V = x.size(0), self.num_visible
         bl = None if betas is None else [float(t) for t in (betas.tolist() if hasattr(betas, "tolist") else betas)]
         if bl is not None and len(bl) < 2:
-            raise ValueError("train_epoch_persistent: betas needs at least two inverse temperatures (None: plain PCD)")
+            raise ValueError(f"{who}: betas needs at least two inverse temperatures (None: plain PCD)")
         Rn = 1 if bl is None else len(bl)
         chains = self.__dict__.get("_pcd")
         if (chains is None or chains.device != x.device or chains.size(1) != V or chains.size(0) % Rn != 0
@@ -297,16 +307,15 @@ class RBM(nn.Module):
             self._pcd_replicas = Rn
             self._pt_try = self._pt_acc = None
         Bc = chains.size(0) // Rn
-        kw = {"data_binary": eng.binary_hint(data)} if hasattr(eng, "binary_hint") else {}
         if bl is None:
-            return eng.pcd_step(self, x, chains[:b], lr, mom, CD, self._rng(b), monitor=monitor, **kw)
+            return chains[:b], CD
         # a short batch: the first b rows of every replica, as one [R b, V] tensor of their own for the sweep
         short = b < Bc
         state = chains.view(Rn, Bc, V)[:, :b].reshape(Rn * b, V) if short else chains
         self._pt_try, self._pt_acc = eng.pt_sweep(self, state, bl, CD, self._rng(Rn * b), self._pt_try, self._pt_acc)
         if short:
             chains.view(Rn, Bc, V)[:, :b] = state.view(Rn, b, V)
-        return eng.pcd_step(self, x, chains[(Rn - 1) * Bc:(Rn - 1) * Bc + b], lr, mom, 0, self._rng(b), monitor=monitor, **kw)
+        return chains[(Rn - 1) * Bc:(Rn - 1) * Bc + b], 0
 
     def pt_swap_rates(self):
         """Accepted / proposed exchanges per neighbouring pair of replicas since the chains were created: a float64 CPU tensor
@@ -316,6 +325,47 @@ class RBM(nn.Module):
             return None
         ta = torch.stack([t, a]).cpu().double()
         return torch.where(ta[0] > 0, ta[1] / ta[0].clamp(min=1.0), torch.full_like(ta[0], float("nan")))
+
+    # ---- centered update: the centering trick / enhanced gradient (extension) -------------
+    @torch.no_grad()
+    def train_epoch_centered(self, data: torch.Tensor, epoch: int, max_epochs: int, CD: int = 1, persistent: bool = False, betas=None,
+                             slide: float = 0.01, offsets: str = "data", monitor: bool = True):
+        """One update on one mini-batch with the centered gradient (Montavon & Mueller 2012; Cho, Raiko & Ilin 2011; Melchior,
+        Fischer & Wiskott 2016): the RBM is centered around the offsets ``mu`` (visible) and ``lam`` (hidden), which follow the
+        batch means by ``slide`` in [0, 1] per call -- ``offsets="data"``: the means of the data and of p(h | data); ``"enhanced"``:
+        the average of those and the model's.  The stored parameters stay the normal ones (a centered RBM is the normal RBM with
+        the biases ``b - W lam`` and ``c - W^T mu``), so every other method and the pickle are unaffected.  Learning rate and
+        momentum follow ``train_epoch``'s schedule.
+
+        The phases are ``train_epoch``'s (CD-``CD`` from the data) or, with ``persistent=True`` or ``betas``, those of
+        ``train_epoch_persistent`` on the same chains ``self._pcd`` (``betas``: ``CD`` tempering sweeps, then the update from the
+        ``beta = 1`` replica).  The offsets live in ``self._ctr_mu`` / ``self._ctr_lam`` (``centering_offsets()``): created on first
+        use, or after a device change, by running that call with ``slide = 1`` from zeros -- the first batch's means --, never
+        pickled.
+
+        Returns the 0-d loss of the phases' method, or None with ``monitor=False``.  No reference counterpart; no data-parallel
+        split."""
+        if _E.dp.active():
+            raise NotImplementedError("train_epoch_centered has no data-parallel split")
+        if offsets not in ("data", "enhanced"):
+            raise ValueError(f"train_epoch_centered: offsets = {offsets!r}, must be 'data' or 'enhanced'")
+        lr, mom = self._lr_mom(epoch)
+        eng, x = self._eng(), self._in(data)
+        particles, k = (self._negative_chains(eng, x, betas, CD, "train_epoch_centered") if (persistent or betas is not None)
+                        else (None, CD))
+        mu, lam = self.__dict__.get("_ctr_mu"), self.__dict__.get("_ctr_lam")
+        if mu is None or lam is None or mu.device != x.device or lam.device != x.device:
+            mu = self._ctr_mu = torch.zeros(self.num_visible, dtype=torch.float32, device=x.device)
+            lam = self._ctr_lam = torch.zeros(self.num_hidden, dtype=torch.float32, device=x.device)
+            slide = 1.0
+        kw = {"data_binary": eng.binary_hint(data)} if hasattr(eng, "binary_hint") else {}
+        return eng.centered_step(self, x, particles, lr, mom, k, self._rng(x.size(0)), mu, lam, float(slide),
+                                 1 if offsets == "enhanced" else 0, monitor=monitor, **kw)
+
+    def centering_offsets(self):
+        """``(mu [V], lam [H])``, the offsets of train_epoch_centered as they stand (the live tensors), or None before its first call."""
+        mu, lam = self.__dict__.get("_ctr_mu"), self.__dict__.get("_ctr_lam")
+        return None if mu is None or lam is None else (mu, lam)
 
     # ---- supervised step on the labels (extension; DESIGN §22) ---------------------------------------
     @torch.no_grad()
