@@ -422,6 +422,39 @@ int imdbn_rbm_centered_step(const imdbn_rbm_desc* d, const float* data, int64_t 
                             const imdbn_cd_opts* o, imdbn_rng* rng, float* mu, float* lam, float slide, int mode,
                             float* loss_out, float* scratch, void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- one delta-rule step of a directed layer (imdbn/models/idbn.py: updown_step; the up-down / contrastive wake-sleep algorithm of
+ * Hinton, Osindero & Teh 2006) -------------------------------------------------------------------------------------
+ * A directed sigmoid layer predicts `target` from `in` through the descriptor's weights: N_in = V, N_out = H for IMDBN_DELTA_UP
+ * (recognition), N_in = H, N_out = V for IMDBN_DELTA_DOWN (generative).  in [B][N_in], target [B][N_out]: fp32, 0/1 or real in [0, 1],
+ * row strides ldi >= N_in, ldt >= N_out.
+ *   a = hid_bias + in W (UP) | vis_bias + in W^T (DOWN)       the logits of imdbn_rbm_prop_up / imdbn_rbm_prop_down at T = 1 with
+ *                                                             logits_only, bit for bit
+ *   p = sigmoid(a) (fp32),  r = target - p
+ *   out_rowlp[b] = sum_j (target_j a_j - softplus(a_j))       double [B], nullable: log p(target | in) of the factorial Bernoulli layer
+ *                                                             (a real target: minus the cross-entropy; target = p: minus the entropy)
+ * With o != NULL the update, g in the [V][H] layout of W:  UP g = in^T r / B,  DOWN g = r^T in / B;
+ *   W_m = momentum W_m + lr (g - weight_decay W), W += W_m;   m = momentum m + lr colsum(r) / B, bias += m
+ * for the PREDICTING bias and its momentum only (hid_bias / hb_m for UP, vis_bias / vb_m for DOWN); the other bias and its momentum
+ * buffer are not touched.  Of o only lr, momentum and weight_decay are read; cd_k, sparsity, the prefetch fields and fwd_out must be
+ * zero.  out_rowlp is evaluated on the parameters on entry; o == NULL evaluates only and writes no parameter.
+ * Launches, plain, on `stream`, no host sync: the operand preparation of `in`, the logits propagation, delta_rows (one pass over the
+ * logits: the planes of target and of -p the weight pass reads, the column partials of r, the row partials of out_rowlp),
+ * delta_finish (bias, out_rowlp), the update kernel of imdbn_rbm_cd_step with the pairs (in, target) and (in, p).
+ * Sums: softplus and the row sum in double -- per 64-column tile lane l takes column l, the 64 lanes meet in a fixed butterfly, the
+ * tiles are added in ascending order: fixed by N_out, a row gives the same bits alone and inside any batch.  colsum(r): fp32, 8 rows
+ * per partial in row order, the partials in index order.  g: the update kernel's exact products, in^T target - in^T p in one fp32
+ * accumulator (r itself is never rounded into an operand).  No draws, no floating-point atomics; the same call on the same state
+ * gives the same bits.  The row padding of W / W_m is neither read nor written.
+ * IMDBN_E_INVALID (naming the value) before the first launch, nothing touched: null d / in / target, dir outside {0, 1}, ldi < N_in,
+ * ldt < N_out, B < 1, o == NULL together with out_rowlp == NULL (nothing to do), with o: a null momentum buffer, a non-zero cd_k /
+ * sparsity / prefetch field / fwd_out.  IMDBN_E_UNSUPPORTED: DOWN on a descriptor with softmax groups.
+ * Workspace: imdbn_ws_bytes(V, H, B). */
+#define IMDBN_DELTA_UP   0   /* recognition: in [B][V] predicts target [B][H] through W and hid_bias   */
+#define IMDBN_DELTA_DOWN 1   /* generative:  in [B][H] predicts target [B][V] through W^T and vis_bias */
+int imdbn_rbm_delta_step(const imdbn_rbm_desc* d, int dir, const float* in, int64_t ldi, const float* target, int64_t ldt, int B,
+                         const imdbn_cd_opts* o /* NULL: evaluate only */, double* out_rowlp /* [B], nullable */,
+                         void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- parallel tempering over persistent chains (Desjardins et al. 2010; Cho, Raiko & Ilin 2010) -----------------
  * state [R M][V]: fp32, 0/1, one-hot inside softmax groups, row stride lds >= V, IN PLACE; replica r owns the rows [r M, (r + 1) M)
  * and samples p_beta(v) ~ exp(beta b.v + S(beta, v)), S(beta, v) = sum_j softplus(beta x_j(v)), x(v) = c + v W, at beta = betas[r].

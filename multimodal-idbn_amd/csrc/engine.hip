@@ -4,8 +4,9 @@
 // the reference's draw order, and enqueue kernels on the caller's stream.
 // No host synchronisation, no allocation, no global state besides tuning knobs, the thread-local
 // error string, what is known per device ordinal and the optional profiling events.
-// The host code is one translation unit in four files: this one (context, CD / chain / factor orchestration, the C entries),
-// host_layout.hpp (knobs, workspace layout, Route), host_prop.hpp (propagation launchers), host_update.hpp (update launchers).
+// The host code is one translation unit in five files: this one (context, CD / chain / factor orchestration, the C entries),
+// host_layout.hpp (knobs, workspace layout, Route), host_prop.hpp (propagation launchers), host_update.hpp (update launchers),
+// host_delta.hpp (the delta-rule step of a directed layer).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,6 +37,7 @@
 #include "kernels_pll.hpp"
 #include "kernels_pt.hpp"
 #include "kernels_centered.hpp"
+#include "kernels_delta.hpp"
 
 using namespace imdbn;
 
@@ -170,6 +172,7 @@ int setup(Ctx& c, int B, void* ws, size_t ws_bytes) {
 
 #include "host_prop.hpp"
 #include "host_update.hpp"
+#include "host_delta.hpp"
 
 // The caller's fp32 rows x (visible rows when `up`, hidden rows otherwise) into the row-major operand form of their side, then the
 // propagation from it with `f`.
@@ -1769,6 +1772,12 @@ int imdbn_rbm_centered_step(const imdbn_rbm_desc* d, const float* data, int64_t 
     hipLaunchKernelGGL(centered_finish, dim3(cdiv(std::max(V, H), 256) + 1), dim3(256), 0, c.s, a);
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+// ---- one delta-rule step of a directed layer (host_delta.hpp; kernels_delta.hpp) ------------------------------------------
+int imdbn_rbm_delta_step(const imdbn_rbm_desc* d, int dir, const float* in, int64_t ldi, const float* target, int64_t ldt, int B,
+                         const imdbn_cd_opts* o, double* out_rowlp, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    return delta_step(d, dir, in, ldi, target, ldt, B, o, out_rowlp, ws, ws_bytes, S(stream));
 }
 
 // rows [row, row + ...) of a draw tensor that spans more rows than the launch it feeds

@@ -703,6 +703,70 @@ class HipEngine:
         self._call("imdbn_rbm_assoc_update", C.byref(d), _ptr(ts[0]), ts[0].stride(0), _ptr(ts[1]), ts[1].stride(0), _ptr(ts[2]),
                    ts[2].stride(0), _ptr(ts[3]), ts[3].stride(0), B, C.byref(o), *self._ws_tail(dev, d.V, d.H, B))
 
+    # ---- up-down fine-tuning of a stack ----------------------------------------------------------------
+    def delta_step(self, rbm, direction, x, target, lr=0.0, mom=0.0, apply=True, rowlp=True):
+        """One delta-rule step of the directed layer ``rbm`` (imdbn_rbm_delta_step): ``direction`` ``"up"`` (``x`` ``[B, V]``
+        predicts ``target`` ``[B, H]`` through ``W`` and ``hid_bias``) or ``"down"`` (``x`` ``[B, H]`` predicts ``target`` ``[B, V]``
+        through ``W^T`` and ``vis_bias``).  With ``apply`` the weights and the predicting bias move by ``lr``, ``mom`` and the RBM's
+        weight decay (the other bias and its momentum are untouched); with ``rowlp`` the call returns ``log p(target | x)`` per row
+        under the parameters on entry, a float64 device tensor ``[B]``, else None.  No draws, no host sync."""
+        if direction not in ("up", "down"):
+            raise N.EngineError(f"delta_step: direction must be 'up' or 'down', got {direction!r}")
+        if not apply and not rowlp:
+            raise N.EngineError("delta_step: apply=False and rowlp=False leave nothing to do")
+        d = self._desc(rbm, bool(apply))
+        up = direction == "up"
+        n_in, n_out = (d.V, d.H) if up else (d.H, d.V)
+        x, t = _f32c(x), _f32c(target)
+        if x.dim() != 2 or t.dim() != 2 or x.size(1) != n_in or t.size(1) != n_out or x.size(0) != t.size(0) or x.device != t.device:
+            raise N.EngineError(f"delta_step({direction}): needs x [B, {n_in}] and target [B, {n_out}] on one device")
+        B, dev = x.size(0), x.device
+        o = self._opts(rbm, lr, mom, 0) if apply else None
+        lp = torch.empty(max(B, 1), dtype=torch.float64, device=dev) if rowlp else None
+        self._call("imdbn_rbm_delta_step", C.byref(d), N.DELTA_UP if up else N.DELTA_DOWN, _ptr(x), x.stride(0), _ptr(t), t.stride(0), B,
+                   _ref(o), _ptr(lp), *self._ws_tail(dev, d.V, d.H, max(B, 1)))
+        return lp
+
+    def updown_step(self, rec_layers, gen_layers, data, epoch_scalars, CD, particles, rng, monitor: bool = True):
+        """One up-down (contrastive wake-sleep) step of a stack (Hinton, Osindero & Teh 2006): ``rec_layers`` the L RBMs bottom
+        first (recognition weights of the directed layers, and the undirected top RBM), ``gen_layers`` the L - 1 generative twins.
+        On one stream, no host sync: the wake pass up the recognition weights (``("u", H_l)`` per layer), ``pcd_step`` of the top
+        RBM on the top wake state, the sleep pass down the generative weights from the particles after that call (``("u", V_l)``
+        per layer, every sample drawn before any update), then the generative delta steps on the wake states and the recognition
+        delta steps on the sleep states.  ``epoch_scalars``: ``(lr, mom)`` per layer; twin l uses entry l.  ``particles``: None (a
+        fresh copy of the top wake state: CD-``CD`` from it), ``"persistent"`` (the top RBM's own chains, ``RBM._negative_chains``)
+        or a ``[B, V_top]`` tensor advanced in place.  Returns ``{"wake": [s_1 ..], "sleep": [s'_0 ..], "particles", "wake_nll",
+        "sleep_nll", "top_loss"}``; the three monitors are 0-d device scalars, None with ``monitor=False``."""
+        from . import dp
+        if dp.active():
+            raise NotImplementedError("updown_step has no data-parallel split")
+        L = len(rec_layers)
+        if L < 1 or len(gen_layers) != L - 1 or len(epoch_scalars) != L:
+            raise N.EngineError(f"updown_step: {L} layers need {max(L - 1, 0)} generative twins and {L} (lr, mom) pairs")
+        top = rec_layers[-1]
+        wake = [_f32c(data)]
+        for rbm in rec_layers[:-1]:
+            wake.append(self.prop_up(rbm, wake[-1], sample=True, rng=rng)[1])
+        s_top = wake[-1]
+        k = int(CD)
+        if particles is None:
+            particles = s_top.clone()
+        elif isinstance(particles, str):
+            particles, k = top._negative_chains(self, s_top, None, k, "updown_step")
+        lr, mom = epoch_scalars[-1]
+        top_loss = self.pcd_step(top, s_top, particles, lr, mom, k, rng, monitor=monitor)
+        sleep = [particles]
+        for g in reversed(gen_layers):
+            sleep.insert(0, self.sample_visible(g, self.prop_down(g, sleep[0]), rng))
+        lp_w = [self.delta_step(g, "down", wake[l + 1], wake[l], *epoch_scalars[l], rowlp=monitor) for l, g in enumerate(gen_layers)]
+        lp_s = [self.delta_step(r, "up", sleep[l], sleep[l + 1], *epoch_scalars[l], rowlp=monitor) for l, r in enumerate(rec_layers[:-1])]
+        out = {"wake": wake[1:], "sleep": sleep[:-1], "particles": particles, "wake_nll": None, "sleep_nll": None, "top_loss": top_loss}
+        if monitor:
+            zero = torch.zeros((), dtype=torch.float64, device=s_top.device)
+            out["wake_nll"] = -torch.stack(lp_w).sum(0).mean() if lp_w else zero
+            out["sleep_nll"] = -torch.stack(lp_s).sum(0).mean() if lp_s else zero
+        return out
+
     # ---- RCCL through the C ABI (a binder without torch.distributed; the classes use torch.distributed) ---------------
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(128)

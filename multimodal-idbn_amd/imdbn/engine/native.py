@@ -14,6 +14,7 @@ ABI_VERSION = 4
 PARITY_F32, FAST_BF16 = 0, 1
 RNG_PHILOX, RNG_REPLAY = 0, 1
 BOUND_ENTROPY, BOUND_LOGQ = 0, 1                      # imdbn_rbm_bound_step mode (IMDBN_BOUND_*)
+DELTA_UP, DELTA_DOWN = 0, 1                           # imdbn_rbm_delta_step dir (IMDBN_DELTA_*)
 DATA_UNKNOWN, DATA_BINARY, DATA_REAL = 0, 1, 2      # imdbn_cd_opts.data_binary / next_binary (IMDBN_DATA_*)
 ROUTE_UP = ("fused", "stream_bits", "stream_real", "partial4", "partial")                    # imdbn_debug_last_route (IMDBN_ROUTE_UP_*)
 ROUTE_DOWN = ("k2_stream", "down_fused", "down_chunks2", "down_chunks4", "down_tiled")        # ... (IMDBN_ROUTE_DOWN_*)
@@ -121,6 +122,7 @@ SIGNATURES = {
     "imdbn_centered_scratch_floats": (_SZ, [_INT, _INT]),
     "imdbn_rbm_centered_step": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _P, _I64, C.POINTER(CdOpts), C.POINTER(Rng), _P, _P, C.c_float, _INT,
                                        _P, _P, _P, _SZ, _P]),
+    "imdbn_rbm_delta_step": (_INT, [C.POINTER(RbmDesc), _INT, _P, _I64, _P, _I64, _INT, C.POINTER(CdOpts), _P, _P, _SZ, _P]),
     "imdbn_rbm_pt_sweep": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _INT, C.POINTER(_F), _INT, C.POINTER(Rng), _P, _P, _P, _SZ, _P]),
     "imdbn_packed_delta_floats": (_SZ, [_INT, _INT]),
     "imdbn_rbm_prefetch_ok": (_INT, [C.POINTER(RbmDesc), _INT]),

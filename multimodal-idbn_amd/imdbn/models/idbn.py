@@ -168,7 +168,7 @@ class iDBN:
         cur = rows_on_device(x, self.device)
         for rbm in self.layers:
             cur = rbm.forward(cur)
-        for rbm in reversed(self.layers):
+        for rbm in reversed(self._down_layers()):
             cur = rbm.backward(cur)
         return cur
 
@@ -176,9 +176,90 @@ class iDBN:
     def decode(self, top: torch.Tensor) -> torch.Tensor:
         """idbn.py:356-359."""
         cur = top.to(self.device)
-        for rbm in reversed(self.layers):
+        for rbm in reversed(self._down_layers()):
             cur = rbm.backward(cur)
         return cur
+
+    # ---- up-down fine-tuning of the whole stack (extension; Hinton, Osindero & Teh 2006; DESIGN §25) ----------------
+    def is_untied(self) -> bool:
+        return self.__dict__.get("gen_layers") is not None
+
+    def _down_layers(self) -> List[RBM]:
+        """The RBMs a top-down pass goes through, bottom first: the generative twins of an untied model under its top RBM, else
+        ``layers``."""
+        gen = self.__dict__.get("gen_layers")
+        return self.layers if gen is None else list(gen) + [self.layers[-1]]
+
+    @torch.no_grad()
+    def untie(self) -> List[RBM]:
+        """Give every directed layer (all but the top RBM) generative weights of its own: ``self.gen_layers[l]`` is an ``RBM`` of
+        the shape, row pitch, device and hyper-parameters of ``layers[l]`` holding copies of its ``W`` and ``vis_bias`` (the two
+        parameters a top-down pass reads) and zero momenta; ``layers`` stay the recognition weights.  Idempotent.  ``__init__`` does
+        not create the attribute: a model that is never untied keeps its attribute set and its pickle."""
+        gen = self.__dict__.get("gen_layers")
+        if gen is not None:
+            return gen
+        gen = []
+        for r in self.layers[:-1]:
+            g = RBM.__new__(RBM)                      # not the constructor: it would draw an initial W from torch's generator
+            torch.nn.Module.__init__(g)
+            for k in ("num_visible", "num_hidden", "lr", "weight_decay", "momentum", "dynamic_lr", "final_momentum", "sparsity_factor"):
+                setattr(g, k, getattr(r, k))
+            g.sparsity, g.softmax_groups = False, []
+            dev = r.W.device
+            W = torch.empty_strided(tuple(r.W.shape), tuple(r.W.stride()), dtype=torch.float32, device=dev)
+            W.copy_(r.W.data)
+            g.W = torch.nn.Parameter(W, requires_grad=False)
+            g.hid_bias = torch.nn.Parameter(r.hid_bias.data.clone(), requires_grad=False)
+            g.vis_bias = torch.nn.Parameter(r.vis_bias.data.clone(), requires_grad=False)
+            g.W_m = torch.empty_strided(tuple(W.shape), tuple(W.stride()), dtype=torch.float32, device=dev).zero_()
+            g.hb_m, g.vb_m = torch.zeros_like(g.hid_bias.data), torch.zeros_like(g.vis_bias.data)
+            gen.append(g)
+        self.gen_layers = gen
+        return gen
+
+    @torch.no_grad()
+    def updown_step(self, data: torch.Tensor, epoch: int, max_epochs: int, CD: int = 1, persistent: bool = False, lr_scale: float = 1.0,
+                    monitor: bool = True):
+        """One up-down step on one mini-batch (unties the model on first use): the engine's ``updown_step`` -- wake pass, CD-``CD``
+        on the top RBM from the top wake state (``persistent``: PCD on the top RBM's own chains), sleep pass, the generative delta
+        rule on the wake states and the recognition delta rule on the sleep states.  Every layer uses its own RBM's learning-rate
+        and momentum schedule (``lr`` times ``lr_scale``) and weight decay.  Returns ``{"wake_nll", "sleep_nll", "top_loss"}`` as
+        0-d device scalars -- minus the mean over the batch of the summed log-probabilities of the generative / recognition
+        predictions before this call's update, and the top RBM's mean-field reconstruction error -- or None with
+        ``monitor=False`` (nothing is then evaluated for them).  No host sync; no data-parallel split."""
+        from imdbn import engine as _E
+        if _E.dp.active():
+            raise NotImplementedError("updown_step has no data-parallel split")
+        gen = self.untie()
+        x = rows_on_device(data, self.device)
+        scalars = []
+        for r in self.layers:
+            lr, mom = r._lr_mom(epoch)
+            scalars.append((lr * float(lr_scale), mom))
+        out = self.layers[-1]._eng().updown_step(self.layers, gen, x, scalars, int(CD), "persistent" if persistent else None,
+                                                 self.layers[-1]._rng(x.size(0)), monitor=monitor)
+        return {k: out[k] for k in ("wake_nll", "sleep_nll", "top_loss")} if monitor else None
+
+    def finetune_updown(self, epochs: int, CD: int = 1, persistent: bool = False, lr_scale: float = 0.1, log_every: int = 0):
+        """``epochs`` passes of ``updown_step`` over ``self.dataloader`` (explicit only: ``train`` never calls it and no
+        ``params`` key turns it on).  ``log_every`` > 0: the monitors of every ``log_every``-th epoch are evaluated, fetched in ONE
+        host read after the epoch's last batch and appended to ``self.updown_history`` as ``(epoch, wake_nll, sleep_nll,
+        top_loss)`` batch means; otherwise nothing is evaluated and the host never reads."""
+        self.updown_history = getattr(self, "updown_history", [])
+        for epoch in range(int(epochs)):
+            watch = int(log_every) > 0 and epoch % int(log_every) == 0
+            mons = []
+            for item in batches(self.dataloader):
+                m = self.updown_step(rows_on_device(item[0], self.device), epoch, epochs, CD=CD, persistent=persistent, lr_scale=lr_scale,
+                                     monitor=watch)
+                if watch:
+                    mons.append(torch.stack([m["wake_nll"].double(), m["sleep_nll"].double(), m["top_loss"].double()]))
+            if mons:
+                w, s, t = torch.stack(mons).mean(0).cpu().tolist()
+                self.updown_history.append((epoch, w, s, t))
+                if self.wandb_run:
+                    self.wandb_run.log({"idbn/wake_nll": w, "idbn/sleep_nll": s, "idbn/top_loss": t, "epoch": epoch})
 
     @torch.no_grad()
     def log_likelihood_bound(self, v: torch.Tensor, log_z_top, **kw) -> torch.Tensor:
@@ -196,6 +277,20 @@ class iDBN:
     def save_model(self, path: str):
         """idbn.py:370-372: pickle of {"layers", "params"} (live RBM modules)."""
         model_copy = {"layers": self.layers, "params": self.params}
+        if self.is_untied():
+            model_copy["gen_layers"] = self.gen_layers      # RBM.__getstate__: contiguous, no native descriptor
         with open(path, "wb") as f:
             pickle.dump(model_copy, f)
         print(f"[iDBN] Model saved to {path}")
+
+    def load_model(self, path: str):
+        """Read back what ``save_model`` wrote into this model (same architecture): the layers, and the generative twins when the
+        saved model was untied (a tied file leaves this model tied)."""
+        with open(path, "rb") as f:
+            saved = pickle.load(f)
+        self.layers = [rbm.to(self.device) for rbm in saved["layers"]]
+        self.params = saved.get("params", self.params)
+        self.__dict__.pop("gen_layers", None)
+        if saved.get("gen_layers") is not None:
+            self.gen_layers = [rbm.to(self.device) for rbm in saved["gen_layers"]]
+        return self

@@ -162,9 +162,30 @@ def _log_scalars(model, prefix: str, res: dict, keys):
         run.log({prefix + k: res[k] for k in keys if res[k] is not None})
 
 
-def _directed(layers, v, dev, n_samples, mode, rng):
+def _gen(model):
+    """The generative twins of an untied iDBN (``iDBN.untie``), else None: the model is tied and runs the tied lines."""
+    return getattr(model, "__dict__", {}).get("gen_layers")
+
+
+def _directed_untied(layers, gen, cur, mode, rng):
+    """``_directed``'s layer loop for recognition weights ``layers`` and generative twins ``gen``: per layer the wake sample
+    ``h ~ q_R(. | v)`` on the tied path's draw (``("u", H)``), then three evaluate-only ``delta_step``s at most:
+    ``acc += log p_G(v | h)`` (down on the twin) and ``acc -= log q_R(h | v)`` (mode ``logq``: up with the sample as target) or
+    ``acc += `` the entropy of ``q_R(. | v)`` (mode ``entropy``: up with the probabilities as target gives minus the entropy)."""
+    acc = None
+    for rbm, g in zip(layers, gen):
+        eng = _E.get_engine(rbm.W.data)
+        p, h = eng.prop_up(rbm, cur, sample=True, rng=rng)
+        lp = eng.delta_step(g, "down", h, cur, apply=False) - eng.delta_step(rbm, "up", cur, h if mode == "logq" else p, apply=False)
+        acc = lp if acc is None else acc + lp
+        cur = h
+    return acc, cur
+
+
+def _directed(layers, v, dev, n_samples, mode, rng, gen=None):
     """The directed layers ``layers`` (binary, bottom first) above the rows ``v``: every row ``n_samples`` times (row b's samples are
-    the engine rows b S .. b S + S - 1), one ``bound_step`` per layer.  ``(acc, top state, B, S)``; ``acc`` None without layers."""
+    the engine rows b S .. b S + S - 1), one ``bound_step`` per layer.  ``(acc, top state, B, S)``; ``acc`` None without layers.
+    ``gen``: the generative twins of an untied model (``_directed_untied``)."""
     if mode not in ("entropy", "logq"):
         raise ValueError("mode must be 'entropy' or 'logq'")
     S = int(n_samples)
@@ -176,6 +197,8 @@ def _directed(layers, v, dev, n_samples, mode, rng):
     B = cur.size(0)
     if S > 1:
         cur = cur.repeat_interleave(S, 0)
+    if gen is not None:
+        return _directed_untied(layers, gen, cur, mode, rng) + (B, S)
     acc = None
     for rbm in layers:
         acc, cur = _E.get_engine(rbm.W.data).bound_step(rbm, cur, rng, acc=acc, mode=mode)
@@ -262,9 +285,9 @@ def _stack(model):
     return layers
 
 
-def _sample_values(layers, v, log_z_top, n_samples, mode, rng) -> torch.Tensor:
+def _sample_values(layers, v, log_z_top, n_samples, mode, rng, gen=None) -> torch.Tensor:
     top = layers[-1]
-    acc, cur, B, S = _directed(layers[:-1], v, top.W.device, n_samples, mode, rng)
+    acc, cur, B, S = _directed(layers[:-1], v, top.W.device, n_samples, mode, rng, gen)
     w = -top.free_energy(cur).double() - log_z_top
     if acc is not None:
         w = acc + w
@@ -277,7 +300,7 @@ def dbn_sample_values(model, v: torch.Tensor, log_z_top, n_samples: int = 1, mod
     the device (row b's samples are the engine rows b S .. b S + S - 1 of the replicated batch).  One ``bound_step`` per directed
     layer, ``free_energy`` on the top RBM, no host sync.  ``model``: an ``iDBN`` or an ``RBM`` (a stack of one: no draw, and the
     value is ``log_likelihood``).  ``log_z_top``: log Z of the TOP RBM (``estimate_log_partition(model.layers[-1])``)."""
-    return _sample_values(_stack(model), v, log_z_top, n_samples, mode, _draws(seed))
+    return _sample_values(_stack(model), v, log_z_top, n_samples, mode, _draws(seed), _gen(model))
 
 
 @torch.no_grad()
@@ -317,7 +340,7 @@ def evaluate_dbn_bound(model, loader=None, log_z_top: Optional[float] = None, n_
     rng = _draws(ais_kwargs.get("seed"))
 
     def sums(batch):
-        w = _sample_values(layers, _first(batch), log_z_top, n_samples, "logq" if importance else "entropy", rng)
+        w = _sample_values(layers, _first(batch), log_z_top, n_samples, "logq" if importance else "entropy", rng, _gen(model))
         return (_logmeanexp_rows(w) if importance else w.mean(1)).sum().reshape(1)
 
     (s,), n = _sum_batches(loader, max_batches, sums, 1)
@@ -535,11 +558,11 @@ def evaluate_log_likelihood_sandwich(model, loader=None, max_batches: Optional[i
     return res
 
 
-def _conservative_values(layers, v, n_samples, n_chains, betas, base_vis_bias, rng, max_rows):
+def _conservative_values(layers, v, n_samples, n_chains, betas, base_vis_bias, rng, max_rows, gen=None):
     """``(w [B, S], ess [B, S])``: the directed layers as ``_sample_values`` in mode ``entropy``, the top term from reverse AIS on the
     sampled top-layer states."""
     top = layers[-1]
-    acc, cur, B, S = _directed(layers[:-1], v, top.W.device, n_samples, "entropy", rng)
+    acc, cur, B, S = _directed(layers[:-1], v, top.W.device, n_samples, "entropy", rng, gen)
     w, ess, _ = _reverse_rows(top, cur, n_chains, betas, base_vis_bias, rng, max_rows)
     if acc is not None:
         w = acc.to(w.device) + w
@@ -555,7 +578,7 @@ def dbn_conservative_bound(model, v: torch.Tensor, n_samples: int = 8, n_chains:
     model).  In expectation a lower bound on the variational bound of the stack whose top is the annealing model; float64 ``[B]``
     on the device, no host sync.  ``model``: an ``iDBN`` or an ``RBM`` (a stack of one: ``reverse_ais_log_likelihood``)."""
     betas = linear_betas(n_betas) if betas is None else betas
-    return _conservative_values(_stack(model), v, n_samples, n_chains, betas, base_vis_bias, _draws(seed), max_rows)[0].mean(1)
+    return _conservative_values(_stack(model), v, n_samples, n_chains, betas, base_vis_bias, _draws(seed), max_rows, _gen(model))[0].mean(1)
 
 
 @torch.no_grad()
@@ -574,7 +597,7 @@ def evaluate_dbn_bound_conservative(model, loader=None, n_samples: int = 8, n_ch
     rng = _draws(seed)
 
     def sums(batch):
-        w, ess = _conservative_values(layers, _first(batch), n_samples, n_chains, betas, base_vis_bias, rng, max_rows)
+        w, ess = _conservative_values(layers, _first(batch), n_samples, n_chains, betas, base_vis_bias, rng, max_rows, _gen(model))
         return torch.stack([w.mean(1).sum(), ess.mean(1).sum()])
 
     t, n = _sum_batches(loader, max_batches, sums, 2)
