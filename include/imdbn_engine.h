@@ -158,7 +158,9 @@ int    imdbn_set_tuning(int ksplit_up, int ksplit_down);
  * "down_rows" (0 or a multiple of 4 in [4, 32]), "k2s_rows" (0 or a multiple of 8 in [8, 48]), "chain_rows" ([0, 16]),
  * "min_rank_loop".  Testing, 1 = take the other kernel path: "generic_k3" (the unaligned-shape K3), "generic_k1",
  * "no_fused_up", "no_k1s", "no_k1s_real", "no_k2s", "no_bits", "no_prefetch", "no_adaptive", "no_chain_kernel",
- * "no_chain_pair", "no_down_chunks", "no_down_tiled", "no_rank_loop", "no_rank_acc".  Experiments: "k1s_lds_pad" (bytes,
+ * "no_chain_pair", "no_down_chunks", "no_down_tiled", "no_rank_loop", "no_rank_acc", "no_update_bin"
+ * (0/1 batches update through assoc_update_planes, not the two-plane kernel), "k3_tpb" (visible tiles per block of the streaming
+ * update kernels, clamped to [0, 64]; 0 = automatic).  Experiments: "k1s_lds_pad" (bytes,
  * clamped to [0, 65536]), "k1s_force_na".  Process-wide only: "dbg" (timeline stamps).  None of them changes results
  * beyond fp32 summation order, none is needed for normal use */
 int    imdbn_set_option(const char* name, int value);
@@ -191,6 +193,11 @@ enum { IMDBN_ROUTE_UP_FUSED = 0, IMDBN_ROUTE_UP_STREAM_BITS = 1, IMDBN_ROUTE_UP_
 enum { IMDBN_ROUTE_DOWN_K2_STREAM = 0, IMDBN_ROUTE_DOWN_FUSED = 1, IMDBN_ROUTE_DOWN_CHUNKS2 = 2, IMDBN_ROUTE_DOWN_CHUNKS4 = 3,
        IMDBN_ROUTE_DOWN_TILED = 4 };
 int    imdbn_debug_last_route(int route[5]);
+/* test aid, likewise for the weight update: rec[0] = the kernel the last update of the CALLING THREAD launched (IMDBN_UPDATE_*; the
+ * last launch of a multi-chunk batch; -1 until the thread has run an update), rec[1] = visible tiles per block of that launch
+ * (0 for the generic kernel).  Host code only; the routes are NOT part of the ABI */
+enum { IMDBN_UPDATE_GENERIC = 0, IMDBN_UPDATE_PLANES = 1, IMDBN_UPDATE_BIN = 2, IMDBN_UPDATE_RANKS = 3 };
+int    imdbn_debug_last_update(int rec[2]);
 
 /* *dev_offset += n on `stream` (see imdbn_rng.dev_offset).  Every engine call is a plain sequence of kernel launches on the caller's
  * stream -- no host synchronisation, no allocation, no memcpy -- so it can be recorded with hipStreamBeginCapture. */

@@ -586,6 +586,12 @@ int imdbn_debug_last_route(int route[5]) {
     return 0;
 }
 
+int imdbn_debug_last_update(int rec[2]) {
+    if (!rec) return fail(IMDBN_E_INVALID, "imdbn_debug_last_update: null buffer");
+    rec[0] = t_update.kernel; rec[1] = t_update.tpb;
+    return 0;
+}
+
 int imdbn_profile_read(double* total_ms, int* launches) {
     double tot = 0.0;
     for (size_t i = 0; i + 1 < g_prof.used; i += 2) {
@@ -1183,6 +1189,7 @@ static int apply_factors_impl(const imdbn_rbm_desc* d, const void* head, size_t 
                                  : (acc ? assoc_update_planes_ranks<1, true> : assoc_update_planes_ranks<1, false>);
         hipLaunchKernelGGL(k, k3_grid(c, brows), dim3(256), 0, c.s, f, rl, tpb, b, brows);
         HIPCHK(hipGetLastError());
+        ran_update(IMDBN_UPDATE_RANKS, tpb);
         return prof.end(c.s);
     }
     for (int rk = 0; rk < n_ranks; ++rk) {

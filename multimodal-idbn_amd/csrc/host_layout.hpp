@@ -28,6 +28,8 @@ struct Tuning {
     int k1s_lds_pad = 0;             // experiment: extra dynamic LDS (bytes) for the bit-plane k1_stream
     int no_chain_pair = 0;           // testing: imdbn_rbm_chain_pair runs its chains one after the other
     int no_down_tiled = 0;           // testing: multi-chunk real-valued K2 without the LDS-tiled kernel
+    int no_update_bin = 0;           // testing: single-chunk updates of one-term visible operands run assoc_update_planes, not assoc_update_bin
+    int k3_tpb = 0;                  // testing: visible tiles per block of the streaming update kernels (0 = automatic: ~one block per CU)
     int no_down_chunks = 0;          // testing: the fused K2 of a multi-chunk batch runs one block per (tile, 64-row chunk)
     int k1s_force_na = 0;            // experiment: bit-plane operands run on the kernel instantiation that can also read bf16 terms
 };
@@ -51,6 +53,7 @@ const Opt g_opts[] = {
     {"no_prefetch", &Tuning::no_prefetch}, {"no_adaptive", &Tuning::no_adaptive}, {"k1s_force_na", &Tuning::k1s_force_na},
     {"no_k1s", &Tuning::no_k1s}, {"no_k1s_real", &Tuning::no_k1s_real}, {"no_k2s", &Tuning::no_k2s},
     {"no_down_chunks", &Tuning::no_down_chunks}, {"no_down_tiled", &Tuning::no_down_tiled},
+    {"no_update_bin", &Tuning::no_update_bin}, {"k3_tpb", &Tuning::k3_tpb, OPT_CLAMP, 0, 64},
 };
 
 int set_opt(Tuning& t, const char* name, int value) {
@@ -297,7 +300,7 @@ Route make_route(const imdbn_rbm_desc* d, const Layout& L) {
     r.prefetch = r.vec4 && !t.no_prefetch;
     r.next_on_k1 = r.k2s_cd && r.vbits && r.k1s;
     r.rides = !r.k2s_cd || r.next_on_k1;
-    r.tpb = std::max(1, cdiv(cdiv(L.H, 128) * cdiv(L.V, 128), std::max(cu_count(), 1)));
+    r.tpb = t.k3_tpb > 0 ? t.k3_tpb : std::max(1, cdiv(cdiv(L.H, 128) * cdiv(L.V, 128), std::max(cu_count(), 1)));
     // The per-item choice of k1_stream holds one exactness-map entry per thread for a K slice's items (<= 32) and one for a span
     // of the update kernel (<= 256 entries); layers outside that read data of unknown content from the bf16 terms throughout
     // (same numbers, all three-term forms prepared) ... and one block of the (first batch chunk of the) positive-phase K1 per

@@ -53,6 +53,12 @@ int launch_bias(Ctx& c, const BiasArgs& b) {
     return 0;
 }
 
+// ---- testing aid: which update kernel the last launch_assoc / rank-loop update of this THREAD launched, and with how many visible
+// tiles per block (imdbn_debug_last_update; the codes are IMDBN_UPDATE_* of the header).  Written where the launch is made
+struct UpdateRec { int kernel = -1, tpb = 0; };
+thread_local UpdateRec t_update;
+inline void ran_update(int kernel, int tpb) { t_update.kernel = kernel; t_update.tpb = tpb; }
+
 // ---- streaming update kernel: float4 weight tiles, LDS-staged planes, ~one block per CU, each streaming Route::tpb visible
 // tiles with its hidden planes resident in LDS.  One launch per 64-row batch chunk or gathered rank block `i` of `n`
 // (kernels_gemm.hpp AssocPlanesArgs::pass: only, first, middle, last); `br` extra block rows update the biases / reduce the loss
@@ -66,9 +72,12 @@ int k3_pass(int i, int n) { return n == 1 ? 0 : (i == 0 ? 1 : (i == n - 1 ? 3 : 
 // block rows of a fused bias / loss update: >= 2 blocks, one reduces the loss, the rest stride the biases
 int k3_bias_rows(const Layout& L) { return cdiv(L.H, 128) >= 2 ? 1 : 2; }
 dim3 k3_grid(const Ctx& c, int br) { return dim3(cdiv(c.L.H, 128), cdiv(cdiv(c.L.V, 128), c.r.tpb) + br); }
-int launch_k3_planes(Ctx& c, int mode_stats, const AssocPlanesArgs& f, int pass, const BiasArgs& bb, int br) {
-    hipLaunchKernelGGL(k3_insts[mode_stats != 0][c.ht == 3][pass], k3_grid(c, br), dim3(256), 0, c.s, f, c.r.tpb, bb, br);
+// `bin`: the two-plane kernel of a single-chunk update with one-term visible operands (assoc_update_bin: same grid and arguments)
+int launch_k3_planes(Ctx& c, int mode_stats, const AssocPlanesArgs& f, int pass, const BiasArgs& bb, int br, bool bin = false) {
+    const K3Fn k = bin ? (c.ht == 3 ? assoc_update_bin<3> : assoc_update_bin<1>) : k3_insts[mode_stats != 0][c.ht == 3][pass];
+    hipLaunchKernelGGL(k, k3_grid(c, br), dim3(256), 0, c.s, f, c.r.tpb, bb, br);
     HIPCHK(hipGetLastError());
+    ran_update(bin ? IMDBN_UPDATE_BIN : IMDBN_UPDATE_PLANES, c.r.tpb);
     return 0;
 }
 
@@ -90,9 +99,13 @@ int launch_assoc(Ctx& c, int mode_stats, const imdbn_cd_opts* o, int vpos_terms,
         BiasArgs bz;
         memset(&bz, 0, sizeof(bz));
         const int nchunk = L.Bp / 64;      // the bias / loss blocks ride on the last chunk
+        // one-term visible operands on both sides: known here, or (vpos_terms == 0: an untagged batch, the bench's default) known
+        // only to the device from the exactness map -- the kernel then branches once, at entry, to the old body for anything else
+        const bool bin = !mode_stats && nchunk == 1 && vneg_terms == 1 && (vpos_terms == 1 || (vpos_terms == 0 && vpos_flag)) &&
+                         !tune().no_update_bin;
         for (int ch = 0; ch < nchunk; ++ch) {
             f.b0 = 64 * ch;
-            CHK(launch_k3_planes(c, mode_stats, f, k3_pass(ch, nchunk), bias ? *bias : bz, (bias && ch == nchunk - 1) ? k3_bias_rows(L) : 0));
+            CHK(launch_k3_planes(c, mode_stats, f, k3_pass(ch, nchunk), bias ? *bias : bz, (bias && ch == nchunk - 1) ? k3_bias_rows(L) : 0, bin));
         }
         return prof.end(c.s);
     }
@@ -109,6 +122,7 @@ int launch_assoc(Ctx& c, int mode_stats, const imdbn_cd_opts* o, int vpos_terms,
     hipLaunchKernelGGL(c.ht == 3 ? (mode_stats ? assoc_update<1, 3> : assoc_update<0, 3>) : (mode_stats ? assoc_update<1, 1> : assoc_update<0, 1>),
                        dim3(cdiv(L.H, 128), cdiv(L.V, 64)), dim3(256), 0, c.s, a);
     HIPCHK(hipGetLastError());
+    ran_update(IMDBN_UPDATE_GENERIC, 0);
     CHK(prof.end(c.s));
     if (bias) CHK(launch_bias(c, *bias));          // generic K3: bias update as its own launch
     return 0;

@@ -1227,30 +1227,44 @@ __device__ __forceinline__ void k3_body_ranks_acc(const AssocPlanesArgs& a, cons
     }
 }
 
+// ---- what the kernels around the k3 bodies share -----------------------------------------------------------
+// The last `bias_rows` block rows of the grid do the (tiny, independent) bias / loss update of rbm.py:216-226 instead of a
+// dependent launch of their own: they only touch the bias vectors.  true: this block was one of them and is done.
+__device__ __forceinline__ bool k3_bias_block(const BiasArgs& bias, int bias_rows, char* smem) {
+    if (bias_rows > 0 && (int)blockIdx.y >= (int)gridDim.y - bias_rows) {
+        bias_work(bias, (blockIdx.y - (gridDim.y - bias_rows)) * gridDim.x + blockIdx.x, bias_rows * gridDim.x,
+                  reinterpret_cast<double*>(smem));
+        return true;
+    }
+    return false;
+}
+// XCD-aware block -> (hidden tile bx, visible chunk by) map.  Blocks are dealt round-robin to the 8 XCDs
+// (private L2 each), so give XCD x the sub-grid (xa of the hidden tiles) x (xc of the visible chunks),
+// xa*xc = 8: the operand planes a block stages were then already fetched into THIS L2 by a neighbour
+// (plane traffic ~60 MB -> ~11 MB at 10000x1500).  Placement only changes speed, never results.
+__device__ __forceinline__ void k3_block_map(int bias_rows, int& bx, int& by) {
+    bx = blockIdx.x; by = blockIdx.y;
+    const int nbx = gridDim.x, nby = gridDim.y - bias_rows;
+    int xa = 0;
+    if (nbx % 2 == 0 && nby % 4 == 0) xa = 2; else if (nbx % 4 == 0 && nby % 2 == 0) xa = 4;
+    else if (nby % 8 == 0) xa = 1; else if (nbx % 8 == 0) xa = 8;
+    if (xa) {
+        const int xc = 8 / xa, sa = nbx / xa, sc = nby / xc;      // sub-grid of one XCD: sa x sc blocks
+        const int p = blockIdx.y * nbx + blockIdx.x;              // dispatch order
+        const int xcd = p & 7, slot = p >> 3;
+        bx = (xcd % xa) * sa + slot % sa;
+        by = (xcd / xa) * sc + slot / sa;
+    }
+}
+
 // ACC = rank loop outside the tile loop (k3_body_ranks_acc; needs tiles_per_block <= 4); one body per kernel
 template <int HT, bool ACC>
 __global__ __launch_bounds__(256, 1) void assoc_update_planes_ranks(const AssocPlanesArgs a, const RankLoopArgs rl, int tiles_per_block,
                                                                     const BiasArgs bias, int bias_rows) {
     __shared__ __attribute__((aligned(16))) char smem[K3_LDS_BYTES];
-    if (bias_rows > 0 && (int)blockIdx.y >= (int)gridDim.y - bias_rows) {
-        bias_work(bias, (blockIdx.y - (gridDim.y - bias_rows)) * gridDim.x + blockIdx.x, bias_rows * gridDim.x,
-                  reinterpret_cast<double*>(smem));
-        return;
-    }
-    int bx = blockIdx.x, by = blockIdx.y;
-    {
-        const int nbx = gridDim.x, nby = gridDim.y - bias_rows;
-        int xa = 0;
-        if (nbx % 2 == 0 && nby % 4 == 0) xa = 2; else if (nbx % 4 == 0 && nby % 2 == 0) xa = 4;
-        else if (nby % 8 == 0) xa = 1; else if (nbx % 8 == 0) xa = 8;
-        if (xa) {
-            const int xc = 8 / xa, sa = nbx / xa, sc = nby / xc;
-            const int p = blockIdx.y * nbx + blockIdx.x;
-            const int xcd = p & 7, slot = p >> 3;
-            bx = (xcd % xa) * sa + slot % sa;
-            by = (xcd / xa) * sc + slot / sa;
-        }
-    }
+    if (k3_bias_block(bias, bias_rows, smem)) return;
+    int bx, by;
+    k3_block_map(bias_rows, bx, by);
     const int tile0 = by * tiles_per_block;
     const int ncbv = ((a.V + 15) / 16 * 16 + 63) / 64;
     int nap = a.vpos_terms;
@@ -1273,34 +1287,177 @@ __global__ __launch_bounds__(256, 1) void assoc_update_planes(const AssocPlanesA
     //  progress; the preparation rides on a read-only stream instead: k1_stream's negative-phase launch.)
     // The last `bias_rows` block rows of the grid do the (tiny, independent) bias / loss update of
     // rbm.py:216-226 instead of a dependent launch of their own: they only touch the bias vectors.
-    if (bias_rows > 0 && (int)blockIdx.y >= (int)gridDim.y - bias_rows) {
-        bias_work(bias, (blockIdx.y - (gridDim.y - bias_rows)) * gridDim.x + blockIdx.x, bias_rows * gridDim.x,
-                  reinterpret_cast<double*>(smem));
-        return;
-    }
-    // XCD-aware block -> (hidden tile bx, visible chunk by) map.  Blocks are dealt round-robin to the 8 XCDs
-    // (private L2 each), so give XCD x the sub-grid (xa of the hidden tiles) x (xc of the visible chunks),
-    // xa*xc = 8: the operand planes a block stages were then already fetched into THIS L2 by a neighbour
-    // (plane traffic ~60 MB -> ~11 MB at 10000x1500).  Placement only changes speed, never results.
-    int bx = blockIdx.x, by = blockIdx.y;
-    {
-        const int nbx = gridDim.x, nby = gridDim.y - bias_rows;
-        int xa = 0;
-        if (nbx % 2 == 0 && nby % 4 == 0) xa = 2; else if (nbx % 4 == 0 && nby % 2 == 0) xa = 4;
-        else if (nby % 8 == 0) xa = 1; else if (nbx % 8 == 0) xa = 8;
-        if (xa) {
-            const int xc = 8 / xa, sa = nbx / xa, sc = nby / xc;      // sub-grid of one XCD: sa x sc blocks
-            const int p = blockIdx.y * nbx + blockIdx.x;              // dispatch order
-            const int xcd = p & 7, slot = p >> 3;
-            bx = (xcd % xa) * sa + slot % sa;
-            by = (xcd / xa) * sc + slot / sa;
-        }
-    }
+    if (k3_bias_block(bias, bias_rows, smem)) return;
+    int bx, by;
+    k3_block_map(bias_rows, bx, by);
     const int tile0 = by * tiles_per_block;
     const int ncbv = ((a.V + 15) / 16 * 16 + 63) / 64;
     const int nap = operand_terms(a.vpos_flag, ncbv, a.Bp / 8, (tile0 * 128) / 64, (tile0 + tiles_per_block) * 2, a.vpos_terms);
     const int nan_ = a.vneg_terms;
     k3_body<MODE, HT, PASS>(a, smem, bx, by, tiles_per_block, nap, nan_);
+}
+
+// ---- the update of a 0/1 batch: two planes per tile ---------------------------------------------------------
+// MODE 0, one 64-row chunk, ONE bf16 term on both visible sides (binary data, sampled negative phase): P = 2, so a wave needs
+// two of its four 4-KB slices per tile.  Same block map, hidden-plane layout, MFMA order (positive plane, then the negated
+// negative plane, same fragments) and epilogue arithmetic as k3_body<0, HT, 0>: the results are bit-identical.  What differs is
+// the VMEM schedule of a wave:
+//   * the four slices are two buffers {0,1} / {2,3}; tile `it` reads buffer it & 1.  Two DMA batches per tile, not four, no
+//     run-time plane count, no clamped plane index;
+//   * the slices of tile it+1 are requested after the MFMAs of tile it (fragments consumed: lgkmcnt(0)) and BEFORE its epilogue
+//     stores, so the wait for them at the top of tile it+1 leaves those stores in flight: they drain under that tile's MFMAs
+//     instead of in front of them (k3_body waits vmcnt(32) behind its own stores: vmcnt retires in order and counts stores);
+//   * a wave holds at most 64 unacknowledged memory operations, and 8 DMA + 32 stores + 32 prefetch loads are 72.  So the
+//     prefetch of the next weight tile is cut in two: K3B_TOP of its 16 float4 row pairs before the MFMAs, the rest after them
+//     together with the next slices.  At the wait nothing younger than the slices is then queued behind a store acknowledgement;
+//   * the prologue requests tile 0's slices with the hidden planes: one wait and the one barrier cover both.
+// VMEM order of one wave (L = 2 float4 loads per row pair, W and W_m):
+//   prologue: [24 or 8 DMA hidden planes] [8 DMA slices(0) -> buffer 0] [32 L tile 0]  vmcnt(32)  barrier
+//   tile it : [2*K3B_TOP L tile it+1]  vmcnt(32 + 2*K3B_TOP)  MFMAs  lgkmcnt(0)  [2*(16-K3B_TOP) L tile it+1]
+//             [8 DMA slices(it+1) -> buffer (it+1) & 1, only if that tile exists]  [32 stores of tile it]
+// The counted wait of tile it+1 needs "slices(it+1) landed": behind the last of those DMAs the wave has issued exactly the 32
+// stores of tile it and the 2*K3B_TOP loads, so vmcnt(32 + 2*K3B_TOP) is exact.  All 32 stores are really issued whenever a
+// next tile exists: then every row of tile it is < V, and lane 0 of every wave has cok (h0 < H), so no store is skipped on an
+// empty exec mask.  (Tile 0: the prologue's wait already covered its slices; the count is then merely loose.)  The last tile's
+// partial rows come with no later wait.  Counts checked in the -save-temps ISA of both instantiations.
+constexpr int K3B_TOP = 12;
+static_assert(32 + 2 * K3B_TOP <= 63, "the vmcnt field holds 6 bits");
+
+template <int HT>
+__device__ __forceinline__ void k3_body_bin(const AssocPlanesArgs& a, char* smem, int bx, int by, int tiles_per_block) {
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, r = l & 31, kh = l >> 5;
+    const int h0 = bx * 128;
+    const int tile0 = by * tiles_per_block;
+    const int n_vtiles = (a.V + 127) / 128;
+    const int n_my = min(tiles_per_block, n_vtiles - tile0);
+    const int colc = min(h0 + 4 * r, a.H - 4);
+    const bool cok = (h0 + 4 * r) < a.H;          // H % 4 == 0: a float4 is entirely inside or outside
+    const bool n_pow2 = (__float_as_uint(a.n) & 0x7fffffu) == 0u;      // d / n == d * (1/n) exactly
+    const float inv_n = 1.0f / a.n;
+
+    char* sHp = smem;
+    char* sHn = smem + 3 * K3_PLANE;
+    char* sV = smem + K3_VIS0 + w * (4 * K3_SLICE);                    // this wave's two buffers of two slices
+    const uint32_t sV_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)sV);
+
+    // row pairs [R0, R1) of the weight tile at v0: W and W_m, interleaved as k3_body loads them
+    auto load_rows = [&](auto r0_tag, auto r1_tag, float4 (&wo)[16], float4 (&mo)[16], int v0, bool valid) {
+#pragma unroll
+        for (int reg = decltype(r0_tag)::value; reg < decltype(r1_tag)::value; ++reg) {
+            const int row = valid ? min(v0 + 32 * w + mfma_row(reg, l), a.V - 1) : tile0 * 128;
+            const int64_t idx = (int64_t)row * a.ldw + colc;
+            wo[reg] = *reinterpret_cast<const float4*>(a.W + idx);
+            mo[reg] = *reinterpret_cast<const float4*>(a.Wm + idx);
+        }
+    };
+    // positive and negative plane of rows v0w..v0w+31 -> buffer `buf`
+    auto dma_slices = [&](int buf, int v0w) {
+#pragma unroll
+        for (int ph = 0; ph < 2; ++ph)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int i = l + 64 * q, row = i >> 3, c = (i & 7) ^ ((row >> 1) & 7);      // source chunk for LDS position i
+                k3_dma16((ph ? a.vneg : a.vpos) + (int64_t)min(v0w + row, a.V - 1) * a.Bp + a.b0 + 8 * c,
+                         sV_lds + (2 * buf + ph) * K3_SLICE + q * 1024);
+            }
+    };
+    using I0 = std::integral_constant<int, 0>;
+    using IT = std::integral_constant<int, K3B_TOP>;
+    using IE = std::integral_constant<int, 16>;
+
+    float4 wA[16], mA[16], wB[16], mB[16];
+    const bool st = a.dbg != 0;
+    const int sblk = by * gridDim.x + bx;
+    stamp(st, sblk, 0);
+    // hidden planes as in k3_body (same LDS image), tile 0's slices, the whole first weight tile; then ONE wait, ONE barrier
+    const uint32_t sH_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)smem);
+#pragma unroll
+    for (int ph = 0; ph < 2; ++ph)
+#pragma unroll
+        for (int tb = 0; tb < HT; ++tb)
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) {
+                const int j = 4 * w + jj, i = 64 * j + l, lrow = i >> 3, pos = i & 7;
+                const int row = 4 * (lrow & 31) + (lrow >> 5), c = pos ^ ((lrow >> 1) & 7);
+                const bf16_t* src = (ph ? a.hneg : a.hpos) + tb * a.hts + (int64_t)min(h0 + row, a.H - 1) * a.Bp + a.b0 + 8 * c;
+                k3_dma16(src, sH_lds + (3 * ph + tb) * K3_PLANE + j * 1024);
+            }
+    dma_slices(0, tile0 * 128 + 32 * w);
+    __builtin_amdgcn_sched_barrier(0);
+    load_rows(I0{}, IE{}, wA, mA, tile0 * 128, true);
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt vmcnt(32)" ::: "memory");                   // planes and slices(0) arrived; the 32 weight loads stay in flight
+    __syncthreads();                                                    // the ONLY block barrier
+    stamp(st, sblk, 1);
+
+    auto tile = [&](int it, auto buf_tag, float4 (&wc)[16], float4 (&mc)[16], float4 (&wn)[16], float4 (&mn)[16]) {
+        constexpr int BUF = decltype(buf_tag)::value;
+        const int v0 = (tile0 + it) * 128;
+        const bool more = it + 1 < n_my;                                  // block-uniform
+        load_rows(I0{}, IT{}, wn, mn, v0 + 128, more);                    // first part of the next tile's weights
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt vmcnt(%0)" :: "i"(32 + 2 * K3B_TOP) : "memory");     // this tile's slices arrived; the previous tile's stores and the loads above stay in flight
+        f32x16 acc[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+        k3_mfma_wave<HT>(acc, sHp, sV + (2 * BUF) * K3_SLICE, r, kh);
+        k3_mfma_wave<HT>(acc, sHn, sV + (2 * BUF + 1) * K3_SLICE, r, kh);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               // all fragment reads done
+        __builtin_amdgcn_sched_barrier(0);
+        load_rows(IT{}, IE{}, wn, mn, v0 + 128, more);                    // the rest of the next tile's weights
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) dma_slices(BUF ^ 1, v0 + 128 + 32 * w);                 // the other buffer: last read by the previous tile's MFMAs
+        __builtin_amdgcn_sched_barrier(0);
+        auto epilogue = [&](auto pow2_tag) {
+            constexpr bool POW2 = decltype(pow2_tag)::value;
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int row = v0 + 32 * w + mfma_row(reg, l);
+                if (row < a.V && cok) {
+                    const float4 d = make_float4(acc[0][reg], acc[1][reg], acc[2][reg], acc[3][reg]);   // pos_assoc - neg_assoc
+                    const int64_t idx = (int64_t)row * a.ldw + h0 + 4 * r;
+                    const float4 w0 = wc[reg];
+                    float4 m = mc[reg];
+                    const float gx = POW2 ? d.x * inv_n : d.x / a.n, gy = POW2 ? d.y * inv_n : d.y / a.n;
+                    const float gz = POW2 ? d.z * inv_n : d.z / a.n, gw = POW2 ? d.w * inv_n : d.w / a.n;
+                    m.x = m.x * a.mom; m.x = m.x + a.lr * (gx - a.wd * w0.x);        // rbm.py:212
+                    m.y = m.y * a.mom; m.y = m.y + a.lr * (gy - a.wd * w0.y);
+                    m.z = m.z * a.mom; m.z = m.z + a.lr * (gz - a.wd * w0.z);
+                    m.w = m.w * a.mom; m.w = m.w + a.lr * (gw - a.wd * w0.w);
+                    *reinterpret_cast<float4*>(a.Wm + idx) = m;
+                    *reinterpret_cast<float4*>(a.W + idx) = make_float4(w0.x + m.x, w0.y + m.y, w0.z + m.z, w0.w + m.w);   // :213
+                }
+            }
+        };
+        if (n_pow2) epilogue(std::true_type{}); else epilogue(std::false_type{});
+        stamp(st, sblk, 2 + it);
+    };
+    for (int it = 0; it < n_my; it += 2) {
+        tile(it, std::integral_constant<int, 0>{}, wA, mA, wB, mB);
+        if (it + 1 < n_my) tile(it + 1, std::integral_constant<int, 1>{}, wB, mB, wA, mA);
+    }
+}
+
+// Routed by launch_assoc for a single-chunk MODE-0 update whose visible operands are one-term as far as the host knows; where the
+// positive operand's term count is only known on the device (exactness map of an untagged batch), anything but one term
+// branches ONCE, here, to k3_body<0, HT, 0>: a mixed or real-valued batch gets the old kernel's result from the old body.
+template <int HT>
+__global__ __launch_bounds__(256, 1) void assoc_update_bin(const AssocPlanesArgs a, int tiles_per_block,
+                                                           const BiasArgs bias, int bias_rows) {
+    __shared__ __attribute__((aligned(16))) char smem[K3_LDS_BYTES];
+    if (k3_bias_block(bias, bias_rows, smem)) return;
+    int bx, by;
+    k3_block_map(bias_rows, bx, by);
+    const int tile0 = by * tiles_per_block;
+    const int ncbv = ((a.V + 15) / 16 * 16 + 63) / 64;
+    const int nap = operand_terms(a.vpos_flag, ncbv, a.Bp / 8, (tile0 * 128) / 64, (tile0 + tiles_per_block) * 2, a.vpos_terms);
+    if (nap != 1) {                                                  // (the host routes here only with a one-term negative operand)
+        k3_body<0, HT, 0>(a, smem, bx, by, tiles_per_block, nap, a.vneg_terms);
+        return;
+    }
+    k3_body_bin<HT>(a, smem, bx, by, tiles_per_block);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -102,6 +102,7 @@ SIGNATURES = {
     "imdbn_debug_stamps": (_INT, [C.POINTER(C.c_longlong), _INT]),
     "imdbn_debug_ws_offset": (_INT, [_INT, _INT, _INT, C.c_char_p, C.POINTER(_SZ)]),
     "imdbn_debug_last_route": (_INT, [C.POINTER(_INT)]),
+    "imdbn_debug_last_update": (_INT, [C.POINTER(_INT)]),
     "imdbn_rng_advance": (_INT, [_P, C.c_uint64, _P]),
     "imdbn_rbm_prop_up": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _F, C.POINTER(Rng), _P, _I64, _P, _I64, _P, _SZ, _P]),
     "imdbn_rbm_forward": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _INT, _P, _I64, _P, _SZ, _P]),

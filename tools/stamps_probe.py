@@ -18,11 +18,14 @@ rbm = RBM(V, H, 0.1, 1e-4, 0.5, dynamic_lr=True, final_momentum=0.95).to(dev)
 xs = [(torch.rand(B, V) > 0.9).float().to(dev) for _ in range(4)]
 if "--tag" in sys.argv:
     for t in xs: t._imdbn_binary = True
+for kv in sys.argv[1:]:      # engine options, e.g. no_update_bin=1
+    if "=" in kv:
+        eng.set_option(kv.split("=")[0], int(kv.split("=")[1]))
 E.set_rng(E.PhiloxRng(seed=2))
 for which, bit, nslots in (("K1 k1_stream POSITIVE phase: start, bits+ring landed, loop done, reduced, published, [last arriver:] combined, epilogue done", 2048, 7),
                            ("K1 k1_stream (last launch = negative phase): start, bits+ring landed, loop done, reduced, published, [last arriver:] combined, epilogue done", 64, 7),
                            ("K2 k2_stream: start, bits staged, loop done, reduced, epilogue done, loss done", 128, 6),
-                           ("K3 assoc_update_planes", 512, 6)):
+                           ("K3 assoc_update_bin (assoc_update_planes with no_update_bin=1): start, planes landed, tile 0..3 done", 512, 6)):
     eng.set_option("dbg", bit)
     for i in range(20):
         rbm.train_epoch(xs[i % 4], 0, 1, CD=1, next_data=xs[(i + 1) % 4])
