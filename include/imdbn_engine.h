@@ -462,6 +462,48 @@ int imdbn_rbm_delta_step(const imdbn_rbm_desc* d, int dir, const float* in, int6
                          const imdbn_cd_opts* o /* NULL: evaluate only */, double* out_rowlp /* [B], nullable */,
                          void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- one back-propagation step through a sigmoid layer (imdbn/models/idbn.py: autoencoder_step; the autoencoder fine-tuning of
+ * Hinton & Salakhutdinov 2006) --------------------------------------------------------------------------------------
+ * The layer of the descriptor is read in one or both directions.  The up pair is (x_v [B][V], e_h [B][H]): the layer maps x_v through
+ * W to hidden pre-activations and e_h is the error there.  The down pair is (x_h [B][H], e_v [B][V]): the layer maps x_h through W^T to
+ * visible pre-activations and e_v is the error there.  Each pair is given whole or not at all (both pointers NULL); fp32, row strides
+ * ldxv / ldev >= V, ldeh / ldxh >= H.  An error is the ASCENT direction at a pre-activation (for a cross-entropy output layer:
+ * target - p); an input x is the sigmoid output of the layer before it.
+ *   err_v_out = (e_h W^T) * x_v * (1 - x_v)     [B][V], row stride ldov >= V, nullable, needs the up pair:   the error at the
+ *                                               pre-activations that produced x_v
+ *   err_h_out = (e_v W) * x_h * (1 - x_h)       [B][H], row stride ldoh >= H, nullable, needs the down pair: ... that produced x_h
+ * Both from the parameters on entry: every launch that reads W for them precedes the update on the stream.  The product carries no
+ * bias: it is the logits-only propagation of imdbn_rbm_prop_down / imdbn_rbm_prop_up on a zero bias, bit for bit -- a real, signed
+ * operand through whatever kernel route that propagation takes -- and the epilogue q * (x * (1 - x)) runs in fp32.
+ * With o != NULL the update, g in the [V][H] layout of W:  g = (x_v^T e_h + e_v^T x_h) / B, an absent pair contributing nothing;
+ *   W_m = momentum W_m + lr (g - weight_decay W), W += W_m;
+ *   with the up pair:    hb_m = momentum hb_m + lr colsum(e_h) / B, hid_bias += hb_m
+ *   with the down pair:  vb_m = momentum vb_m + lr colsum(e_v) / B, vis_bias += vb_m
+ * a bias without its pair is not touched, and neither is its momentum.  Both pairs at once are the exact gradient step of a layer
+ * whose weights are used in both directions (the tied top RBM of an unrolled stack).  Of o only lr, momentum and weight_decay are
+ * read; cd_k, sparsity, the prefetch fields and fwd_out must be zero.  o == NULL back-propagates only and writes no parameter.
+ * Launches, plain, on `stream`, no host sync, no draws, no allocation: per error output the operand preparation of the error rows, a
+ * memset node that clears the zero bias, the logits-only propagation and backprop_apply; with o, per pair the operand preparation
+ * of the input rows (their planes) and backprop_rows (one pass over the error rows: their planes, the column partials, and with one
+ * pair only the zero planes of the other slot), then backprop_finish (the biases) and the update kernel of imdbn_rbm_cd_step with
+ * (vpos, hpos) = (x_v, e_h) and (vneg, hneg) = (e_v, x_h), the hidden planes of the second pair stored as they are to be added.
+ * Sums: colsum: fp32, 8 rows per partial in row order, the partials in index order.  g: the update kernel's exact products, both
+ * pairs in one fp32 accumulator.  No floating-point atomics; every order is fixed by (V, H, B): the same call on the same state gives
+ * the same bits.  The row padding of W / W_m is neither read nor written.
+ * IMDBN_E_INVALID (naming the value) before the first launch, nothing touched: a null descriptor, half a pair, no pair at all,
+ * err_v_out without the up pair or err_h_out without the down pair, o == NULL with both outputs NULL (nothing to do), a leading
+ * dimension below its width, B < 1, with o: a null momentum buffer, a non-zero cd_k / sparsity / prefetch field / fwd_out.
+ * IMDBN_E_UNSUPPORTED: a descriptor with softmax groups.
+ * Workspace: imdbn_ws_bytes(V, H, B).  The planes and column partials of both pairs fit the layout of a CD pass (two visible and two
+ * hidden plane slots, four column-partial buffers): no scratch argument is needed. */
+int imdbn_rbm_backprop_step(const imdbn_rbm_desc* d,
+                            const float* x_v, int64_t ldxv, const float* e_h, int64_t ldeh,   /* up pair:   x_v [B][V], e_h [B][H]; both or neither */
+                            const float* x_h, int64_t ldxh, const float* e_v, int64_t ldev,   /* down pair: x_h [B][H], e_v [B][V]; both or neither */
+                            int B, const imdbn_cd_opts* o /* NULL: back-propagate only */,
+                            float* err_v_out, int64_t ldov,   /* nullable, needs the up pair   */
+                            float* err_h_out, int64_t ldoh,   /* nullable, needs the down pair */
+                            void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- parallel tempering over persistent chains (Desjardins et al. 2010; Cho, Raiko & Ilin 2010) -----------------
  * state [R M][V]: fp32, 0/1, one-hot inside softmax groups, row stride lds >= V, IN PLACE; replica r owns the rows [r M, (r + 1) M)
  * and samples p_beta(v) ~ exp(beta b.v + S(beta, v)), S(beta, v) = sum_j softplus(beta x_j(v)), x(v) = c + v W, at beta = betas[r].

@@ -4,9 +4,9 @@
 // the reference's draw order, and enqueue kernels on the caller's stream.
 // No host synchronisation, no allocation, no global state besides tuning knobs, the thread-local
 // error string, what is known per device ordinal and the optional profiling events.
-// The host code is one translation unit in five files: this one (context, CD / chain / factor orchestration, the C entries),
+// The host code is one translation unit in six files: this one (context, CD / chain / factor orchestration, the C entries),
 // host_layout.hpp (knobs, workspace layout, Route), host_prop.hpp (propagation launchers), host_update.hpp (update launchers),
-// host_delta.hpp (the delta-rule step of a directed layer).
+// host_delta.hpp (the delta-rule step of a directed layer), host_backprop.hpp (the back-propagation step through a sigmoid layer).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,6 +38,7 @@
 #include "kernels_pt.hpp"
 #include "kernels_centered.hpp"
 #include "kernels_delta.hpp"
+#include "kernels_backprop.hpp"
 
 using namespace imdbn;
 
@@ -173,6 +174,7 @@ int setup(Ctx& c, int B, void* ws, size_t ws_bytes) {
 #include "host_prop.hpp"
 #include "host_update.hpp"
 #include "host_delta.hpp"
+#include "host_backprop.hpp"
 
 // The caller's fp32 rows x (visible rows when `up`, hidden rows otherwise) into the row-major operand form of their side, then the
 // propagation from it with `f`.
@@ -1785,6 +1787,13 @@ int imdbn_rbm_centered_step(const imdbn_rbm_desc* d, const float* data, int64_t 
 int imdbn_rbm_delta_step(const imdbn_rbm_desc* d, int dir, const float* in, int64_t ldi, const float* target, int64_t ldt, int B,
                          const imdbn_cd_opts* o, double* out_rowlp, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
     return delta_step(d, dir, in, ldi, target, ldt, B, o, out_rowlp, ws, ws_bytes, S(stream));
+}
+
+// ---- one back-propagation step through a sigmoid layer (host_backprop.hpp; kernels_backprop.hpp) -------------------------
+int imdbn_rbm_backprop_step(const imdbn_rbm_desc* d, const float* x_v, int64_t ldxv, const float* e_h, int64_t ldeh,
+                            const float* x_h, int64_t ldxh, const float* e_v, int64_t ldev, int B, const imdbn_cd_opts* o,
+                            float* err_v_out, int64_t ldov, float* err_h_out, int64_t ldoh, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    return backprop_step(d, x_v, ldxv, e_h, ldeh, x_h, ldxh, e_v, ldev, B, o, err_v_out, ldov, err_h_out, ldoh, ws, ws_bytes, S(stream));
 }
 
 // rows [row, row + ...) of a draw tensor that spans more rows than the launch it feeds

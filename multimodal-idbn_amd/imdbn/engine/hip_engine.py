@@ -767,6 +767,89 @@ class HipEngine:
             out["sleep_nll"] = -torch.stack(lp_s).sum(0).mean() if lp_s else zero
         return out
 
+    # ---- backprop fine-tuning of the unrolled stack as a deep autoencoder -------------------------------
+    def backprop_step(self, rbm, up=None, down=None, lr=0.0, mom=0.0, apply=True, want_v=False, want_h=False):
+        """One back-propagation step through the sigmoid layer ``rbm`` (imdbn_rbm_backprop_step).  ``up`` = ``(x_v, e_h)``: the
+        layer's input ``[B, V]`` in the upward direction and the error at its hidden pre-activations ``[B, H]``; ``down`` =
+        ``(x_h, e_v)``: its input ``[B, H]`` in the downward direction and the error at its visible pre-activations ``[B, V]``.
+        Errors are ascent directions.  Returns ``(err_v, err_h)``: ``(e_h W^T) x_v (1 - x_v)`` with ``want_v`` (needs ``up``) and
+        ``(e_v W) x_h (1 - x_h)`` with ``want_h`` (needs ``down``), from the parameters on entry; a part not asked for is None.
+        With ``apply`` the weights move along ``(x_v^T e_h + e_v^T x_h) / B`` and the bias of every pair present along its error's
+        column mean, by ``lr``, ``mom`` and the RBM's weight decay.  No draws, no host sync."""
+        if up is None and down is None:
+            raise N.EngineError("backprop_step: needs an up pair, a down pair or both")
+        if (want_v and up is None) or (want_h and down is None):
+            raise N.EngineError("backprop_step: want_v needs the up pair, want_h the down pair")
+        if not apply and not want_v and not want_h:
+            raise N.EngineError("backprop_step: apply=False without want_v or want_h leaves nothing to do")
+        d = self._desc(rbm, bool(apply))
+        pairs = []
+        for nm, pair, n_x, n_e in (("up", up, d.V, d.H), ("down", down, d.H, d.V)):
+            if pair is None:
+                pairs.append((None, None))
+                continue
+            x, e = _f32c(pair[0]), _f32c(pair[1])
+            if x.dim() != 2 or e.dim() != 2 or x.size(1) != n_x or e.size(1) != n_e or x.size(0) != e.size(0) or x.device != e.device:
+                raise N.EngineError(f"backprop_step: the {nm} pair needs x [B, {n_x}] and e [B, {n_e}] on one device")
+            pairs.append((x, e))
+        first = pairs[0][0] if pairs[0][0] is not None else pairs[1][0]
+        B, dev = first.size(0), first.device
+        if any(x is not None and (x.size(0) != B or x.device != dev) for x, _ in pairs):
+            raise N.EngineError("backprop_step: the two pairs need the same rows on one device")
+        o = self._opts(rbm, lr, mom, 0) if apply else None
+        err_v = torch.empty(B, d.V, device=dev) if want_v else None
+        err_h = torch.empty(B, d.H, device=dev) if want_h else None
+        ld = lambda t: 0 if t is None else t.stride(0)
+        (xv, eh), (xh, ev) = pairs
+        self._call("imdbn_rbm_backprop_step", C.byref(d), _ptr(xv), ld(xv), _ptr(eh), ld(eh), _ptr(xh), ld(xh), _ptr(ev), ld(ev), B, _ref(o),
+                   _ptr(err_v), ld(err_v), _ptr(err_h), ld(err_h), *self._ws_tail(dev, d.V, d.H, max(B, 1)))
+        return err_v, err_h
+
+    def autoencoder_step(self, rec_layers, gen_layers, data, epoch_scalars, monitor: bool = True):
+        """One backprop step on the reconstruction cross-entropy of the stack unrolled into an encoder and a decoder (Hinton &
+        Salakhutdinov 2006): ``rec_layers`` the L RBMs bottom first (the encoder; the top RBM is tied: its weights also open the
+        decoder), ``gen_layers`` the L - 1 generative twins (the rest of the decoder).  On one stream, no host sync, no draws:
+        ``a_0 = data``, ``a_l = forward`` of layer l; ``d_L = a_L`` and ``d_{l-1}`` the deterministic ``backward`` through the top
+        RBM (l = L) or twin l - 1 -- ``d_0`` is ``iDBN.reconstruct(data)``, bit for bit; ``e_0 = data - d_0``.  Then down the
+        decoder ``backprop_step(gen[l-1], down=(d_l, e_{l-1}))`` for l = 1 .. L - 1, the top RBM with both pairs
+        ``up=(a_{L-1}, f_L), down=(a_L, e_{L-1})`` -- ``f_L`` from an evaluate-only call on the same parameters -- and
+        ``backprop_step(rec[l-1], up=(a_{l-1}, f_l))`` for l = L - 1 .. 1.  ``epoch_scalars``: ``(lr, mom)`` per layer; twin l uses
+        entry l.  Returns ``{"recon": d_0, "code": a_L, "xent", "mse"}``: ``xent`` is minus the batch mean of the rows'
+        ``sum_j data_j z_j - softplus(z_j)`` on the decoder's output logits ``z`` in float64, ``mse`` the mean of ``e_0^2``; both
+        0-d device scalars on the parameters on entry, None with ``monitor=False`` (nothing is then computed for them)."""
+        from . import dp
+        if dp.active():
+            raise NotImplementedError("autoencoder_step has no data-parallel split")
+        L = len(rec_layers)
+        if L < 1 or len(gen_layers) != L - 1 or len(epoch_scalars) != L:
+            raise N.EngineError(f"autoencoder_step: {L} layers need {max(L - 1, 0)} generative twins and {L} (lr, mom) pairs")
+        top = rec_layers[-1]
+        x = _f32c(data)
+        a = [x]
+        for rbm in rec_layers:
+            cur = a[-1] if len(a) > 1 else data             # the caller's tensor carries the 0/1 tag, its fp32 form may be a copy
+            out = self.forward(rbm, cur, data_binary=self.binary_hint(cur)) if hasattr(self, "forward") else self.prop_up(rbm, cur)
+            out._imdbn_binary = False
+            a.append(out)
+        down = list(gen_layers) + [top]                     # the layer a top-down pass goes through below level l + 1
+        dec = [None] * L + [a[L]]
+        for l in range(L, 0, -1):
+            dec[l - 1] = self.prop_down(down[l - 1], dec[l])
+        xent = mse = None
+        if monitor:                                         # before any update: the output layer's parameters on entry
+            xent = -self.delta_step(down[0], "down", dec[1], x, apply=False).mean()
+        e = x - dec[0]
+        if monitor:
+            mse = (e * e).mean()
+        for l in range(1, L):
+            e = self.backprop_step(gen_layers[l - 1], down=(dec[l], e), lr=epoch_scalars[l - 1][0], mom=epoch_scalars[l - 1][1], want_h=True)[1]
+        lr, mom = epoch_scalars[L - 1]
+        f = self.backprop_step(top, down=(a[L], e), apply=False, want_h=True)[1]
+        f = self.backprop_step(top, up=(a[L - 1], f), down=(a[L], e), lr=lr, mom=mom, want_v=L > 1)[0]
+        for l in range(L - 1, 0, -1):
+            f = self.backprop_step(rec_layers[l - 1], up=(a[l - 1], f), lr=epoch_scalars[l - 1][0], mom=epoch_scalars[l - 1][1], want_v=l > 1)[0]
+        return {"recon": dec[0], "code": a[L], "xent": xent, "mse": mse}
+
     # ---- RCCL through the C ABI (a binder without torch.distributed; the classes use torch.distributed) ---------------
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(128)

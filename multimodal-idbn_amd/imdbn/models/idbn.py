@@ -261,6 +261,47 @@ class iDBN:
                 if self.wandb_run:
                     self.wandb_run.log({"idbn/wake_nll": w, "idbn/sleep_nll": s, "idbn/top_loss": t, "epoch": epoch})
 
+    # ---- backprop fine-tuning of the unrolled stack as a deep autoencoder (extension; Hinton & Salakhutdinov 2006) ----
+    @torch.no_grad()
+    def autoencoder_step(self, data: torch.Tensor, epoch: int, max_epochs: int, lr_scale: float = 1.0, monitor: bool = True):
+        """One backprop step on one mini-batch (unties the model on first use): the engine's ``autoencoder_step`` -- the stack
+        unrolled into an encoder (``layers``) and a decoder (the top RBM's own weights, then the generative twins), the gradient
+        of the reconstruction cross-entropy of ``reconstruct(data)`` sent back through every sigmoid layer.  Every layer uses its
+        own RBM's learning-rate and momentum schedule (``lr`` times ``lr_scale``) and weight decay.  Returns ``{"xent", "mse"}``
+        as 0-d device scalars -- the batch mean of the rows' cross-entropy between ``data`` and its reconstruction, and the mean
+        squared reconstruction error, both before this call's update -- or None with ``monitor=False`` (nothing is then evaluated
+        for them).  No host sync; no data-parallel split."""
+        from imdbn import engine as _E
+        if _E.dp.active():
+            raise NotImplementedError("autoencoder_step has no data-parallel split")
+        gen = self.untie()
+        x = rows_on_device(data, self.device)
+        scalars = []
+        for r in self.layers:
+            lr, mom = r._lr_mom(epoch)
+            scalars.append((lr * float(lr_scale), mom))
+        out = self.layers[-1]._eng().autoencoder_step(self.layers, gen, x, scalars, monitor=monitor)
+        return {k: out[k] for k in ("xent", "mse")} if monitor else None
+
+    def finetune_autoencoder(self, epochs: int, lr_scale: float = 0.1, log_every: int = 0):
+        """``epochs`` passes of ``autoencoder_step`` over ``self.dataloader`` (explicit only: ``train`` never calls it and no
+        ``params`` key turns it on).  ``log_every`` > 0: the monitors of every ``log_every``-th epoch are evaluated, fetched in ONE
+        host read after the epoch's last batch and appended to ``self.autoencoder_history`` as ``(epoch, xent, mse)`` batch means;
+        otherwise nothing is evaluated and the host never reads."""
+        self.autoencoder_history = getattr(self, "autoencoder_history", [])
+        for epoch in range(int(epochs)):
+            watch = int(log_every) > 0 and epoch % int(log_every) == 0
+            mons = []
+            for item in batches(self.dataloader):
+                m = self.autoencoder_step(rows_on_device(item[0], self.device), epoch, epochs, lr_scale=lr_scale, monitor=watch)
+                if watch:
+                    mons.append(torch.stack([m["xent"].double(), m["mse"].double()]))
+            if mons:
+                x, s = torch.stack(mons).mean(0).cpu().tolist()
+                self.autoencoder_history.append((epoch, x, s))
+                if self.wandb_run:
+                    self.wandb_run.log({"idbn/autoencoder_xent": x, "idbn/autoencoder_mse": s, "epoch": epoch})
+
     @torch.no_grad()
     def log_likelihood_bound(self, v: torch.Tensor, log_z_top, **kw) -> torch.Tensor:
         """Variational lower bound on log p(v) of the whole stack per row, float64 ``[B]``
