@@ -198,6 +198,13 @@ int    imdbn_debug_last_route(int route[5]);
  * (0 for the generic kernel).  Host code only; the routes are NOT part of the ABI */
 enum { IMDBN_UPDATE_GENERIC = 0, IMDBN_UPDATE_PLANES = 1, IMDBN_UPDATE_BIN = 2, IMDBN_UPDATE_RANKS = 3 };
 int    imdbn_debug_last_update(int rec[2]);
+/* test aid, likewise for the chains (imdbn_rbm_chain*, the positive phase of imdbn_rbm_clamped_*): rec[0] = how the last chain of the
+ * CALLING THREAD ran (IMDBN_CHAIN_*: one launch per half step, the row-parallel chain kernel, or that kernel running both chains of
+ * a pair in one launch; -1 until the thread has run a chain), rec[1] = batch rows per block of the kernel launch, rec[2] = its
+ * blocks (both 0 for IMDBN_CHAIN_PER_LAUNCH), rec[3] = the records of chain 0 (its steps plus a traced baseline).  A pair that does
+ * not run as one launch reports its second chain's run.  Host code only; the routes are NOT part of the ABI */
+enum { IMDBN_CHAIN_PER_LAUNCH = 0, IMDBN_CHAIN_KERNEL = 1, IMDBN_CHAIN_KERNEL_PAIR = 2 };
+int    imdbn_debug_last_chain(int rec[4]);
 
 /* *dev_offset += n on `stream` (see imdbn_rng.dev_offset).  Every engine call is a plain sequence of kernel launches on the caller's
  * stream -- no host synchronisation, no allocation, no memcpy -- so it can be recorded with hipStreamBeginCapture. */

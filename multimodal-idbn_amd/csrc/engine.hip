@@ -264,6 +264,12 @@ int cd_phases(Ctx& c, const float* data, int64_t ldd, const imdbn_cd_opts* o, co
 }
 
 // ---- row-parallel chain kernel (kernels_chain.hpp) -------------------------------------------
+// testing aid: how the last chain call of this THREAD ran (imdbn_debug_last_chain; the codes are IMDBN_CHAIN_* of the header): the
+// route, rows per block and blocks of the kernel launch, records of chain 0.  Written where the decision / the launch is made
+struct ChainRun { int route = -1, rows = 0, blocks = 0, recs = 0; };
+thread_local ChainRun t_chain;
+inline void ran_chain(int route, int rows, int blocks, int recs) { t_chain.route = route; t_chain.rows = rows; t_chain.blocks = blocks; t_chain.recs = recs; }
+
 bool chain_kernel_ok(const Ctx& c, int n_steps) {
     const Layout& L = c.L;
     if (tune().no_chain_kernel || !L.k4_planes || n_steps < 2 || n_steps > CHAIN_MAX_STEPS) return false;
@@ -383,6 +389,7 @@ int launch_k4(Ctx& c, const ChainSpec& s0, int off0, const ChainSpec* s1, int of
     if (c.nw == 3) hipLaunchKernelGGL(k4_chain<2>, grid, dim3(64 * K4_WAVES), 0, c.s, a);      // PARITY: fp16 hi + lo terms
     else           hipLaunchKernelGGL(k4_chain<1>, grid, dim3(64 * K4_WAVES), 0, c.s, a);
     HIPCHK(hipGetLastError());
+    ran_chain(s1 ? IMDBN_CHAIN_KERNEL_PAIR : IMDBN_CHAIN_KERNEL, a.rows, (int)grid.x, s0.n_recs());
     return 0;
 }
 
@@ -405,6 +412,7 @@ int run_chain(Ctx& c, const ChainSpec& s, bool want_stats) {
         c.hid_bits_ok = false;
         return 0;
     }
+    ran_chain(IMDBN_CHAIN_PER_LAUNCH, 0, 0, s.n_recs());
     const int s_base = s.base();
     // the traces of the per-launch path: the window of the step's fp32 v_prob (f_vp), of its fp32 h_prob (f_h)
     auto copy_window = [&](const imdbn_chain_trace* tr, const float* src, int ld, int slot) -> int {
@@ -484,7 +492,9 @@ int run_chain_pair(Ctx& c, const ChainSpec& sa, const ChainSpec& sb) {
         return 0;
     }
     CHK(run_chain(c, sa, false));
-    return run_chain(c, sb, false);
+    CHK(run_chain(c, sb, false));
+    t_chain.recs = sa.n_recs();      // the record describes the launch(es) of the LAST chain run, the record count chain 0
+    return 0;
 }
 
 hipStream_t S(imdbn_stream_t s) { return (hipStream_t)s; }
@@ -591,6 +601,12 @@ int imdbn_debug_last_route(int route[5]) {
 int imdbn_debug_last_update(int rec[2]) {
     if (!rec) return fail(IMDBN_E_INVALID, "imdbn_debug_last_update: null buffer");
     rec[0] = t_update.kernel; rec[1] = t_update.tpb;
+    return 0;
+}
+
+int imdbn_debug_last_chain(int rec[4]) {
+    if (!rec) return fail(IMDBN_E_INVALID, "imdbn_debug_last_chain: null buffer");
+    rec[0] = t_chain.route; rec[1] = t_chain.rows; rec[2] = t_chain.blocks; rec[3] = t_chain.recs;
     return 0;
 }
 

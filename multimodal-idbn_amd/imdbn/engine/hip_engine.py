@@ -136,6 +136,14 @@ class HipEngine:
                 "down": N.ROUTE_DOWN[r[2]] if r[2] >= 0 else None, "down_epilogue": "general" if r[3] else "lean",
                 "finish_groups": bool(r[4])}
 
+    def last_chain(self) -> dict:
+        """Test aid: how the last chain call of this thread ran (imdbn_debug_last_chain): ``{"route": "per_launch" | "kernel" |
+        "kernel_pair" or None, "rows": batch rows per block, "blocks": blocks of the launch (both 0 per launch), "recs": records of
+        chain 0, a traced baseline included}``; the names are ``native.CHAIN_ROUTE``."""
+        r = (C.c_int * 4)()
+        self._call("imdbn_debug_last_chain", r)
+        return {"route": N.CHAIN_ROUTE[r[0]] if r[0] >= 0 else None, "rows": r[1], "blocks": r[2], "recs": r[3]}
+
     def _workspace(self, dev, V, H, B):
         # one workspace per (device, shape, STREAM): two same-shape RBMs driven from two streams must not share scratch
         key = (dev, V, H, B, torch.cuda.current_stream(dev).cuda_stream if torch.device(dev).type == "cuda" else 0)

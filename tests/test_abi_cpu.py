@@ -66,6 +66,28 @@ def test_last_route_record_starts_empty_and_names_every_family():
     assert got[-1] == {"up": None, "up_epilogue": "lean", "down": None, "down_epilogue": "lean", "finish_groups": False}
 
 
+def test_last_chain_record_starts_empty_and_names_every_route():
+    """imdbn_debug_last_chain (host code, a testing aid): a thread that has run no chain reports no route; the names the binding gives
+    the codes follow the header's IMDBN_CHAIN_* enum."""
+    import ctypes as C
+    import threading
+    lib = native.lib()
+    assert lib.imdbn_debug_last_chain(None) != 0
+    got = []
+
+    def fresh_thread():
+        r = (C.c_int * 4)(7, 7, 7, 7)
+        got.append((lib.imdbn_debug_last_chain(r), list(r)))
+    t = threading.Thread(target=fresh_thread); t.start(); t.join()
+    assert got == [(0, [-1, 0, 0, 0])]
+    src = open(os.path.join(ROOT, "include", "imdbn_engine.h")).read()
+    codes = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"IMDBN_CHAIN_([A-Z0-9_]+) = (\d+)", src)}
+    assert codes == {name: i for i, name in enumerate(native.CHAIN_ROUTE)} and len(codes) == 3
+    from imdbn.engine.hip_engine import HipEngine
+    t = threading.Thread(target=lambda: got.append(HipEngine().last_chain())); t.start(); t.join()
+    assert got[-1] == {"route": None, "rows": 0, "blocks": 0, "recs": 0}
+
+
 def test_options_handle_is_separate_from_the_process_defaults():
     """imdbn_options: a per-caller copy of the knobs, bound to the calling thread with imdbn_use_options."""
     import ctypes as C
