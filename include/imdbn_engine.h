@@ -180,7 +180,8 @@ int    imdbn_profile_read(double* total_ms, int* launches);   /* synchronises th
  * propagation kernels record when the "dbg" option enables them; synchronises the device */
 int    imdbn_debug_stamps(long long* out, int n);
 /* test / tuning aid: byte offset of a named internal buffer inside the workspace of an (V, H, B) call ("vis_bits0/1", "hid_bits",
- * "vis_tr0/1", "hid_tr0/1", "cs_hpos/hneg/vpos/vneg", "flags", "partial", "vis_rm1"); the layout is NOT part of the ABI */
+ * "vis_tr0/1", "hid_tr0/1", "cs_hpos/hneg/vpos/vneg", "flags", "partial", "vis_rm1", and of the prefetch slots 1 / 2 "pf_tr1/2",
+ * "pf_bits1/2"); the layout is NOT part of the ABI */
 int    imdbn_debug_ws_offset(int V, int H, int B, const char* name, size_t* offset);
 /* test aid: which kernel family the last up (v -> h) and the last down (h -> v) propagation of the CALLING THREAD launched,
  * recorded by the launchers where they launch (host code only; the routes themselves are NOT part of the ABI).
@@ -205,6 +206,16 @@ int    imdbn_debug_last_update(int rec[2]);
  * not run as one launch reports its second chain's run.  Host code only; the routes are NOT part of the ABI */
 enum { IMDBN_CHAIN_PER_LAUNCH = 0, IMDBN_CHAIN_KERNEL = 1, IMDBN_CHAIN_KERNEL_PAIR = 2 };
 int    imdbn_debug_last_chain(int rec[4]);
+/* test aid, likewise for the CD pass (imdbn_rbm_cd_step / _cd_stats / _cd_factors / _cd_factors_wire, and the CD pass of the calls
+ * built on it), whose first launches imdbn_debug_last_route no longer shows at the end of the call: rec[0] = the up family of the
+ * positive-phase K1 of the last CD pass of the CALLING THREAD, rec[1] = the down family of its first K2, rec[2] = the up family of
+ * its last K1 (IMDBN_ROUTE_*; -1 until the thread has run a CD pass), rec[3] = where the next batch (imdbn_cd_opts.next_data) was
+ * prepared (IMDBN_CD_NEXT_*: not at all -- no hint, or the route ignores it --, by a prep_operand launch of its own, by extra blocks
+ * of the fused K2, by extra blocks of the negative-phase k1_stream), rec[4] = the prefetch slot the data were read from
+ * (imdbn_cd_opts.data_slot, 0 = none), rec[5] = 1 if that preparation decided the forms per 64-column item (a batch of unknown
+ * content).  Host code only; the routes are NOT part of the ABI */
+enum { IMDBN_CD_NEXT_NONE = 0, IMDBN_CD_NEXT_OWN_LAUNCH = 1, IMDBN_CD_NEXT_FUSED_K2 = 2, IMDBN_CD_NEXT_K1_STREAM = 3 };
+int    imdbn_debug_last_cd(int rec[6]);
 
 /* *dev_offset += n on `stream` (see imdbn_rng.dev_offset).  Every engine call is a plain sequence of kernel launches on the caller's
  * stream -- no host synchronisation, no allocation, no memcpy -- so it can be recorded with hipStreamBeginCapture. */

@@ -214,6 +214,12 @@ struct LabelSide {
     }
 };
 
+// testing aid: how the last CD pass of this THREAD ran (imdbn_debug_last_cd): the families of its positive-phase K1, its first K2 and
+// its last K1 as the launchers recorded them (t_route), where the next batch was prepared (IMDBN_CD_NEXT_*), the data slot consumed
+// and whether the preparation decided per item.  Written where the decision is made (cd_prologue) / behind the launch (cd_phases)
+struct CdRec { int pos_up = -1, first_down = -1, last_up = -1, next_on = 0, slot = 0, adaptive = 0; };
+thread_local CdRec t_cd;
+
 // rbm.py:199-209: positive phase, CD-k Gibbs, statistics left in the workspace operand buffers.
 int cd_phases(Ctx& c, const float* data, int64_t ldd, const imdbn_cd_opts* o, const PrepArgs* next = nullptr) {
     const Layout& L = c.L;
@@ -233,6 +239,8 @@ int cd_phases(Ctx& c, const float* data, int64_t ldd, const imdbn_cd_opts* o, co
         const int rc = prop(c, true, OpIn{L.vis_rm[0], c.nw == 1 ? 1 : 0, L.flags, L.vis_bits[0], data_operand_kind(o->data_binary)}, f);
         c.pos_phase = false;
         CHK(rc);
+        t_cd.pos_up = t_route.up;
+        if (next) t_cd.next_on = next_on_k1 ? IMDBN_CD_NEXT_K1_STREAM : IMDBN_CD_NEXT_FUSED_K2;
     }
     for (int it = 0; it < o->cd_k; ++it) {
         const bool last = (it == o->cd_k - 1);
@@ -250,6 +258,7 @@ int cd_phases(Ctx& c, const float* data, int64_t ldd, const imdbn_cd_opts* o, co
             f.loss_ref = data; f.ld_ref = ldd; f.loss_src = 1; f.loss_part = L.loss_part;
             if (vbits) f.op.bits = L.vis_bits[1];
             CHK(prop(c, false, OpIn{L.hid_rm, 1, nullptr}, f, (it == 0 && !next_on_k1) ? next : nullptr));
+            if (it == 0) t_cd.first_down = t_route.down;
         }
         {   // h_prob = up(v); h = 1[h_prob > U]  (the last draw is consumed but unused, rbm.py:208)
             FinishArgs f = new_finish();
@@ -258,6 +267,7 @@ int cd_phases(Ctx& c, const float* data, int64_t ldd, const imdbn_cd_opts* o, co
             f.op.tr = L.hid_tr[1]; f.op.tr_terms = c.ht; f.tr_src = 1; f.op.tr_negate = 1;
             f.colsum_part = L.cs_hneg; f.colsum_src = 1;
             CHK(prop(c, true, OpIn{L.vis_rm[1], 1, nullptr, vbits ? L.vis_bits[1] : nullptr, 1}, f, (it == 0 && next_on_k1) ? next : nullptr));
+            if (last) t_cd.last_up = t_route.up;
         }
     }
     return 0;
@@ -587,6 +597,8 @@ int imdbn_debug_ws_offset(int V, int H, int B, const char* name, size_t* offset)
     else if (!strcmp(name, "cs_hneg")) p = L.cs_hneg; else if (!strcmp(name, "cs_vpos")) p = L.cs_vpos;
     else if (!strcmp(name, "cs_vneg")) p = L.cs_vneg; else if (!strcmp(name, "flags")) p = L.flags;
     else if (!strcmp(name, "partial")) p = L.partial; else if (!strcmp(name, "vis_rm1")) p = L.vis_rm[1];
+    else if (!strcmp(name, "pf_tr1")) p = L.pf_tr[0]; else if (!strcmp(name, "pf_tr2")) p = L.pf_tr[1];
+    else if (!strcmp(name, "pf_bits1")) p = L.pf_bits[0]; else if (!strcmp(name, "pf_bits2")) p = L.pf_bits[1];
     else return fail(IMDBN_E_INVALID, "debug_ws_offset: unknown buffer %s", name);
     *offset = (size_t)((const char*)p - fake);
     return 0;
@@ -601,6 +613,12 @@ int imdbn_debug_last_route(int route[5]) {
 int imdbn_debug_last_update(int rec[2]) {
     if (!rec) return fail(IMDBN_E_INVALID, "imdbn_debug_last_update: null buffer");
     rec[0] = t_update.kernel; rec[1] = t_update.tpb;
+    return 0;
+}
+
+int imdbn_debug_last_cd(int rec[6]) {
+    if (!rec) return fail(IMDBN_E_INVALID, "imdbn_debug_last_cd: null buffer");
+    rec[0] = t_cd.pos_up; rec[1] = t_cd.first_down; rec[2] = t_cd.last_up; rec[3] = t_cd.next_on; rec[4] = t_cd.slot; rec[5] = t_cd.adaptive;
     return 0;
 }
 
@@ -969,6 +987,7 @@ static int cd_prologue(Ctx& c, const imdbn_cd_opts* o, PrepArgs& pn, bool& rides
         return fail(IMDBN_E_INVALID, "cd: bad prefetch slots (data %d, next %d)", o->data_slot, o->next_slot);
     const bool has_next = o->next_data && c.r.prefetch;
     memset(&pn, 0, sizeof(pn));
+    t_cd = CdRec{};
     if (has_next) {            // target buffers are taken before the data slot is swapped in
         const Layout& L = c.L;
         const int t = o->next_slot - 1;
@@ -993,7 +1012,9 @@ static int cd_prologue(Ctx& c, const imdbn_cd_opts* o, PrepArgs& pn, bool& rides
         pn.zero = nullptr; pn.n_zero = 0;
         hipLaunchKernelGGL(prep_operand, dim3(cdiv(std::max(pn.N, pn.op.ldrm), 64), c.L.P), dim3(256), 0, c.s, pn);
         HIPCHK(hipGetLastError());
+        t_cd.next_on = IMDBN_CD_NEXT_OWN_LAUNCH;
     }
+    t_cd.slot = o->data_slot; t_cd.adaptive = pn.adaptive;
     if (o->data_slot) { use_slot(c.L, o->data_slot); c.data_prepped = true; c.cnt_ok = true; c.fix_slot = o->data_binary == IMDBN_DATA_UNKNOWN; }
     return 0;
 }
@@ -1136,6 +1157,7 @@ int imdbn_rbm_cd_factors(const imdbn_rbm_desc* d, const float* data, int64_t ldd
     if (!factor_mode_ok(d, B, false)) return fail(IMDBN_E_UNSUPPORTED, "cd_factors: needs <= 64 rows per rank, 16-B aligned weight rows, no softmax groups");
     Ctx c(d, rng, S(stream));
     CHK(setup(c, B, ws, ws_bytes));
+    t_cd = CdRec{};      // no prologue: nothing prepared, no slot
     CHK(cd_phases(c, data, ldd, o));
     return c.rng.finish();
 }
@@ -1773,7 +1795,7 @@ int imdbn_rbm_centered_step(const imdbn_rbm_desc* d, const float* data, int64_t 
     Ctx c(d, rng, S(stream));
     CHK(setup(c, B, ws, ws_bytes));
     if (particles) CHK(pcd_phases(c, data, ldd, particles, ldp, o, loss_out != nullptr));
-    else CHK(cd_phases(c, data, ldd, o));
+    else { t_cd = CdRec{}; CHK(cd_phases(c, data, ldd, o)); }
     CHK(c.rng.finish());
     CHK(launch_assoc(c, 1, o, c.nw == 1 ? 1 : 0, c.L.flags, 1, 1.0f, scratch));
     const Layout& L = c.L;

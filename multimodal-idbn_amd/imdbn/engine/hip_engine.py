@@ -144,6 +144,16 @@ class HipEngine:
         self._call("imdbn_debug_last_chain", r)
         return {"route": N.CHAIN_ROUTE[r[0]] if r[0] >= 0 else None, "rows": r[1], "blocks": r[2], "recs": r[3]}
 
+    def last_cd(self) -> dict:
+        """Test aid: how the last CD pass of this thread ran (imdbn_debug_last_cd): ``{"pos_up": up family of the positive-phase K1,
+        "first_down": down family of the first K2, "last_up": up family of the last K1 (names as in ``last_route``, None before the
+        first pass), "next": where the next batch was prepared (``native.CD_NEXT``), "slot": prefetch slot the data were read from
+        (0: none), "adaptive": the preparation decided per 64-column item}``."""
+        r = (C.c_int * 6)()
+        self._call("imdbn_debug_last_cd", r)
+        return {"pos_up": N.ROUTE_UP[r[0]] if r[0] >= 0 else None, "first_down": N.ROUTE_DOWN[r[1]] if r[1] >= 0 else None,
+                "last_up": N.ROUTE_UP[r[2]] if r[2] >= 0 else None, "next": N.CD_NEXT[r[3]], "slot": r[4], "adaptive": bool(r[5])}
+
     def _workspace(self, dev, V, H, B):
         # one workspace per (device, shape, STREAM): two same-shape RBMs driven from two streams must not share scratch
         key = (dev, V, H, B, torch.cuda.current_stream(dev).cuda_stream if torch.device(dev).type == "cuda" else 0)

@@ -18,6 +18,7 @@ DELTA_UP, DELTA_DOWN = 0, 1                           # imdbn_rbm_delta_step dir
 DATA_UNKNOWN, DATA_BINARY, DATA_REAL = 0, 1, 2      # imdbn_cd_opts.data_binary / next_binary (IMDBN_DATA_*)
 ROUTE_UP = ("fused", "stream_bits", "stream_real", "partial4", "partial")                    # imdbn_debug_last_route (IMDBN_ROUTE_UP_*)
 CHAIN_ROUTE = ("per_launch", "kernel", "kernel_pair")                                       # imdbn_debug_last_chain (IMDBN_CHAIN_*)
+CD_NEXT = ("none", "own_launch", "fused_k2", "k1_stream")                                    # imdbn_debug_last_cd (IMDBN_CD_NEXT_*)
 ROUTE_DOWN = ("k2_stream", "down_fused", "down_chunks2", "down_chunks4", "down_tiled")        # ... (IMDBN_ROUTE_DOWN_*)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -105,6 +106,7 @@ SIGNATURES = {
     "imdbn_debug_last_route": (_INT, [C.POINTER(_INT)]),
     "imdbn_debug_last_update": (_INT, [C.POINTER(_INT)]),
     "imdbn_debug_last_chain": (_INT, [C.POINTER(_INT)]),
+    "imdbn_debug_last_cd": (_INT, [C.POINTER(_INT)]),
     "imdbn_rng_advance": (_INT, [_P, C.c_uint64, _P]),
     "imdbn_rbm_prop_up": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _F, C.POINTER(Rng), _P, _I64, _P, _I64, _P, _SZ, _P]),
     "imdbn_rbm_forward": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _INT, _P, _I64, _P, _SZ, _P]),

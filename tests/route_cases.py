@@ -136,7 +136,7 @@ def up_cases():
                             sample=sample, operand=kind, opts=opts, groups=(),
                             route={"up": route, "up_epilogue": _lean(route, T == 1.0, not sample)}))
     # the bit plane of a batch the caller asserts to be 0/1 (forward(data_binary=True), T = 1): k1_stream's lean bit-plane instantiation.
-    # Its general instantiation runs only inside the CD pass, which test_philox_cd_step_matches_oracle pins.
+    # Its general instantiation runs only inside the CD pass, which test_cd_routes_gpu.py pins on every route (cd_cases.py).
     for B in (33, 130):
         out.append(dict(kind="forward", id=f"forward-stream_bits-1040x36-B{B}", V=1040, H=36, B=B, T=1.0, sample=False, operand="binary",
                         opts={}, groups=(), route={"up": "stream_bits", "up_epilogue": "lean"}))

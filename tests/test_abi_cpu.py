@@ -88,6 +88,28 @@ def test_last_chain_record_starts_empty_and_names_every_route():
     assert got[-1] == {"route": None, "rows": 0, "blocks": 0, "recs": 0}
 
 
+def test_last_cd_record_starts_empty_and_names_every_carrier():
+    """imdbn_debug_last_cd (host code, a testing aid): a thread that has run no CD pass reports no family, no preparation and no slot;
+    the names the binding gives the carriers follow the header's IMDBN_CD_NEXT_* enum."""
+    import ctypes as C
+    import threading
+    lib = native.lib()
+    assert lib.imdbn_debug_last_cd(None) != 0
+    got = []
+
+    def fresh_thread():
+        r = (C.c_int * 6)(7, 7, 7, 7, 7, 7)
+        got.append((lib.imdbn_debug_last_cd(r), list(r)))
+    t = threading.Thread(target=fresh_thread); t.start(); t.join()
+    assert got == [(0, [-1, -1, -1, 0, 0, 0])]
+    src = open(os.path.join(ROOT, "include", "imdbn_engine.h")).read()
+    codes = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"IMDBN_CD_NEXT_([A-Z0-9_]+) = (\d+)", src)}
+    assert codes == {name: i for i, name in enumerate(native.CD_NEXT)} and len(codes) == 4
+    from imdbn.engine.hip_engine import HipEngine
+    t = threading.Thread(target=lambda: got.append(HipEngine().last_cd())); t.start(); t.join()
+    assert got[-1] == {"pos_up": None, "first_down": None, "last_up": None, "next": "none", "slot": 0, "adaptive": False}
+
+
 def test_options_handle_is_separate_from_the_process_defaults():
     """imdbn_options: a per-caller copy of the knobs, bound to the calling thread with imdbn_use_options."""
     import ctypes as C
