@@ -713,17 +713,25 @@ __global__ __launch_bounds__(256) void assoc_update(const AssocArgs a) {
 //     shaped for it: a wave owns 32(v) x 128(h) as FOUR INTERLEAVED 32x32 MFMA tiles
 //     (column of tile t, lane r = h0 + 4r + t), i.e. one float4 per lane per accumulator row ->
 //     512-B contiguous row segments per half-wave (measured 1.3-1.5x the dword shape, tools/membench).
-//     All 32 float4 loads (W, W_m) are issued at kernel entry and land under the staging + MFMAs.
+//     The 32 float4 loads (W, W_m) of a tile are issued a tile ahead and land under the MFMAs.
 //   * The operands are the pre-split transposed bf16 planes written by finish/prep
 //     (tr[t][feature][Bp], 8 batch rows = 16 B).  K = batch is tiny (64 per chunk), so a block copies
-//     the planes of its 128 hidden and 128 visible features into LDS with plain coalesced 16-B
-//     copies; every fragment is then ONE ds_read_b128 with no VALU work in the MFMA loop.  LDS rows
-//     are padded to 144 B and hidden rows are stored permuted (feature 4r+t at row t*32+r) so that
-//     consecutive lanes read consecutive rows: (9*row + chunk) mod 16 is a bijection -> conflict-free.
+//     the planes of its 128 hidden features and of each tile's 128 visible features into LDS by
+//     LDS-DMA (k3_dma16: no staging registers); every fragment is then ONE ds_read_b128 with no VALU
+//     work in the MFMA loop.
+//   * LDS, 160 KB static (all of a CU's): 6 hidden planes of 16 KB (positive terms 0..2, negated
+//     negative terms 3..5; k3_dma_hidden), then per wave 4 slices of 4 KB (32 visible rows of one plane;
+//     k3_dma_slice).  A row is the 128 B of one batch chunk, unpadded; its 16-B chunk c sits at
+//     position c ^ ((row >> 1) & 7) (k3_swz), so the 16 consecutive rows a ds_read_b128 phase reads
+//     of one chunk cover all 64 banks.  Hidden rows are permuted (feature 4r+t at row t*32+r): lane r
+//     of a B fragment owns output columns 4r..4r+3, the float4 of the weight tile.
 //   * History (profiles/r01_*): fragment loads straight from global were L2-latency bound (98 us);
 //     an fp32-MFMA variant was matrix-pipe bound (91 us); fp32 in LDS + in-register splitting was
 //     VALU bound at one wave per SIMD (75 us).
-// grid = (ceil(H/128), ceil(V/128)), block = 256 (wave w: rows v0+32w..+31), 144 KB dynamic LDS.
+// grid = (ceil(H/128), ceil(ceil(V/128) / tiles_per_block) + bias_rows), block = 256 (wave w: rows v0+32w..+31).
+// The four bodies below (k3_body, k3_body_ranks, k3_body_ranks_acc, k3_body_bin) differ ONLY in their VMEM schedule --
+// the order of LDS-DMA, weight prefetch, waits, barriers and MFMAs; the addressing, the weight-row load and the
+// epilogue are the helpers k3_wave .. k3_apply.
 // ------------------------------------------------------------------------------------------
 constexpr int K3_ROWB = 128;                 // LDS row: 64 bf16 (one batch chunk), unpadded; 16-B chunk c of row r sits at
                                              // position c ^ ((r >> 1) & 7): 16 consecutive rows x one chunk = 64 distinct banks
@@ -752,34 +760,6 @@ struct AssocPlanesArgs {
 };
 
 __device__ __forceinline__ int k3_swz(int row, int c) { return row * K3_ROWB + ((c ^ ((row >> 1) & 7)) << 4); }
-
-// copy NPL hidden planes of 128 features x 64 batch rows into LDS (whole block, once).  Feature 4r+t goes to
-// row t*32+r so that lane r of an MFMA B fragment owns output columns 4r..4r+3 (float4 weight accesses).
-// Per plane a thread moves 4 of the 1024 16-B chunks; all loads are issued before the first LDS write.
-template <int NPL>
-__device__ __forceinline__ void k3_stage(char* dst, const bf16_t* src, int64_t term_stride, int f0, int F,
-                                         int Bp, bool negate) {
-    const int tid = threadIdx.x;
-    uint4 x[NPL][4];
-#pragma unroll
-    for (int pl = 0; pl < NPL; ++pl)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int i = tid + 256 * q, row = i >> 3, c = i & 7;
-            x[pl][q] = *reinterpret_cast<const uint4*>(src + pl * term_stride + (int64_t)min(f0 + row, F - 1) * Bp + 8 * c);
-        }
-#pragma unroll
-    for (int pl = 0; pl < NPL; ++pl)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int i = tid + 256 * q, row = i >> 3, c = i & 7;
-            uint4 v = x[pl][q];
-            if (negate) { v.x ^= 0x80008000u; v.y ^= 0x80008000u; v.z ^= 0x80008000u; v.w ^= 0x80008000u; }
-            const int lrow = (row & 3) * 32 + (row >> 2);
-            *reinterpret_cast<uint4*>(dst + pl * K3_PLANE + k3_swz(lrow, c)) = v;
-        }
-    __builtin_amdgcn_sched_barrier(0);     // keep the batches apart: at most NPL*4 staging registers live at once
-}
 
 // gfx950 direct global -> LDS load: lane i's 16 bytes land at LDS[lds_off + 16*i] (checked on hardware:
 // tools/ldsdma_test.hip).  No destination registers, no ds_write.  Written as asm because the builtin form is a
@@ -811,6 +791,140 @@ __device__ __forceinline__ void k3_mfma_wave(f32x16 (&acc)[4], const char* sH, c
     }
 }
 
+__device__ __forceinline__ void k3_zero(f32x16 (&acc)[4]) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+}
+
+// ---- what the four k3 bodies share: per-wave constants, the two LDS-DMA images, the weight-row load, the epilogue ----------
+struct K3Wave {
+    int w, l, r, kh;                 // wave of the block, lane, the lane's MFMA row / float4 column, its K half
+    int h0, tile0, n_my;             // first hidden column; first visible tile and number of visible tiles of this block
+    int colc; bool cok;              // the lane's float4 column clamped for loads; whether it exists (H % 4 == 0: a float4 is entirely inside or outside)
+    bool n_pow2; float inv_n;        // d / n == d * (1/n) exactly
+    const char *sHp, *sHn, *sV;      // positive / negated negative hidden planes; this wave's four slices
+    uint32_t sH_lds, sV_lds;         // the LDS addresses of sHp and sV, wave-uniform (k3_dma16's M0)
+};
+
+__device__ __forceinline__ K3Wave k3_wave(const AssocPlanesArgs& a, char* smem, int bx, int by, int tiles_per_block) {
+    K3Wave k;
+    const int tid = threadIdx.x;
+    k.w = tid >> 6; k.l = tid & 63; k.r = k.l & 31; k.kh = k.l >> 5;
+    k.h0 = bx * 128;
+    k.tile0 = by * tiles_per_block;
+    k.n_my = min(tiles_per_block, (a.V + 127) / 128 - k.tile0);
+    k.colc = min(k.h0 + 4 * k.r, a.H - 4);
+    k.cok = (k.h0 + 4 * k.r) < a.H;
+    k.n_pow2 = (__float_as_uint(a.n) & 0x7fffffu) == 0u;
+    k.inv_n = 1.0f / a.n;
+    k.sHp = smem;
+    k.sHn = smem + 3 * K3_PLANE;
+    k.sV = smem + K3_VIS0 + k.w * (4 * K3_SLICE);
+    k.sH_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)smem);
+    k.sV_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) const char*)k.sV);
+    return k;
+}
+
+// The block's 2 x HT hidden planes (pos, neg) x 16 KB straight into LDS (gfx950 LDS-DMA, no staging registers): 16
+// wave-instructions per plane dealt to the four waves, 8 HT per wave.  elem_off = what the caller adds to the source, in bf16
+// elements (the batch chunk a.b0, or a rank block's offset).  Plane 3*ph + tb; LDS chunk i' = 8*lrow + pos holds chunk
+// pos ^ ((lrow >> 1) & 7) of feature row 4*(lrow & 31) + (lrow >> 5) (lane r of a B fragment owns columns 4r..4r+3).
+// The negative-phase planes are stored negated by their producer (OperandOut::tr_negate).
+template <int HT>
+__device__ __forceinline__ void k3_dma_hidden(const AssocPlanesArgs& a, const K3Wave& k, int64_t elem_off) {
+#pragma unroll
+    for (int ph = 0; ph < 2; ++ph)
+#pragma unroll
+        for (int tb = 0; tb < HT; ++tb)
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) {
+                const int j = 4 * k.w + jj, i = 64 * j + k.l, lrow = i >> 3, pos = i & 7;
+                const int row = 4 * (lrow & 31) + (lrow >> 5), c = pos ^ ((lrow >> 1) & 7);
+                const bf16_t* src = (ph ? a.hneg : a.hpos) + elem_off + tb * a.hts + (int64_t)min(k.h0 + row, a.H - 1) * a.Bp + 8 * c;
+                k3_dma16(src, k.sH_lds + (3 * ph + tb) * K3_PLANE + j * 1024);
+            }
+}
+
+// visible plane `pl` of a tile: the nap positive terms first, then the negative terms
+__device__ __forceinline__ const bf16_t* k3_vis_plane(const AssocPlanesArgs& a, int nap, int pl) {
+    return pl < nap ? a.vpos + pl * a.vts : a.vneg + (pl - nap) * a.vts;
+}
+
+// This wave's 32 rows (v0 + 32w ..) of ONE visible plane -> its slice `slot`: four LDS-DMA ops.  Addressing only: which plane
+// goes to which slot, and when, is the caller's schedule.
+__device__ __forceinline__ void k3_dma_slice(const AssocPlanesArgs& a, const K3Wave& k, const bf16_t* src_plane, int64_t elem_off,
+                                             int v0, int slot) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int i = k.l + 64 * q, row = i >> 3, c = (i & 7) ^ ((row >> 1) & 7);      // source chunk for LDS position i
+        k3_dma16(src_plane + (int64_t)min(v0 + 32 * k.w + row, a.V - 1) * a.Bp + elem_off + 8 * c, k.sV_lds + slot * K3_SLICE + q * 1024);
+    }
+}
+
+// Rows [R0, R1) of the 16 MFMA rows of this wave's weight tile at v0 -> registers, interleaved: W into wo (LOAD_W) and W_m into
+// mo (LOAD_M); STATS: what a later statistics pass adds to, a.delta, into mo.  The prefetch of a non-existent next tile
+// (!valid) collapses onto one row, so that no conditional sits between the loads and the counted wait behind them.
+template <int R0, int R1, bool LOAD_W = true, bool LOAD_M = true, bool STATS = false>
+__device__ __forceinline__ void k3_load_rows(const AssocPlanesArgs& a, const K3Wave& k, float4 (&wo)[16], float4 (&mo)[16],
+                                             int v0, bool valid) {
+#pragma unroll
+    for (int reg = R0; reg < R1; ++reg) {
+        const int row = valid ? min(v0 + 32 * k.w + mfma_row(reg, k.l), a.V - 1) : k.tile0 * 128;
+        const int64_t idx = (int64_t)row * (STATS ? a.H : a.ldw) + k.colc;
+        if constexpr (LOAD_W) wo[reg] = *reinterpret_cast<const float4*>(a.W + idx);
+        if constexpr (LOAD_M) mo[reg] = *reinterpret_cast<const float4*>((STATS ? a.delta : a.Wm) + idx);
+    }
+}
+
+// The epilogue of this wave's tile at v0: acc = pos_assoc - neg_assoc.  MODE 0: the momentum update of rbm.py:212-213 on the
+// tile's weights (wc, mc), in the PASS form AssocPlanesArgs describes; MODE 1: the statistics to a.delta (later chunks add).
+// POW2: n is a power of two, the statistics are scaled by d * (1/n) instead of d / n (the same bits, no division sequence).
+template <int MODE, int PASS, bool POW2>
+__device__ __forceinline__ void k3_apply_rows(const AssocPlanesArgs& a, const K3Wave& k, int v0, const f32x16 (&acc)[4],
+                                              const float4 (&wc)[16], const float4 (&mc)[16]) {
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+        const int row = v0 + 32 * k.w + mfma_row(reg, k.l);
+        if (row < a.V && k.cok) {
+            const float4 d = make_float4(acc[0][reg], acc[1][reg], acc[2][reg], acc[3][reg]);
+            if constexpr (MODE == 0) {
+                const int64_t idx = (int64_t)row * a.ldw + k.h0 + 4 * k.r;
+                float4 w0 = make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (PASS != 2) w0 = wc[reg];                           // middle passes never load W
+                float4 m = mc[reg];
+                const float gx = POW2 ? d.x * k.inv_n : d.x / a.n, gy = POW2 ? d.y * k.inv_n : d.y / a.n;
+                const float gz = POW2 ? d.z * k.inv_n : d.z / a.n, gw = POW2 ? d.w * k.inv_n : d.w / a.n;
+                if constexpr (PASS <= 1) {                                       // single chunk, or the first of several
+                    m.x = m.x * a.mom; m.x = m.x + a.lr * (gx - a.wd * w0.x);        // rbm.py:212
+                    m.y = m.y * a.mom; m.y = m.y + a.lr * (gy - a.wd * w0.y);
+                    m.z = m.z * a.mom; m.z = m.z + a.lr * (gz - a.wd * w0.z);
+                    m.w = m.w * a.mom; m.w = m.w + a.lr * (gw - a.wd * w0.w);
+                } else {                                                         // later chunks: the statistics term only
+                    m.x = m.x + a.lr * gx; m.y = m.y + a.lr * gy; m.z = m.z + a.lr * gz; m.w = m.w + a.lr * gw;
+                }
+                *reinterpret_cast<float4*>(a.Wm + idx) = m;
+                if constexpr (PASS == 0 || PASS == 3)
+                    *reinterpret_cast<float4*>(a.W + idx) = make_float4(w0.x + m.x, w0.y + m.y, w0.z + m.z, w0.w + m.w);   // :213
+                // (non-temporal stores were tried here in round 2: 51.3 us against 49.4 event-timed -- the tail of this kernel is
+                //  not dirty lines lingering in L2.  Round 3: write-through (sc1) stores for the LAST tile of every block, so that
+                //  the launch ends with nothing dirty in the L2s: 46.7 us with and without, rocprofv3, same box)
+            } else {
+                float4 o = d;
+                if constexpr (PASS >= 2) { const float4 p = mc[reg]; o = make_float4(p.x + d.x, p.y + d.y, p.z + d.z, p.w + d.w); }
+                *reinterpret_cast<float4*>(a.delta + (int64_t)row * a.H + k.h0 + 4 * k.r) = o;
+            }
+        }
+    }
+}
+template <int MODE, int PASS>
+__device__ __forceinline__ void k3_apply(const AssocPlanesArgs& a, const K3Wave& k, int v0, const f32x16 (&acc)[4],
+                                         const float4 (&wc)[16], const float4 (&mc)[16]) {
+    if (k.n_pow2) k3_apply_rows<MODE, PASS, true>(a, k, v0, acc, wc, mc);
+    else          k3_apply_rows<MODE, PASS, false>(a, k, v0, acc, wc, mc);
+}
+
 // Streaming form: block (bx, by) owns hidden columns [128*bx, +128) and the `tiles_per_block` visible tiles
 // starting at tile by*tiles_per_block; wave w owns rows 32w..32w+31 of every tile.  The hidden planes (pos and
 // NEGATED neg, HT terms: 96 KB) are staged once and stay in LDS.  nap / nan = number of bf16 terms (1 or 3) of the
@@ -829,155 +943,67 @@ template <int MODE, int HT, int PASS>
 __device__ __forceinline__ void k3_body(const AssocPlanesArgs& a, char* smem, int bx, int by, int tiles_per_block,
                                         int nap, int nan_) {
     const int P = nap + nan_;                                       // 2, 4 or 6 planes per tile
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, r = l & 31, kh = l >> 5;
-    const int h0 = bx * 128;
-    const int tile0 = by * tiles_per_block;
-    const int n_vtiles = (a.V + 127) / 128;
-    const int n_my = min(tiles_per_block, n_vtiles - tile0);
-    const int colc = min(h0 + 4 * r, a.H - 4);
-    const bool cok = (h0 + 4 * r) < a.H;          // H % 4 == 0: a float4 is entirely inside or outside
-    const bool n_pow2 = (__float_as_uint(a.n) & 0x7fffffu) == 0u;      // d / n == d * (1/n) exactly
-    const float inv_n = 1.0f / a.n;
+    const K3Wave kw = k3_wave(a, smem, bx, by, tiles_per_block);
 
-    char* sHp = smem;
-    char* sHn = smem + 3 * K3_PLANE;
-    char* sV = smem + K3_VIS0 + w * (4 * K3_SLICE);                    // this wave's four slices
-    const uint32_t sV_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)sV);
-
-    // Register loads one load_tile issues (middle passes of a multi-chunk batch do not read W).  The hand-written
+    // One load_tile reads W and W_m (middle passes of a multi-chunk batch do not read W) or, for the statistics of a later
+    // batch chunk, delta: NPF register loads.  The hand-written
     // "planes / slices have landed" waits below are s_waitcnt vmcnt(NPF): vmcnt retires in order, the DMAs precede the
     // prefetch, so exactly the NPF prefetch loads may stay in flight.  The count must equal the loads the compiler really
     // emits: tests/test_isa_cpu.py checks it in the gfx950 ISA of every instantiation.
-    constexpr int NPF = MODE == 0 ? (PASS == 2 ? 16 : 32) : (PASS >= 2 ? 16 : 0);
+    constexpr bool LOAD_W = MODE == 0 && PASS != 2, LOAD_M = MODE == 0 || PASS >= 2;
+    constexpr int NPF = 16 * (LOAD_W + LOAD_M);
     auto load_tile = [&](float4 (&wo)[16], float4 (&mo)[16], int v0, bool valid) {
-        if constexpr (MODE == 0) {
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int row = valid ? min(v0 + 32 * w + mfma_row(reg, l), a.V - 1) : tile0 * 128;
-                const int64_t idx = (int64_t)row * a.ldw + colc;
-                if constexpr (PASS != 2) wo[reg] = *reinterpret_cast<const float4*>(a.W + idx);
-                mo[reg] = *reinterpret_cast<const float4*>(a.Wm + idx);
-            }
-        } else {
-            if constexpr (PASS >= 2) {                           // statistics of a later batch chunk: add to delta
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                    const int row = valid ? min(v0 + 32 * w + mfma_row(reg, l), a.V - 1) : tile0 * 128;
-                    mo[reg] = *reinterpret_cast<const float4*>(a.delta + (int64_t)row * a.H + colc);
-                }
-            }
-        }
+        k3_load_rows<0, 16, LOAD_W, LOAD_M, MODE != 0>(a, kw, wo, mo, v0, valid);
     };
-    // plane pl (positive terms first, then negative terms) of rows v0w..v0w+31 -> slice `slot`
-    auto dma_plane = [&](int slot, int pl, int v0w) {
-        pl = min(pl, P - 1);
-        const bf16_t* src = pl < nap ? a.vpos + pl * a.vts : a.vneg + (pl - nap) * a.vts;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int i = l + 64 * q, row = i >> 3, c = (i & 7) ^ ((row >> 1) & 7);      // source chunk for LDS position i
-            k3_dma16(src + (int64_t)min(v0w + row, a.V - 1) * a.Bp + a.b0 + 8 * c, sV_lds + slot * K3_SLICE + q * 1024);
-        }
-    };
+    // plane pl of the tile at v0 -> slice `slot`; unused slices are still loaded (clamped plane index, L2 hits)
+    auto dma_plane = [&](int slot, int pl, int v0) { k3_dma_slice(a, kw, k3_vis_plane(a, nap, min(pl, P - 1)), a.b0, v0, slot); };
 
     float4 wA[16], mA[16], wB[16], mB[16];
     const bool st = a.dbg != 0;
     const int sblk = by * gridDim.x + bx;
     stamp(st, sblk, 0);
-    // hidden planes, once per block: 2 x HT planes x 16 KB straight into LDS (gfx950 LDS-DMA, no staging registers),
-    // 16 wave-instructions per plane dealt to the four waves; THEN the first weight tile, so that "planes arrived"
-    // is a vmcnt(32) that leaves the weight loads in flight.  LDS chunk i' = 8*lrow + pos holds chunk
-    // pos ^ ((lrow >> 1) & 7) of feature row 4*(lrow & 31) + (lrow >> 5) (lane r of a B fragment owns columns 4r..4r+3).
-    // The negative-phase planes are stored negated by their producer (OperandOut::tr_negate).
-    const uint32_t sH_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)smem);
-#pragma unroll
-    for (int ph = 0; ph < 2; ++ph)
-#pragma unroll
-        for (int tb = 0; tb < HT; ++tb)
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-                const int j = 4 * w + jj, i = 64 * j + l, lrow = i >> 3, pos = i & 7;
-                const int row = 4 * (lrow & 31) + (lrow >> 5), c = pos ^ ((lrow >> 1) & 7);
-                const bf16_t* src = (ph ? a.hneg : a.hpos) + tb * a.hts + (int64_t)min(h0 + row, a.H - 1) * a.Bp + a.b0 + 8 * c;
-                k3_dma16(src, sH_lds + (3 * ph + tb) * K3_PLANE + j * 1024);
-            }
+    // hidden planes, once per block; THEN the first weight tile, so that "planes arrived" is a vmcnt(32) that leaves the
+    // weight loads in flight
+    k3_dma_hidden<HT>(a, kw, a.b0);
     __builtin_amdgcn_sched_barrier(0);
-    load_tile(wA, mA, tile0 * 128, true);
+    load_tile(wA, mA, kw.tile0 * 128, true);
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt vmcnt(%0)" :: "i"(MODE == 0 ? NPF : 0) : "memory");
     __syncthreads();                                                    // the ONLY block barrier
     stamp(st, sblk, 1);
 
     auto tile = [&](int it, float4 (&wc)[16], float4 (&mc)[16], float4 (&wn)[16], float4 (&mn)[16]) {
-        const int v0 = (tile0 + it) * 128;
+        const int v0 = (kw.tile0 + it) * 128;
         // the previous tile's MFMAs have consumed their fragments (ds_reads retire before the MFMA issues)
 #pragma unroll
-        for (int p = 0; p < 4; ++p) dma_plane(p, p, v0 + 32 * w);
+        for (int p = 0; p < 4; ++p) dma_plane(p, p, v0);
         __builtin_amdgcn_sched_barrier(0);
-        load_tile(wn, mn, v0 + 128, it + 1 < n_my);                      // next tile's weights: in flight for the whole tile
+        load_tile(wn, mn, v0 + 128, it + 1 < kw.n_my);                   // next tile's weights: in flight for the whole tile
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt vmcnt(%0)" :: "i"(MODE == 0 ? NPF : 0) : "memory");     // slices arrived; prefetch still in flight
         f32x16 acc[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+        k3_zero(acc);
 #pragma unroll
         for (int p = 0; p < 6; ++p) {
             if (p < P) {                                                  // block-uniform
                 if (p >= 4) {                                             // 3+3 terms only: planes 4, 5 reuse slices 0, 1
                     if (p == 4) {
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // fragments of planes 0, 1 are in registers
-                        dma_plane(0, 4, v0 + 32 * w);
-                        dma_plane(1, 5, v0 + 32 * w);
+                        dma_plane(0, 4, v0);
+                        dma_plane(1, 5, v0);
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     }
                 }
-                k3_mfma_wave<HT>(acc, p < nap ? sHp : sHn, sV + (p & 3) * K3_SLICE, r, kh);
+                k3_mfma_wave<HT>(acc, p < nap ? kw.sHp : kw.sHn, kw.sV + (p & 3) * K3_SLICE, kw.r, kw.kh);
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               // all fragment reads done before the next tile's DMA overwrites the slices
-        auto epilogue = [&](auto pow2_tag) {
-            constexpr bool POW2 = decltype(pow2_tag)::value;
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int row = v0 + 32 * w + mfma_row(reg, l);
-                if (row < a.V && cok) {
-                    const float4 d = make_float4(acc[0][reg], acc[1][reg], acc[2][reg], acc[3][reg]);   // pos_assoc - neg_assoc
-                    if constexpr (MODE == 0) {
-                        const int64_t idx = (int64_t)row * a.ldw + h0 + 4 * r;
-                        float4 w0 = make_float4(0.f, 0.f, 0.f, 0.f);
-                        if constexpr (PASS != 2) w0 = wc[reg];                           // middle passes never load W
-                        float4 m = mc[reg];
-                        const float gx = POW2 ? d.x * inv_n : d.x / a.n, gy = POW2 ? d.y * inv_n : d.y / a.n;
-                        const float gz = POW2 ? d.z * inv_n : d.z / a.n, gw = POW2 ? d.w * inv_n : d.w / a.n;
-                        if constexpr (PASS <= 1) {                                       // single chunk, or the first of several
-                            m.x = m.x * a.mom; m.x = m.x + a.lr * (gx - a.wd * w0.x);        // rbm.py:212
-                            m.y = m.y * a.mom; m.y = m.y + a.lr * (gy - a.wd * w0.y);
-                            m.z = m.z * a.mom; m.z = m.z + a.lr * (gz - a.wd * w0.z);
-                            m.w = m.w * a.mom; m.w = m.w + a.lr * (gw - a.wd * w0.w);
-                        } else {                                                         // later chunks: the statistics term only
-                            m.x = m.x + a.lr * gx; m.y = m.y + a.lr * gy; m.z = m.z + a.lr * gz; m.w = m.w + a.lr * gw;
-                        }
-                        *reinterpret_cast<float4*>(a.Wm + idx) = m;
-                        if constexpr (PASS == 0 || PASS == 3)
-                            *reinterpret_cast<float4*>(a.W + idx) = make_float4(w0.x + m.x, w0.y + m.y, w0.z + m.z, w0.w + m.w);   // :213
-                        // (non-temporal stores were tried here in round 2: 51.3 us against 49.4 event-timed -- the tail of this kernel is
-                        //  not dirty lines lingering in L2.  Round 3: write-through (sc1) stores for the LAST tile of every block, so that
-                        //  the launch ends with nothing dirty in the L2s: 46.7 us with and without, rocprofv3, same box)
-                    } else {
-                        float4 o = d;
-                        if constexpr (PASS >= 2) { const float4 p = mc[reg]; o = make_float4(p.x + d.x, p.y + d.y, p.z + d.z, p.w + d.w); }
-                        *reinterpret_cast<float4*>(a.delta + (int64_t)row * a.H + h0 + 4 * r) = o;
-                    }
-                }
-            }
-        };
-        if (n_pow2) epilogue(std::true_type{}); else epilogue(std::false_type{});
+        k3_apply<MODE, PASS>(a, kw, v0, acc, wc, mc);
         stamp(st, sblk, 2 + it);
     };
-    for (int it = 0; it < n_my; it += 2) {
+    for (int it = 0; it < kw.n_my; it += 2) {
         tile(it, wA, mA, wB, mB);
-        if (it + 1 < n_my) tile(it + 1, wB, mB, wA, mA);
+        if (it + 1 < kw.n_my) tile(it + 1, wB, mB, wA, mA);
     }
 }
 
@@ -995,71 +1021,24 @@ template <int HT>
 __device__ __forceinline__ void k3_body_ranks(const AssocPlanesArgs& a, const RankLoopArgs& rl, char* smem, int bx, int by,
                                               int tiles_per_block, int nap, int nan_) {
     const int P = nap + nan_;                                       // planes per tile and rank: 2 or 4 (host guarantees <= 4)
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, r = l & 31, kh = l >> 5;
-    const int h0 = bx * 128;
-    const int tile0 = by * tiles_per_block;
-    const int n_vtiles = (a.V + 127) / 128;
-    const int n_my = min(tiles_per_block, n_vtiles - tile0);
-    const int colc = min(h0 + 4 * r, a.H - 4);
-    const bool cok = (h0 + 4 * r) < a.H;
-    const bool n_pow2 = (__float_as_uint(a.n) & 0x7fffffu) == 0u;
-    const float inv_n = 1.0f / a.n;
-    char* sHp = smem;
-    char* sHn = smem + 3 * K3_PLANE;
-    char* sV = smem + K3_VIS0 + w * (4 * K3_SLICE);
-    const uint32_t sV_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)sV);
-    const uint32_t sH_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)smem);
-
-    auto load_tile = [&](float4 (&wo)[16], float4 (&mo)[16], int v0, bool valid) {
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int row = valid ? min(v0 + 32 * w + mfma_row(reg, l), a.V - 1) : tile0 * 128;
-            const int64_t idx = (int64_t)row * a.ldw + colc;
-            wo[reg] = *reinterpret_cast<const float4*>(a.W + idx);
-            mo[reg] = *reinterpret_cast<const float4*>(a.Wm + idx);
-        }
-    };
-    auto dma_rank = [&](int rk, int v0w) {                          // hidden planes + this wave's visible slices of rank rk
-        const int64_t ro = (int64_t)rk * rl.stride_h, rov = (int64_t)rk * rl.stride_v;
-#pragma unroll
-        for (int ph = 0; ph < 2; ++ph)
-#pragma unroll
-            for (int tb = 0; tb < HT; ++tb)
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {
-                    const int j = 4 * w + jj, i = 64 * j + l, lrow = i >> 3, pos = i & 7;
-                    const int row = 4 * (lrow & 31) + (lrow >> 5), c = pos ^ ((lrow >> 1) & 7);
-                    const bf16_t* src = (ph ? a.hneg : a.hpos) + ro + tb * a.hts + (int64_t)min(h0 + row, a.H - 1) * a.Bp + 8 * c;
-                    k3_dma16(src, sH_lds + (3 * ph + tb) * K3_PLANE + j * 1024);
-                }
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const int pl = min(p, P - 1);
-            const bf16_t* src = (pl < nap ? a.vpos + pl * a.vts : a.vneg + (pl - nap) * a.vts) + rov;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int i = l + 64 * q, row = i >> 3, c = (i & 7) ^ ((row >> 1) & 7);
-                k3_dma16(src + (int64_t)min(v0w + row, a.V - 1) * a.Bp + 8 * c, sV_lds + p * K3_SLICE + q * 1024);
-            }
-        }
-    };
+    const K3Wave kw = k3_wave(a, smem, bx, by, tiles_per_block);
 
     float4 wA[16], mA[16], wB[16], mB[16];
-    load_tile(wA, mA, tile0 * 128, true);
+    k3_load_rows<0, 16>(a, kw, wA, mA, kw.tile0 * 128, true);
     auto tile = [&](int it, float4 (&wc)[16], float4 (&mc)[16], float4 (&wn)[16], float4 (&mn)[16]) {
-        const int v0 = (tile0 + it) * 128;
+        const int v0 = (kw.tile0 + it) * 128;
         f32x16 acc[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+        k3_zero(acc);
         for (int rk = 0; rk < rl.n_ranks; ++rk) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __syncthreads();                                         // every wave is done with the previous rank's planes
-            dma_rank(rk, v0 + 32 * w);
+            k3_dma_hidden<HT>(a, kw, (int64_t)rk * rl.stride_h);     // rank rk: its hidden planes, then this wave's four slices
+#pragma unroll
+            for (int p = 0; p < 4; ++p)                              // (clamped plane index, as in k3_body)
+                k3_dma_slice(a, kw, k3_vis_plane(a, nap, min(p, P - 1)), (int64_t)rk * rl.stride_v, v0, p);
             __builtin_amdgcn_sched_barrier(0);
             if (rk == 0) {                                           // next tile's weights: behind this rank's planes in the VMEM queue
-                load_tile(wn, mn, v0 + 128, it + 1 < n_my);
+                k3_load_rows<0, 16>(a, kw, wn, mn, v0 + 128, it + 1 < kw.n_my);
                 __builtin_amdgcn_sched_barrier(0);
                 asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
             } else {
@@ -1068,35 +1047,14 @@ __device__ __forceinline__ void k3_body_ranks(const AssocPlanesArgs& a, const Ra
             __syncthreads();                                         // the hidden planes (staged by all four waves) are complete
 #pragma unroll
             for (int p = 0; p < 4; ++p)
-                if (p < P) k3_mfma_wave<HT>(acc, p < nap ? sHp : sHn, sV + p * K3_SLICE, r, kh);
+                if (p < P) k3_mfma_wave<HT>(acc, p < nap ? kw.sHp : kw.sHn, kw.sV + p * K3_SLICE, kw.r, kw.kh);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        auto epilogue = [&](auto pow2_tag) {
-            constexpr bool POW2 = decltype(pow2_tag)::value;
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int row = v0 + 32 * w + mfma_row(reg, l);
-                if (row < a.V && cok) {
-                    const float4 d = make_float4(acc[0][reg], acc[1][reg], acc[2][reg], acc[3][reg]);
-                    const int64_t idx = (int64_t)row * a.ldw + h0 + 4 * r;
-                    const float4 w0 = wc[reg];
-                    float4 m = mc[reg];
-                    const float gx = POW2 ? d.x * inv_n : d.x / a.n, gy = POW2 ? d.y * inv_n : d.y / a.n;
-                    const float gz = POW2 ? d.z * inv_n : d.z / a.n, gw = POW2 ? d.w * inv_n : d.w / a.n;
-                    m.x = m.x * a.mom; m.x = m.x + a.lr * (gx - a.wd * w0.x);        // rbm.py:212
-                    m.y = m.y * a.mom; m.y = m.y + a.lr * (gy - a.wd * w0.y);
-                    m.z = m.z * a.mom; m.z = m.z + a.lr * (gz - a.wd * w0.z);
-                    m.w = m.w * a.mom; m.w = m.w + a.lr * (gw - a.wd * w0.w);
-                    *reinterpret_cast<float4*>(a.Wm + idx) = m;
-                    *reinterpret_cast<float4*>(a.W + idx) = make_float4(w0.x + m.x, w0.y + m.y, w0.z + m.z, w0.w + m.w);   // :213
-                }
-            }
-        };
-        if (n_pow2) epilogue(std::true_type{}); else epilogue(std::false_type{});
+        k3_apply<0, 0>(a, kw, v0, acc, wc, mc);
     };
-    for (int it = 0; it < n_my; it += 2) {
+    for (int it = 0; it < kw.n_my; it += 2) {
         tile(it, wA, mA, wB, mB);
-        if (it + 1 < n_my) tile(it + 1, wB, mB, wA, mA);
+        if (it + 1 < kw.n_my) tile(it + 1, wB, mB, wA, mA);
     }
 }
 
@@ -1109,71 +1067,32 @@ template <int HT>
 __device__ __forceinline__ void k3_body_ranks_acc(const AssocPlanesArgs& a, const RankLoopArgs& rl, char* smem, int bx, int by,
                                                   int tiles_per_block, int nap, int nan_) {
     const int P = nap + nan_;                                       // planes per tile and rank: 2 or 4
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, r = l & 31, kh = l >> 5;
-    const int h0 = bx * 128;
-    const int tile0 = by * tiles_per_block;
-    const int n_vtiles = (a.V + 127) / 128;
-    const int n_my = min(tiles_per_block, n_vtiles - tile0);
-    const int colc = min(h0 + 4 * r, a.H - 4);
-    const bool cok = (h0 + 4 * r) < a.H;
-    const bool n_pow2 = (__float_as_uint(a.n) & 0x7fffffu) == 0u;
-    const float inv_n = 1.0f / a.n;
-    char* sHp = smem;
-    char* sHn = smem + 3 * K3_PLANE;
-    char* sV = smem + K3_VIS0 + w * (4 * K3_SLICE);
-    const uint32_t sV_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)sV);
-    const uint32_t sH_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)smem);
+    const K3Wave kw = k3_wave(a, smem, bx, by, tiles_per_block);
     const bool dbl = P <= 2;                                        // two slot pairs: stage tile t+1 under the MFMAs of tile t
 
-    auto dma_hidden = [&](int rk) {                                  // 2 x HT planes of rank rk, all four waves: 8 HT ops per wave
-        const int64_t ro = (int64_t)rk * rl.stride_h;
-#pragma unroll
-        for (int ph = 0; ph < 2; ++ph)
-#pragma unroll
-            for (int tb = 0; tb < HT; ++tb)
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {
-                    const int j = 4 * w + jj, i = 64 * j + l, lrow = i >> 3, pos = i & 7;
-                    const int row = 4 * (lrow & 31) + (lrow >> 5), c = pos ^ ((lrow >> 1) & 7);
-                    const bf16_t* src = (ph ? a.hneg : a.hpos) + ro + tb * a.hts + (int64_t)min(h0 + row, a.H - 1) * a.Bp + 8 * c;
-                    k3_dma16(src, sH_lds + (3 * ph + tb) * K3_PLANE + j * 1024);
-                }
-    };
-    // this wave's visible slices of (rank rk, rows v0w ..): planes 0..1 into slots base, base+1 (dbl) or planes 0..3 into slots 0..3;
+    // this wave's visible slices of (rank rk, tile at v0): planes 0..1 into slots base, base+1 (dbl) or planes 0..3 into slots 0..3;
     // always 8 (dbl) or 16 ops
-    auto dma_slices = [&](int rk, int v0w, int base) {
-        const int64_t ro = (int64_t)rk * rl.stride_v;
+    auto dma_slices = [&](int rk, int v0, int base) {
         const int np = dbl ? 2 : 4;
-        for (int p = 0; p < np; ++p) {
-            const int pl = min(p, P - 1);
-            const bf16_t* src = (pl < nap ? a.vpos + pl * a.vts : a.vneg + (pl - nap) * a.vts) + ro;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int i = l + 64 * q, row = i >> 3, c = (i & 7) ^ ((row >> 1) & 7);
-                k3_dma16(src + (int64_t)min(v0w + row, a.V - 1) * a.Bp + 8 * c, sV_lds + (base + p) * K3_SLICE + q * 1024);
-            }
-        }
+        for (int p = 0; p < np; ++p)
+            k3_dma_slice(a, kw, k3_vis_plane(a, nap, min(p, P - 1)), (int64_t)rk * rl.stride_v, v0, base + p);
     };
     f32x16 acc[4][4];
 #pragma unroll
-    for (int it = 0; it < 4; ++it)
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[it][t][i] = 0.f;
+    for (int it = 0; it < 4; ++it) k3_zero(acc[it]);
 
     for (int rk = 0; rk < rl.n_ranks; ++rk) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __syncthreads();                                             // every wave is done with the previous rank's planes and slices
-        dma_hidden(rk);
-        dma_slices(rk, tile0 * 128 + 32 * w, 0);
+        k3_dma_hidden<HT>(a, kw, (int64_t)rk * rl.stride_h);
+        dma_slices(rk, kw.tile0 * 128, 0);
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
-            if (it < n_my) {                                         // block-uniform
+            if (it < kw.n_my) {                                      // block-uniform
                 const int base = dbl ? 2 * (it & 1) : 0;
                 if (dbl) {
-                    if (it + 1 < n_my) {
-                        dma_slices(rk, (tile0 + it + 1) * 128 + 32 * w, 2 * ((it + 1) & 1));      // its previous readers (tile it-1) are done: same wave
+                    if (it + 1 < kw.n_my) {
+                        dma_slices(rk, (kw.tile0 + it + 1) * 128, 2 * ((it + 1) & 1));             // its previous readers (tile it-1) are done: same wave
                         asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                           // everything but those 8 ops has landed
                     } else {
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1181,50 +1100,31 @@ __device__ __forceinline__ void k3_body_ranks_acc(const AssocPlanesArgs& a, cons
                 } else {
                     if (it > 0) {
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                         // tile it-1's LDS reads are done
-                        dma_slices(rk, (tile0 + it) * 128 + 32 * w, 0);
+                        dma_slices(rk, (kw.tile0 + it) * 128, 0);
                     }
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 }
                 if (it == 0) __syncthreads();                        // the hidden planes (staged by all four waves) are complete
                 for (int p = 0; p < P; ++p)
-                    k3_mfma_wave<HT>(acc[it], p < nap ? sHp : sHn, sV + (base + p) * K3_SLICE, r, kh);
+                    k3_mfma_wave<HT>(acc[it], p < nap ? kw.sHp : kw.sHn, kw.sV + (base + p) * K3_SLICE, kw.r, kw.kh);
                 if (dbl) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // before the slot pair is restaged two tiles later
             }
         }
     }
-    // phase 2: one read-modify-write of the block's weight tiles
-    float4 wc[16], mc[16];
+    // phase 2: one read-modify-write of the block's weight tiles.  The power-of-two choice is taken once around the tile loop,
+    // not per tile as k3_apply would: with all 256 accumulator registers live, a branch inside every unrolled tile spills
+    auto phase2 = [&](auto pow2_tag) {
+        float4 wc[16], mc[16];
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {
-        if (it < n_my) {
-            const int v0 = (tile0 + it) * 128;
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int row = min(v0 + 32 * w + mfma_row(reg, l), a.V - 1);
-                const int64_t idx = (int64_t)row * a.ldw + colc;
-                wc[reg] = *reinterpret_cast<const float4*>(a.W + idx);
-                mc[reg] = *reinterpret_cast<const float4*>(a.Wm + idx);
-            }
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int row = v0 + 32 * w + mfma_row(reg, l);
-                if (row < a.V && cok) {
-                    const float4 d = make_float4(acc[it][0][reg], acc[it][1][reg], acc[it][2][reg], acc[it][3][reg]);
-                    const int64_t idx = (int64_t)row * a.ldw + h0 + 4 * r;
-                    const float4 w0 = wc[reg];
-                    float4 m = mc[reg];
-                    const float gx = n_pow2 ? d.x * inv_n : d.x / a.n, gy = n_pow2 ? d.y * inv_n : d.y / a.n;
-                    const float gz = n_pow2 ? d.z * inv_n : d.z / a.n, gw = n_pow2 ? d.w * inv_n : d.w / a.n;
-                    m.x = m.x * a.mom; m.x = m.x + a.lr * (gx - a.wd * w0.x);        // rbm.py:212
-                    m.y = m.y * a.mom; m.y = m.y + a.lr * (gy - a.wd * w0.y);
-                    m.z = m.z * a.mom; m.z = m.z + a.lr * (gz - a.wd * w0.z);
-                    m.w = m.w * a.mom; m.w = m.w + a.lr * (gw - a.wd * w0.w);
-                    *reinterpret_cast<float4*>(a.Wm + idx) = m;
-                    *reinterpret_cast<float4*>(a.W + idx) = make_float4(w0.x + m.x, w0.y + m.y, w0.z + m.z, w0.w + m.w);   // :213
-                }
+        for (int it = 0; it < 4; ++it) {
+            if (it < kw.n_my) {
+                const int v0 = (kw.tile0 + it) * 128;
+                k3_load_rows<0, 16>(a, kw, wc, mc, v0, true);
+                k3_apply_rows<0, 0, decltype(pow2_tag)::value>(a, kw, v0, acc[it], wc, mc);
             }
         }
-    }
+    };
+    if (kw.n_pow2) phase2(std::true_type{}); else phase2(std::false_type{});
 }
 
 // ---- what the kernels around the k3 bodies share -----------------------------------------------------------
@@ -1325,66 +1225,22 @@ static_assert(32 + 2 * K3B_TOP <= 63, "the vmcnt field holds 6 bits");
 
 template <int HT>
 __device__ __forceinline__ void k3_body_bin(const AssocPlanesArgs& a, char* smem, int bx, int by, int tiles_per_block) {
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, r = l & 31, kh = l >> 5;
-    const int h0 = bx * 128;
-    const int tile0 = by * tiles_per_block;
-    const int n_vtiles = (a.V + 127) / 128;
-    const int n_my = min(tiles_per_block, n_vtiles - tile0);
-    const int colc = min(h0 + 4 * r, a.H - 4);
-    const bool cok = (h0 + 4 * r) < a.H;          // H % 4 == 0: a float4 is entirely inside or outside
-    const bool n_pow2 = (__float_as_uint(a.n) & 0x7fffffu) == 0u;      // d / n == d * (1/n) exactly
-    const float inv_n = 1.0f / a.n;
-
-    char* sHp = smem;
-    char* sHn = smem + 3 * K3_PLANE;
-    char* sV = smem + K3_VIS0 + w * (4 * K3_SLICE);                    // this wave's two buffers of two slices
-    const uint32_t sV_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)sV);
-
-    // row pairs [R0, R1) of the weight tile at v0: W and W_m, interleaved as k3_body loads them
-    auto load_rows = [&](auto r0_tag, auto r1_tag, float4 (&wo)[16], float4 (&mo)[16], int v0, bool valid) {
-#pragma unroll
-        for (int reg = decltype(r0_tag)::value; reg < decltype(r1_tag)::value; ++reg) {
-            const int row = valid ? min(v0 + 32 * w + mfma_row(reg, l), a.V - 1) : tile0 * 128;
-            const int64_t idx = (int64_t)row * a.ldw + colc;
-            wo[reg] = *reinterpret_cast<const float4*>(a.W + idx);
-            mo[reg] = *reinterpret_cast<const float4*>(a.Wm + idx);
-        }
+    const K3Wave kw = k3_wave(a, smem, bx, by, tiles_per_block);         // kw.sV: this wave's two buffers of two slices
+    // positive and negative plane of this wave's rows of the tile at v0 -> buffer `buf`
+    auto dma_slices = [&](int buf, int v0) {
+        k3_dma_slice(a, kw, a.vpos, a.b0, v0, 2 * buf);
+        k3_dma_slice(a, kw, a.vneg, a.b0, v0, 2 * buf + 1);
     };
-    // positive and negative plane of rows v0w..v0w+31 -> buffer `buf`
-    auto dma_slices = [&](int buf, int v0w) {
-#pragma unroll
-        for (int ph = 0; ph < 2; ++ph)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int i = l + 64 * q, row = i >> 3, c = (i & 7) ^ ((row >> 1) & 7);      // source chunk for LDS position i
-                k3_dma16((ph ? a.vneg : a.vpos) + (int64_t)min(v0w + row, a.V - 1) * a.Bp + a.b0 + 8 * c,
-                         sV_lds + (2 * buf + ph) * K3_SLICE + q * 1024);
-            }
-    };
-    using I0 = std::integral_constant<int, 0>;
-    using IT = std::integral_constant<int, K3B_TOP>;
-    using IE = std::integral_constant<int, 16>;
 
     float4 wA[16], mA[16], wB[16], mB[16];
     const bool st = a.dbg != 0;
     const int sblk = by * gridDim.x + bx;
     stamp(st, sblk, 0);
     // hidden planes as in k3_body (same LDS image), tile 0's slices, the whole first weight tile; then ONE wait, ONE barrier
-    const uint32_t sH_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)smem);
-#pragma unroll
-    for (int ph = 0; ph < 2; ++ph)
-#pragma unroll
-        for (int tb = 0; tb < HT; ++tb)
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-                const int j = 4 * w + jj, i = 64 * j + l, lrow = i >> 3, pos = i & 7;
-                const int row = 4 * (lrow & 31) + (lrow >> 5), c = pos ^ ((lrow >> 1) & 7);
-                const bf16_t* src = (ph ? a.hneg : a.hpos) + tb * a.hts + (int64_t)min(h0 + row, a.H - 1) * a.Bp + a.b0 + 8 * c;
-                k3_dma16(src, sH_lds + (3 * ph + tb) * K3_PLANE + j * 1024);
-            }
-    dma_slices(0, tile0 * 128 + 32 * w);
+    k3_dma_hidden<HT>(a, kw, a.b0);
+    dma_slices(0, kw.tile0 * 128);
     __builtin_amdgcn_sched_barrier(0);
-    load_rows(I0{}, IE{}, wA, mA, tile0 * 128, true);
+    k3_load_rows<0, 16>(a, kw, wA, mA, kw.tile0 * 128, true);
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt vmcnt(32)" ::: "memory");                   // planes and slices(0) arrived; the 32 weight loads stay in flight
     __syncthreads();                                                    // the ONLY block barrier
@@ -1392,51 +1248,28 @@ __device__ __forceinline__ void k3_body_bin(const AssocPlanesArgs& a, char* smem
 
     auto tile = [&](int it, auto buf_tag, float4 (&wc)[16], float4 (&mc)[16], float4 (&wn)[16], float4 (&mn)[16]) {
         constexpr int BUF = decltype(buf_tag)::value;
-        const int v0 = (tile0 + it) * 128;
-        const bool more = it + 1 < n_my;                                  // block-uniform
-        load_rows(I0{}, IT{}, wn, mn, v0 + 128, more);                    // first part of the next tile's weights
+        const int v0 = (kw.tile0 + it) * 128;
+        const bool more = it + 1 < kw.n_my;                               // block-uniform
+        // W and W_m of the next tile, rows interleaved as k3_body loads them: first part [0, K3B_TOP)
+        k3_load_rows<0, K3B_TOP>(a, kw, wn, mn, v0 + 128, more);
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt vmcnt(%0)" :: "i"(32 + 2 * K3B_TOP) : "memory");     // this tile's slices arrived; the previous tile's stores and the loads above stay in flight
         f32x16 acc[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
-        k3_mfma_wave<HT>(acc, sHp, sV + (2 * BUF) * K3_SLICE, r, kh);
-        k3_mfma_wave<HT>(acc, sHn, sV + (2 * BUF + 1) * K3_SLICE, r, kh);
+        k3_zero(acc);
+        k3_mfma_wave<HT>(acc, kw.sHp, kw.sV + (2 * BUF) * K3_SLICE, kw.r, kw.kh);
+        k3_mfma_wave<HT>(acc, kw.sHn, kw.sV + (2 * BUF + 1) * K3_SLICE, kw.r, kw.kh);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               // all fragment reads done
         __builtin_amdgcn_sched_barrier(0);
-        load_rows(IT{}, IE{}, wn, mn, v0 + 128, more);                    // the rest of the next tile's weights
+        k3_load_rows<K3B_TOP, 16>(a, kw, wn, mn, v0 + 128, more);        // the rest of the next tile's weights
         __builtin_amdgcn_sched_barrier(0);
-        if (more) dma_slices(BUF ^ 1, v0 + 128 + 32 * w);                 // the other buffer: last read by the previous tile's MFMAs
+        if (more) dma_slices(BUF ^ 1, v0 + 128);                          // the other buffer: last read by the previous tile's MFMAs
         __builtin_amdgcn_sched_barrier(0);
-        auto epilogue = [&](auto pow2_tag) {
-            constexpr bool POW2 = decltype(pow2_tag)::value;
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int row = v0 + 32 * w + mfma_row(reg, l);
-                if (row < a.V && cok) {
-                    const float4 d = make_float4(acc[0][reg], acc[1][reg], acc[2][reg], acc[3][reg]);   // pos_assoc - neg_assoc
-                    const int64_t idx = (int64_t)row * a.ldw + h0 + 4 * r;
-                    const float4 w0 = wc[reg];
-                    float4 m = mc[reg];
-                    const float gx = POW2 ? d.x * inv_n : d.x / a.n, gy = POW2 ? d.y * inv_n : d.y / a.n;
-                    const float gz = POW2 ? d.z * inv_n : d.z / a.n, gw = POW2 ? d.w * inv_n : d.w / a.n;
-                    m.x = m.x * a.mom; m.x = m.x + a.lr * (gx - a.wd * w0.x);        // rbm.py:212
-                    m.y = m.y * a.mom; m.y = m.y + a.lr * (gy - a.wd * w0.y);
-                    m.z = m.z * a.mom; m.z = m.z + a.lr * (gz - a.wd * w0.z);
-                    m.w = m.w * a.mom; m.w = m.w + a.lr * (gw - a.wd * w0.w);
-                    *reinterpret_cast<float4*>(a.Wm + idx) = m;
-                    *reinterpret_cast<float4*>(a.W + idx) = make_float4(w0.x + m.x, w0.y + m.y, w0.z + m.z, w0.w + m.w);   // :213
-                }
-            }
-        };
-        if (n_pow2) epilogue(std::true_type{}); else epilogue(std::false_type{});
+        k3_apply<0, 0>(a, kw, v0, acc, wc, mc);
         stamp(st, sblk, 2 + it);
     };
-    for (int it = 0; it < n_my; it += 2) {
+    for (int it = 0; it < kw.n_my; it += 2) {
         tile(it, std::integral_constant<int, 0>{}, wA, mA, wB, mB);
-        if (it + 1 < n_my) tile(it + 1, std::integral_constant<int, 1>{}, wB, mB, wA, mA);
+        if (it + 1 < kw.n_my) tile(it + 1, std::integral_constant<int, 1>{}, wB, mB, wA, mA);
     }
 }
 
