@@ -332,6 +332,34 @@ int imdbn_rbm_label_loglik(const imdbn_rbm_desc* d, const float* z, int64_t ldz,
 int imdbn_rbm_label_step(const imdbn_rbm_desc* d, const float* z, int64_t ldz, int N, int Dz, int K, const int32_t* gt,
                          const imdbn_cd_opts* o, double* out_logp, float* scratch, void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- log p(y | z) of the joint RBM as an output layer: its error at the code z (imdbn/models/imdbn.py: discriminative_step; DESIGN
+ * section 27) ----
+ * d, z, gt, base, a_k, s, p_k, hpos, hneg as in imdbn_rbm_label_step.  From the parameters on entry:
+ *   out_logp[row]  the bits of imdbn_rbm_label_step / imdbn_rbm_label_loglik (joint - marginal); NaN when t is outside [0, K)
+ *   out_pred[row]  (nullable) argmax_k a_k over the double class values of the same row pass, the lowest k on a tie; written for every
+ *                  row whatever gt holds (-1 only where every class value is NaN)
+ *   e_j = hpos_j - hneg_j                     fp32 [N][H], one subtraction
+ *   g_z = e W[:Dz]^T                          = d log p(t | z) / d z  (the visible biases of the code cancel)
+ *   err_z = g_z z (1 - z)                     [N][Dz], row stride lde: the ascent direction at the pre-activations that produced z, the
+ *                                             e_h imdbn_rbm_backprop_step expects for the layer whose output z is
+ * A row whose label is outside [0, K) gets logp = NaN and an exact zero row of err_z; nothing is read through its label.  g_z is the
+ * logits-only down propagation of imdbn_rbm_backprop_step's err_v_out on the descriptor cut to its first Dz weight rows, without a
+ * bias (a signed real operand, whatever kernel route that shape takes), the product with z (1 - z) one fp32 multiplication.
+ * o != NULL: also the update of imdbn_rbm_label_step; the six parameter and momentum tensors after the call are bit for bit those of
+ * imdbn_rbm_label_step on the same state (lr, momentum, weight_decay are read; cd_k, sparsity, the prefetch fields and fwd_out must be
+ * zero).  o == NULL: the head is frozen, no parameter is written and the momentum pointers may be null.
+ * Launch order (plain launches on `stream`): the propagation of base; the row kernel (logp, pred, r, hpos, hneg, e); with o the
+ * label-row update (it writes W[Dz:] and the label biases only, and is the last reader of base); the propagation of e through W[:Dz]
+ * and the z (1 - z) epilogue (they read W[:Dz] only); with o the code-side update (the only writer of W[:Dz] and hid_bias), last.
+ * Every order is fixed by (Dz, K, H, N); no floating-point atomics, no draws; the same call on the same state gives the same bits.
+ * scratch: N (K + 3 H) floats of the caller's (device; r, hpos, hneg, e between the launches; contents on return unspecified).
+ * IMDBN_E_INVALID (naming the value) before the first launch, no parameter and no output touched: the cases of
+ * imdbn_rbm_label_step (a null o excepted), a null err_z, lde < Dz; with o a null momentum buffer or a non-zero cd_k, sparsity,
+ * prefetch field or fwd_out.  Workspace: imdbn_ws_bytes(Dz, H, N).  No host synchronisation. */
+int imdbn_rbm_label_backprop_step(const imdbn_rbm_desc* d, const float* z, int64_t ldz, int N, int Dz, int K, const int32_t* gt,
+                                  const imdbn_cd_opts* o, double* out_logp, int32_t* out_pred, float* err_z, int64_t lde,
+                                  float* scratch, void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- exact pseudo-log-likelihood (imdbn/utils/likelihood.py: pseudo_log_likelihood) -----------------------------
  * PLL(v) = sum over sites of log p(v_site | v_rest), a site being every visible column outside the softmax groups and every group
  * as a whole.  No reference counterpart; built over the free energy above: with x = hid_bias + v W, sigma = sigmoid(x), s_i = 1 - 2 v_i,

@@ -1957,38 +1957,91 @@ int imdbn_rbm_assoc_update(const imdbn_rbm_desc* d, const float* vpos, int64_t l
 // W[:Dz] gets z^T hpos - z^T hneg, hid_bias the column sums of hpos - hneg, the code columns of vis_bias their momentum.
 // Its operand preparation writes vis_tr / hid_tr / flags / column sums: f_h and the scratch are out of its way, and the label kernel
 // has read base and the label rows before the update kernel starts (one stream), so both halves see the parameters on entry.
-int imdbn_rbm_label_step(const imdbn_rbm_desc* d, const float* z, int64_t ldz, int N, int Dz, int K, const int32_t* gt,
-                         const imdbn_cd_opts* o, double* out_logp, float* scratch, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
-    CHK(check_desc(d, true));
-    CHK(LabelSide::check("label_step", d, Dz, K));
-    if (Dz + K != d->V) return fail(IMDBN_E_INVALID, "label_step: Dz + K = %d is not V = %d", Dz + K, d->V);
-    if (N < 1) return fail(IMDBN_E_INVALID, "label_step: N = %d rows", N);
-    if (ldz < Dz) return fail(IMDBN_E_INVALID, "label_step: ldz %lld < Dz %d", (long long)ldz, Dz);
-    if (!z || !gt || !o || !out_logp || !scratch)
-        return fail(IMDBN_E_INVALID, "label_step: null %s", !z ? "z" : (!gt ? "gt" : (!o ? "opts" : (!out_logp ? "out_logp" : "scratch"))));
-    LabelSide s(d, Dz, S(stream));
+// label_grad_call is that step (bp = false) and imdbn_rbm_label_backprop_step (bp = true; o may then be NULL: nothing is written).
+static int label_grad_call(const char* name, bool bp, const imdbn_rbm_desc* d, const float* z, int64_t ldz, int N, int Dz, int K, const int32_t* gt,
+                           const imdbn_cd_opts* o, double* out_logp, int32_t* out_pred, float* err_z, int64_t lde, float* scratch,
+                           void* ws, size_t ws_bytes, hipStream_t stream) {
+    CHK(check_desc(d, o != nullptr || !bp));
+    CHK(LabelSide::check(name, d, Dz, K));
+    if (Dz + K != d->V) return fail(IMDBN_E_INVALID, "%s: Dz + K = %d is not V = %d", name, Dz + K, d->V);
+    if (N < 1) return fail(IMDBN_E_INVALID, "%s: N = %d rows", name, N);
+    if (ldz < Dz) return fail(IMDBN_E_INVALID, "%s: ldz %lld < Dz %d", name, (long long)ldz, Dz);
+    if (!z || !gt || (!o && !bp) || !out_logp || !scratch)
+        return fail(IMDBN_E_INVALID, "%s: null %s", name, !z ? "z" : (!gt ? "gt" : (!o && !bp ? "opts" : (!out_logp ? "out_logp" : "scratch"))));
+    if (bp) {
+        if (!err_z) return fail(IMDBN_E_INVALID, "%s: null err_z", name);
+        if (lde < Dz) return fail(IMDBN_E_INVALID, "%s: lde %lld < Dz %d", name, (long long)lde, Dz);
+        if (o && (o->cd_k || o->sparsity || o->next_data || o->next_slot || o->data_slot || o->next_binary || o->fwd_out))
+            return fail(IMDBN_E_INVALID, "%s: cd_k, sparsity, the prefetch fields and fwd_out must be zero (cd_k %d, sparsity %d, next_data %p, "
+                        "next_slot %d, data_slot %d, next_binary %d, fwd_out %p)", name, o->cd_k, o->sparsity, (const void*)o->next_data, o->next_slot,
+                        o->data_slot, o->next_binary, (const void*)o->fwd_out);
+    }
+    LabelSide s(d, Dz, stream);
     CHK(s.propagate(z, ldz, N, ws, ws_bytes));
     Ctx& c = s.c;
+    const Layout& L = c.L;
     const int H = d->H;
-    LabelGradArgs g{};
-    g.j.base = s.base; g.j.ldb = H;
-    g.j.z = z; g.j.ldz = ldz;
-    g.j.bz = s.bz; g.j.by = s.by;
-    g.j.Wy = s.Wy; g.j.ldw = d->ldw;
-    g.j.gt = gt; g.j.N = N; g.j.Dz = Dz; g.j.K = K; g.j.H = H;
-    g.logp = out_logp;
-    g.r = scratch; g.hpos = scratch + (size_t)N * K; g.hneg = g.hpos + (size_t)N * H;
-    hipLaunchKernelGGL(label_grad_rows, dim3(cdiv(N, ROW_WAVES)), dim3(64 * ROW_WAVES), 0, c.s, g);
+    LabelBackpropArgs g{};
+    JointArgs& j = g.g.j;
+    j.base = s.base; j.ldb = H;
+    j.z = z; j.ldz = ldz;
+    j.bz = s.bz; j.by = s.by;
+    j.Wy = s.Wy; j.ldw = d->ldw;
+    j.gt = gt; j.N = N; j.Dz = Dz; j.K = K; j.H = H;
+    g.g.logp = out_logp;
+    g.g.r = scratch; g.g.hpos = scratch + (size_t)N * K; g.g.hneg = g.g.hpos + (size_t)N * H;
+    g.pred = out_pred; g.e = g.g.hneg + (size_t)N * H;
+    if (bp) {
+        hipLaunchKernelGGL(label_backprop_rows, dim3(cdiv(N, ROW_WAVES)), dim3(64 * ROW_WAVES), 0, c.s, g);
+    } else {
+        hipLaunchKernelGGL(label_grad_rows, dim3(cdiv(N, ROW_WAVES)), dim3(64 * ROW_WAVES), 0, c.s, g.g);
+    }
     HIPCHK(hipGetLastError());
-    LabelUpdateArgs u{};
-    u.base = s.base; u.ldb = H; u.r = g.r;
-    u.U = d->W + (int64_t)Dz * d->ldw; u.Um = d->W_m + (int64_t)Dz * d->ldw; u.ldw = d->ldw;
-    u.by = d->vis_bias + Dz; u.bym = d->vb_m + Dz;
-    u.N = N; u.K = K; u.H = H;
-    u.lr = o->lr; u.mom = o->momentum; u.wd = o->weight_decay; u.n = (float)N;
-    hipLaunchKernelGGL(label_grad_update, dim3((unsigned)(((int64_t)K * H + K + 255) / 256)), dim3(256), 0, c.s, u);
-    HIPCHK(hipGetLastError());
-    return assoc_from_tensors(c, z, ldz, g.hpos, H, z, ldz, g.hneg, H, o, false);
+    if (o) {
+        LabelUpdateArgs u{};
+        u.base = s.base; u.ldb = H; u.r = g.g.r;
+        u.U = d->W + (int64_t)Dz * d->ldw; u.Um = d->W_m + (int64_t)Dz * d->ldw; u.ldw = d->ldw;
+        u.by = d->vis_bias + Dz; u.bym = d->vb_m + Dz;
+        u.N = N; u.K = K; u.H = H;
+        u.lr = o->lr; u.mom = o->momentum; u.wd = o->weight_decay; u.n = (float)N;
+        hipLaunchKernelGGL(label_grad_update, dim3((unsigned)(((int64_t)K * H + K + 255) / 256)), dim3(256), 0, c.s, u);
+        HIPCHK(hipGetLastError());
+    }
+    if (bp) {   // err_z = (e W[:Dz]^T) z (1 - z): host_backprop.hpp's err_v_out on the cut descriptor, its visible bias at zeros
+        HIPCHK(hipMemsetAsync(L.cs_vneg, 0, (size_t)Dz * sizeof(float), c.s));
+        float* vis_bias = s.dz.vis_bias;
+        s.dz.vis_bias = L.cs_vneg;
+        CHK(prep(c, g.e, H, H, L.hid_rm, L.Hpad, nullptr, L.flags_h));
+        FinishArgs f = new_finish();
+        f.logits_only = 1;
+        f.out_prob = L.f_v[0]; f.ld_prob = Dz;
+        CHK(prop(c, false, OpIn{L.hid_rm, c.nw == 1 ? 1 : 0, L.flags_h}, f));
+        s.dz.vis_bias = vis_bias;
+        BackpropApplyArgs a;
+        memset(&a, 0, sizeof(a));
+        a.B = N; a.N = Dz; a.q = L.f_v[0]; a.ldq = Dz; a.x = z; a.ldx = ldz; a.out = err_z; a.ldo = lde;
+        hipLaunchKernelGGL(backprop_apply, dim3(cdiv(Dz, 256), cdiv(N, 8)), dim3(256), 0, c.s, a);
+        HIPCHK(hipGetLastError());
+    }
+    if (!o) return 0;
+    return assoc_from_tensors(c, z, ldz, g.g.hpos, H, z, ldz, g.g.hneg, H, o, false);
+}
+
+int imdbn_rbm_label_step(const imdbn_rbm_desc* d, const float* z, int64_t ldz, int N, int Dz, int K, const int32_t* gt,
+                         const imdbn_cd_opts* o, double* out_logp, float* scratch, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    return label_grad_call("label_step", false, d, z, ldz, N, Dz, K, gt, o, out_logp, nullptr, nullptr, 0, scratch, ws, ws_bytes, S(stream));
+}
+
+// ---- log p(y | z) of the joint RBM as an output layer: its error at the code, and optionally the step above ----------
+// Launch order, plain, on the caller's stream: the propagation of base (prep_operand of z, the up route) into f_h; label_backprop_rows
+// (logp, pred, r, hpos, hneg, e into the caller's arrays); with o, label_grad_update -- it writes W[Dz:] only and is the last reader
+// of base; a memset of the zero bias, prep_operand of e (hid_rm, flags_h), the logits-only down propagation on the cut descriptor
+// (its partial buffer and f_v[0]: not f_h, not the scratch) and backprop_apply (err_z) -- they read W[:Dz] only; with o, the code-side
+// update of label_step (operand planes, column sums, the update kernel: the only writer of W[:Dz], hid_bias and their momenta, last).
+int imdbn_rbm_label_backprop_step(const imdbn_rbm_desc* d, const float* z, int64_t ldz, int N, int Dz, int K, const int32_t* gt,
+                                  const imdbn_cd_opts* o, double* out_logp, int32_t* out_pred, float* err_z, int64_t lde,
+                                  float* scratch, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    return label_grad_call("label_backprop_step", true, d, z, ldz, N, Dz, K, gt, o, out_logp, out_pred, err_z, lde, scratch, ws, ws_bytes, S(stream));
 }
 
 // ---- C1: collectives over RCCL for callers that do not go through torch.distributed ------------------------------------

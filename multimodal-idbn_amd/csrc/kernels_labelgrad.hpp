@@ -14,6 +14,11 @@
 //                       chain, and applies rbm.py:212-224 without the sparsity term to U, W_m[Dz:], b_y and vb_m[Dz:].  Each
 //                       thread reads and writes its own parameter only.
 //
+//   label_backprop_rows label_grad_rows (one row function serves both: the same bits in logp, r, hpos and hneg) that also leaves
+//                       e_j = hpos_j - hneg_j (one fp32 subtraction; an exact zero row for an invalid label) -- the error
+//                       imdbn_rbm_label_backprop_step sends down through W[:Dz] -- and pred = argmax_k a_k over the
+//                       double class values of pass 1 (the lowest k on a tie, whatever gt holds).
+//
 // The code side (W[:Dz], hid_bias, the momentum of b_z) is the update kernel's, from z, hpos and hneg (engine.hip).  No atomics,
 // no LDS; every sum has an order fixed by (Dz, K, H, N).
 #pragma once
@@ -28,7 +33,31 @@ struct LabelGradArgs {
     float* hpos; float* hneg;              // [N][H]
 };
 
-__global__ __launch_bounds__(64 * ROW_WAVES) void label_grad_rows(const LabelGradArgs g) {
+struct LabelBackpropArgs {
+    LabelGradArgs g;
+    int32_t* pred;                         // [N], nullable
+    float* e;                              // [N][H]
+};
+
+// index of the first maximum of a row of K doubles in the label slots, the same in every lane: the larger value first, the lower
+// index on ties, NaN never wins (-1 for a row in which nothing wins)
+__device__ __forceinline__ int slots_argmax_f64(const double (&v)[4], int l, int K) {
+    double best = -INFINITY; int bi = 0x7fffffff;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int c = l + 64 * q;
+        if (c < K && (v[q] > best || (v[q] == best && c < bi))) { best = v[q]; bi = c; }
+    }
+    for (int o = 32; o >= 1; o >>= 1) {
+        const double w = __shfl_xor(best, o); const int j = __shfl_xor(bi, o);
+        if (w > best || (w == best && j < bi)) { best = w; bi = j; }
+    }
+    return bi < K ? bi : -1;
+}
+
+// One row of label_grad_rows / label_backprop_rows.  BP adds pred and e and changes nothing else: one source, the same bits.
+template <bool BP>
+__device__ __forceinline__ void label_grad_row(const LabelGradArgs& g, int32_t* pred, float* e_out) {
     const JointArgs& a = g.j;
     const int lane = wave_lane(), row = wave_row();
     if (row >= a.N) return;      // wave-uniform
@@ -39,6 +68,10 @@ __global__ __launch_bounds__(64 * ROW_WAVES) void label_grad_rows(const LabelGra
     const bool ok = t >= 0 && t < a.K;      // wave-uniform
     const double at = slots_pick(val, t);
     if (lane == 0) g.logp[row] = ok ? at - marg : (double)NAN;
+    if (BP && pred) {
+        const int best = slots_argmax_f64(val, lane, a.K);
+        if (lane == 0) pred[row] = best;
+    }
     float pf[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -50,8 +83,12 @@ __global__ __launch_bounds__(64 * ROW_WAVES) void label_grad_rows(const LabelGra
     const float* base = a.base + (int64_t)row * a.ldb;
     float* hp = g.hpos + (int64_t)row * a.H;
     float* hn = g.hneg + (int64_t)row * a.H;
+    float* er = BP ? e_out + (int64_t)row * a.H : nullptr;
     if (!ok) {
-        for (int j = lane; j < a.H; j += 64) { hp[j] = 0.f; hn[j] = 0.f; }
+        for (int j = lane; j < a.H; j += 64) {
+            hp[j] = 0.f; hn[j] = 0.f;
+            if (BP) er[j] = 0.f;
+        }
         return;
     }
     for (int j0 = 0; j0 < a.H; j0 += 64) {      // every lane walks k: slots_pick is a wave-wide shuffle
@@ -65,9 +102,16 @@ __global__ __launch_bounds__(64 * ROW_WAVES) void label_grad_rows(const LabelGra
             neg = fmaf(pk, s, neg);
             if (k == t) pos = s;
         }
-        if (in) { hp[j] = pos; hn[j] = neg; }
+        if (in) {
+            hp[j] = pos; hn[j] = neg;
+            if (BP) er[j] = pos - neg;
+        }
     }
 }
+
+__global__ __launch_bounds__(64 * ROW_WAVES) void label_grad_rows(const LabelGradArgs g) { label_grad_row<false>(g, nullptr, nullptr); }
+
+__global__ __launch_bounds__(64 * ROW_WAVES) void label_backprop_rows(const LabelBackpropArgs b) { label_grad_row<true>(b.g, b.pred, b.e); }
 
 struct LabelUpdateArgs {
     const float* base; int64_t ldb;        // [N][H], as pass 1 read it

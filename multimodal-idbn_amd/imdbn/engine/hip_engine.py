@@ -868,6 +868,70 @@ class HipEngine:
             f = self.backprop_step(rec_layers[l - 1], up=(a[l - 1], f), lr=epoch_scalars[l - 1][0], mom=epoch_scalars[l - 1][1], want_v=l > 1)[0]
         return {"recon": dec[0], "code": a[L], "xent": xent, "mse": mse}
 
+    # ---- discriminative fine-tuning of a stack through the joint RBM's exact class posterior ------------
+    def label_backprop_step(self, rbm, z: torch.Tensor, K: int, gt: torch.Tensor, lr: float = 0.0, mom: float = 0.0, apply: bool = True,
+                            want_pred: bool = False):
+        """``log p(gt | z)`` of the joint RBM ``rbm`` over ``[z (Dz) | labels (K)]`` as an output layer
+        (imdbn_rbm_label_backprop_step).  Returns ``(logp, err_z, pred)``, all from the parameters on entry: ``logp`` the float64
+        ``[N]`` of ``label_step`` (the same bits; NaN where ``gt`` is outside ``[0, K)``), ``err_z`` ``[N, Dz]`` =
+        ``d log p / d z * z (1 - z)`` -- the ``e_h`` of ``backprop_step`` for the layer that produced ``z``; an exact zero row for an
+        invalid label -- and, with ``want_pred``, ``pred`` int32 ``[N]`` = ``argmax_k`` of the class values (else None).  With
+        ``apply`` the update of ``label_step`` (the same bits in all six tensors); without it no parameter is written.  No
+        draws, no host sync."""
+        d = self._desc(rbm, bool(apply))
+        if not z.is_cuda or z.dim() != 2:
+            raise N.EngineError("label_backprop_step needs a HIP tensor z [N, Dz]")
+        z = _f32c(z)
+        n, Dz = z.shape
+        dev = z.device
+        g = _on(gt, dev, torch.int32)
+        if g is None or g.numel() != n:
+            raise N.EngineError("label_backprop_step: gt must hold one label per row of z")
+        K = int(K)
+        o = self._opts(rbm, lr, mom, 0) if apply else None
+        logp = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        pred = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if want_pred else None
+        err = torch.empty(max(n, 1), Dz, device=dev)
+        need = max(n, 1) * (max(K, 0) + 3 * d.H)
+        scratch = self._buffer(("label_backprop_step", dev, torch.cuda.current_stream(dev).cuda_stream), lambda: _f32(dev, need), need)
+        self._call("imdbn_rbm_label_backprop_step", C.byref(d), _ptr(z), z.stride(0), n, Dz, K, _ptr(g), _ref(o), _ptr(logp), _ptr(pred),
+                   _ptr(err), err.stride(0), _ptr(scratch), *self._ws_tail(dev, Dz, d.H, max(n, 1)))
+        return logp, err, pred
+
+    def discriminative_step(self, layers, joint, data, K, gt, epoch_scalars, head_scalars, train_head: bool = True, monitor: bool = True):
+        """One backprop step on ``-mean log p(gt | data)`` of a stack read as a classifier (Hinton & Salakhutdinov 2006; Larochelle
+        & Bengio 2008): ``layers`` the L RBMs of the image stack bottom first (their recognition half: ``W`` and ``hid_bias``),
+        ``joint`` the joint RBM over ``[code | K labels]`` whose exact class posterior is the output layer.  On one stream, no host
+        sync, no draws: ``a_0 = data``, ``a_l = forward`` of layer l; ``label_backprop_step(joint, a_L)`` (with ``train_head`` the
+        step of ``label_step`` at ``head_scalars = (lr, mom)``, else the head is frozen) gives ``f_L``; then
+        ``backprop_step(layers[l-1], up=(a_{l-1}, f_l), want_v=l > 1)`` for l = L .. 1 with ``epoch_scalars[l-1] = (lr, mom)``.
+        Returns ``{"code": a_L, "nll", "acc"}``: ``nll = -nanmean(logp)`` (float64) and ``acc`` the share of the rows with a valid
+        label whose argmax class is the label, 0-d device scalars on the parameters on entry; None with ``monitor=False``.  Only
+        ``layers`` and ``joint`` are written: no generative twin is read or touched."""
+        from . import dp
+        if dp.active():
+            raise NotImplementedError("discriminative_step has no data-parallel split")
+        L = len(layers)
+        if L < 1 or len(epoch_scalars) != L:
+            raise N.EngineError(f"discriminative_step: {L} layers need {L} (lr, mom) pairs")
+        a = [_f32c(data)]
+        for rbm in layers:
+            cur = a[-1] if len(a) > 1 else data             # the caller's tensor carries the 0/1 tag, its fp32 form may be a copy
+            out = self.forward(rbm, cur, data_binary=self.binary_hint(cur)) if hasattr(self, "forward") else self.prop_up(rbm, cur)
+            out._imdbn_binary = False
+            a.append(out)
+        g = _on(gt, a[L].device, torch.int32)
+        lr, mom = head_scalars
+        logp, f, pred = self.label_backprop_step(joint, a[L], K, g, lr, mom, apply=bool(train_head), want_pred=bool(monitor))
+        nll = acc = None
+        if monitor:
+            ok = (g >= 0) & (g < int(K))
+            nll = -torch.nanmean(logp)
+            acc = ((pred == g) & ok).sum().double() / ok.sum().double()
+        for l in range(L, 0, -1):
+            f = self.backprop_step(layers[l - 1], up=(a[l - 1], f), lr=epoch_scalars[l - 1][0], mom=epoch_scalars[l - 1][1], want_v=l > 1)[0]
+        return {"code": a[L], "nll": nll, "acc": acc}
+
     # ---- RCCL through the C ABI (a binder without torch.distributed; the classes use torch.distributed) ---------------
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(128)

@@ -117,6 +117,8 @@ SIGNATURES = {
     "imdbn_rows_logmeanexp": (_INT, [_P, _INT, _INT, _P, _P, _P]),
     "imdbn_rbm_label_loglik": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _INT, _INT, _P, _P, _P, _P, _SZ, _P]),
     "imdbn_rbm_label_step": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _INT, _INT, _P, C.POINTER(CdOpts), _P, _P, _P, _SZ, _P]),
+    "imdbn_rbm_label_backprop_step": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _INT, _INT, _P, C.POINTER(CdOpts), _P, _P, _P, _I64, _P,
+                                             _P, _SZ, _P]),
     "imdbn_rbm_pseudo_loglik": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _P, _P, _I64, _P, _SZ, _P]),
     "imdbn_rbm_bound_step": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _INT, C.POINTER(Rng), _P, _P, _I64, _P, _SZ, _P]),
     "imdbn_rbm_prop_down": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _F, _INT, _P, _I64, _P, _SZ, _P]),

@@ -279,6 +279,53 @@ class iMDBN(nn.Module):
             self.finetune_sup_nll.append(float(torch.stack(nll).mean()) if nll else float("nan"))
         return self.finetune_sup_nll
 
+    # ---- discriminative fine-tuning of the whole model (extension; Hinton & Salakhutdinov 2006, Larochelle & Bengio 2008) ----
+    @torch.no_grad()
+    def discriminative_step(self, img: torch.Tensor, y: torch.Tensor, epoch: int, max_epochs: int, lr_scale: float = 1.0,
+                            head_lr_scale: float = 1.0, train_head: bool = True, monitor: bool = True):
+        """One backprop step on ``-mean log p(y | img)`` on one mini-batch: the engine's ``discriminative_step`` -- the exact class
+        posterior of the joint RBM is the output layer and its error goes back through every recognition layer of
+        ``image_idbn``.  ``y``: one-hot rows ``[B, K]`` or integer labels ``[B]``.  Every image layer uses its own learning-rate and
+        momentum schedule (``lr`` times ``lr_scale``) and weight decay, the joint RBM its own times ``head_lr_scale``
+        (``train_head=False``: the joint RBM is only read).  Generative twins of an untied ``image_idbn`` are not touched and the
+        model is not untied.  Returns ``{"nll", "acc"}`` as 0-d device scalars on the parameters on entry, or None with
+        ``monitor=False``.  No host sync; no data-parallel split."""
+        if _E.dp.active():
+            raise NotImplementedError("discriminative_step has no data-parallel split")
+        x = rows_on_device(img, self.device)
+        y = y.to(self.device)
+        gt = y.argmax(dim=1) if y.dim() == 2 else y
+        layers = self.image_idbn.layers
+        scalars = []
+        for r in layers:
+            lr, mom = r._lr_mom(epoch)
+            scalars.append((lr * float(lr_scale), mom))
+        lr, mom = self.joint_rbm._lr_mom(epoch)
+        out = self.joint_rbm._eng().discriminative_step(layers, self.joint_rbm, x, self.num_labels, gt, scalars,
+                                                        (lr * float(head_lr_scale), mom), train_head=train_head, monitor=monitor)
+        return {k: out[k] for k in ("nll", "acc")} if monitor else None
+
+    def finetune_discriminative(self, epochs: int, lr_scale: float = 0.1, head_lr_scale: float = 0.3, train_head: bool = True,
+                                log_every: int = 0):
+        """``epochs`` passes of ``discriminative_step`` over ``self.dataloader`` (explicit only: ``train_joint`` never calls it and
+        no ``params`` key turns it on).  ``log_every`` > 0: the monitors of every ``log_every``-th epoch are evaluated, fetched in
+        ONE host read after the epoch's last batch and appended to ``self.discriminative_history`` as ``(epoch, nll, acc)`` batch
+        means; otherwise nothing is evaluated and the host never reads."""
+        self.discriminative_history = getattr(self, "discriminative_history", [])
+        for epoch in range(int(epochs)):
+            watch = int(log_every) > 0 and epoch % int(log_every) == 0
+            mons = []
+            for img, y in batches(self.dataloader):
+                m = self.discriminative_step(img, y, epoch, epochs, lr_scale=lr_scale, head_lr_scale=head_lr_scale,
+                                             train_head=train_head, monitor=watch)
+                if watch:
+                    mons.append(torch.stack([m["nll"].double(), m["acc"].double()]))
+            if mons:
+                nll, acc = torch.stack(mons).mean(0).cpu().tolist()
+                self.discriminative_history.append((epoch, nll, acc))
+                if self.wandb_run:
+                    self.wandb_run.log({"joint/discriminative_nll": nll, "joint/discriminative_acc": acc, "epoch": epoch})
+
     # ---- cross-modal inference (imdbn.py:386-488) -------------------------------------------------
     @torch.no_grad()
     def _cross_reconstruct(self, z_img: torch.Tensor, y_onehot: torch.Tensor,

@@ -382,6 +382,19 @@ class RBM(nn.Module):
         logp = self._eng().label_step(self, self._in(z), int(num_labels), gt, float(lr_mult) * lr, mom)
         return -torch.nanmean(logp)
 
+    @torch.no_grad()
+    def label_backprop(self, z: torch.Tensor, gt: torch.Tensor, epoch: int, max_epochs: int, num_labels: int, lr_mult: float = 1.0,
+                       apply: bool = True):
+        """``log p(gt | z)`` of a joint RBM over ``[z | one-hot label]`` as an output layer (extension): returns
+        ``(logp, err_z, pred)`` of the engine's ``label_backprop_step`` -- ``err_z`` is the error at the pre-activations that
+        produced ``z``, ready for ``backprop_step`` of the layer below -- all under the parameters on entry.  With ``apply`` the
+        step of ``train_epoch_labels`` (the same schedule, the same bits); without it the RBM is only read.  No draws."""
+        if _E.dp.active():
+            raise NotImplementedError("label_backprop has no data-parallel split")
+        lr, mom = self._lr_mom(epoch)
+        return self._eng().label_backprop_step(self, self._in(z), int(num_labels), gt, float(lr_mult) * lr, mom, apply=bool(apply),
+                                               want_pred=True)
+
     # ---- schedules (rbm.py:229-238) -------------------------------------------------------------
     def _lin_schedule(self, t, t_max, start, end):
         if t_max <= 1:
