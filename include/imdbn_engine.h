@@ -771,6 +771,40 @@ int imdbn_cross_metrics(const float* p, int64_t ldp, int B, int K, const float* 
                         const float* row_mse, int npix, int topk, const imdbn_cross_metrics_out* out, void* ws, size_t ws_bytes,
                         imdbn_stream_t stream);
 
+/* ---- pairwise free-energy scores of a joint RBM over [z1 (D1) | z2 (D2)], D2 = V - D1 (imdbn/utils/retrieval.py) ---------------
+ * z1[Q][D1] (row stride ld1) are the queries, z2[N][D2] (ld2) the candidates; every (q, n) is scored in one sweep:
+ *   S[q][n] = -F([z1_q | z2_n]) = z1_q . b[:D1] + z2_n . b[D1:] + sum_j softplus(c_j + (z1_q W[:D1])_j + (z2_n W[D1:])_j)
+ *           a = c + z1 W[:D1] and b = z2 W[D1:] are the logits path of imdbn_rbm_prop_up on the two cuts of the descriptor; the two
+ *           bias dots are fp32 sums in a fixed order; per pair the fp32 terms softplus(a_qj + b_nj) = max(x, 0) + log(1 + exp(-|x|))
+ *           (hardware exp2 / log2) are added for j = 0 .. H - 1 in order into a double, and S is that total rounded to fp32.
+ *           A (query row, candidate row) pair scores the same bits whatever Q, N, k, the workspace size, the outputs requested
+ *           or the other rows; identical candidate rows tie exactly.  Error bound: DESIGN §28.
+ *   rank_q[q] = #{n : S[q][n] > S[q][g]} + #{n < g : S[q][n] == S[q][g]}, g = gt_q[q]: the place of the true partner in a stable
+ *           descending sort (the rule of imdbn_cross_metrics);  score_q[q] = S[q][g], the very bits the sweep gives that pair.
+ *   rank_n[n], score_n[n]: the same over the column S[.][n] against S[gt_n[n]][n] -- the other direction from the same scores.
+ *   top_idx[Q][k], top_score[Q][k]: per query the first k candidates in rank order (score descending, the lower index on ties,
+ *           NaN never a candidate); fewer than k candidates: padded with -1 / -inf.
+ *   scores[Q][N] (row stride lds), nullable: the whole matrix, for small panels and tests.  Without it no score reaches memory.
+ *   A gt entry outside its range ([0, N) for gt_q, [0, Q) for gt_n) is a caller error handled without a fault: that row gets rank
+ *   -1 and score NaN, nothing is read through it.  A NaN score is never greater than, equal to, or a candidate for anything.
+ *   Integer counts, no floating-point atomics: the same call leaves the same bits.  No host synchronisation; parameters are read only.
+ *   Limits (IMDBN_E_INVALID otherwise, naming the value, before the first launch and with no output touched): Q, N >= 1,
+ *           1 <= D1 < V, ld1 >= D1, ld2 >= D2, lds >= N, 0 <= k <= 64, z1 / z2 / out not NULL, a rank or score output needs its gt,
+ *           k > 0 needs top_idx and top_score, something must be requested.  Softmax groups: IMDBN_E_UNSUPPORTED.
+ *   Workspace: 256-byte aligned, at least imdbn_pair_ws_bytes(V, H, Q, N, k) (IMDBN_E_WORKSPACE below that; 0 for arguments outside
+ *           the limits).  Every further A(4 Q) + (k > 0 ? 2 A(4 Q k) : 0) bytes, A(x) = x rounded up to 256, let the candidates
+ *           split into one more chunk (up to ceil(N / 64), about 2048 blocks in all) -- more blocks, the same result. */
+typedef struct imdbn_pair_out {
+    int32_t* rank_q;  float* score_q;          /* [Q], nullable; need gt_q */
+    int32_t* rank_n;  float* score_n;          /* [N], nullable; need gt_n */
+    int32_t* top_idx; float* top_score;        /* [Q][k], padded -1 / -inf; required iff k > 0 */
+    float*   scores;  int64_t lds;             /* [Q][N] nullable, lds >= N: small panels and tests */
+} imdbn_pair_out;
+size_t imdbn_pair_ws_bytes(int V, int H, int Q, int N, int k);
+int imdbn_rbm_pair_scores(const imdbn_rbm_desc* d, int D1, const float* z1, int64_t ld1, int Q,
+                          const float* z2, int64_t ld2, int N, const int32_t* gt_q, const int32_t* gt_n, int k,
+                          const imdbn_pair_out* out, void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- whole RBM.train_epoch_clamped (rbm.py:402-483) -------------------------------------- */
 /* positive phase = chain(n_init steps) ; negative = cd_k steps from v+ ; update with o->lr */
 int imdbn_rbm_clamped_step(const imdbn_rbm_desc* d, const float* v_known, const float* mask, int64_t ldk, int B,

@@ -29,6 +29,7 @@
 #include "kernels_knn.hpp"
 #include "kernels_energy.hpp"
 #include "kernels_metrics.hpp"
+#include "kernels_pair.hpp"
 #include "kernels_ais.hpp"
 #include "kernels_reverse_ais.hpp"
 #include "kernels_bound.hpp"
@@ -1573,6 +1574,9 @@ int imdbn_cross_metrics(const float* p, int64_t ldp, int B, int K, const float* 
     HIPCHK(hipGetLastError());
     return 0;
 }
+
+// ---- pairwise free-energy scores and retrieval ranks (imdbn/utils/retrieval.py; kernels_pair.hpp) -------------------
+#include "host_pair.hpp"
 
 // rbm.py:443-471: v+ by conditional inference, H+, CD-k from v+ (optionally re-clamped / sampled), H-.
 // Leaves the statistics operands in the workspace exactly as cd_phases does.

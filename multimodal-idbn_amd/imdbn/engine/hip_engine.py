@@ -1352,6 +1352,48 @@ class HipEngine:
                    _ptr(idx), _ptr(sc), _ptr(ws), ws.numel(), self._stream(dev))
         return idx, sc
 
+    # ---- pairwise free-energy scores (imdbn/utils/retrieval.py) -------------------------------------------------------------
+    def pair_scores(self, rbm, z1: torch.Tensor, z2: torch.Tensor, gt_q: Optional[torch.Tensor] = None,
+                    gt_n: Optional[torch.Tensor] = None, k: int = 0, return_scores: bool = False) -> dict:
+        """Every query ``z1`` ``[Q, D1]`` against every candidate ``z2`` ``[N, D2]`` under the joint RBM ``rbm`` over
+        ``[z1 | z2]`` (imdbn_rbm_pair_scores): ``S[q, n] = -F([z1_q | z2_n])``.  With ``gt_q`` ``[Q]``: ``rank_q`` (int32, the 0-based
+        place of candidate ``gt_q[q]`` in a stable descending sort of row q; -1 for an entry outside ``[0, N)``) and ``score_q``
+        (``S[q, gt_q[q]]``, NaN there); with ``gt_n`` ``[N]``: ``rank_n`` / ``score_n`` over the columns; with ``k > 0``: ``top_idx`` /
+        ``top_score`` ``[Q, k]`` padded with -1 / -inf; with ``return_scores``: ``scores`` ``[Q, N]``.  Device tensors, no host sync."""
+        d = self._desc(rbm, False)
+        if not (z1.is_cuda and z2.is_cuda) or z1.dim() != 2 or z2.dim() != 2 or z1.size(1) < 1 or z1.size(1) + z2.size(1) != d.V:
+            raise N.EngineError(f"pair_scores needs HIP tensors z1 [Q, D1] and z2 [N, D2] with D1 + D2 = {d.V}")
+        dev = z1.device
+        z1, z2 = _f32c(z1), _f32c(z2.to(dev))
+        (Q, D1), n = z1.shape, z2.size(0)
+        k = int(k)
+        gq, gn = _on(gt_q, dev, torch.int32), _on(gt_n, dev, torch.int32)
+        if (gq is not None and gq.numel() != Q) or (gn is not None and gn.numel() != n):
+            raise N.EngineError("pair_scores: gt_q [Q] and gt_n [N] must match z1 and z2")
+        o = {}
+        if gq is not None:
+            o["rank_q"], o["score_q"] = _i32(dev, max(Q, 1)), _f32(dev, max(Q, 1))
+        if gn is not None:
+            o["rank_n"], o["score_n"] = _i32(dev, max(n, 1)), _f32(dev, max(n, 1))
+        if k > 0:
+            o["top_idx"], o["top_score"] = _i32(dev, max(Q, 1), k), _f32(dev, max(Q, 1), k)
+        if return_scores:
+            o["scores"] = _f32(dev, max(Q, 1), max(n, 1))
+        out = N.PairOut()
+        for name, t in o.items():
+            setattr(out, name, t.data_ptr())
+        out.lds = max(n, 1)
+        # the header's minimum plus room for the candidate chunks of about 2048 blocks (fewer chunks: fewer blocks, the same result)
+        A = lambda b: (int(b) + 255) // 256 * 256
+        kk = min(max(k, 0), 64)
+        chunks = min(max(1, -(-2048 // -(-max(Q, 1) // 64))), -(-max(n, 1) // 64))
+        need = int(self._lib.imdbn_pair_ws_bytes(d.V, d.H, max(Q, 1), max(n, 1), kk)) + (chunks - 1) * (A(4 * Q) + (2 * A(4 * Q * kk) if kk else 0))
+        ws = self._buffer(("pair", dev, torch.cuda.current_stream(dev).cuda_stream),
+                          lambda: torch.empty(need, dtype=torch.uint8, device=dev), at_least=need)
+        self._call("imdbn_rbm_pair_scores", C.byref(d), D1, _ptr(z1), z1.stride(0), Q, _ptr(z2), z2.stride(0), n, _ptr(gq), _ptr(gn), k,
+                   C.byref(out), _ptr(ws), ws.numel(), self._stream(dev))
+        return o
+
     # ---- clamped CD (the joint RBM's update) ----------------------------------------------------------------------------
     def _clamped_cd(self, name: str, rbm, d, v_known, mask, init_steps, mu, o, sample_h, sample_v, rng, out: torch.Tensor):
         """clamped_step / clamped_stats: entry `name`(desc, v_known, mask, ld, B, init steps, mu, opts, rng, out, workspace tail)."""

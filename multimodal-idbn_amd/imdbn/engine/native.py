@@ -77,6 +77,10 @@ class EnergyOut(C.Structure):
                                           "margin_energy", "fe_top1", "fe_gap", "F", "y_final")]
 
 
+class PairOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("rank_q", "score_q", "rank_n", "score_n", "top_idx", "top_score", "scores")] + [("lds", C.c_int64)]
+
+
 class CrossMetricsOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("pred", "gt", "p_pred", "p_true", "rank", "acc", "confusion", "class_sums")]
 
@@ -162,6 +166,8 @@ SIGNATURES = {
     "imdbn_energy_trace": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _INT, _INT, _INT, _P, _P, _I64, C.c_double, _INT, C.c_double,
                                   C.POINTER(EnergyOut), _P, _SZ, _P]),
     "imdbn_cross_metrics": (_INT, [_P, _I64, _INT, _INT, _P, _I64, _P, _P, _INT, _INT, C.POINTER(CrossMetricsOut), _P, _SZ, _P]),
+    "imdbn_pair_ws_bytes": (_SZ, [_INT, _INT, _INT, _INT, _INT]),
+    "imdbn_rbm_pair_scores": (_INT, [C.POINTER(RbmDesc), _INT, _P, _I64, _INT, _P, _I64, _INT, _P, _P, _INT, C.POINTER(PairOut), _P, _SZ, _P]),
     "imdbn_rbm_clamped_step": (_INT, [C.POINTER(RbmDesc), _P, _P, _I64, _INT, _INT, C.POINTER(ChainStep), _P, _I64, _INT,
                                       C.POINTER(CdOpts), C.POINTER(Rng), _P, _P, _SZ, _P]),
     "imdbn_rbm_assoc_update": (_INT, [C.POINTER(RbmDesc), _P, _I64, _P, _I64, _P, _I64, _P, _I64, _INT, C.POINTER(CdOpts), _P, _SZ, _P]),

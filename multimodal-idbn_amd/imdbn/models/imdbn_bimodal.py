@@ -200,6 +200,11 @@ class iMDBN_BiModal(nn.Module):
             h = rbm.forward(h)
         return h
 
+    def evaluate_retrieval(self, loader=None, **kw):
+        """Held-out retrieval in both directions over the pairs of ``loader`` (imdbn.utils.retrieval.evaluate_retrieval)."""
+        from imdbn.utils import retrieval as _RT
+        return _RT.evaluate_retrieval(self, loader, **kw)
+
     # ---- joint training (:711-826) ---------------------------------------------------------------
     def train_joint(self, epochs: int, log_every: int = 5, log_every_pca: int = 25, log_every_probe: int = 10,
                     log_every_trajectory: int = 50):

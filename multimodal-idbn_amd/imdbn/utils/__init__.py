@@ -7,6 +7,7 @@ from . import imdbn_logging
 from . import bimodal_logging
 from . import cross_eval
 from . import likelihood
+from . import retrieval
 
 __all__ = ["batches", "rows_on_device", "rbm_free_energy", "class_free_energies", "probe_utils", "conditional_steps", "imdbn_logging", "bimodal_logging",
-           "cross_eval", "likelihood"]
+           "cross_eval", "likelihood", "retrieval"]
