@@ -155,7 +155,7 @@ int check_desc(const imdbn_rbm_desc* d, bool need_momentum) {
             return fail(IMDBN_E_UNSUPPORTED, "softmax group %d is %d wide; at most %d supported", g, d->group_end[g] - d->group_start[g], GROUP_WMAX);
         for (int k = 0; k < g; ++k)
             if (d->group_start[g] < d->group_end[k] && d->group_start[k] < d->group_end[g])
-                return fail(IMDBN_E_UNSUPPORTED, "overlapping softmax groups %d and %d", k, g);
+                return fail(IMDBN_E_INVALID, "overlapping softmax groups %d and %d", k, g);
     }
     if (d->mode != IMDBN_PARITY_F32 && d->mode != IMDBN_FAST_BF16) return fail(IMDBN_E_INVALID, "bad mode %d", d->mode);
     return 0;

@@ -6,8 +6,9 @@ at which the twin's estimates lie within 3 of its own standard errors of the enu
 test docstrings state what the seeds 1..8 gave).  Every FORWARD / GROUPS / REVERSE / PATH seed is one whose smallest Bernoulli margin
 |p - u| outside the softmax groups in the twin is at least MARGIN and whose smallest categorical-CDF margin is at least MARGIN
 (forward; in GROUPS the first such seed, counting from 1) or CAT_MARGIN (reverse), so the device (fp32 sigmoid and softmax, another
-summation order in the logits) must take every decision as the twin does.  `python tests/anneal_cases.py` prints, for every case, the
-first seed that meets the margins next to the pinned one."""
+summation order in the logits) must take every decision as the twin does.  The `four256` rows (four groups, one 256 wide) also keep
+FOUR256_CAT_MARGIN at their categorical picks.  `python tests/anneal_cases.py` prints, for every case, the first seed that meets the
+margins next to the pinned one."""
 from dataclasses import dataclass
 
 import numpy as np
@@ -64,6 +65,12 @@ class Row:
     gen_seed: int = None        # of the parameters (None: 100 + V)
 
 
+FOUR256 = ((0, 5), (20, 276), (276, 290), (299, 300))
+# what a pinned seed of a four256 row keeps at its categorical picks besides the table's own margin: group_cases.cat_margin(256),
+# the distance two fp32 cumulative sums over 256 softmax probabilities can lie apart, rounded up
+FOUR256_CAT_MARGIN = 2.5e-5
+
+
 def _g(V, H, *rest, **kw):
     """A GROUPS row: its parameters come from the generator 500 + V + H."""
     return Row(V, H, *rest, gen_seed=500 + V + H, **kw)
@@ -88,6 +95,9 @@ GROUPS = {
     "plain": _g(20, 12, 5, 3, 1.0, True, "uneven", 1),                                   # n_groups = 0: imdbn_rbm_ais bit for bit
     "paper": _g(532, 256, 64, 5, 0.05, True, "linear", 14, groups=((500, 532),)),        # the paper's joint shape
     "wide": _g(1100, 40, 8, 2, 0.05, False, "linear", 2, groups=((1092, 1100),)),        # the split-K up route
+    # four groups (pick[q] for q = 2, 3): one at column 0, a 256-wide one across columns 64, 128 and 256 next to its neighbour, a
+    # width-1 group at the last column.  Its seed is the first whose categorical margin is also >= FOUR256_CAT_MARGIN
+    "four256": _g(300, 12, 5, 3, 0.1, True, "linear", 3, groups=FOUR256),
 }
 
 # as FORWARD with R start rows in the place of M chains; one softmax group; K = 1; R = 70 (two 64-row chunks)
@@ -101,6 +111,7 @@ REVERSE = {
     "group": Row(25, 12, 6, 5, 1.0, True, "linear", 1, groups=((20, 25),)),
     "one": Row(20, 12, 5, 1, 1.0, True, "linear", 1),
     "rows70": Row(20, 12, 70, 6, 1.0, True, "uneven", 2),
+    "four256": Row(300, 12, 6, 3, 0.1, True, "linear", 1, groups=FOUR256),                # as GROUPS["four256"]: the one of the wide group is found by lanes striding 64
 }
 
 
@@ -207,6 +218,6 @@ if __name__ == "__main__":
                     m, cm = A.reverse_ais_logw(c["W"], c["b"], c["c"], c["bA"], c["groups"], c["betas"], c["x"], PhiloxStream(seed))[2:]
                 else:
                     m, cm = A.ais_logw(c["W"], c["b"], c["c"], c["bA"], c["betas"], c["M"], PhiloxStream(seed), c["groups"])[2:]
-                if m >= MARGIN and cm >= cat:
+                if m >= MARGIN and cm >= (max(cat, FOUR256_CAT_MARGIN) if name == "four256" else cat):
                     break
             print(f"{what} {name}: first seed {seed} (pinned {c['seed']}), margins {m:.3g} / {cm:.3g}")

@@ -49,7 +49,7 @@ NORMAL_ERR = 8 * U * 5.77
 SIGMOID_ERR = 4 * U
 CHAIN_PER_LAUNCH, CHAIN_KERNEL, CHAIN_KERNEL_PAIR = 0, 1, 2      # include/imdbn_engine.h IMDBN_CHAIN_*
 OPTION_DEFAULTS = {"chain_rows": 0, "no_chain_kernel": 0, "no_chain_pair": 0}
-GROUPS = ("rows", "auto", "fast", "geometry", "gemm", "lds", "steps", "pitch")
+GROUPS = ("rows", "auto", "fast", "geometry", "gemm", "lds", "steps", "pitch", "wide")
 NOMINAL_CU = 256                               # what the CPU tests resolve ("cu", m, a) batches with
 
 # ---- what the host derives from a call (csrc/engine.hip chain_kernel_ok, run_chain_pair, launch_k4) ---------------------------------
@@ -505,9 +505,39 @@ def group_pitch():
             _case("pitch", "150x48-strided-inputs", V, H, 5, [("mix", 6), ("vmode2", 4)], groups, Dz=145, strided=True, seed=82)]
 
 
+def lds_edge(gw, H=48, mode="parity"):
+    """(largest V the kernel admits with one group `gw` wide at this H, the first it rejects), from kernel_ok alone."""
+    ok = [V for V in range(gw, PLANES_MAX + 1) if kernel_ok(V, H, ((V - gw, V),), mode, 3)]
+    return ok[-1], next(V for V in range(ok[-1] + 1, PLANES_MAX + 2) if not kernel_ok(V, H, ((V - gw, V),), mode, 3))
+
+
+WIDE_SHAPES = ((150, 48, ((117, 150),)), (300, 48, ((44, 300),)))      # JOINT with a group of 33; widened for one of 256
+
+
+def group_wide():
+    """One group of 33 (the first width past a wave's 32 lanes of logits per row pair) and of 256 (GROUP_WMAX): the group logits
+    glog[row * GW + j], the noise drawn ahead gz[(gp * gwd + gc) * 2] and their 8-wide loops beyond gwd = 32; the two gw terms of
+    chain_kernel_ok's LDS sum at the admission edge of a 256-wide group."""
+    out = []
+    for V, H, groups in WIDE_SHAPES:
+        w = groups[0][1] - groups[0][0]
+        for kind in ("mix", "noisy", "vmode2"):
+            for rows in (2, 16):
+                B = 5 if rows == 2 else 19
+                out.append(_case("wide", f"{V}x{H}-w{w}-{kind}-r{rows}", V, H, B, [(kind, 6 if kind == "mix" else 4)], groups,
+                                 opts={"chain_rows": rows}, rows=rows, Dz=(V - w - 7 if kind == "mix" else None), seed=91 + w, width=w))
+        out.append(_case("wide", f"{V}x{H}-w{w}-r2-pair", V, H, 5, [("mix", 6), ("vmode2", 4)], groups, opts={"chain_rows": 2}, rows=2,
+                         seed=92 + w, width=w))
+    for V, admitted in zip(lds_edge(GROUP_WMAX), (True, False)):
+        out.append(_case("wide", f"lds-{V}x48-g{GROUP_WMAX}", V, 48, 3, [("mix", 3)], ((V - GROUP_WMAX, V),), seed=93, width=GROUP_WMAX,
+                         admitted=admitted))
+    return out
+
+
 @functools.lru_cache(maxsize=None)
 def _all():
-    cs = group_rows() + group_auto() + group_fast() + group_geometry() + group_gemm() + group_lds() + group_steps() + group_pitch()
+    cs = (group_rows() + group_auto() + group_fast() + group_geometry() + group_gemm() + group_lds() + group_steps() + group_pitch()
+          + group_wide())
     assert len({c["id"] for c in cs}) == len(cs), "duplicate case id"
     return tuple(cs)
 

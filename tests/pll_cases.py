@@ -16,6 +16,9 @@ CASES = {
     "one_tile": (64, 64, 1, ()),                   # whole tiles only, a single row
     "group_end": (47, 24, 9, ((40, 47),)),         # a group ending at V
     "two_groups": (60, 40, 6, ((10, 13), (50, 60))),
+    "k65": (90, 12, 5, ((25, 90),)),               # K = 65 labels: lane 0 of pll_rows_finish takes j = 0 and 64; the ones are counted in two trips
+    "k256": (280, 12, 5, ((24, 280),)),            # K = 256, the widest group: four trips of every 64-lane loop
+    "four": (150, 12, 6, ((0, 5), (60, 133), (133, 140), (147, 150))),      # four groups: one at column 0, two sharing a boundary, one ending at V
 }
 SCALES = (0.1, 1.0)
 TILE_COLS, TILE_ROWS, CHUNK = 16, 64, 128

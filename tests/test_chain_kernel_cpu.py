@@ -128,6 +128,25 @@ def test_table_covers_every_path():
     assert {c["mode"] for c in cs} == {"parity", "fast"}
 
 
+def test_wide_group_rows_reach_both_widths_every_schedule_and_the_lds_edge_of_a_256_wide_group():
+    wide = CC.cases("wide")
+    chains = [c for c in wide if "admitted" not in c]
+    for w in (33, 256):
+        mine = [c for c in chains if c["width"] == w]
+        assert {(c["chains"][0]["kind"], c["rows"]) for c in mine if len(c["chains"]) == 1} == {(k, r) for k in ("mix", "noisy", "vmode2") for r in (2, 16)}
+        assert sum(len(c["chains"]) == 2 for c in mine) == 1 and all(c["groups"][0][1] - c["groups"][0][0] == w for c in mine)
+        assert all(CC.expected(c)[0] in (KERNEL, PAIR) and CC.expected(c)[1] == c["rows"] for c in mine)
+    assert 33 > 32 and CC.GROUP_WMAX == 256
+    # the admission edge at gw = 256, from kernel_ok alone: both gw terms of the byte count are at their largest
+    lo, hi = CC.lds_edge(256)
+    assert hi == lo + 1 and CC.lds_bytes(lo, 48, 256, "parity") <= CC.K4_LDS_BYTES < CC.lds_bytes(hi, 48, 256, "parity")
+    assert (CC.K4_ROWS * 257 * 4, (CC.K4_ROWS // 2) * 256 * 8) == (16448, 16384)
+    edge = {c["V"]: c for c in wide if "admitted" in c}
+    assert set(edge) == {lo, hi} and edge[lo]["admitted"] and not edge[hi]["admitted"]
+    assert CC.expected(edge[lo])[0] == KERNEL and CC.expected(edge[hi])[0] == PER_LAUNCH
+    assert lo > CC.lds_edge(5)[0] - 300 and CC.lds_edge(5)[0] > lo      # a narrow group is admitted further out
+
+
 def test_lds_byte_count_puts_the_limit_shapes_on_their_side():
     L = CC.K4_LDS_BYTES
     assert CC.lds_bytes(1024, 352, 0, "parity") == 155008 <= L and CC.lds_bytes(1024, 352, 5, "parity") == L      # the group case fills it

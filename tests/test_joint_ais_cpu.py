@@ -98,6 +98,14 @@ def test_pinned_parity_seeds_keep_their_margins(name):
         assert (v[:, s:e].sum(1) == 1).all()
 
 
+def test_four_group_row_has_a_256_wide_group_and_keeps_the_wide_group_margin():
+    c = Cs.case(Cs.GROUPS, "four256")
+    assert [e - s for s, e in c["groups"]] == [5, 256, 14, 1] and c["groups"][0][0] == 0 and c["groups"][3][1] == c["V"]
+    _, v, m, cm = _twin(c)
+    assert m >= Cs.MARGIN and cm >= Cs.FOUR256_CAT_MARGIN >= Cs.MARGIN
+    assert len({int(i) for i in v[:, 20:276].argmax(1)}) > 1          # the wide group's picks are not all one column
+
+
 # ---- 2. host logic on the test double ---------------------------------------------------------------------------------
 def _sched_view(sched):
     return [(k, n if k == "u" else None) for k, n in sched]

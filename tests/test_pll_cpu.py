@@ -118,6 +118,22 @@ def test_twin_marks_rows_that_are_not_states():
     assert np.array_equal(site[keep], clean[keep]) and np.array_equal(tot[keep], clean_tot[keep])
 
 
+def test_twin_marks_a_wide_group_with_two_distant_ones_or_none():
+    c = P.case("k256", 1.0)
+    (s, e), = c["groups"]
+    v = c["v"].copy()
+    v[1, s:e] = 0.0
+    v[1, s + 3] = v[1, s + 203] = 1.0                                   # more than 64 columns apart
+    v[3, s:e] = 0.0                                                     # no one at all
+    site, tot = O.sites(c["W"], c["b"], c["c"], v, c["groups"])
+    clean, clean_tot = O.sites(c["W"], c["b"], c["c"], c["v"], c["groups"])
+    assert np.isnan(tot[[1, 3]]).all() and np.isnan(site[[1, 3]]).all()
+    keep = np.delete(np.arange(c["N"]), [1, 3])
+    assert np.array_equal(site[keep], clean[keep]) and np.array_equal(tot[keep], clean_tot[keep])
+    # the new rows are what they are named for
+    assert [e - s for s, e in P.CASES["k65"][3]] == [65] and [e - s for s, e in P.CASES["k256"][3]] == [256] and len(P.CASES["four"][3]) == 4
+
+
 # ---- 2. the kernel's formula against the twin -------------------------------------------------------------------------
 @pytest.mark.parametrize("scale", P.SCALES)
 @pytest.mark.parametrize("name", list(P.CASES))

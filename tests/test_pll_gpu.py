@@ -104,6 +104,23 @@ def test_rows_that_are_not_states_are_nan_and_only_they(eng):
     assert torch.isnan(p3[2]) and torch.isnan(s3[2]).all() and torch.isfinite(p3[[0, 1, 3, 4]]).all()
 
 
+def test_a_wide_group_with_two_distant_ones_or_none_is_nan(eng):
+    """K = 256: the ones of a group are counted by 64 lanes in four trips -- two ones more than 64 columns apart fall to different
+    trips (and, 200 apart, to different lanes); a group with no one at all must not pass as a state either."""
+    c = P.case("k256", 1.0)
+    (s, e), = c["groups"]
+    r = device_rbm(c)
+    pll, site = _run(eng, c, r=r)
+    v = c["v"].copy()
+    v[1, s:e] = 0.0
+    v[1, s + 3] = v[1, s + 203] = 1.0
+    v[3, s:e] = 0.0
+    p2, s2 = _run(eng, c, v=dev(v), r=r)
+    keep = torch.tensor([n not in (1, 3) for n in range(c["N"])], device=DEV)
+    assert torch.isnan(p2[~keep]).all() and torch.isnan(s2[~keep]).all()
+    assert torch.equal(p2[keep], pll[keep]) and torch.equal(s2[keep], site[keep])
+
+
 # ---- 5. errors --------------------------------------------------------------------------------------------------------
 def _raw(eng, r, x, N=None, ldv=None, lds=None, with_site=True, null_pll=False):
     """The export called directly on sentinel-filled outputs -> (EngineError message or None, out_pll, out_site)."""

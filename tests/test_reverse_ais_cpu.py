@@ -97,6 +97,23 @@ def test_rows_that_are_not_states_are_nan_and_only_they():
     assert np.isnan(lme[[0, 2]]).all() and np.isfinite(lme[1]) and np.isnan(ess[[0, 2]]).all() and np.isfinite(ess[1])
 
 
+def test_four_group_row_keeps_its_margins_and_marks_a_wide_group_with_two_distant_ones_or_none():
+    c = Cs.case(Cs.REVERSE, "four256")
+    assert [e - s for s, e in c["groups"]] == [5, 256, 14, 1]
+    logw, u1, m, cm = A.reverse_ais_logw(c["W"], c["b"], c["c"], c["bA"], c["groups"], c["betas"], c["x"], PhiloxStream(c["seed"]))
+    print(f"four256: Bernoulli margin {m:.3g}, categorical margin {cm:.3g}")
+    assert m >= Cs.MARGIN and cm >= Cs.FOUR256_CAT_MARGIN >= Cs.CAT_MARGIN and np.isfinite(logw).all()
+    for s, e in c["groups"]:
+        assert (u1[:, s:e].sum(1) == 1).all()
+    s, e = c["groups"][1]
+    x = c["x"].copy()
+    x[1, s:e] = 0.0
+    x[1, s + 3] = x[1, s + 203] = 1.0                                   # more than 64 columns apart
+    x[4, s:e] = 0.0                                                     # no one at all
+    bad, _, _, _ = A.reverse_ais_logw(c["W"], c["b"], c["c"], c["bA"], c["groups"], c["betas"], x, PhiloxStream(c["seed"]))
+    assert np.isnan(bad[[1, 4]]).all() and np.isfinite(np.delete(bad, [1, 4])).all()
+
+
 # ---- 2. host logic of imdbn/utils/likelihood.py on the test double ----------------------------------------------------
 @pytest.mark.parametrize("name", ["tiny_bA", "group", "one"])
 def test_schedule_is_what_the_double_consumed(double, name):

@@ -37,7 +37,7 @@ def _close(got, want, H, what):
 # wide: the constructor's padded pitch (float4 weight rows: k2_stream reads the hidden bit plane); wide_bA: rows 301 floats apart
 # (unaligned: the fused K2 reads the bit plane); one: K = 1; rows70: two 64-row chunks
 @pytest.mark.parametrize("name,pitch", [("tiny", None), ("tiny_bA", None), ("mid", None), ("mid_bA", 75), ("wide", None), ("wide_bA", 301),
-                                        ("group", None), ("one", None), ("rows70", None)])
+                                        ("group", None), ("one", None), ("rows70", None), ("four256", None)])
 def test_parity_with_the_twin(eng, name, pitch):
     from imdbn import engine as E
     from imdbn.engine import rng as R
@@ -232,6 +232,21 @@ def test_rows_that_are_not_states_are_nan_and_only_they(eng):
     x[2, 19] = 0.5
     lw = eng.reverse_ais(device_rbm(c), torch.from_numpy(x).to(DEV), c["betas"], E.PhiloxRng(1)).cpu().numpy()
     assert np.isnan(lw[2]) and np.isfinite(np.delete(lw, 2)).all()
+
+
+def test_a_wide_group_with_two_distant_ones_or_none_is_nan(eng):
+    """Four groups, one 256 wide: rais_load_v counts a group's ones with lanes striding 64 -- two ones 200 columns apart, and a
+    group with none, must both be marked; the other rows are those of the clean run."""
+    from imdbn import engine as E
+    c, logw, _, _, _ = _twin("four256")
+    s, e = c["groups"][1]
+    x = c["x"].copy()
+    x[1, s:e] = 0.0
+    x[1, s + 3] = x[1, s + 203] = 1.0
+    x[4, s:e] = 0.0
+    lw = eng.reverse_ais(device_rbm(c), torch.from_numpy(x).to(DEV), c["betas"], E.PhiloxRng(c["seed"]), base_vis_bias=base_bias(c)).cpu().numpy()
+    assert np.isnan(lw[[1, 4]]).all() and np.isfinite(np.delete(lw, [1, 4])).all()
+    _close(np.delete(lw, [1, 4]), np.delete(logw, [1, 4]), c["H"], "good rows next to NaN rows")
 
 
 # ---- 6. nothing else moved --------------------------------------------------------------------------------------------
