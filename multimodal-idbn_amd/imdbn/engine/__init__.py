@@ -27,7 +27,11 @@ _rng = None
 
 
 def set_engine_for_testing(engine):
-    """Install (or with ``None`` remove) a test double implementing the HipEngine interface."""
+    """Install (or with ``None`` remove) a test double implementing the HipEngine interface.
+
+    ``HipEngine`` is the definition: the models and utils call the engine unconditionally and never ask it what it can do, so a
+    double must implement every call the code under test makes, with ``HipEngine``'s parameter names and order
+    (tests/test_engine_contract_cpu.py checks both sides; DESIGN "The engine contract" lists the calls)."""
     global _override
     _override = engine
 

@@ -53,7 +53,6 @@ def _on(t: Optional[torch.Tensor], dev, dtype) -> Optional[torch.Tensor]:
 
 class HipEngine:
     name = "hip"
-    fused_forward = True        # cd_step(forward=True): imdbn_cd_opts.fwd_out
 
     def __init__(self):
         self._lib = N.lib()
@@ -846,7 +845,7 @@ class HipEngine:
         a = [x]
         for rbm in rec_layers:
             cur = a[-1] if len(a) > 1 else data             # the caller's tensor carries the 0/1 tag, its fp32 form may be a copy
-            out = self.forward(rbm, cur, data_binary=self.binary_hint(cur)) if hasattr(self, "forward") else self.prop_up(rbm, cur)
+            out = self.forward(rbm, cur, data_binary=self.binary_hint(cur))
             out._imdbn_binary = False
             a.append(out)
         down = list(gen_layers) + [top]                     # the layer a top-down pass goes through below level l + 1
@@ -917,7 +916,7 @@ class HipEngine:
         a = [_f32c(data)]
         for rbm in layers:
             cur = a[-1] if len(a) > 1 else data             # the caller's tensor carries the 0/1 tag, its fp32 form may be a copy
-            out = self.forward(rbm, cur, data_binary=self.binary_hint(cur)) if hasattr(self, "forward") else self.prop_up(rbm, cur)
+            out = self.forward(rbm, cur, data_binary=self.binary_hint(cur))
             out._imdbn_binary = False
             a.append(out)
         g = _on(gt, a[L].device, torch.int32)

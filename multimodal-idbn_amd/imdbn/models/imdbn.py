@@ -360,11 +360,7 @@ class iMDBN(nn.Module):
             jr._mu_pull = None
         gibbs = dict(v_known=v_known, known_mask=km, n_steps=steps, sample_h=False, sample_v=False)
         nmf = dict(v_known=vk_y, known_mask=km_y, n_steps=steps, T0=3.0, T1=1.0, sigma0=0.9, hot_frac=0.7, sharpen_last=3, T_cold_plus=0.9)
-        if hasattr(jr, "_chain_pair"):
-            v_img2txt, v_chain = jr._chain_pair(gibbs, nmf)
-        else:
-            v_img2txt = jr.conditional_gibbs(**gibbs)
-            v_chain = jr.noisy_meanfield_annealed(**nmf)
+        v_img2txt, v_chain = jr._chain_pair(gibbs, nmf)
         p_y_given_img = v_img2txt[:, Dz:]
         km = km_y
         if getattr(self, "live_best_of_k", False):

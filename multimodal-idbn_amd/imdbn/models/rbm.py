@@ -125,7 +125,7 @@ class RBM(nn.Module):
     def forward(self, v: torch.Tensor, T: float = 1.0) -> torch.Tensor:
         """p(h|v) = sigmoid((v W + c)/max(1e-6,T))   (rbm.py:92)."""
         eng = self._eng()
-        if T == 1.0 and hasattr(eng, "forward") and hasattr(eng, "binary_hint"):
+        if T == 1.0:
             # the same path as the forward fused into train_epoch(return_forward=True): bit-identical results
             out = eng.forward(self, self._in(v), data_binary=eng.binary_hint(v))
         else:
@@ -234,35 +234,29 @@ class RBM(nn.Module):
         # 0/1 batches (binary images) are read as bit planes by the positive phase; what a batch contains is found out on the
         # device (imdbn_cd_opts.data_binary = unknown) unless the caller's tensor object carries a loader's tag (``_in`` makes a
         # fresh view every call)
-        kw = {"data_binary": eng.binary_hint(data)} if hasattr(eng, "binary_hint") else {}
+        hint = eng.binary_hint(data)
         dp = _E.dp
         if dp.active():
-            B = x.size(0)
+            B, world = x.size(0), dp.world_size()
             dp.validate_rows(B, x.device)
-            ret = (lambda loss: (loss, self.forward(data))) if return_forward else (lambda loss: loss)
-            if dp.mode() == "factors" and hasattr(eng, "factor_mode_ok") and eng.factor_mode_ok(self, B):
-                # exchange the factors (~7 MB per rank at 10000 x 1500; 2 MB in wire form) instead of the fp32 statistics (60 MB)
-                world = dp.world_size()
-                if hasattr(eng, "cd_factors_wire"):
-                    # three calls per step: CD pass into the wire form (the visible planes as bits: the sample always, the data
-                    # when declared binary; with the next-batch hint), all-gather, update
-                    binary = dp.binary_data()
-                    wire = eng.cd_factors_wire(self, x, CD, rng, binary, next_data=next_data, **kw)
-                    wires = dp.all_gather_blocks(eng.compact_gather_buffer(self, B, world, binary), wire)
-                    return ret(eng.apply_wire(self, wires, B, B * world, binary, lr, mom))
-                block = eng.cd_factors(self, x, CD, rng, **kw)
-                gathered = dp.all_gather_blocks(eng.gather_buffer(self, B, world), block)
-                return ret(eng.apply_factors(self, gathered, B, B * world, lr, mom))
-            buf = eng.packed_buffer(self) if hasattr(eng, "packed_buffer") else None
-            packed = eng.cd_stats(self, x, CD, rng, out=buf, **kw, **({"next_data": next_data} if (next_data is not None and hasattr(eng, "prefetch_ok")) else {}))
-            dp.all_reduce_sum(packed)
-            return ret(eng.apply_delta(self, packed, B * dp.world_size(), lr, mom))
-        if return_forward and getattr(eng, "fused_forward", False):
-            loss, h = eng.cd_step(self, x, lr, mom, CD, rng, next_data=next_data, forward=True, **kw)
-            h._imdbn_binary = False
-            return loss, h
-        loss = eng.cd_step(self, x, lr, mom, CD, rng, next_data=next_data, **kw)
-        return (loss, self.forward(data)) if return_forward else loss
+            if dp.mode() == "factors" and eng.factor_mode_ok(self, B):
+                # exchange the factors (~7 MB per rank at 10000 x 1500; 2 MB in wire form) instead of the fp32 statistics (60 MB).
+                # Three calls per step: CD pass into the wire form (the visible planes as bits: the sample always, the data when
+                # declared binary; with the next-batch hint), all-gather, update
+                binary = dp.binary_data()
+                wire = eng.cd_factors_wire(self, x, CD, rng, binary, next_data=next_data, data_binary=hint)
+                wires = dp.all_gather_blocks(eng.compact_gather_buffer(self, B, world, binary), wire)
+                loss = eng.apply_wire(self, wires, B, B * world, binary, lr, mom)
+            else:
+                packed = eng.cd_stats(self, x, CD, rng, out=eng.packed_buffer(self), data_binary=hint, next_data=next_data)
+                dp.all_reduce_sum(packed)
+                loss = eng.apply_delta(self, packed, B * world, lr, mom)
+            return (loss, self.forward(data)) if return_forward else loss
+        if not return_forward:
+            return eng.cd_step(self, x, lr, mom, CD, rng, next_data=next_data, data_binary=hint)
+        loss, h = eng.cd_step(self, x, lr, mom, CD, rng, next_data=next_data, data_binary=hint, forward=True)
+        h._imdbn_binary = False
+        return loss, h
 
     # ---- persistent chains: PCD-k and parallel tempering (extension) --------------------
     @torch.no_grad()
@@ -287,8 +281,7 @@ class RBM(nn.Module):
         lr, mom = self._lr_mom(epoch)
         eng, x = self._eng(), self._in(data)
         particles, k = self._negative_chains(eng, x, betas, CD, "train_epoch_persistent")
-        kw = {"data_binary": eng.binary_hint(data)} if hasattr(eng, "binary_hint") else {}
-        return eng.pcd_step(self, x, particles, lr, mom, k, self._rng(x.size(0)), monitor=monitor, **kw)
+        return eng.pcd_step(self, x, particles, lr, mom, k, self._rng(x.size(0)), data_binary=eng.binary_hint(data), monitor=monitor)
 
     def _negative_chains(self, eng, x: torch.Tensor, betas, CD: int, who: str):
         """The persistent chains behind one update on the batch ``x`` (train_epoch_persistent, train_epoch_centered): creates
@@ -358,9 +351,8 @@ class RBM(nn.Module):
             mu = self._ctr_mu = torch.zeros(self.num_visible, dtype=torch.float32, device=x.device)
             lam = self._ctr_lam = torch.zeros(self.num_hidden, dtype=torch.float32, device=x.device)
             slide = 1.0
-        kw = {"data_binary": eng.binary_hint(data)} if hasattr(eng, "binary_hint") else {}
         return eng.centered_step(self, x, particles, lr, mom, k, self._rng(x.size(0)), mu, lam, float(slide),
-                                 1 if offsets == "enhanced" else 0, monitor=monitor, **kw)
+                                 1 if offsets == "enhanced" else 0, data_binary=eng.binary_hint(data), monitor=monitor)
 
     def centering_offsets(self):
         """``(mu [V], lam [H])``, the offsets of train_epoch_centered as they stand (the live tensors), or None before its first call."""
@@ -479,12 +471,8 @@ class RBM(nn.Module):
     @torch.no_grad()
     def _chain_pair(self, gibbs: dict, nmf: dict):
         """``conditional_gibbs(**gibbs)`` and ``noisy_meanfield_annealed(**nmf)`` (run in that order by the reference,
-        imdbn.py:424-449) as ONE engine call where the engine offers it: the two chains are independent (they share only the
-        read-only weights), so they run side by side in one launch.  Same draws in the same order, same results as the two calls.
-        Returns (v_gibbs, v_nmf)."""
-        eng = self._eng()
-        if not hasattr(eng, "chain_pair"):
-            return self.conditional_gibbs(**gibbs), self.noisy_meanfield_annealed(**nmf)
+        imdbn.py:424-449) as ONE engine call: the two chains are independent (they share only the read-only weights), so they
+        run side by side in one launch.  Same draws in the same order, same results as the two calls.  Returns (v_gibbs, v_nmf)."""
         g = dict(n_steps=30, sample_h=False, sample_v=False); g.update(gibbs)
         n = dict(n_steps=72, T0=3.0, T1=1.0, sigma0=0.9, hot_frac=0.7, sharpen_last=3, T_cold_plus=0.9); n.update(nmf)
         steps_g = [_step(sample_h=g["sample_h"], vmode=1 if g["sample_v"] else 0, clamp=True) for _ in range(int(g["n_steps"]))]
@@ -493,7 +481,7 @@ class RBM(nn.Module):
         steps_n = self._nmf_steps(n["n_steps"], n["T0"], n["T1"], n["sigma0"], n["sharpen_last"], n["T_cold_plus"], eta0 if mu is not None else 0.0)
         a = {"v_known": self._in(g["v_known"]), "mask": self._in(g["known_mask"]), "steps": steps_g}
         b = {"v_known": self._in(n["v_known"]), "mask": self._in(n["known_mask"]), "steps": steps_n, "mu": mu}
-        return eng.chain_pair(self, a, b, self._rng(a["v_known"].size(0)))
+        return self._eng().chain_pair(self, a, b, self._rng(a["v_known"].size(0)))
 
     # ---- clamped CD (rbm.py:402-483) -------------------------------------------------------------
     @torch.no_grad()
@@ -527,8 +515,7 @@ class RBM(nn.Module):
             # this rank's rows of the global batch; one all-reduce of the packed statistics
             B = vk.size(0)
             dp.validate_rows(B, vk.device)
-            buf = eng.packed_buffer(self) if hasattr(eng, "packed_buffer") else None
-            packed = eng.clamped_stats(self, vk, km, init, mu, CD, sample_h, sample_v, reclamp_negative, rng, out=buf)
+            packed = eng.clamped_stats(self, vk, km, init, mu, CD, sample_h, sample_v, reclamp_negative, rng, out=eng.packed_buffer(self))
             dp.all_reduce_sum(packed)
             return eng.apply_delta(self, packed, B * dp.world_size(), aux_lr_mult * lr, mom, sparsity=False)
         return eng.clamped_step(self, vk, km, init, mu, aux_lr_mult * lr, mom, CD, sample_h, sample_v, reclamp_negative, rng)

@@ -63,7 +63,7 @@ def step(st, z, K, gt, lr, mom, wd):
 
 class LabelGradOracleEngine(LikelihoodOracleEngine):
     """The likelihood test double plus ``label_step`` from the twin (the RBM's fp32 tensors updated in place).  ``calls`` records
-    ("label_step", rows, lr, mom) and the names of the generative updates, in call order."""
+    ("label_step", rows, lr, mom) and ("clamped_step",) next to the base double's ("cd_step", ...), in call order."""
 
     def label_step(self, rbm, z, K, gt, lr, mom):
         self.calls.append(("label_step", int(z.shape[0]), float(lr), float(mom)))
@@ -73,10 +73,6 @@ class LabelGradOracleEngine(LikelihoodOracleEngine):
         for k, arr in st.items():
             arr[...] = new[k].astype(np.float32)
         return torch.from_numpy(logp)
-
-    def cd_step(self, *a, **k):
-        self.calls.append(("cd_step",))
-        return super().cd_step(*a, **k)
 
     def clamped_step(self, *a, **k):
         self.calls.append(("clamped_step",))

@@ -14,6 +14,7 @@ import torch
 
 import oracle.rbm_oracle as O
 from oracle.draws import PhiloxStream
+from imdbn.engine.hip_engine import HipEngine
 from imdbn.engine.rng import PhiloxRng, ReplayRng
 
 F32 = np.float32
@@ -78,6 +79,12 @@ class OracleEngine:
             (s.uniform if kind == "u" else s.normal)((B, n))
         s.done()
 
+    binary_hint = staticmethod(HipEngine.binary_hint)       # pure host logic: the tensor's tag -> a native.DATA_* code
+
+    def forward(self, rbm, v, data_binary=None):            # the hint changes no result
+        self.calls.append(("forward", tuple(v.shape)))
+        return self.prop_up(rbm, v)
+
     def prop_up(self, rbm, v, T=1.0, sample=False, rng=None):
         st = self._state(rbm)
         p = O.forward(st, _np(v), T)
@@ -107,48 +114,62 @@ class OracleEngine:
         s.done()
         return tuple(self._t(x) for x in out)
 
-    def cd_step(self, rbm, data, lr, mom, cd_k, rng, next_data=None):       # the prefetch hint changes no result
+    def cd_step(self, rbm, data, lr, mom, cd_k, rng, next_data=None, data_binary=None, forward=False):
+        """Neither hint changes a result; ``forward``: also ``forward(data)`` under the updated weights (imdbn_cd_opts.fwd_out)."""
+        self.calls.append(("cd_step", tuple(data.shape), int(cd_k), bool(forward)))
         st = self._state(rbm, True)
         s = _Src(rng)
         stats = O.cd_statistics(st, _np(data), cd_k, s)
         s.done()
         O.apply_cd_update(st, stats, lr, mom, stats["n"], st.sparsity)
-        return self._t(np.array(stats["sq_err"].mean(dtype=F32))).reshape(())
+        loss = self._t(np.array(stats["sq_err"].mean(dtype=F32))).reshape(())
+        return (loss, self.forward(rbm, data)) if forward else loss
 
     # data-parallel split: same packed layout as include/imdbn_engine.h
     def packed_floats(self, V, H):
         return ((V * H + 2 * H + V + 1) + 3) // 4 * 4
 
-    def cd_stats(self, rbm, data, cd_k, rng, out=None):
+    def packed_buffer(self, rbm):
+        return torch.zeros(self.packed_floats(*rbm.W.shape), dtype=torch.float32)
+
+    def _packed(self, st, x, sq_err, out=None):
+        """The statistics `x` and the summed squared error in the packed layout, written into `out` when there is one."""
+        V, H = st.W.shape
+        p = np.zeros(self.packed_floats(V, H), F32)
+        o = V * H
+        p[:o] = (x["pos_assoc"] - x["neg_assoc"]).ravel()
+        p[o:o + H] = x["pos_h_sum"] - x["neg_h_sum"]
+        p[o + H:o + H + V] = x["data_sum"] - x["v_sum"]
+        p[o + H + V:o + 2 * H + V] = x["pos_h_sum"]
+        p[o + 2 * H + V] = sq_err
+        return self._t(p) if out is None else out.copy_(self._t(p))
+
+    def _cd_packed(self, rbm, data, cd_k, rng, out=None):
         st = self._state(rbm)
         s = _Src(rng)
         x = O.cd_statistics(st, _np(data), cd_k, s)
         s.done()
-        V, H = st.W.shape
-        p = np.zeros(self.packed_floats(V, H), F32)
-        p[:V * H] = (x["pos_assoc"] - x["neg_assoc"]).ravel()
-        o = V * H
-        p[o:o + H] = x["pos_h_sum"] - x["neg_h_sum"]
-        p[o + H:o + H + V] = x["data_sum"] - x["v_sum"]
-        p[o + H + V:o + 2 * H + V] = x["pos_h_sum"]
-        p[o + 2 * H + V] = x["sq_err"].sum(dtype=F32)
-        return self._t(p)
+        return self._packed(st, x, x["sq_err"].sum(dtype=F32), out)
 
-    # ---- factor exchange (host-logic stand-in: a rank's "factor block" is its packed statistics as bytes) ----
+    def cd_stats(self, rbm, data, cd_k, rng, out=None, data_binary=None, next_data=None):
+        self.calls.append(("cd_stats", tuple(data.shape), int(cd_k)))
+        return self._cd_packed(rbm, data, cd_k, rng, out)
+
+    # ---- factor exchange (host-logic stand-in: a rank's "wire block" is its packed statistics as bytes) ----
     def factor_mode_ok(self, rbm, B) -> bool:
         return 1 <= B <= 64 and not (getattr(rbm, "softmax_groups", None) or [])
 
-    def cd_factors(self, rbm, data, cd_k, rng):
-        return self.cd_stats(rbm, data, cd_k, rng).contiguous().view(torch.uint8)
+    def cd_factors_wire(self, rbm, data, cd_k, rng, binary, next_data=None, data_binary=None):
+        self.calls.append(("cd_factors_wire", tuple(data.shape), int(cd_k), bool(binary)))
+        return self._cd_packed(rbm, data, cd_k, rng).view(torch.uint8)
 
-    def gather_buffer(self, rbm, B, world):
-        V, H = rbm.W.shape
-        return torch.empty(world, 4 * self.packed_floats(V, H), dtype=torch.uint8)
+    def compact_gather_buffer(self, rbm, B, world, binary):
+        return torch.empty(world, 4 * self.packed_floats(*rbm.W.shape), dtype=torch.uint8)
 
-    def apply_factors(self, rbm, gathered, rows_per_rank, global_B, lr, mom):
-        assert gathered.dtype == torch.uint8 and gathered.dim() == 2
-        packed = gathered.view(torch.float32).sum(0)
-        return self.apply_delta(rbm, packed, global_B, lr, mom)
+    def apply_wire(self, rbm, wires, rows_per_rank, global_B, binary, lr, mom):
+        self.calls.append(("apply_wire", tuple(wires.shape), int(rows_per_rank), int(global_B), bool(binary)))
+        assert wires.dtype == torch.uint8 and wires.dim() == 2
+        return self.apply_delta(rbm, wires.view(torch.float32).sum(0), global_B, lr, mom)
 
     def apply_delta(self, rbm, packed, global_B, lr, mom, sparsity=None):
         st = self._state(rbm, True)
@@ -210,6 +231,19 @@ class OracleEngine:
         s.done()
         return self._t(v)
 
+    def chain_pair(self, rbm, a, b, rng):
+        """The two chains one after the other on ONE draw source: a, then b (DESIGN: run_chain_pair)."""
+        self.calls.append(("chain_pair", len(a["steps"]), len(b["steps"])))
+        st = self._state(rbm)
+        s = _Src(rng)
+        out = []
+        for ch in (a, b):
+            mu = ch.get("mu")
+            out.append(self._t(self._run_chain(st, _np(ch["v_known"]), _np(ch["mask"]), ch["steps"], s, ch.get("init_uniform", True),
+                                               None if mu is None else _np(mu))))
+        s.done()
+        return tuple(out)
+
     def _clamped_stats(self, st, v_known, mask, init_steps, mu, cd_k, sample_h, sample_v, reclamp, rng):
         s = _Src(rng)
         vk, km = _np(v_known), _np(mask)
@@ -235,12 +269,4 @@ class OracleEngine:
     def clamped_stats(self, rbm, v_known, mask, init_steps, mu, cd_k, sample_h, sample_v, reclamp, rng, out=None):
         st = self._state(rbm)
         x, v_plus, v_neg = self._clamped_stats(st, v_known, mask, init_steps, mu, cd_k, sample_h, sample_v, reclamp, rng)
-        V, H = st.W.shape
-        p = np.zeros(self.packed_floats(V, H), F32)
-        o = V * H
-        p[:o] = (x["pos_assoc"] - x["neg_assoc"]).ravel()
-        p[o:o + H] = x["pos_h_sum"] - x["neg_h_sum"]
-        p[o + H:o + H + V] = x["data_sum"] - x["v_sum"]
-        p[o + H + V:o + 2 * H + V] = x["pos_h_sum"]
-        p[o + 2 * H + V] = ((v_plus - v_neg) ** 2).sum(dtype=F32)
-        return self._t(p)
+        return self._packed(st, x, ((v_plus - v_neg) ** 2).sum(dtype=F32), out)

@@ -218,16 +218,6 @@ def test_data_parallel_raises(double, monkeypatch):
 
 
 # ---- 5. iDBN.train -------------------------------------------------------------------------------------------------------------
-class _Logged(OracleEngine):
-    """The plain double with a log of the engine methods iDBN.train reaches."""
-
-    def __getattribute__(self, name):
-        v = object.__getattribute__(self, name)
-        if callable(v) and not name.startswith("_") and name != "calls":
-            object.__getattribute__(self, "calls").append(name)
-        return v
-
-
 def _idbn(params, eng):
     from torch.utils.data import DataLoader, TensorDataset
     from imdbn.models import iDBN
@@ -246,16 +236,17 @@ def _idbn(params, eng):
 
 
 def test_idbn_train_without_the_key_is_todays_call_sequence():
-    """Without params["CENTERED"] an engine double that lacks the new call is enough, and the methods iDBN.train reaches are, in
-    order, the parent's: per batch one cd_step per layer with the lower layer's forward between them."""
+    """Without params["CENTERED"] an engine double that lacks the new call is enough, and the engine calls iDBN.train makes are, in
+    order, the parent's: per batch one cd_step per layer, the lower layer's with its forward fused in (the double's cd_step
+    records the forward it runs for ``forward=True``)."""
     try:
-        eng = _Logged()
+        eng = OracleEngine()
         plain = _idbn({}, eng)
         off = _idbn({"CENTERED": False, "CENTERED_OFFSETS": "enhanced"}, PcdOracleEngine())
     finally:
         E.set_engine_for_testing(None)
-    per_batch = ["cd_step", "prop_up", "cd_step"]
-    assert eng.calls == per_batch * 3 * 2                               # 20 rows in batches of 8: three per epoch, two epochs
+    per_batch = lambda rows: [("cd_step", (rows, 12), 1, True), ("forward", (rows, 12)), ("cd_step", (rows, 7), 1, False)]
+    assert eng.calls == (per_batch(8) + per_batch(8) + per_batch(4)) * 2        # 20 rows in batches of 8: three per epoch, two epochs
     for a, b in zip(plain.layers, off.layers):
         assert _same(a, b) and b.centering_offsets() is None
     assert all(torch.equal(a, b) for a, b in zip(plain.loss_history, off.loss_history))
@@ -270,11 +261,14 @@ def test_idbn_train_with_the_key_routes_every_layer_through_the_centered_update(
         both = _idbn({"CENTERED": 0.2, "CENTERED_OFFSETS": "enhanced", "PERSISTENT": True}, e2)
     finally:
         E.set_engine_for_testing(None)
-    assert [c[0] for c in e1.calls] == ["centered_step"] * 12 and all(c[1] is None for c in e1.calls)
-    assert [c[3] for c in e1.calls[:4]] == [1.0, 1.0, 0.01, 0.01] and {c[4] for c in e1.calls} == {0}
+    # per batch: the lower layer's update, its forward (the engine's T = 1 forward call), the upper layer's update
+    assert [c[0] for c in e1.calls] == ["centered_step", "forward", "centered_step"] * 6
+    s1, s2 = ([c for c in e.calls if c[0] == "centered_step"] for e in (e1, e2))
+    assert len(s1) == 12 and all(c[1] is None for c in s1)
+    assert [c[3] for c in s1[:4]] == [1.0, 1.0, 0.01, 0.01] and {c[4] for c in s1} == {0}
     assert all(r.centering_offsets() is not None and "_pcd" not in r.__dict__ for r in on.layers)
     assert not torch.equal(on.layers[0].W.data, plain.layers[0].W.data)
     assert len(on.loss_history) == 2 and torch.isfinite(on.loss_history[0]).all()
     # persistent chains only where the input is binary: the first layer; the second keeps CD phases
     assert "_pcd" in both.layers[0].__dict__ and "_pcd" not in both.layers[1].__dict__
-    assert [(c[1], c[3], c[4]) for c in e2.calls[:4]] == [((8, 12), 1.0, 1), (None, 1.0, 1), ((8, 12), 0.2, 1), (None, 0.2, 1)]
+    assert [(c[1], c[3], c[4]) for c in s2[:4]] == [((8, 12), 1.0, 1), (None, 1.0, 1), ((8, 12), 0.2, 1), (None, 0.2, 1)]

@@ -151,9 +151,9 @@ def _double():
     class Double(OracleEngine):
         calls = 0
 
-        def decode_sqerr(self, layers, z, ref, ref_row=None, chunk=1024):
+        def decode_sqerr(self, idbn_layers, z, ref, ref_row=None, chunk=1024):
             cur = z
-            for rbm in reversed(list(layers)):
+            for rbm in reversed(list(idbn_layers)):
                 cur = self.prop_down(rbm, cur)
             return torch.from_numpy(CO.row_mse(cur.numpy(), ref.numpy()).astype(np.float32))
 

@@ -151,7 +151,9 @@ def test_imdbn_discriminative_step_issues_the_documented_call_sequence_and_match
     n0 = len(double.calls)
     jb = _params(m2.joint_rbm)
     assert m2.discriminative_step(x, torch.from_numpy(yi[:8]), 7, 10, lr_scale=0.5, train_head=False, monitor=False) is None
-    assert double.calls[n0 + 1][5:] == (False, False)
+    # discriminative_step, the two layers' forward (the engine's own call, never prop_up), then the head
+    assert [c[0] for c in double.calls[n0:n0 + 4]] == ["discriminative_step", "forward", "forward", "label_backprop_step"]
+    assert double.calls[n0 + 3][5:] == (False, False)
     assert all(torch.equal(p, q) for p, q in zip(jb, _params(m2.joint_rbm)))
     for r, s in zip(m2.image_idbn.layers, m.image_idbn.layers):
         assert torch.equal(r.W.data, s.W.data)                          # the layers' step does not depend on the head's update

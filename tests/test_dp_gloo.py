@@ -40,7 +40,8 @@ def _worker(rank, world, port, out_dir, mode="allreduce"):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    E.set_engine_for_testing(OracleEngine())
+    eng = OracleEngine()
+    E.set_engine_for_testing(eng)
     E.dp.enable(mode=mode)
     assert E.dp.active() and E.dp.world_size() == world and E.dp.rank() == rank and E.dp.mode() == mode
     r, X = _make(groups=(mode == "allreduce"))
@@ -51,14 +52,15 @@ def _worker(rank, world, port, out_dir, mode="allreduce"):
         shard = torch.from_numpy(X[s, rank * per:(rank + 1) * per])
         losses.append(float(r.train_epoch(shard, 7, 10, CD=2)))
     np.savez(os.path.join(out_dir, f"rank{rank}.npz"), W=r.W.data.numpy(), hb=r.hid_bias.data.numpy(),
-             vb=r.vis_bias.data.numpy(), Wm=r.W_m.numpy(), losses=np.array(losses, np.float32))
+             vb=r.vis_bias.data.numpy(), Wm=r.W_m.numpy(), losses=np.array(losses, np.float32), calls=np.array([c[0] for c in eng.calls]))
     dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("mode", ["allreduce", "factors"])
 def test_two_rank_update_equals_single_rank(tmp_path, mode):
-    """mode "factors": the all-gather exchange of per-rank blocks (the test double's block is its packed statistics;
-    the real factor block is exercised on the GPU by test_factor_exchange_*)."""
+    """mode "factors": the shipped three-call wire path -- ``cd_factors_wire``, the all-gather of the per-rank wire blocks into
+    ``compact_gather_buffer``, ``apply_wire`` -- and never the all-reduce of ``cd_stats`` (the test double's wire block is its
+    packed statistics as bytes; the real wire form is exercised on the GPU by tests/test_exchange_gpu.py)."""
     import socket
     import torch.multiprocessing as mp
     from imdbn import engine as E
@@ -83,6 +85,11 @@ def test_two_rank_update_equals_single_rank(tmp_path, mode):
     b = np.load(tmp_path / "rank1.npz")
     for k in ("W", "hb", "vb", "Wm"):
         np.testing.assert_array_equal(a[k], b[k])          # replicas stay bit-identical
+    for rank_calls in (a["calls"].tolist(), b["calls"].tolist()):
+        if mode == "factors":
+            assert rank_calls == ["cd_factors_wire", "apply_wire"] * STEPS and "cd_stats" not in rank_calls
+        else:
+            assert rank_calls == ["cd_stats"] * STEPS
     from golden_utils import rel_fro
     assert rel_fro(a["W"], r.W.data.numpy()) < 1e-6
     assert rel_fro(a["hb"], r.hid_bias.data.numpy()) < 1e-5

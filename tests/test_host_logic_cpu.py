@@ -59,6 +59,43 @@ def test_energy_utils_host_logic():
     P.case_class_free_energies("cpu")
 
 
+def test_chain_pair_is_the_two_chains_one_after_the_other():
+    """RBM._chain_pair is ONE engine call, ``chain_pair``, and gives what ``conditional_gibbs`` then
+    ``noisy_meanfield_annealed`` give on the same seed, bit for bit, with the same number of draws.  The joint RBM of
+    imdbn_small (28 x 16, one softmax group) with masks that leave columns free and sampled states, so the position of the
+    draw cursor between the two chains matters; the second chain has the mu-pull."""
+    from imdbn.models import RBM
+    fx = P.Fixture("imdbn_small_100_40_20_j16.npz")
+    Dz, K, B = fx.meta["sizes"][-1], fx.meta["K"], 5
+    g = torch.Generator().manual_seed(11)
+
+    def run(pair):
+        r = RBM(Dz + K, fx.meta["joint_hidden"], 0.1, 1e-4, 0.5, softmax_groups=[(Dz, Dz + K)])
+        P.set_params(r, "cpu", fx["joint_W"], fx["joint_hid_bias"], fx["joint_vis_bias"])
+        r._mu_pull = {"mu_k": mu, "eta0": 0.15}
+        eng = OracleEngine()
+        E.set_engine_for_testing(eng)
+        E.manual_seed(9)
+        out = r._chain_pair(gibbs, nmf) if pair else (r.conditional_gibbs(**gibbs), r.noisy_meanfield_annealed(**nmf))
+        return out, E.get_rng().offset, eng.calls
+
+    vk_z, vk_y = torch.zeros(B, Dz + K), torch.zeros(B, Dz + K)
+    vk_z[:, :Dz] = torch.rand(B, Dz, generator=g)
+    vk_y[torch.arange(B), Dz + torch.arange(B) % K] = 1.0
+    km_z, km_y = torch.zeros(B, Dz + K), torch.zeros(B, Dz + K)
+    km_z[:, :Dz - 3] = 1.0                                  # three code columns and the labels stay free
+    km_y[:, Dz:] = 1.0
+    mu = torch.rand(B, Dz, generator=g)
+    gibbs = dict(v_known=vk_z, known_mask=km_z, n_steps=4, sample_h=True, sample_v=True)
+    nmf = dict(v_known=vk_y, known_mask=km_y, n_steps=5, T0=3.0, T1=1.0, sigma0=0.9, hot_frac=0.7, sharpen_last=3, T_cold_plus=0.9)
+    (pa, pb), n_pair, calls = run(True)
+    (sa, sb), n_seq, calls_seq = run(False)
+    assert calls == [("chain_pair", 5, 5)] and calls_seq == []        # 4 steps + the un-clamped pass; 5 steps
+    assert n_pair == n_seq > 0
+    assert torch.equal(pa, sa) and torch.equal(pb, sb)
+    assert not torch.equal(pa[:, Dz - 3:], vk_z[:, Dz - 3:]) and pb[:, :Dz].min() > 0      # the free columns moved
+
+
 def test_batches_helper_is_the_dataloader():
     """imdbn.utils.batches slices a sequential TensorDataset loader and defers to the DataLoader otherwise."""
     from torch.utils.data import DataLoader, TensorDataset

@@ -196,7 +196,7 @@ def test_train_joint_with_w_sup_issues_one_label_step_per_batch_after_the_genera
             assert got[0] == "label_step" and got[1] == B
             steps.append(got)
         else:
-            assert got == w
+            assert got[:1] == w                          # (the base double's cd_step record also carries shape, k and forward)
     for i, got in enumerate(steps):
         lr, mom = jr._lr_mom(i // NB)
         assert got[2] == pytest.approx(0.5 * lr, rel=1e-12) and got[3] == mom
@@ -237,7 +237,8 @@ def test_finetune_joint_labels_returns_one_value_per_epoch(labelgrad_double):
         n0 = len(labelgrad_double.calls)
         out = m.finetune_joint_labels(3, lr_scale=0.3)
         assert E.get_rng().offset == 0
-    steps = labelgrad_double.calls[n0:]
+    assert [c[0] for c in labelgrad_double.calls[n0:]] == ["forward", "label_step"] * (3 * NB)     # represent(), then the step
+    steps = labelgrad_double.calls[n0 + 1::2]
     assert len(out) == 3 and np.isfinite(out).all() and out == m.finetune_sup_nll
     assert len(steps) == 3 * NB and all(s[0] == "label_step" and s[1] == B for s in steps)
     for i, s in enumerate(steps):
