@@ -475,6 +475,51 @@ int imdbn_rbm_centered_step(const imdbn_rbm_desc* d, const float* data, int64_t 
                             const imdbn_cd_opts* o, imdbn_rng* rng, float* mu, float* lam, float slide, int mode,
                             float* loss_out, float* scratch, void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- Gaussian visible units with learned variances (imdbn/models/grbm.py: GaussianRBM; Cho, Ilin & Raiko 2011) ----
+ * The parameters of the descriptor plus logvar [V] (device), sigma_i^2 = exp(logvar_i); with u = v exp(-logvar):
+ *     p(h_j | v) = sigmoid(c_j + (u W)_j),   p(v_i | h) = N(b_i + (h W^T)_i, sigma_i^2),
+ *     F(v) = sum_i (v_i - b_i)^2 / (2 sigma_i^2) - sum_j softplus(c_j + (u W)_j)
+ * Softmax groups: IMDBN_E_UNSUPPORTED.  All calls are plain launches on the caller's stream: no host sync, no allocation, no
+ * floating-point atomics, every sum in an order fixed by the shapes and the device's CU count (the same call on the same state gives
+ * the same bits); the row padding of W / W_m is neither read nor written.  An argument error names the offending value and touches
+ * nothing.  Workspace: imdbn_ws_bytes(V, H, B).
+ *   gauss_prop_up      out_prob = sigmoid(((v exp(-logvar)) W + c) / T); out_sample (nullable) = 1[out_prob > U], draws ("u", H).
+ *   gauss_prop_down    out_mean = b + h W^T, bit for bit the logits_only output of imdbn_rbm_prop_down at T = 1; out_sample (nullable)
+ *                      = out_mean + exp(logvar / 2) n, draws ("n", V).
+ *   gauss_sample_visible   out = mean + exp(logvar / 2) n for a caller's mean [B][V], draws ("n", V); no workspace.
+ *   gauss_free_energy  out_F [B] = F(v).
+ *   gauss_cd_step      one CD-k update, n = B:
+ *       u0 = data exp(-z); P0 = sigmoid(u0 W + c); h = 1[P0 > U]                                                      ("u", H)
+ *       cd_k >= 1 times:  m = b + h W^T;  v = m + exp(z / 2) n with sample_v, else v = m                              ("n", V)
+ *                         u = v exp(-z); P = sigmoid(u W + c); on every step but the last h = 1[P > U]                ("u", H)
+ *       draws_used = cd_k (1 + sample_v).  With u1 / P1 / v of the last step, S = u0^T P0 - u1^T P1 (the update kernel's exact
+ *       products), q0_i = sum_b (data_bi - b_i)^2, q1_i = sum_b (v_bi - b_i)^2, r_i = sum_j W_ij S_ij (W, b as on entry):
+ *           gW = S / n,  gb = colsum(u0 - u1) / n,  gc = colsum(P0 - P1) / n,  gz_i = exp(-z_i) (q0_i - q1_i) / (2 n) - r_i / n
+ *           W_m = mom W_m + lr (gW - wd W), W += W_m;  vb_m = mom vb_m + lr gb, vis_bias += vb_m;
+ *           hb_m = mom hb_m + lr gc - [sparsity] lr (colsum(P0) / n - target), hid_bias += hb_m;
+ *           lr_z != 0:  logvar_m = mom logvar_m + lr_z gz, logvar = min(max(logvar + logvar_m, z_lo), z_hi)
+ *           (lr_z == 0: logvar and logvar_m -- which may then be NULL -- are not touched)
+ *       loss_out (nullable) = mean((data - m_last)^2).  Of o: cd_k, lr, momentum, weight_decay, sparsity, sparsity_target are read;
+ *       the prefetch fields and fwd_out must be zero; the data are always read as real.
+ *       scratch: device, imdbn_gauss_scratch_floats(V, H, B) floats (the V H statistics, the [B][V] mean and u, the partials), 16-byte
+ *       aligned for the float4 kernel.
+ * IMDBN_E_INVALID: a null argument, a leading dimension below its row length, B < 1, cd_k < 1, NaN lr_z, z_lo > z_hi or NaN,
+ * sample_v outside {0, 1}, a null rng where draws are needed, a non-zero prefetch field or fwd_out; IMDBN_E_RNG: a replay tape
+ * shorter than the draws. */
+int imdbn_rbm_gauss_prop_up(const imdbn_rbm_desc* d, const float* logvar, const float* v, int64_t ldv, int B, float T, imdbn_rng* rng,
+                            float* out_prob, int64_t ldo, float* out_sample, int64_t lds, void* ws, size_t ws_bytes, imdbn_stream_t stream);
+int imdbn_rbm_gauss_prop_down(const imdbn_rbm_desc* d, const float* logvar, const float* h, int64_t ldh, int B, imdbn_rng* rng,
+                              float* out_mean, int64_t ldo, float* out_sample, int64_t lds, void* ws, size_t ws_bytes,
+                              imdbn_stream_t stream);
+int imdbn_rbm_gauss_sample_visible(const imdbn_rbm_desc* d, const float* logvar, const float* mean, int64_t ldm, int B, imdbn_rng* rng,
+                                   float* out, int64_t ldo, imdbn_stream_t stream);
+int imdbn_rbm_gauss_free_energy(const imdbn_rbm_desc* d, const float* logvar, const float* v, int64_t ldv, int B, float* out_F,
+                                void* ws, size_t ws_bytes, imdbn_stream_t stream);
+size_t imdbn_gauss_scratch_floats(int V, int H, int B);
+int imdbn_rbm_gauss_cd_step(const imdbn_rbm_desc* d, float* logvar, float* logvar_m, const float* data, int64_t ldd, int B,
+                            const imdbn_cd_opts* o, float lr_z, float z_lo, float z_hi, int sample_v, imdbn_rng* rng, float* loss_out,
+                            float* scratch, void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- one delta-rule step of a directed layer (imdbn/models/idbn.py: updown_step; the up-down / contrastive wake-sleep algorithm of
  * Hinton, Osindero & Teh 2006) -------------------------------------------------------------------------------------
  * A directed sigmoid layer predicts `target` from `in` through the descriptor's weights: N_in = V, N_out = H for IMDBN_DELTA_UP

@@ -38,6 +38,7 @@
 #include "kernels_pll.hpp"
 #include "kernels_pt.hpp"
 #include "kernels_centered.hpp"
+#include "kernels_gauss.hpp"
 #include "kernels_delta.hpp"
 #include "kernels_backprop.hpp"
 
@@ -1821,6 +1822,227 @@ int imdbn_rbm_centered_step(const imdbn_rbm_desc* d, const float* data, int64_t 
     else      hipLaunchKernelGGL(centered_apply<false>, dim3(p.ctiles, p.nstripes), dim3(256), 0, c.s, a);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(centered_finish, dim3(cdiv(std::max(V, H), 256) + 1), dim3(256), 0, c.s, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ---- Gaussian visible units (imdbn/models/grbm.py; kernels_gauss.hpp) ----------------------------------------------------
+// p(h | v) is the Bernoulli engine applied to u = v e^{-z}, the mean of p(v | h) its logits path: K1 / K2 / K3 are called as they are.
+static int gauss_check(const char* name, const imdbn_rbm_desc* d, bool need_momentum, const float* logvar) {
+    CHK(check_desc(d, need_momentum));
+    if (d->n_groups > 0) return fail(IMDBN_E_UNSUPPORTED, "%s: %d softmax groups on a Gaussian visible layer", name, d->n_groups);
+    if (!logvar) return fail(IMDBN_E_INVALID, "%s: null logvar", name);
+    return 0;
+}
+
+// one gauss_rows launch over [B][V]
+static int launch_gauss_rows(const Ctx& c, const imdbn_rbm_desc* d, const float* logvar, int B, GaussRowsArgs a) {
+    a.bias = d->vis_bias; a.logvar = logvar; a.B = B; a.V = d->V;
+    hipLaunchKernelGGL(gauss_rows, dim3(cdiv(d->V, 256), cdiv(B, GAUSS_RPT)), dim3(256), 0, c.s, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// u = v e^{-z} into `u` (pitch V)
+static int gauss_scale(const Ctx& c, const imdbn_rbm_desc* d, const float* logvar, const float* v, int64_t ldv, int B, float* u) {
+    GaussRowsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.in = v; a.ldi = ldv; a.out_u = u; a.ldu = d->V;
+    return launch_gauss_rows(c, d, logvar, B, a);
+}
+
+int imdbn_rbm_gauss_prop_up(const imdbn_rbm_desc* d, const float* logvar, const float* v, int64_t ldv, int B, float T, imdbn_rng* rng,
+                            float* out_prob, int64_t ldo, float* out_sample, int64_t lds, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(gauss_check("gauss_prop_up", d, false, logvar));
+    if (!v || !out_prob) return fail(IMDBN_E_INVALID, "gauss_prop_up: null %s", !v ? "v" : "out_prob");
+    if (ldv < d->V) return fail(IMDBN_E_INVALID, "gauss_prop_up: ldv %lld < V %d", (long long)ldv, d->V);
+    if (ldo < d->H) return fail(IMDBN_E_INVALID, "gauss_prop_up: ldo %lld < H %d", (long long)ldo, d->H);
+    if (out_sample && lds < d->H) return fail(IMDBN_E_INVALID, "gauss_prop_up: lds %lld < H %d", (long long)lds, d->H);
+    if (out_sample && !rng) return fail(IMDBN_E_INVALID, "gauss_prop_up: null rng with a sample");
+    if (B < 1) return fail(IMDBN_E_INVALID, "gauss_prop_up: B = %d rows", B);
+    if (out_sample) CHK(tape_room("gauss_prop_up", rng, (int64_t)B * d->H, 0));
+    Ctx c(d, rng, S(stream));
+    CHK(setup(c, B, ws, ws_bytes));
+    CHK(gauss_scale(c, d, logvar, v, ldv, B, c.L.f_v[0]));
+    FinishArgs f = new_finish();
+    f.T = T;
+    f.out_prob = out_prob; f.ld_prob = ldo;
+    if (out_sample) { f.vmode = 1; f.uni = c.rng.floats(B, d->H); f.out_final = out_sample; f.ld_final = lds; }
+    CHK(prep_prop(c, true, c.L.f_v[0], d->V, f));
+    return c.rng.finish();
+}
+
+int imdbn_rbm_gauss_prop_down(const imdbn_rbm_desc* d, const float* logvar, const float* h, int64_t ldh, int B, imdbn_rng* rng,
+                              float* out_mean, int64_t ldo, float* out_sample, int64_t lds, void* ws, size_t ws_bytes,
+                              imdbn_stream_t stream) {
+    CHK(gauss_check("gauss_prop_down", d, false, logvar));
+    if (!h || !out_mean) return fail(IMDBN_E_INVALID, "gauss_prop_down: null %s", !h ? "h" : "out_mean");
+    if (ldh < d->H) return fail(IMDBN_E_INVALID, "gauss_prop_down: ldh %lld < H %d", (long long)ldh, d->H);
+    if (ldo < d->V) return fail(IMDBN_E_INVALID, "gauss_prop_down: ldo %lld < V %d", (long long)ldo, d->V);
+    if (out_sample && lds < d->V) return fail(IMDBN_E_INVALID, "gauss_prop_down: lds %lld < V %d", (long long)lds, d->V);
+    if (out_sample && !rng) return fail(IMDBN_E_INVALID, "gauss_prop_down: null rng with a sample");
+    if (B < 1) return fail(IMDBN_E_INVALID, "gauss_prop_down: B = %d rows", B);
+    if (out_sample) CHK(tape_room("gauss_prop_down", rng, (int64_t)B * d->V, 0));
+    Ctx c(d, rng, S(stream));
+    CHK(setup(c, B, ws, ws_bytes));
+    FinishArgs f = new_finish();
+    f.logits_only = 1;                                     // the mean: b + h W^T
+    f.out_prob = out_mean; f.ld_prob = ldo;
+    CHK(prep_prop(c, false, h, ldh, f));
+    if (out_sample) {
+        GaussRowsArgs a;
+        memset(&a, 0, sizeof(a));
+        a.in = out_mean; a.ldi = ldo; a.sample = 1; a.nz = c.rng.floats(B, d->V); a.out_v = out_sample; a.ldv = lds;
+        CHK(launch_gauss_rows(c, d, logvar, B, a));
+    }
+    return c.rng.finish();
+}
+
+int imdbn_rbm_gauss_sample_visible(const imdbn_rbm_desc* d, const float* logvar, const float* mean, int64_t ldm, int B, imdbn_rng* rng,
+                                   float* out, int64_t ldo, imdbn_stream_t stream) {
+    CHK(gauss_check("gauss_sample_visible", d, false, logvar));
+    if (!mean || !out || !rng) return fail(IMDBN_E_INVALID, "gauss_sample_visible: null %s", !mean ? "mean" : (!out ? "out" : "rng"));
+    if (ldm < d->V) return fail(IMDBN_E_INVALID, "gauss_sample_visible: ldm %lld < V %d", (long long)ldm, d->V);
+    if (ldo < d->V) return fail(IMDBN_E_INVALID, "gauss_sample_visible: ldo %lld < V %d", (long long)ldo, d->V);
+    if (B < 1) return fail(IMDBN_E_INVALID, "gauss_sample_visible: B = %d rows", B);
+    CHK(tape_room("gauss_sample_visible", rng, (int64_t)B * d->V, 0));
+    Ctx c(d, rng, S(stream));
+    GaussRowsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.in = mean; a.ldi = ldm; a.sample = 1; a.nz = c.rng.floats(B, d->V); a.out_v = out; a.ldv = ldo;
+    CHK(launch_gauss_rows(c, d, logvar, B, a));
+    return c.rng.finish();
+}
+
+int imdbn_rbm_gauss_free_energy(const imdbn_rbm_desc* d, const float* logvar, const float* v, int64_t ldv, int B, float* out_F,
+                                void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(gauss_check("gauss_free_energy", d, false, logvar));
+    if (!v || !out_F) return fail(IMDBN_E_INVALID, "gauss_free_energy: null %s", !v ? "v" : "out_F");
+    if (ldv < d->V) return fail(IMDBN_E_INVALID, "gauss_free_energy: ldv %lld < V %d", (long long)ldv, d->V);
+    if (B < 1) return fail(IMDBN_E_INVALID, "gauss_free_energy: B = %d rows", B);
+    Ctx c(d, nullptr, S(stream));
+    CHK(setup(c, B, ws, ws_bytes));
+    CHK(gauss_scale(c, d, logvar, v, ldv, B, c.L.f_v[0]));
+    FinishArgs f = new_finish();
+    f.logits_only = 1;                                     // x = u W + c
+    f.out_prob = c.L.f_h; f.ld_prob = d->H;
+    CHK(prep_prop(c, true, c.L.f_v[0], d->V, f));
+    hipLaunchKernelGGL(gauss_free_energy_rows, dim3(B), dim3(256), 0, c.s, v, ldv, d->vis_bias, logvar, d->V, c.L.f_h, (int64_t)d->H, d->H, out_F);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// scratch = [S V H | mean B V | u B V | sum u0, sum u1, q0, q1: RP V each | row_part ctiles V | loss partials], every piece padded
+// to 4 floats; the row partials are sized for whichever plan of gauss_apply (the tiling of centered_apply) has more column tiles
+struct GaussScratch { size_t mean, u, su0, su1, q0, q1, row_part, loss, total; int RP, n_loss; };
+static GaussScratch gauss_scratch(int V, int H, int B) {
+    auto r4 = [](size_t n) { return (n + 3) / 4 * 4; };
+    GaussScratch g;
+    g.RP = cdiv(B, GAUSS_RPT); g.n_loss = cdiv(V, 256) * g.RP;
+    const size_t bv = r4((size_t)B * V), pv = r4((size_t)g.RP * V);
+    const int ctiles = std::max(centered_plan(V, H, false).ctiles, centered_plan(V, H, true).ctiles);
+    g.mean = centered_dw_floats(V, H); g.u = g.mean + bv;
+    g.su0 = g.u + bv; g.su1 = g.su0 + pv; g.q0 = g.su1 + pv; g.q1 = g.q0 + pv;
+    g.row_part = g.q1 + pv; g.loss = g.row_part + r4((size_t)ctiles * V); g.total = g.loss + r4((size_t)g.n_loss);
+    return g;
+}
+size_t imdbn_gauss_scratch_floats(int V, int H, int B) {
+    if (V <= 0 || H <= 0 || B <= 0) return 0;
+    return gauss_scratch(V, H, B).total;
+}
+
+int imdbn_rbm_gauss_cd_step(const imdbn_rbm_desc* d, float* logvar, float* logvar_m, const float* data, int64_t ldd, int B,
+                            const imdbn_cd_opts* o, float lr_z, float z_lo, float z_hi, int sample_v, imdbn_rng* rng, float* loss_out,
+                            float* scratch, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(gauss_check("gauss_cd_step", d, true, logvar));
+    if (!data || !o || !scratch || !rng)
+        return fail(IMDBN_E_INVALID, "gauss_cd_step: null %s", !data ? "data" : (!o ? "opts" : (!scratch ? "scratch" : "rng")));
+    if (lr_z != 0.0f && !logvar_m) return fail(IMDBN_E_INVALID, "gauss_cd_step: null logvar_m with lr_z = %g", (double)lr_z);
+    if (ldd < d->V) return fail(IMDBN_E_INVALID, "gauss_cd_step: ldd %lld < V %d", (long long)ldd, d->V);
+    if (B < 1) return fail(IMDBN_E_INVALID, "gauss_cd_step: B = %d rows", B);
+    if (o->cd_k < 1) return fail(IMDBN_E_INVALID, "gauss_cd_step: cd_k = %d (CD from the data needs cd_k >= 1)", o->cd_k);
+    if (!(lr_z == lr_z)) return fail(IMDBN_E_INVALID, "gauss_cd_step: lr_z = %g", (double)lr_z);
+    if (!(z_lo <= z_hi)) return fail(IMDBN_E_INVALID, "gauss_cd_step: clamp [%g, %g] is empty", (double)z_lo, (double)z_hi);
+    if (sample_v != 0 && sample_v != 1) return fail(IMDBN_E_INVALID, "gauss_cd_step: sample_v = %d outside {0, 1}", sample_v);
+    if (o->next_data || o->next_slot || o->data_slot || o->next_binary || o->fwd_out)
+        return fail(IMDBN_E_INVALID, "gauss_cd_step: the prefetch fields and fwd_out must be zero (next_data %p, next_slot %d, data_slot %d, next_binary %d, fwd_out %p)",
+                    (const void*)o->next_data, o->next_slot, o->data_slot, o->next_binary, (const void*)o->fwd_out);
+    const int V = d->V, H = d->H;
+    CHK(tape_room("gauss_cd_step", rng, (int64_t)o->cd_k * B * H + (int64_t)(sample_v ? o->cd_k : 0) * B * V, 0));
+    Ctx c(d, rng, S(stream));
+    CHK(setup(c, B, ws, ws_bytes));
+    const Layout& L = c.L;
+    const GaussScratch g = gauss_scratch(V, H, B);
+    float* mean = scratch + g.mean;
+    float* u = scratch + g.u;
+    t_cd = CdRec{};
+    {   // u0 = data e^{-z}, its column sums and q0
+        GaussRowsArgs a;
+        memset(&a, 0, sizeof(a));
+        a.in = data; a.ldi = ldd; a.out_u = u; a.ldu = V; a.su_part = scratch + g.su0; a.q_part = scratch + g.q0;
+        CHK(launch_gauss_rows(c, d, logvar, B, a));
+    }
+    CHK(prep(c, u, V, V, L.vis_rm[0], L.Vpad, L.vis_tr[0], L.flags, nullptr, 3));
+    {   // positive phase: P0 = up(u0); h = 1[P0 > U]
+        FinishArgs f = new_finish();
+        f.vmode = 1; f.uni = c.rng.floats(B, H);
+        f.op.rm = L.hid_rm; f.op.rm_terms = 1; f.rm_src = 2;
+        f.op.tr = L.hid_tr[0]; f.op.tr_terms = c.ht; f.tr_src = 1;
+        f.colsum_part = L.cs_hpos; f.colsum_src = 1;
+        CHK(prop(c, true, OpIn{L.vis_rm[0], c.nw == 1 ? 1 : 0, L.flags}, f));
+    }
+    for (int it = 0; it < o->cd_k; ++it) {
+        const bool last = (it == o->cd_k - 1);
+        {   // m = b + h W^T
+            FinishArgs f = new_finish();
+            f.logits_only = 1;
+            f.out_prob = mean; f.ld_prob = V;
+            CHK(prop(c, false, OpIn{L.hid_rm, 1, nullptr}, f));
+        }
+        {   // v = m (+ e^{z/2} n); u = v e^{-z}; on the last step its column sums, q1 and the loss
+            GaussRowsArgs a;
+            memset(&a, 0, sizeof(a));
+            a.in = mean; a.ldi = V; a.out_u = u; a.ldu = V;
+            if (sample_v) { a.sample = 1; a.nz = c.rng.floats(B, V); }
+            if (last) {
+                a.su_part = scratch + g.su1; a.q_part = scratch + g.q1;
+                if (loss_out) { a.ref = data; a.ldr = ldd; a.loss_part = scratch + g.loss; }
+            }
+            CHK(launch_gauss_rows(c, d, logvar, B, a));
+        }
+        CHK(prep(c, u, V, V, L.vis_rm[1], L.Vpad, last ? L.vis_tr[1] : nullptr, nullptr, nullptr, c.rt));
+        {   // P = up(u); h = 1[P > U] on every step but the last
+            FinishArgs f = new_finish();
+            if (!last) {
+                f.vmode = 1; f.uni = c.rng.floats(B, H);
+                f.op.rm = L.hid_rm; f.op.rm_terms = 1; f.rm_src = 2;
+            } else {
+                f.op.tr = L.hid_tr[1]; f.op.tr_terms = c.ht; f.tr_src = 1; f.op.tr_negate = 1;
+                f.colsum_part = L.cs_hneg; f.colsum_src = 1;
+            }
+            CHK(prop(c, true, OpIn{L.vis_rm[1], c.rt, nullptr}, f));
+        }
+    }
+    CHK(c.rng.finish());
+    CHK(launch_assoc(c, 1, o, c.nw == 1 ? 1 : 0, L.flags, c.rt, 1.0f, scratch));
+    const bool vec4 = c.r.vec4 && (((uintptr_t)d->W_m | (uintptr_t)scratch) & 15) == 0;
+    const CenteredPlan p = centered_plan(V, H, vec4);
+    GaussArgs a;
+    memset(&a, 0, sizeof(a));
+    a.W = d->W; a.Wm = d->W_m; a.ldw = d->ldw; a.V = V; a.H = H; a.S = scratch;
+    a.lr = o->lr; a.mom = o->momentum; a.wd = o->weight_decay; a.n = (float)B;
+    a.rps = p.rps; a.tw = p.tw; a.nstripes = p.nstripes; a.ctiles = p.ctiles;
+    a.row_part = scratch + g.row_part;
+    a.hpos = L.cs_hpos; a.hneg = L.cs_hneg; a.P = L.P;
+    a.su0 = scratch + g.su0; a.su1 = scratch + g.su1; a.q0 = scratch + g.q0; a.q1 = scratch + g.q1; a.RP = g.RP;
+    a.hid_bias = d->hid_bias; a.hb_m = d->hb_m; a.vis_bias = d->vis_bias; a.vb_m = d->vb_m; a.logvar = logvar; a.logvar_m = logvar_m;
+    a.lr_z = lr_z; a.z_lo = z_lo; a.z_hi = z_hi;
+    a.sparsity = o->sparsity != 0; a.target = o->sparsity_target;
+    a.loss_part = scratch + g.loss; a.n_loss = g.n_loss; a.loss_den = (float)B * (float)V; a.loss_out = loss_out;
+    if (vec4) hipLaunchKernelGGL(gauss_apply<true>, dim3(p.ctiles, p.nstripes), dim3(256), 0, c.s, a);
+    else      hipLaunchKernelGGL(gauss_apply<false>, dim3(p.ctiles, p.nstripes), dim3(256), 0, c.s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(gauss_finish, dim3(cdiv(std::max(V, H), 256) + 1), dim3(256), 0, c.s, a);
     HIPCHK(hipGetLastError());
     return 0;
 }

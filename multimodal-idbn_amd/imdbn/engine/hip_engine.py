@@ -678,6 +678,99 @@ class HipEngine:
                  _ptr(scratch), prefetch=False, particles=p, nullable_chains=True)
         return loss.reshape(()) if monitor else None
 
+    # ---- Gaussian visible units (imdbn_rbm_gauss_*) ---------------------------------
+    @staticmethod
+    def _logvar(who: str, t, n: int, dev) -> torch.Tensor:
+        """The log-variances (and their momentum) go to the engine as they are: the update writes them in place."""
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32 and t.dim() == 1 and t.numel() == n
+                and t.is_contiguous()):
+            raise N.EngineError(f"{who} must be a contiguous fp32 [{n}] tensor on {dev}")
+        return t
+
+    def gauss_forward(self, rbm, logvar, v, T=1.0, sample=False, rng=None):
+        """p(h | v) of a Gaussian-visible RBM (imdbn_rbm_gauss_prop_up): ``sigmoid(((v exp(-logvar)) W + c) / T)``; with ``sample``
+        also ``1[p > U]`` (one ("u", H) draw): ``(p, h)``.  No host sync."""
+        d = self._desc(rbm, False)
+        v = _f32c(v)
+        B, dev = v.size(0), v.device
+        z = self._logvar("gauss_forward: logvar", logvar, d.V, dev)
+        out = torch.empty(B, d.H, device=dev)
+        smp = torch.empty(B, d.H, device=dev) if sample else None
+        sched = [("u", d.H)] if sample else []
+        r, keep = self._rng(rng, sched, B, dev) if sample else (None, None)
+        self._call("imdbn_rbm_gauss_prop_up", C.byref(d), _ptr(z), _ptr(v), v.stride(0), B, float(T), _ref(r), _ptr(out), out.stride(0),
+                   _ptr(smp), d.H, *self._ws_tail(dev, d.V, d.H, B))
+        if sample:
+            self._done(rng, r, sched)
+            return out, smp
+        return out
+
+    def gauss_backward(self, rbm, logvar, h, sample=False, rng=None):
+        """The mean of p(v | h) of a Gaussian-visible RBM (imdbn_rbm_gauss_prop_down): ``b + h W^T``, the bits of
+        ``prop_down(logits_only=True)``; with ``sample`` also ``mean + exp(logvar / 2) n`` (one ("n", V) draw): ``(mean, v)``."""
+        d = self._desc(rbm, False)
+        h = _f32c(h)
+        B, dev = h.size(0), h.device
+        z = self._logvar("gauss_backward: logvar", logvar, d.V, dev)
+        out = torch.empty(B, d.V, device=dev)
+        smp = torch.empty(B, d.V, device=dev) if sample else None
+        sched = [("n", d.V)] if sample else []
+        r, keep = self._rng(rng, sched, B, dev) if sample else (None, None)
+        self._call("imdbn_rbm_gauss_prop_down", C.byref(d), _ptr(z), _ptr(h), h.stride(0), B, _ref(r), _ptr(out), out.stride(0),
+                   _ptr(smp), d.V, *self._ws_tail(dev, d.V, d.H, B))
+        if sample:
+            self._done(rng, r, sched)
+            return out, smp
+        return out
+
+    def gauss_sample_visible(self, rbm, logvar, mean, rng):
+        """v ~ N(mean, exp(logvar)) for a caller's ``mean`` ``[B, V]`` (imdbn_rbm_gauss_sample_visible): one ("n", V) draw."""
+        d = self._desc(rbm, False)
+        m = _f32c(mean)
+        B, dev = m.size(0), m.device
+        z = self._logvar("gauss_sample_visible: logvar", logvar, d.V, dev)
+        out = torch.empty(B, d.V, device=dev)
+        sched = [("n", d.V)]
+        r, keep = self._rng(rng, sched, B, dev)
+        self._call("imdbn_rbm_gauss_sample_visible", C.byref(d), _ptr(z), _ptr(m), m.stride(0), B, C.byref(r), _ptr(out), out.stride(0),
+                   self._stream(dev))
+        self._done(rng, r, sched)
+        return out
+
+    def gauss_free_energy(self, rbm, logvar, v):
+        """F(v) = sum (v - b)^2 / (2 sigma^2) - sum softplus(c + (v / sigma^2) W) per row, fp32 ``[B]`` (imdbn_rbm_gauss_free_energy)."""
+        d = self._desc(rbm, False)
+        v = _f32c(v)
+        B, dev = v.size(0), v.device
+        z = self._logvar("gauss_free_energy: logvar", logvar, d.V, dev)
+        out = torch.empty(B, device=dev)
+        self._call("imdbn_rbm_gauss_free_energy", C.byref(d), _ptr(z), _ptr(v), v.stride(0), B, _ptr(out), *self._ws_tail(dev, d.V, d.H, B))
+        return out
+
+    def gauss_cd_step(self, rbm, logvar, logvar_m, data, lr, mom, cd_k, rng, lr_z, z_lo=float("-inf"), z_hi=float("inf"),
+                      sample_v=True, monitor: bool = True):
+        """One CD-``cd_k`` update of a Gaussian-visible RBM with learned variances (imdbn_rbm_gauss_cd_step):
+        the parameters and momentum buffers of ``rbm`` and -- with ``lr_z != 0`` -- ``logvar`` / ``logvar_m`` ``[V]`` (fp32, updated
+        in place, ``logvar`` clamped into ``[z_lo, z_hi]``).  ``sample_v``: the negative visible state is drawn from N(mean,
+        sigma^2), else it is the mean.  Returns ``mean((data - mean_last)^2)`` as a 0-d device tensor, or None with
+        ``monitor=False``.  No host sync."""
+        d = self._desc(rbm, True)
+        x = _f32c(data)
+        B, dev = x.size(0), x.device
+        z = self._logvar("gauss_cd_step: logvar", logvar, d.V, dev)
+        zm = self._logvar("gauss_cd_step: logvar_m", logvar_m, d.V, dev)
+        o = self._opts(rbm, lr, mom, cd_k, sparsity=getattr(rbm, "sparsity", False))
+        loss = torch.empty(1, device=dev) if monitor else None
+        need = int(self._lib.imdbn_gauss_scratch_floats(d.V, d.H, B))
+        scratch = self._buffer(("gauss", dev, d.V, d.H, B, torch.cuda.current_stream(dev).cuda_stream),
+                               lambda: torch.empty(need, dtype=torch.float32, device=dev), need)
+        sched = R.sched_gauss_cd(d.V, d.H, o.cd_k, sample_v)
+        r, keep = self._rng(rng, sched, B, dev)
+        self._call("imdbn_rbm_gauss_cd_step", C.byref(d), _ptr(z), _ptr(zm), _ptr(x), x.stride(0), B, C.byref(o), float(lr_z), float(z_lo),
+                   float(z_hi), int(bool(sample_v)), C.byref(r), _ptr(loss), _ptr(scratch), *self._ws_tail(dev, d.V, d.H, B))
+        self._done(rng, r, sched)
+        return loss.reshape(()) if monitor else None
+
     def pt_sweep(self, rbm, state, betas, n_sweeps: int, rng, swap_try: Optional[torch.Tensor] = None,
                  swap_acc: Optional[torch.Tensor] = None):
         """``n_sweeps`` parallel-tempering sweeps (imdbn_rbm_pt_sweep) over ``state`` ``[R M, V]`` (fp32 0/1, updated in place), R =

@@ -78,6 +78,15 @@ def sched_pcd(V: int, H: int, groups, cd_k: int) -> Schedule:
     return int(cd_k) * ([("u", H)] + sched_sample_visible(V, groups))
 
 
+def sched_gauss_cd(V: int, H: int, cd_k: int, sample_v: bool) -> Schedule:
+    """imdbn_rbm_gauss_cd_step: the positive-phase h, then per step the normals of v (with sample_v) and, on every step but the
+    last, the next h: cd_k (1 + sample_v) draws."""
+    s: Schedule = [("u", H)]
+    for it in range(int(cd_k)):
+        s += ([("n", V)] if sample_v else []) + ([("u", H)] if it < int(cd_k) - 1 else [])
+    return s
+
+
 def sched_pt(V: int, H: int, groups, n_replicas: int, n_sweeps: int) -> Schedule:
     """imdbn_rbm_pt_sweep, every tensor over all R M rows: per sweep one Gibbs step and, with R >= 2, the ("u", 1) of the exchange."""
     return int(n_sweeps) * ([("u", H)] + sched_sample_visible(V, groups) + ([("u", 1)] if int(n_replicas) >= 2 else []))

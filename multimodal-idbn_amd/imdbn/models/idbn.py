@@ -14,6 +14,7 @@ from typing import List, Optional
 
 import torch
 
+from imdbn.models.grbm import GaussianRBM
 from imdbn.models.rbm import RBM
 from imdbn.utils import batches, rows_on_device
 
@@ -75,8 +76,14 @@ class iDBN:
         except Exception:
             pass
 
+        # extension, off by default: params["GAUSSIAN_VISIBLE"] makes layer 0 a GaussianRBM (real-valued inputs with
+        # learned variances; params["GAUSSIAN_LR_SIGMA_MULT"], ["GAUSSIAN_LOGVAR_MIN"], ["GAUSSIAN_LOGVAR_MAX"] are its arguments)
+        self.gaussian_visible = bool(self.params.get("GAUSSIAN_VISIBLE", False))
         for i in range(len(layer_sizes) - 1):                                       # idbn.py:149-161
-            rbm = RBM(
+            gauss = dict(lr_sigma_mult=float(self.params.get("GAUSSIAN_LR_SIGMA_MULT", 1.0)),
+                         logvar_min=float(self.params.get("GAUSSIAN_LOGVAR_MIN", float("-inf"))),
+                         logvar_max=float(self.params.get("GAUSSIAN_LOGVAR_MAX", float("inf")))) if (self.gaussian_visible and i == 0) else None
+            rbm = (RBM if gauss is None else GaussianRBM)(
                 num_visible=layer_sizes[i],
                 num_hidden=layer_sizes[i + 1],
                 learning_rate=self.params["LEARNING_RATE"],
@@ -86,6 +93,7 @@ class iDBN:
                 final_momentum=self.params["FINAL_MOMENTUM"],
                 sparsity=(self.sparsity_last and i == len(layer_sizes) - 2),
                 sparsity_factor=self.sparsity_factor,
+                **(gauss or {}),
             ).to(self.device)
             self.layers.append(rbm)
 
@@ -131,7 +139,11 @@ class iDBN:
                 for li, rbm in enumerate(self.layers):
                     # update + forward of the same batch as one engine call; the top layer's forward (computed and
                     # dropped by the reference, idbn.py:203) has no side effect and is not run
-                    if centered is not None:
+                    if isinstance(rbm, GaussianRBM):      # its own CD update; no persistent or centered form
+                        loss = rbm.train_epoch(v, epoch, epochs, CD=self.cd_k)
+                        if li < last:
+                            v = rbm.forward(v)
+                    elif centered is not None:
                         chains = persistent and binary_input(v)
                         loss = rbm.train_epoch_centered(v, epoch, epochs, CD=self.cd_k, persistent=chains, betas=pt_betas if chains else None,
                                                         slide=centered, offsets=ctr_offsets)
@@ -181,6 +193,11 @@ class iDBN:
         return cur
 
     # ---- up-down fine-tuning of the whole stack (extension; Hinton, Osindero & Teh 2006) ----------------
+    def _no_gaussian(self, who: str):
+        """The fine-tuning passes and the bounds treat every layer as Bernoulli: refused on a stack with a Gaussian layer."""
+        if any(isinstance(r, GaussianRBM) for r in self.layers):
+            raise ValueError(f"iDBN.{who}: needs Bernoulli visible units; layer 0 of this stack is a GaussianRBM (DESIGN section 29)")
+
     def is_untied(self) -> bool:
         return self.__dict__.get("gen_layers") is not None
 
@@ -199,6 +216,7 @@ class iDBN:
         gen = self.__dict__.get("gen_layers")
         if gen is not None:
             return gen
+        self._no_gaussian("untie")
         gen = []
         for r in self.layers[:-1]:
             g = RBM.__new__(RBM)                      # not the constructor: it would draw an initial W from torch's generator
@@ -229,6 +247,7 @@ class iDBN:
         predictions before this call's update, and the top RBM's mean-field reconstruction error -- or None with
         ``monitor=False`` (nothing is then evaluated for them).  No host sync; no data-parallel split."""
         from imdbn import engine as _E
+        self._no_gaussian("updown_step")
         if _E.dp.active():
             raise NotImplementedError("updown_step has no data-parallel split")
         gen = self.untie()
@@ -272,6 +291,7 @@ class iDBN:
         squared reconstruction error, both before this call's update -- or None with ``monitor=False`` (nothing is then evaluated
         for them).  No host sync; no data-parallel split."""
         from imdbn import engine as _E
+        self._no_gaussian("autoencoder_step")
         if _E.dp.active():
             raise NotImplementedError("autoencoder_step has no data-parallel split")
         gen = self.untie()
@@ -306,12 +326,14 @@ class iDBN:
     def log_likelihood_bound(self, v: torch.Tensor, log_z_top, **kw) -> torch.Tensor:
         """Variational lower bound on log p(v) of the whole stack per row, float64 ``[B]``
         (``imdbn.utils.likelihood.dbn_lower_bound``; ``log_z_top`` = log Z of the top RBM)."""
+        self._no_gaussian("log_likelihood_bound")
         from imdbn.utils.likelihood import dbn_lower_bound
         return dbn_lower_bound(self, v, log_z_top, **kw)
 
     def log_likelihood_bound_conservative(self, v: torch.Tensor, **kw) -> torch.Tensor:
         """The stack's lower bound with the reverse-AIS estimate as its top term, float64 ``[B]``
         (``imdbn.utils.likelihood.dbn_conservative_bound``; no AIS estimate of log Z enters)."""
+        self._no_gaussian("log_likelihood_bound_conservative")
         from imdbn.utils.likelihood import dbn_conservative_bound
         return dbn_conservative_bound(self, v, **kw)
 

@@ -86,6 +86,8 @@ def _bottom(model):
 
 
 def _check_binary(rbm):
+    if getattr(rbm, "gaussian_visible", False):
+        raise ValueError("the likelihood estimators need Bernoulli visibles: this RBM's visible layer is Gaussian (DESIGN section 29)")
     if getattr(rbm, "softmax_groups", None):
         raise ValueError("AIS likelihood needs an RBM with binary visibles and no softmax groups")
 
@@ -512,6 +514,8 @@ def reverse_ais_log_likelihood(rbm, v: torch.Tensor, n_chains: int = 16, n_betas
     ``max_rows // n_chains`` (engine rows = rows x chains); a chunk's draws are keyed on ``first_row * n_chains``, so a row's chains
     see the same draws whatever the chunking (the same bits while the chunks stay within the same multiple of 64 engine rows, the
     engine's rule for batch sizes).  ``K (2 + G)`` draw tensors for K temperatures and G groups.  No host sync."""
+    if getattr(rbm, "gaussian_visible", False):
+        raise ValueError("reverse_ais_log_likelihood needs Bernoulli visibles: this RBM's visible layer is Gaussian (DESIGN section 29)")
     betas = linear_betas(n_betas) if betas is None else betas
     ll, ess, logw = _reverse_rows(rbm, v, n_chains, betas, base_vis_bias, _draws(seed), max_rows)
     return {"ll": ll, "ess": ess, "logw": logw}
@@ -621,6 +625,8 @@ def pseudo_log_likelihood(model, v: torch.Tensor, return_sites: bool = False):
     term at its observed column, 0 in the group's other columns; a row sums to its PLL).  A row that is not 0/1, or a group without
     exactly one 1, is NaN.  One ``HipEngine.pseudo_loglik`` call; no draws, no host sync."""
     rbm = _bottom(model)
+    if getattr(rbm, "gaussian_visible", False):
+        raise ValueError("pseudo_log_likelihood needs Bernoulli visibles: this RBM's visible layer is Gaussian (DESIGN section 29)")
     return _E.get_engine(rbm.W.data).pseudo_loglik(rbm, rows_on_device(v, rbm.W.device), return_sites=return_sites)
 
 
