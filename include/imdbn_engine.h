@@ -520,6 +520,30 @@ int imdbn_rbm_gauss_cd_step(const imdbn_rbm_desc* d, float* logvar, float* logva
                             const imdbn_cd_opts* o, float lr_z, float z_lo, float z_hi, int sample_v, imdbn_rng* rng, float* loss_out,
                             float* scratch, void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- annealed importance sampling over Gaussian visibles (imdbn/utils/likelihood.py: estimate_gaussian_log_partition; DESIGN
+ * section 30) ---------------------------------------------------------------------------------------------------------------------
+ * M chains from the base-rate model A -- W = 0, c = 0, the variances of the RBM, visible bias b_A -- to the Gaussian-visible RBM of
+ * (d, logvar) through the temperatures betas[0..K] (0 = betas[0] < ... < betas[K] = 1).  With z = logvar, u = v exp(-z), x = c + u W,
+ * q_X(v) = sum_i (v_i - b_X,i)^2 / (2 exp(z_i)) the intermediate distribution is
+ *     p*_beta(v) = exp(-(1 - beta) q_A(v) - beta q_B(v)) prod_j (1 + exp(beta x_j))
+ *   v_1 = b_A + exp(z / 2) n, logw = 0                                                                                      ("n", V)
+ *   k = 1 .. K:  logw += (beta_k - beta_{k-1}) sum_i (b_i - b_A,i) exp(-z_i) (v_i - (b_i + b_A,i) / 2)
+ *                        + sum_j [softplus(beta_k x_j) - softplus(beta_{k-1} x_j)]          (both sums in double, one expression)
+ *                k < K:  h = 1[sigmoid(beta_k x) > U]                                                                      ("u", H)
+ *                        v = ((1 - beta_k) b_A + beta_k (b + h W^T)) + exp(z / 2) n        (fp32, in this order)            ("n", V)
+ *   draws_used = 2 K - 1; Philox is keyed on the global row, so chain i is the same chain whatever M.
+ *   log Z ~= log Z_A + logmeanexp(logw),  log Z_A = H log 2 + (V / 2) log 2 pi + sum_i z_i / 2.
+ * base_vis_bias (nullable) [V]: b_A.  NULL means b_A = b, the RBM's own visible bias -- NOT zeros as in imdbn_rbm_ais: a Gaussian
+ * base model centred on 0 is a useless start for data far from 0, and with b_A = b the visible sum vanishes.
+ * logw: device double [M], written.  out_v (nullable) [M][V], row stride ldo: the final states v_K.  The parameters are only read.
+ * Plain launches on the caller's stream: no host sync, no allocation, no memcpy, no atomics; every row's sums have one order fixed
+ * by (V, H), so the same call on the same state gives the same bits.  Workspace: imdbn_ws_bytes(V, H, M).
+ * An argument error names the offending value, comes before the first launch and leaves logw untouched.  IMDBN_E_INVALID: M < 1,
+ * K < 1, betas[0] != 0, betas[K] != 1, betas not strictly increasing, a null logvar / betas / rng / logw, ldo < V with out_v;
+ * IMDBN_E_WORKSPACE: a short workspace; IMDBN_E_UNSUPPORTED: softmax groups; IMDBN_E_RNG: a replay tape shorter than the draws. */
+int imdbn_rbm_gauss_ais(const imdbn_rbm_desc* d, const float* logvar, const float* betas, int K, int M, const float* base_vis_bias,
+                        imdbn_rng* rng, double* logw, float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- one delta-rule step of a directed layer (imdbn/models/idbn.py: updown_step; the up-down / contrastive wake-sleep algorithm of
  * Hinton, Osindero & Teh 2006) -------------------------------------------------------------------------------------
  * A directed sigmoid layer predicts `target` from `in` through the descriptor's weights: N_in = V, N_out = H for IMDBN_DELTA_UP

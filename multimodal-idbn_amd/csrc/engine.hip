@@ -39,6 +39,7 @@
 #include "kernels_pt.hpp"
 #include "kernels_centered.hpp"
 #include "kernels_gauss.hpp"
+#include "kernels_gauss_ais.hpp"
 #include "kernels_delta.hpp"
 #include "kernels_backprop.hpp"
 
@@ -759,12 +760,14 @@ static int anneal_setup(Anneal& n, const imdbn_rbm_desc* d, int M, const float* 
     return 0;
 }
 
-// x = c + v W of the current state
-static int anneal_logits(Anneal& n) {
+// x = c + v W of the current state; `real`: the state is real-valued fp32 rows of pitch V (imdbn_rbm_gauss_ais: u = v e^{-z}) that
+// go through prep_operand first, the route of imdbn_rbm_gauss_free_energy
+static int anneal_logits(Anneal& n, const float* real = nullptr) {
     const Layout& L = n.c.L;
     FinishArgs f = new_finish();
     f.logits_only = 1;
     f.out_prob = L.f_h; f.ld_prob = L.H;
+    if (real) return prep_prop(n.c, true, real, L.V, f);
     return prop(n.c, true, OpIn{L.vis_rm[0], 1, nullptr}, f);
 }
 
@@ -1930,6 +1933,58 @@ int imdbn_rbm_gauss_free_energy(const imdbn_rbm_desc* d, const float* logvar, co
     hipLaunchKernelGGL(gauss_free_energy_rows, dim3(B), dim3(256), 0, c.s, v, ldv, d->vis_bias, logvar, d->V, c.L.f_h, (int64_t)d->H, d->H, out_F);
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+// Annealed importance sampling over Gaussian visibles (kernels_gauss_ais.hpp): M chains from the base-rate model (W = 0,
+// c = 0, the same variances, visible bias b_A; null = the RBM's own b) to the RBM.  The start kernel, then per temperature:
+// prep_operand on u, the up propagation's raw logits (the route of gauss_free_energy), gauss_ais_weight_sample_h and -- but for the
+// last -- the down propagation's raw mean b + h W^T and gauss_ais_visible, which leaves v, u and the row's visible weight term.
+// Built from the anneal_* pieces of imdbn_rbm_ais.  State buffers are scratch of the workspace no propagation of this call touches:
+// logits in f_h, the mean in f_vp, the fp32 state in f_v[0] (or the caller's out_v), u in f_v[1], the M visible terms (doubles) at
+// the head of vis_rm[1] (>= 96 Bp bytes) -- imdbn_ws_bytes(V, H, M) covers the call.
+int imdbn_rbm_gauss_ais(const imdbn_rbm_desc* d, const float* logvar, const float* betas, int K, int M, const float* base_vis_bias,
+                        imdbn_rng* rng, double* logw, float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(gauss_check("gauss_ais", d, false, logvar));
+    CHK(anneal_check("gauss_ais", d, false, nullptr, 0, M, K, betas, rng, logw, out_v, ldo));
+    CHK(tape_room("gauss_ais", rng, (int64_t)M * d->V + (int64_t)(K - 1) * M * ((int64_t)d->H + d->V), 0));
+    Anneal n(d, rng, stream);
+    CHK(anneal_setup(n, d, M, nullptr, logw, out_v, ldo, ws, ws_bytes));
+    Ctx& c = n.c;
+    const Layout& L = c.L;
+    GaussAisArgs g;
+    memset(&g, 0, sizeof(g));
+    g.M = M; g.Bp = L.Bp; g.V = L.V; g.H = L.H; g.Hpad = L.Hpad;
+    g.vis_bias = d->vis_bias; g.base_bias = base_vis_bias ? base_vis_bias : d->vis_bias; g.logvar = logvar;
+    g.state = n.a.state; g.lds = n.a.lds; g.u = L.f_v[1]; g.ldu = L.V;
+    g.tv = reinterpret_cast<double*>(L.vis_rm[1]);
+    g.x = L.f_h; g.ldx = L.H; g.logw = logw;
+    {   // v_1 = b_A + e^{z/2} n, logw = 0
+        GaussAisArgs s = g;
+        s.nz = c.rng.floats(M, L.V);
+        hipLaunchKernelGGL(gauss_ais_visible, n.grid, n.block, 0, c.s, s);
+        HIPCHK(hipGetLastError());
+    }
+    for (int k = 1; k <= K; ++k) {
+        CHK(anneal_logits(n, g.u));        // x = c + u_k W
+        GaussAisArgs w = g;
+        w.beta_prev = betas[k - 1]; w.beta = betas[k];
+        w.sample = k < K ? 1 : 0;          // the last temperature only weighs
+        if (w.sample) { w.uni = c.rng.floats(M, L.H); w.rm = L.hid_rm; w.bits = L.hid_bits; }
+        hipLaunchKernelGGL(gauss_ais_weight_sample_h, n.grid, n.block, 0, c.s, w);
+        HIPCHK(hipGetLastError());
+        if (k == K) break;
+        c.hid_bits_ok = true;              // hid_bits describes hid_rm: the down half may read the bit plane
+        FinishArgs f = new_finish();
+        f.logits_only = 1;                 // m = b + h W^T
+        f.out_prob = L.f_vp; f.ld_prob = L.V;
+        CHK(prop(c, false, OpIn{L.hid_rm, 1, nullptr}, f));
+        GaussAisArgs s = g;
+        s.mean = L.f_vp; s.ldm = L.V; s.beta = betas[k];
+        s.nz = c.rng.floats(M, L.V);
+        hipLaunchKernelGGL(gauss_ais_visible, n.grid, n.block, 0, c.s, s);
+        HIPCHK(hipGetLastError());
+    }
+    return c.rng.finish();
 }
 
 // scratch = [S V H | mean B V | u B V | sum u0, sum u1, q0, q1: RP V each | row_part ctiles V | loss partials], every piece padded

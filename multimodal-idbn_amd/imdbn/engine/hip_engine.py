@@ -747,6 +747,30 @@ class HipEngine:
         self._call("imdbn_rbm_gauss_free_energy", C.byref(d), _ptr(z), _ptr(v), v.stride(0), B, _ptr(out), *self._ws_tail(dev, d.V, d.H, B))
         return out
 
+    def gauss_ais(self, rbm, logvar, betas, n_chains: int, rng, base_vis_bias: Optional[torch.Tensor] = None, return_state: bool = False):
+        """Annealed importance sampling over Gaussian visibles (imdbn_rbm_gauss_ais): ``n_chains`` chains from the
+        base-rate model (no weights, the variances of ``logvar``, visible bias ``base_vis_bias``; None = the RBM's own ``vis_bias``,
+        not zeros) to ``rbm`` through the temperatures ``betas`` (0 = betas[0] < ... < betas[K] = 1).  Returns the log importance
+        weights, a float64 device tensor ``[n_chains]`` (and the final states ``[n_chains, V]`` with ``return_state``);
+        log Z ~= H log 2 + (V / 2) log 2 pi + sum(logvar) / 2 + logmeanexp(logw).  No host sync."""
+        d = self._desc(rbm, False)
+        dev = rbm.W.device
+        z = self._logvar("gauss_ais: logvar", logvar, d.V, dev)
+        b = [float(x) for x in (betas.tolist() if hasattr(betas, "tolist") else betas)]
+        K, M = len(b) - 1, int(n_chains)
+        arr = (C.c_float * max(1, len(b)))(*b)
+        bA = _on(base_vis_bias, dev, torch.float32)
+        if bA is not None and bA.numel() != d.V:
+            raise N.EngineError(f"gauss_ais: base_vis_bias must have {d.V} elements")
+        logw = torch.empty(max(M, 1), dtype=torch.float64, device=dev)
+        state = torch.empty(max(M, 1), d.V, device=dev) if return_state else None
+        sched = R.sched_gauss_ais(d.V, d.H, max(K, 1))
+        r, keep = self._rng(rng, sched, max(M, 1), dev)
+        self._call("imdbn_rbm_gauss_ais", C.byref(d), _ptr(z), arr, K, M, _ptr(bA), C.byref(r), _ptr(logw), _ptr(state), d.V,
+                   *self._ws_tail(dev, d.V, d.H, max(M, 1)))
+        self._done(rng, r, sched)
+        return (logw, state) if return_state else logw
+
     def gauss_cd_step(self, rbm, logvar, logvar_m, data, lr, mom, cd_k, rng, lr_z, z_lo=float("-inf"), z_hi=float("inf"),
                       sample_v=True, monitor: bool = True):
         """One CD-``cd_k`` update of a Gaussian-visible RBM with learned variances (imdbn_rbm_gauss_cd_step):

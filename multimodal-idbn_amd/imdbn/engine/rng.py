@@ -128,6 +128,12 @@ def sched_ais_groups(V: int, H: int, groups: Sequence[Tuple[int, int]], K: int) 
     return sv + (int(K) - 1) * ([("u", H)] + sv)
 
 
+def sched_gauss_ais(V: int, H: int, K: int) -> Schedule:
+    """imdbn_rbm_gauss_ais over K temperatures: the normals of the initial state, then one (h, v) transition per temperature but the
+    last, h uniform and v normal: 2 K - 1 draws."""
+    return [("n", V)] + (int(K) - 1) * [("u", H), ("n", V)]
+
+
 def sched_reverse_ais(V: int, H: int, groups: Sequence[Tuple[int, int]], K: int) -> Schedule:
     """imdbn_rbm_reverse_ais over K temperatures: one (h, v) transition per temperature, T_K first: K (2 + G) draws for G groups."""
     return int(K) * ([("u", H)] + sched_sample_visible(V, groups))

@@ -9,7 +9,9 @@ The parameterisation of Cho, Ilin & Raiko (2011, "Improved learning of Gaussian-
 Every method body is host-side scalar logic plus calls into the native engine (``HipEngine.gauss_*``), as in ``rbm.py``.  The hidden
 layer is Bernoulli, so ``forward`` feeds a Bernoulli RBM above it (``iDBN`` with ``params["GAUSSIAN_VISIBLE"]``).  The inherited
 methods that assume Bernoulli visibles -- AIS, the pseudo-log-likelihood, the persistent / centered / label / clamped trainers and
-the chains -- raise ``ValueError``: none of them may return a number computed for the wrong model.
+the chains -- raise ``ValueError``: none of them may return a number computed for the wrong model.  The density of THIS model has
+methods of its own, ``gaussian_log_partition`` (AIS over Gaussian visibles, ``HipEngine.gauss_ais``) and ``gaussian_log_likelihood``
+(-F(v) - log Z), over ``imdbn.utils.likelihood``.
 """
 from __future__ import annotations
 
@@ -143,6 +145,18 @@ class GaussianRBM(RBM):
         x = self._in(data)
         return self._eng().gauss_cd_step(self, self._z(), self._zm(), x, lr, mom, int(CD), self._rng(x.size(0)), self.lr_sigma_mult * lr,
                                          z_lo=self.logvar_min, z_hi=self.logvar_max, sample_v=bool(sample_v), monitor=monitor)
+
+    # ---- the density of this model -------------------------------------------------
+    def gaussian_log_partition(self, n_chains: int = 256, n_betas: int = 1000, betas=None, base_vis_bias=None, seed=None) -> dict:
+        """AIS estimate of log Z (``imdbn.utils.likelihood.estimate_gaussian_log_partition``): ``log_z``, ``log_z_base``, ``logw``,
+        ``ess``, ``se``."""
+        from imdbn.utils.likelihood import estimate_gaussian_log_partition
+        return estimate_gaussian_log_partition(self, n_chains=n_chains, n_betas=n_betas, betas=betas, base_vis_bias=base_vis_bias, seed=seed)
+
+    def gaussian_log_likelihood(self, v: torch.Tensor, log_z) -> torch.Tensor:
+        """log p(v) = -F(v) - log Z per row, float64 ``[B]`` (``imdbn.utils.likelihood.gaussian_log_likelihood``)."""
+        from imdbn.utils.likelihood import gaussian_log_likelihood
+        return gaussian_log_likelihood(self, self._in(v), log_z)
 
     # ---- what assumes Bernoulli visibles --------------------------------------------------------
     log_partition = _refuse("log_partition")

@@ -58,6 +58,14 @@ random bit per row is not offered).  Softmax groups are accepted; rows must be 0
 ``iMDBN`` on ``[z | one-hot y]`` with z drawn as the bounds above draw it, and its group term is log p(y | z), the classification
 log-loss, without a chain.  It is a training monitor, not a likelihood: PLL is not comparable with the numbers above.
 
+Gaussian visibles: a ``GaussianRBM`` is refused by everything above -- those estimators describe Bernoulli visibles --
+and has functions of its own.  ``estimate_gaussian_log_partition`` anneals from the base-rate model A with the RBM's
+variances, no weights and visible bias ``base_vis_bias`` (log Z_A = H log 2 + (V / 2) log 2 pi + sum(logvar) / 2) through
+p*_beta(v) = exp(-(1 - beta) q_A(v) - beta q_B(v)) prod_j (1 + exp(beta x_j)), q_X(v) = sum_i (v_i - b_X,i)^2 / (2 sigma_i^2): ONE
+``HipEngine.gauss_ais`` call (imdbn_rbm_gauss_ais).  No ``base_vis_bias`` means the RBM's own visible bias, not zeros: a Gaussian
+centred on 0 is a useless start for data far from 0 (``gaussian_base_rate_bias``: the column means of the data).
+``gaussian_log_likelihood`` is the log-DENSITY -F(v) - log Z; ``evaluate_gaussian_log_likelihood`` its mean over a loader.
+
 Data parallelism: the chains are NOT sharded over ranks -- every rank that calls runs all ``n_chains`` chains and gets the same
 estimate (same seed) or an independent one; sharding the chains is a follow-up.
 """
@@ -76,7 +84,8 @@ __all__ = ["base_rate_bias", "linear_betas", "estimate_log_partition", "log_like
            "base_rate_bias_joint", "estimate_joint_log_partition", "imdbn_sample_values", "imdbn_lower_bound",
            "imdbn_log_likelihood_is", "evaluate_imdbn_bound",
            "reverse_ais_log_likelihood", "evaluate_log_likelihood_sandwich", "dbn_conservative_bound", "evaluate_dbn_bound_conservative",
-           "pseudo_log_likelihood", "evaluate_pseudo_likelihood", "imdbn_pseudo_log_likelihood"]
+           "pseudo_log_likelihood", "evaluate_pseudo_likelihood", "imdbn_pseudo_log_likelihood",
+           "gaussian_base_rate_bias", "estimate_gaussian_log_partition", "gaussian_log_likelihood", "evaluate_gaussian_log_likelihood"]
 
 
 def _bottom(model):
@@ -674,3 +683,74 @@ def imdbn_pseudo_log_likelihood(model, img: torch.Tensor, y: torch.Tensor, seed:
     rows[:, Dz:] = torch.nn.functional.one_hot(torch.where(ok, gt, torch.zeros_like(gt)), K).float() * ok.unsqueeze(1).float()
     pll, sites = _E.get_engine(jr.W.data).pseudo_loglik(jr, rows, return_sites=True)
     return pll, sites[:, Dz:].double().sum(1)
+
+
+# ---- Gaussian visible units (imdbn/models/grbm.py) -------------------------------------------------------------------
+def _check_gaussian(rbm):
+    if not getattr(rbm, "gaussian_visible", False):
+        raise ValueError("the Gaussian likelihood functions need a GaussianRBM (Gaussian visible units, DESIGN section 29); "
+                         "Bernoulli layers have estimate_log_partition / log_likelihood")
+
+
+@torch.no_grad()
+def gaussian_base_rate_bias(data, device=None) -> torch.Tensor:
+    """Visible bias of the Gaussian base-rate model: the column means of the data.  A tensor ``[N, ...]`` or a loader of such batches;
+    sums are accumulated on the device in float64."""
+    it = [data] if isinstance(data, torch.Tensor) else batches(data)
+    tot, n = None, 0
+    for b in it:
+        x = _first(b)
+        x = rows_on_device(x, device if device is not None else x.device).double()
+        tot = x.sum(0) if tot is None else tot + x.sum(0)
+        n += x.size(0)
+    if tot is None or n == 0:
+        raise ValueError("gaussian_base_rate_bias: no rows")
+    return (tot / n).float()
+
+
+def _gaussian_log_z_base(rbm, dev) -> torch.Tensor:
+    """log Z_A of the Gaussian base-rate model (float64 scalar on ``dev``): H log 2 + (V / 2) log 2 pi + sum(logvar) / 2 -- whatever b_A."""
+    V, H = rbm.W.shape
+    return rbm.logvar.data.to(dev).double().sum() * 0.5 + (H * math.log(2.0) + 0.5 * V * math.log(2.0 * math.pi))
+
+
+@torch.no_grad()
+def estimate_gaussian_log_partition(rbm, n_chains: int = 256, n_betas: int = 1000, betas=None, base_vis_bias: Optional[torch.Tensor] = None,
+                                    seed: Optional[int] = None) -> dict:
+    """AIS estimate of log Z of a ``GaussianRBM``: the keys of ``estimate_log_partition`` (``log_z``, ``log_z_base``, ``logw``,
+    ``ess``, ``se``).  ``base_vis_bias`` None: the RBM's own visible bias (module docstring).  One device-to-host copy; ``seed`` as
+    in ``estimate_log_partition``."""
+    _check_gaussian(rbm)
+    if base_vis_bias is not None and base_vis_bias.numel() != rbm.W.shape[0]:
+        raise ValueError(f"base_vis_bias must have {rbm.W.shape[0]} elements")
+    betas = linear_betas(n_betas) if betas is None else betas
+    logw = _E.get_engine(rbm.W.data).gauss_ais(rbm, rbm.logvar.data, betas, int(n_chains), _draws(seed), base_vis_bias=base_vis_bias)
+    return _weight_stats(logw, _gaussian_log_z_base(rbm, logw.device))
+
+
+@torch.no_grad()
+def gaussian_log_likelihood(rbm, v: torch.Tensor, log_z) -> torch.Tensor:
+    """log p(v) = -F(v) - log Z per row, the log-density of a ``GaussianRBM``: a float64 tensor ``[B]`` on the device of ``v``
+    (``rbm.free_energy``; no host sync)."""
+    _check_gaussian(rbm)
+    return -rbm.free_energy(v).double() - log_z
+
+
+@torch.no_grad()
+def evaluate_gaussian_log_likelihood(model, loader=None, log_z: Optional[float] = None, max_batches: Optional[int] = None,
+                                     **ais_kwargs) -> Optional[dict]:
+    """Mean held-out log-density of a ``GaussianRBM`` -- or of the BOTTOM layer of an ``iDBN`` built with ``GAUSSIAN_VISIBLE`` -- over
+    ``loader`` (default ``model.val_loader``; None without one): the keys of ``evaluate_log_likelihood``.  ``log_z`` None: estimated
+    with ``estimate_gaussian_log_partition(**ais_kwargs)``.  Sums on the device, one host sync after the last batch; with a
+    ``wandb_run`` on the model the scalars are logged as ``ll/...``."""
+    rbm = _bottom(model)
+    _check_gaussian(rbm)
+    loader = loader if loader is not None else getattr(model, "val_loader", None)
+    if loader is None:
+        return None
+    log_z, se, ess = _known_or_estimated(log_z, estimate_gaussian_log_partition, rbm, ais_kwargs)
+    (s,), n = _sum_batches(loader, max_batches,
+                           lambda batch: gaussian_log_likelihood(rbm, rows_on_device(_first(batch), rbm.W.device), log_z).sum().reshape(1), 1)
+    res = {"mean_ll": s / max(1, n), "sum_ll": s, "n": n, "log_z": float(log_z), "se": se, "ess": ess}
+    _log_scalars(model, "ll/", res, ("mean_ll", "log_z", "se", "ess"))
+    return res
