@@ -544,6 +544,26 @@ int imdbn_rbm_gauss_cd_step(const imdbn_rbm_desc* d, float* logvar, float* logva
 int imdbn_rbm_gauss_ais(const imdbn_rbm_desc* d, const float* logvar, const float* betas, int K, int M, const float* base_vis_bias,
                         imdbn_rng* rng, double* logw, float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- the bottom bracket of the DBN lower bound under a Gaussian visible layer (imdbn/utils/likelihood.py:
+ * gaussian_dbn_sample_values) ---------------------------------------------------------------------------------------
+ * imdbn_rbm_bound_step for the Gaussian-visible RBM of (d, logvar).  For every row of v [M][V] (real, row stride ldv), with
+ * z = logvar, u = v exp(-z), x = hid_bias + u W, sp = softplus in double:
+ *   h = 1[sigmoid(x) > U]                         -> out_h [M][H] fp32 0/1, row stride ldh (the decision of imdbn_rbm_gauss_prop_up's
+ *                                                    sample under the same draw)
+ *   m = vis_bias + h W^T
+ *   acc[row] += -sum_i ((v_i - m_i)^2 exp(-z_i) / 2 + z_i / 2) - (V / 2) log 2 pi + E       log N(v; m, exp(z)) plus E of
+ *                                                    imdbn_rbm_bound_step (IMDBN_BOUND_ENTROPY / IMDBN_BOUND_LOGQ) on x
+ *   acc[M] (device, double) is only ADDED to (the caller zeroes it): E first, then the row's Gaussian sum, then the constant, two
+ *   launches of one stream.  Every element of the Gaussian sum is formed in double from the fp32 v_i, m_i, z_i.
+ * Draws: ("u", H): draws_used = 1.  Every sum runs in an order fixed by (V, H), the logits and the mean are those of the
+ * propagations, and Philox is keyed on the row: row i is the same whatever M; no floating-point atomics.
+ * Plain launches on the caller's stream: no host sync, no allocation, no memcpy.  Workspace: imdbn_ws_bytes(V, H, M).
+ * An argument error names the offending value, comes before the first launch and leaves acc and out_h untouched.  IMDBN_E_INVALID:
+ * M < 1, unknown mode, null logvar / v / rng / acc / out_h, ldv < V, ldh < H; IMDBN_E_UNSUPPORTED: softmax groups; IMDBN_E_RNG: a
+ * replay tape shorter than the draw; IMDBN_E_WORKSPACE: a short workspace.  The caller's parameters, logvar and v are only read. */
+int imdbn_rbm_gauss_bound_step(const imdbn_rbm_desc* d, const float* logvar, const float* v, int64_t ldv, int M, int mode,
+                               imdbn_rng* rng, double* acc, float* out_h, int64_t ldh, void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- one delta-rule step of a directed layer (imdbn/models/idbn.py: updown_step; the up-down / contrastive wake-sleep algorithm of
  * Hinton, Osindero & Teh 2006) -------------------------------------------------------------------------------------
  * A directed sigmoid layer predicts `target` from `in` through the descriptor's weights: N_in = V, N_out = H for IMDBN_DELTA_UP

@@ -40,6 +40,7 @@
 #include "kernels_centered.hpp"
 #include "kernels_gauss.hpp"
 #include "kernels_gauss_ais.hpp"
+#include "kernels_gauss_bound.hpp"
 #include "kernels_delta.hpp"
 #include "kernels_backprop.hpp"
 
@@ -1984,6 +1985,55 @@ int imdbn_rbm_gauss_ais(const imdbn_rbm_desc* d, const float* logvar, const floa
         hipLaunchKernelGGL(gauss_ais_visible, n.grid, n.block, 0, c.s, s);
         HIPCHK(hipGetLastError());
     }
+    return c.rng.finish();
+}
+
+// The bottom bracket of the DBN lower bound under a Gaussian visible layer (kernels_gauss_bound.hpp):
+// acc[row] += log N(v; b + h W^T, e^z) + E with h ~ q(h | v) = Bernoulli(sigmoid(c + u W)), u = v e^{-z}.  The scale launch of
+// gauss_prop_up, prep_operand and the up propagation's raw logits (the route of gauss_free_energy), bound_entropy_sample_h as
+// imdbn_rbm_bound_step launches it, the down propagation's raw mean from that h, gauss_bound_loglik_rows.  Scratch of the workspace:
+// u in f_v[1], the up logits in f_h, the mean in f_v[0] -- imdbn_ws_bytes(V, H, M) covers the call.
+int imdbn_rbm_gauss_bound_step(const imdbn_rbm_desc* d, const float* logvar, const float* v, int64_t ldv, int M, int mode,
+                               imdbn_rng* rng, double* acc, float* out_h, int64_t ldh, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(gauss_check("gauss_bound_step", d, false, logvar));
+    if (M < 1) return fail(IMDBN_E_INVALID, "gauss_bound_step: M = %d rows", M);
+    if (mode != IMDBN_BOUND_ENTROPY && mode != IMDBN_BOUND_LOGQ) return fail(IMDBN_E_INVALID, "gauss_bound_step: unknown mode %d", mode);
+    if (!v || !rng || !acc || !out_h)
+        return fail(IMDBN_E_INVALID, "gauss_bound_step: null %s", !v ? "v" : (!rng ? "rng" : (!acc ? "acc" : "out_h")));
+    if (ldv < d->V) return fail(IMDBN_E_INVALID, "gauss_bound_step: ldv %lld < V %d", (long long)ldv, d->V);
+    if (ldh < d->H) return fail(IMDBN_E_INVALID, "gauss_bound_step: ldh %lld < H %d", (long long)ldh, d->H);
+    CHK(tape_room("gauss_bound_step", rng, (int64_t)M * d->H, 0));
+    Ctx c(d, rng, S(stream));
+    CHK(setup(c, M, ws, ws_bytes));
+    const Layout& L = c.L;
+    BoundArgs a;
+    memset(&a, 0, sizeof(a));
+    a.M = M; a.Bp = L.Bp; a.V = L.V; a.H = L.H; a.Hpad = L.Hpad; a.mode = mode;
+    a.x = L.f_h; a.ldx = L.H;
+    a.out_h = out_h; a.ldh = ldh; a.rm = L.hid_rm; a.bits = L.hid_bits; a.acc = acc;
+    a.uni = c.rng.floats(M, L.H);
+    CHK(gauss_scale(c, d, logvar, v, ldv, M, L.f_v[1]));       // u = v e^{-z}
+    {   // x = c + u W
+        FinishArgs f = new_finish();
+        f.logits_only = 1;
+        f.out_prob = L.f_h; f.ld_prob = L.H;
+        CHK(prep_prop(c, true, L.f_v[1], L.V, f));
+    }
+    const dim3 grid(L.Bp / ROW_WAVES), block(64 * ROW_WAVES);
+    hipLaunchKernelGGL(bound_entropy_sample_h, grid, block, 0, c.s, a);
+    HIPCHK(hipGetLastError());
+    c.hid_bits_ok = true;                      // hid_bits describes hid_rm: the down half may read the bit plane
+    {   // m = b + h W^T
+        FinishArgs f = new_finish();
+        f.logits_only = 1;
+        f.out_prob = L.f_v[0]; f.ld_prob = L.V;
+        CHK(prop(c, false, OpIn{L.hid_rm, 1, nullptr}, f));
+    }
+    GaussBoundArgs g;
+    memset(&g, 0, sizeof(g));
+    g.M = M; g.V = L.V; g.mean = L.f_v[0]; g.ldm = L.V; g.v = v; g.ldv = ldv; g.logvar = logvar; g.acc = acc;
+    hipLaunchKernelGGL(gauss_bound_loglik_rows, grid, block, 0, c.s, g);
+    HIPCHK(hipGetLastError());
     return c.rng.finish();
 }
 

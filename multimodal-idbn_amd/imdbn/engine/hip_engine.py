@@ -771,6 +771,31 @@ class HipEngine:
         self._done(rng, r, sched)
         return (logw, state) if return_state else logw
 
+    def gauss_bound_step(self, rbm, logvar, v, rng, acc: Optional[torch.Tensor] = None, mode: str = "entropy"):
+        """The bottom bracket of the DBN lower bound under a Gaussian visible layer (imdbn_rbm_gauss_bound_step):
+        draws ``h ~ q(h | v) = Bernoulli(sigmoid(c + (v exp(-logvar)) W))`` and adds ``log N(v; b + h W^T, exp(logvar))`` plus the
+        entropy of q (``mode="entropy"``) or ``-log q(h | v)`` (``mode="logq"``) to ``acc``, a float64 device tensor ``[M]`` (created
+        zeroed when None).  Returns ``(acc, h)``, ``h`` fp32 0/1 ``[M, H]``: what ``bound_step`` of the layer above takes.  No host
+        sync."""
+        d = self._desc(rbm, False)
+        v = _f32c(v)
+        M, dev = v.size(0), v.device
+        z = self._logvar("gauss_bound_step: logvar", logvar, d.V, dev)
+        if mode not in ("entropy", "logq"):
+            raise N.EngineError(f"gauss_bound_step: mode must be 'entropy' or 'logq', got {mode!r}")
+        if acc is None:
+            acc = torch.zeros(max(M, 1), dtype=torch.float64, device=dev)
+        elif acc.dtype != torch.float64 or acc.device != dev or acc.numel() != M or not acc.is_contiguous():
+            raise N.EngineError(f"gauss_bound_step: acc must be a contiguous float64 [{M}] tensor on {dev}")
+        h = torch.empty(max(M, 1), d.H, device=dev)
+        sched = R.sched_bound(d.H)
+        r, keep = self._rng(rng, sched, max(M, 1), dev)
+        self._call("imdbn_rbm_gauss_bound_step", C.byref(d), _ptr(z), _ptr(v), v.stride(0), M,
+                   N.BOUND_LOGQ if mode == "logq" else N.BOUND_ENTROPY, C.byref(r), _ptr(acc), _ptr(h), h.stride(0),
+                   *self._ws_tail(dev, d.V, d.H, max(M, 1)))
+        self._done(rng, r, sched)
+        return acc, h
+
     def gauss_cd_step(self, rbm, logvar, logvar_m, data, lr, mom, cd_k, rng, lr_z, z_lo=float("-inf"), z_hi=float("inf"),
                       sample_v=True, monitor: bool = True):
         """One CD-``cd_k`` update of a Gaussian-visible RBM with learned variances (imdbn_rbm_gauss_cd_step):

@@ -337,6 +337,15 @@ class iDBN:
         from imdbn.utils.likelihood import dbn_conservative_bound
         return dbn_conservative_bound(self, v, **kw)
 
+    @torch.no_grad()
+    def gaussian_log_likelihood_bound(self, v: torch.Tensor, log_z_top, n_samples: int = 8, importance: bool = False,
+                                      seed: Optional[int] = None) -> torch.Tensor:
+        """Variational lower bound on the log-density log p(v) of a stack built with ``GAUSSIAN_VISIBLE`` per row, float64 ``[B]``
+        (``imdbn.utils.likelihood.gaussian_dbn_lower_bound``; ``importance``: ``gaussian_dbn_log_likelihood_is``; ``log_z_top`` =
+        log Z of the top RBM)."""
+        from imdbn.utils.likelihood import gaussian_dbn_log_likelihood_is, gaussian_dbn_lower_bound
+        return (gaussian_dbn_log_likelihood_is if importance else gaussian_dbn_lower_bound)(self, v, log_z_top, n_samples, seed)
+
     def save_model(self, path: str):
         """idbn.py:370-372: pickle of {"layers", "params"} (live RBM modules)."""
         model_copy = {"layers": self.layers, "params": self.params}

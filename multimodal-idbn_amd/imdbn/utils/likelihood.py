@@ -66,6 +66,14 @@ p*_beta(v) = exp(-(1 - beta) q_A(v) - beta q_B(v)) prod_j (1 + exp(beta x_j)), q
 centred on 0 is a useless start for data far from 0 (``gaussian_base_rate_bias``: the column means of the data).
 ``gaussian_log_likelihood`` is the log-DENSITY -F(v) - log Z; ``evaluate_gaussian_log_likelihood`` its mean over a loader.
 
+Stacks with a Gaussian bottom layer (``iDBN`` with ``params["GAUSSIAN_VISIBLE"]``): the generative model is that of the
+stacks paragraph with p(v | h_1) = N(b_1 + h_1 W_1^T, sigma^2) at the bottom and q(h_1 | v) = Bernoulli(sigmoid(c_1 + u W_1)),
+u = v exp(-logvar), as its recognition model; the bottom bracket of ``w`` is log N(v; b_1 + h_1 W_1^T, sigma^2) + E_1, ONE
+``HipEngine.gauss_bound_step`` call (imdbn_rbm_gauss_bound_step), and the Bernoulli layers above go through ``bound_step`` on the same
+accumulator and draw source.  ``gaussian_dbn_sample_values`` / ``gaussian_dbn_lower_bound`` / ``gaussian_dbn_log_likelihood_is`` /
+``evaluate_gaussian_dbn_bound`` are log-DENSITIES; the ``dbn_*`` functions go on refusing a Gaussian layer and these refuse a stack
+whose bottom layer is not Gaussian.
+
 Data parallelism: the chains are NOT sharded over ranks -- every rank that calls runs all ``n_chains`` chains and gets the same
 estimate (same seed) or an independent one; sharding the chains is a follow-up.
 """
@@ -85,7 +93,8 @@ __all__ = ["base_rate_bias", "linear_betas", "estimate_log_partition", "log_like
            "imdbn_log_likelihood_is", "evaluate_imdbn_bound",
            "reverse_ais_log_likelihood", "evaluate_log_likelihood_sandwich", "dbn_conservative_bound", "evaluate_dbn_bound_conservative",
            "pseudo_log_likelihood", "evaluate_pseudo_likelihood", "imdbn_pseudo_log_likelihood",
-           "gaussian_base_rate_bias", "estimate_gaussian_log_partition", "gaussian_log_likelihood", "evaluate_gaussian_log_likelihood"]
+           "gaussian_base_rate_bias", "estimate_gaussian_log_partition", "gaussian_log_likelihood", "evaluate_gaussian_log_likelihood",
+           "gaussian_dbn_sample_values", "gaussian_dbn_lower_bound", "gaussian_dbn_log_likelihood_is", "evaluate_gaussian_dbn_bound"]
 
 
 def _bottom(model):
@@ -753,4 +762,91 @@ def evaluate_gaussian_log_likelihood(model, loader=None, log_z: Optional[float] 
                            lambda batch: gaussian_log_likelihood(rbm, rows_on_device(_first(batch), rbm.W.device), log_z).sum().reshape(1), 1)
     res = {"mean_ll": s / max(1, n), "sum_ll": s, "n": n, "log_z": float(log_z), "se": se, "ess": ess}
     _log_scalars(model, "ll/", res, ("mean_ll", "log_z", "se", "ess"))
+    return res
+
+
+# ---- the whole stack above a Gaussian bottom layer -------------------------------------------------------------
+def _gaussian_stack(model):
+    """The RBMs of a stack with a Gaussian bottom layer, bottom first: the layers of an ``iDBN`` built with ``GAUSSIAN_VISIBLE``, or
+    a ``GaussianRBM`` as a stack of one.  Every layer above the bottom one is Bernoulli without softmax groups."""
+    layers = getattr(model, "layers", None)
+    layers = list(layers) if layers is not None and len(layers) > 0 else [model]
+    if not getattr(layers[0], "gaussian_visible", False):
+        raise ValueError("the Gaussian stack bounds need a GaussianRBM as the bottom layer (an iDBN built with GAUSSIAN_VISIBLE, or a "
+                         "GaussianRBM; DESIGN section 31); Bernoulli stacks have dbn_lower_bound / dbn_log_likelihood_is")
+    if _gen(model) is not None:
+        raise NotImplementedError("the Gaussian stack bounds have no untied form (gen_layers present)")
+    for rbm in layers[1:]:
+        _check_binary(rbm)
+    return layers
+
+
+def _gaussian_sample_values(layers, v, log_z_top, n_samples, mode, rng) -> torch.Tensor:
+    if mode not in ("entropy", "logq"):
+        raise ValueError("mode must be 'entropy' or 'logq'")
+    S = int(n_samples)
+    if S < 1:
+        raise ValueError("n_samples must be >= 1")
+    bottom, top = layers[0], layers[-1]
+    cur = rows_on_device(v, bottom.W.device)
+    B = cur.size(0)
+    if S > 1:
+        cur = cur.repeat_interleave(S, 0)
+    if len(layers) == 1:      # no directed layer, no draw
+        return gaussian_log_likelihood(bottom, cur, log_z_top).view(B, S)
+    acc, cur = _E.get_engine(bottom.W.data).gauss_bound_step(bottom, bottom.logvar.data, cur, rng, acc=None, mode=mode)
+    for rbm in layers[1:-1]:
+        acc, cur = _E.get_engine(rbm.W.data).bound_step(rbm, cur, rng, acc=acc, mode=mode)
+    return (acc + (-top.free_energy(cur).double() - log_z_top)).view(B, S)
+
+
+@torch.no_grad()
+def gaussian_dbn_sample_values(model, v: torch.Tensor, log_z_top, n_samples: int = 1, mode: str = "entropy",
+                               seed: Optional[int] = None) -> torch.Tensor:
+    """``dbn_sample_values`` for a stack with a Gaussian bottom layer (module docstring): float64 ``[B, n_samples]`` on the device
+    (row b's samples are the engine rows b S .. b S + S - 1 of the replicated batch).  One ``gauss_bound_step`` on layer 0, one
+    ``bound_step`` per directed Bernoulli layer on the same accumulator, ``free_energy`` on the top RBM, no host sync.  ``model``: an
+    ``iDBN`` built with ``GAUSSIAN_VISIBLE`` or a ``GaussianRBM`` (a stack of one: no draw, the value is ``gaussian_log_likelihood``
+    and ``log_z_top`` is the Gaussian log Z).  ``log_z_top``: log Z of the TOP RBM."""
+    return _gaussian_sample_values(_gaussian_stack(model), v, log_z_top, n_samples, mode, _draws(seed))
+
+
+@torch.no_grad()
+def gaussian_dbn_lower_bound(model, v: torch.Tensor, log_z_top, n_samples: int = 8, seed: Optional[int] = None) -> torch.Tensor:
+    """Monte-Carlo estimate of the variational lower bound on the log-density log p_DBN(v) per row: the mean of ``n_samples`` values in
+    mode ``entropy``; float64 ``[B]``."""
+    return gaussian_dbn_sample_values(model, v, log_z_top, n_samples, "entropy", seed).mean(1)
+
+
+@torch.no_grad()
+def gaussian_dbn_log_likelihood_is(model, v: torch.Tensor, log_z_top, n_samples: int = 64, seed: Optional[int] = None) -> torch.Tensor:
+    """Importance-sampled estimate of the log-density log p_DBN(v) per row with q as the proposal: the logmeanexp of ``n_samples``
+    values in mode ``logq`` (in expectation a lower bound that tightens with ``n_samples``); float64 ``[B]``."""
+    return _logmeanexp_rows(gaussian_dbn_sample_values(model, v, log_z_top, n_samples, "logq", seed))
+
+
+@torch.no_grad()
+def evaluate_gaussian_dbn_bound(model, loader=None, log_z_top: Optional[float] = None, n_samples: int = 8, max_batches: Optional[int] = None,
+                                importance: bool = False, **ais_kwargs) -> Optional[dict]:
+    """``evaluate_dbn_bound`` for a stack with a Gaussian bottom layer: the mean held-out ``gaussian_dbn_lower_bound``
+    (``importance=True``: ``gaussian_dbn_log_likelihood_is``) over ``loader`` (default ``model.val_loader``; None without one), the
+    same keys.  ``log_z_top`` None: ``estimate_log_partition(top_rbm, **ais_kwargs)`` for two layers and more,
+    ``estimate_gaussian_log_partition`` for a stack of one.  A ``seed`` among ``ais_kwargs`` also carries the hidden samples of all
+    batches; the sum is accumulated on the device and the host synchronises once, after the last batch.  With a ``wandb_run`` on the
+    model the scalars are logged as ``ll/gdbn_...``."""
+    layers = _gaussian_stack(model)
+    loader = loader if loader is not None else getattr(model, "val_loader", None)
+    if loader is None:
+        return None
+    estimate = estimate_log_partition if len(layers) > 1 else estimate_gaussian_log_partition
+    log_z_top, se, ess = _known_or_estimated(log_z_top, estimate, layers[-1], ais_kwargs)
+    rng = _draws(ais_kwargs.get("seed"))
+
+    def sums(batch):
+        w = _gaussian_sample_values(layers, _first(batch), log_z_top, n_samples, "logq" if importance else "entropy", rng)
+        return (_logmeanexp_rows(w) if importance else w.mean(1)).sum().reshape(1)
+
+    (s,), n = _sum_batches(loader, max_batches, sums, 1)
+    res = {"mean_bound": s / max(1, n), "sum_bound": s, "n": n, "log_z_top": float(log_z_top), "se": se, "ess": ess, "n_samples": int(n_samples)}
+    _log_scalars(model, "ll/gdbn_", res, ("mean_bound", "log_z_top", "se", "ess", "n_samples"))
     return res
