@@ -386,6 +386,9 @@ __device__ __forceinline__ float finish_lean8(const FinishArgs& a, int col, int 
 // The same for one column x FOUR rows per thread (k1_stream's last arriver runs its epilogue on all eight waves): the two threads of
 // an 8-row group are lanes l and l + 32 of one wave (rows b0 .. b0 + 3 in the lower half-wave); the four rows are one whole Philox
 // group (row0 % 4 == 0), and the column sum of the 8-row group is lower half + upper half.  No squared error here (K1 has none).
+// Decisions, planes and probabilities are those of finish_lean8 / finish_rows8 bit for bit; the column sum is NOT: it is
+// (r0 + r1 + r2 + r3) + (r4 + r5 + r6 + r7) where they add r0 .. r7 left to right, one ulp apart in a third of the columns
+// (tests/test_row_offset_gpu.py holds the two within update_cases.STATS_TOL).
 __device__ __forceinline__ void finish_lean4(const FinishArgs& a, int col, int b0, const float (&xs)[4], int part_row, float bias, int bshape, int bcols) {
     const bool cok = col < a.N;
     const int cc = min(col, a.N - 1);

@@ -58,8 +58,9 @@ def params(V, H):
     return W, hb, vb
 
 
-def state(V, H, groups=()):
-    W, hb, vb = params(V, H)
+def state(V, H, groups=(), W=None):
+    W0, hb, vb = params(V, H)
+    W = W0 if W is None else W
     return O.RBMState.create(W, 0.1, 1e-4, 0.5, dynamic_lr=True, final_momentum=0.95, softmax_groups=list(groups), hid_bias=hb, vis_bias=vb)
 
 
@@ -87,6 +88,25 @@ def sigmoid64(x):
 def _up_logits64(V, H, kind, B):
     W, hb, _ = params(V, H)
     return operand(kind, B, V).astype(np.float64) @ W.astype(np.float64) + hb.astype(np.float64)
+
+
+def case_params(c):
+    """(W, hb, vb) of a case: params(V, H), with the weights the case carries under "W" in their place (rowoffset_cases.py: the bf16
+    weights of FAST mode)."""
+    W, hb, vb = params(c["V"], c["H"])
+    return c.get("W", W), hb, vb
+
+
+def _case_up_logits64(c):
+    if "W" not in c:
+        return _up_logits64(c["V"], c["H"], c["operand"], c["B"])
+    W, hb, _ = case_params(c)
+    return operand(c["operand"], c["B"], c["V"]).astype(np.float64) @ W.astype(np.float64) + hb.astype(np.float64)
+
+
+def case_stream(c):
+    """The PhiloxStream of a case: its seed, keyed from global row c["row0"] (0 where the case names none)."""
+    return PhiloxStream(c["seed"], row0=c.get("row0", 0))
 
 
 def _down64(W, vb, h):
@@ -145,15 +165,15 @@ def up_cases():
 
 def ref_up(c):
     """float64 probabilities, and with a sample the reference's decisions 1[p > u] on the PhiloxStream draw."""
-    p = sigmoid64(_up_logits64(c["V"], c["H"], c["operand"], c["B"]) / max(1e-6, c["T"]))
-    s = (p > PhiloxStream(c["seed"]).uniform((c["B"], c["H"]))).astype(F32) if c["sample"] else None
+    p = sigmoid64(_case_up_logits64(c) / max(1e-6, c["T"]))
+    s = (p > case_stream(c).uniform((c["B"], c["H"]))).astype(F32) if c["sample"] else None
     return p, s
 
 
 def oracle_up(c):
-    st = state(c["V"], c["H"])
+    st = state(c["V"], c["H"], W=c.get("W"))
     p = O.forward(st, operand(c["operand"], c["B"], c["V"]), c["T"])
-    s = O._bern(p, PhiloxStream(c["seed"]).uniform(p.shape)) if c["sample"] else None
+    s = O._bern(p, case_stream(c).uniform(p.shape)) if c["sample"] else None
     return p, s
 
 
@@ -236,9 +256,9 @@ def gibbs_draws(c):
 def ref_gibbs(c):
     """float64 (v_next, v_prob, h, h_prob) with the decisions taken on the PhiloxStream draws."""
     V, H, B = c["V"], c["H"], c["B"]
-    W, hb, vb = params(V, H)
-    ps = PhiloxStream(c["seed"])
-    h_prob = sigmoid64(_up_logits64(V, H, c["operand"], B))
+    W, hb, vb = case_params(c)
+    ps = case_stream(c)
+    h_prob = sigmoid64(_case_up_logits64(c))
     h = (h_prob > ps.uniform((B, H))).astype(np.float64) if c["sample_h"] else h_prob
     v_prob = probs64(_down64(W, vb, h), 1.0, c["groups"])
     v_next = v_prob
@@ -253,8 +273,8 @@ def ref_gibbs(c):
 
 
 def oracle_gibbs(c):
-    st = state(c["V"], c["H"], c["groups"])
-    return O.gibbs_step(st, operand(c["operand"], c["B"], c["V"]), PhiloxStream(c["seed"]), c["sample_h"], c["sample_v"])
+    st = state(c["V"], c["H"], c["groups"], W=c.get("W"))
+    return O.gibbs_step(st, operand(c["operand"], c["B"], c["V"]), case_stream(c), c["sample_h"], c["sample_v"])
 
 
 # ---- wide chains and the clamped update (through the RBM methods) -------------------------------------------------------------------
@@ -319,7 +339,7 @@ def oracle_chain(c):
     """(final state or loss, oracle state after the call)"""
     st = state(c["V"], c["H"], c["groups"])
     vk, km, mu = chain_inputs(c)
-    ps = PhiloxStream(c["seed"])
+    ps = case_stream(c)
     if mu is not None:
         st.mu_pull = {"mu_k": mu, "eta0": 0.15}
     if c["method"] == "train_epoch_clamped":
