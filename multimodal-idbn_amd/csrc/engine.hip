@@ -190,6 +190,21 @@ int prep_prop(Ctx& c, bool up, const float* x, int64_t ldx, const FinishArgs& f)
     return prop(c, up, OpIn{rm, c.nw == 1 ? 1 : 0, flags}, f);
 }
 
+// The two raw-logit propagations the likelihood calls are built from.  x = c + rows W of fp32 `rows` (pitch ld) into f_h at pitch H:
+static int up_logits(Ctx& c, const float* rows, int64_t ld) {
+    FinishArgs f = new_finish();
+    f.logits_only = 1;
+    f.out_prob = c.L.f_h; f.ld_prob = c.L.H;
+    return prep_prop(c, true, rows, ld, f);
+}
+// ... and b + h W^T of the h in hid_rm (one term) into `out` at pitch V.
+static int down_logits(Ctx& c, float* out) {
+    FinishArgs f = new_finish();
+    f.logits_only = 1;
+    f.out_prob = out; f.ld_prob = c.L.V;
+    return prop(c, false, OpIn{c.L.hid_rm, 1, nullptr}, f);
+}
+
 // What imdbn_energy_trace and imdbn_rbm_label_loglik start from: a joint RBM over [z | y | ...] with the code in the first Dz visible
 // columns and K labels behind it.  check() opens either call (`name`, for the messages), the call's own checks follow it, then
 // propagate() leaves base = z W[:Dz] + c -- the logits path of prop_up on the descriptor cut to its first Dz weight rows -- in the
@@ -210,11 +225,8 @@ struct LabelSide {
     LabelSide(const LabelSide&) = delete;      // c.d points at dz
     int propagate(const float* z, int64_t ldz, int N, void* ws, size_t ws_bytes) {
         CHK(setup(c, N, ws, ws_bytes));
-        FinishArgs f = new_finish();
-        f.logits_only = 1;
-        f.out_prob = c.L.f_h; f.ld_prob = c.L.H;
         base = c.L.f_h;
-        return prep_prop(c, true, z, ldz, f);
+        return up_logits(c, z, ldz);
     }
 };
 
@@ -696,10 +708,7 @@ int imdbn_rbm_free_energy(const imdbn_rbm_desc* d, const float* v, int64_t ldv, 
     if (!v || !out_F || ldv < d->V) return fail(IMDBN_E_INVALID, "free_energy: bad tensor argument");
     Ctx c(d, nullptr, S(stream));
     CHK(setup(c, B, ws, ws_bytes));
-    FinishArgs f = new_finish();
-    f.logits_only = 1;                                     // x = v W + c
-    f.out_prob = c.L.f_h; f.ld_prob = d->H;
-    CHK(prep_prop(c, true, v, ldv, f));
+    CHK(up_logits(c, v, ldv));                             // x = v W + c
     hipLaunchKernelGGL(free_energy_rows, dim3(B), dim3(256), 0, c.s, v, ldv, d->vis_bias, d->V, c.L.f_h, (int64_t)d->H, d->H, out_F);
     HIPCHK(hipGetLastError());
     return 0;
@@ -765,10 +774,10 @@ static int anneal_setup(Anneal& n, const imdbn_rbm_desc* d, int M, const float* 
 // go through prep_operand first, the route of imdbn_rbm_gauss_free_energy
 static int anneal_logits(Anneal& n, const float* real = nullptr) {
     const Layout& L = n.c.L;
+    if (real) return up_logits(n.c, real, L.V);
     FinishArgs f = new_finish();
     f.logits_only = 1;
     f.out_prob = L.f_h; f.ld_prob = L.H;
-    if (real) return prep_prop(n.c, true, real, L.V, f);
     return prop(n.c, true, OpIn{L.vis_rm[0], 1, nullptr}, f);
 }
 
@@ -880,49 +889,6 @@ int imdbn_rows_logmeanexp(const double* logw, int N, int M, double* out_lme, dou
     hipLaunchKernelGGL(rows_logmeanexp, dim3(cdiv(N, ROW_WAVES)), dim3(64 * ROW_WAVES), 0, S(stream), logw, N, M, out_lme, out_ess);
     HIPCHK(hipGetLastError());
     return 0;
-}
-
-// One directed layer of the DBN lower bound: the up propagation's raw logits, bound_entropy_sample_h (h ~ q(h | v) in
-// the caller's fp32 form and both operand forms, entropy / -log q in double), the down propagation's raw logits from that h, and
-// bound_loglik_rows (log p(v | h) in double).  Scratch as in imdbn_rbm_ais: the up logits in f_h, the down logits in f_v[0].
-int imdbn_rbm_bound_step(const imdbn_rbm_desc* d, const float* v, int64_t ldv, int M, int mode, imdbn_rng* rng, double* acc,
-                         float* out_h, int64_t ldh, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
-    CHK(check_desc(d, false));
-    if (d->n_groups > 0) return fail(IMDBN_E_UNSUPPORTED, "bound_step: softmax groups are not supported (n_groups = %d)", d->n_groups);
-    if (M < 1) return fail(IMDBN_E_INVALID, "bound_step: M = %d rows", M);
-    if (mode != IMDBN_BOUND_ENTROPY && mode != IMDBN_BOUND_LOGQ) return fail(IMDBN_E_INVALID, "bound_step: unknown mode %d", mode);
-    if (!v || !rng || !acc || !out_h) return fail(IMDBN_E_INVALID, "bound_step: null %s", !v ? "v" : (!rng ? "rng" : (!acc ? "acc" : "out_h")));
-    if (ldv < d->V) return fail(IMDBN_E_INVALID, "bound_step: ldv %lld < V %d", (long long)ldv, d->V);
-    if (ldh < d->H) return fail(IMDBN_E_INVALID, "bound_step: ldh %lld < H %d", (long long)ldh, d->H);
-    Ctx c(d, rng, S(stream));
-    CHK(setup(c, M, ws, ws_bytes));
-    const Layout& L = c.L;
-    BoundArgs a;
-    memset(&a, 0, sizeof(a));
-    a.M = M; a.Bp = L.Bp; a.V = L.V; a.H = L.H; a.Hpad = L.Hpad; a.mode = mode;
-    a.x = L.f_h; a.ldx = L.H; a.a = L.f_v[0]; a.lda = L.V; a.v = v; a.ldv = ldv;
-    a.out_h = out_h; a.ldh = ldh; a.rm = L.hid_rm; a.bits = L.hid_bits; a.acc = acc;
-    a.uni = c.rng.floats(M, L.H);
-    if (c.rng.bad) return c.rng.finish();      // a short replay tape is an error like the others: before the first launch
-    {   // x = c + v W
-        FinishArgs f = new_finish();
-        f.logits_only = 1;
-        f.out_prob = L.f_h; f.ld_prob = L.H;
-        CHK(prep_prop(c, true, v, ldv, f));
-    }
-    const dim3 grid(L.Bp / ROW_WAVES), block(64 * ROW_WAVES);
-    hipLaunchKernelGGL(bound_entropy_sample_h, grid, block, 0, c.s, a);
-    HIPCHK(hipGetLastError());
-    c.hid_bits_ok = true;                      // hid_bits describes hid_rm: the down half may read the bit plane
-    {   // a = b + h W^T
-        FinishArgs f = new_finish();
-        f.logits_only = 1;
-        f.out_prob = L.f_v[0]; f.ld_prob = L.V;
-        CHK(prop(c, false, OpIn{L.hid_rm, 1, nullptr}, f));
-    }
-    hipLaunchKernelGGL(bound_loglik_rows, grid, block, 0, c.s, a);
-    HIPCHK(hipGetLastError());
-    return c.rng.finish();
 }
 
 int imdbn_rbm_prop_down(const imdbn_rbm_desc* d, const float* h, int64_t ldh, int B, float T, int logits_only,
@@ -1525,12 +1491,7 @@ int imdbn_rbm_pseudo_loglik(const imdbn_rbm_desc* d, const float* v, int64_t ldv
     Ctx c(d, nullptr, S(stream));
     CHK(setup(c, N, ws, ws_bytes));
     const Layout& L = c.L;
-    {   // x = c + v W
-        FinishArgs f = new_finish();
-        f.logits_only = 1;
-        f.out_prob = L.f_h; f.ld_prob = L.H;
-        CHK(prep_prop(c, true, v, ldv, f));
-    }
+    CHK(up_logits(c, v, ldv));                 // x = c + v W
     PllArgs a;
     memset(&a, 0, sizeof(a));
     a.v = v; a.ldv = ldv; a.sig = L.f_h; a.ldx = L.H;
@@ -1927,10 +1888,7 @@ int imdbn_rbm_gauss_free_energy(const imdbn_rbm_desc* d, const float* logvar, co
     Ctx c(d, nullptr, S(stream));
     CHK(setup(c, B, ws, ws_bytes));
     CHK(gauss_scale(c, d, logvar, v, ldv, B, c.L.f_v[0]));
-    FinishArgs f = new_finish();
-    f.logits_only = 1;                                     // x = u W + c
-    f.out_prob = c.L.f_h; f.ld_prob = d->H;
-    CHK(prep_prop(c, true, c.L.f_v[0], d->V, f));
+    CHK(up_logits(c, c.L.f_v[0], d->V));                   // x = u W + c
     hipLaunchKernelGGL(gauss_free_energy_rows, dim3(B), dim3(256), 0, c.s, v, ldv, d->vis_bias, logvar, d->V, c.L.f_h, (int64_t)d->H, d->H, out_F);
     HIPCHK(hipGetLastError());
     return 0;
@@ -1975,10 +1933,7 @@ int imdbn_rbm_gauss_ais(const imdbn_rbm_desc* d, const float* logvar, const floa
         HIPCHK(hipGetLastError());
         if (k == K) break;
         c.hid_bits_ok = true;              // hid_bits describes hid_rm: the down half may read the bit plane
-        FinishArgs f = new_finish();
-        f.logits_only = 1;                 // m = b + h W^T
-        f.out_prob = L.f_vp; f.ld_prob = L.V;
-        CHK(prop(c, false, OpIn{L.hid_rm, 1, nullptr}, f));
+        CHK(down_logits(c, L.f_vp));       // m = b + h W^T
         GaussAisArgs s = g;
         s.mean = L.f_vp; s.ldm = L.V; s.beta = betas[k];
         s.nz = c.rng.floats(M, L.V);
@@ -1988,53 +1943,67 @@ int imdbn_rbm_gauss_ais(const imdbn_rbm_desc* d, const float* logvar, const floa
     return c.rng.finish();
 }
 
-// The bottom bracket of the DBN lower bound under a Gaussian visible layer (kernels_gauss_bound.hpp):
-// acc[row] += log N(v; b + h W^T, e^z) + E with h ~ q(h | v) = Bernoulli(sigmoid(c + u W)), u = v e^{-z}.  The scale launch of
-// gauss_prop_up, prep_operand and the up propagation's raw logits (the route of gauss_free_energy), bound_entropy_sample_h as
-// imdbn_rbm_bound_step launches it, the down propagation's raw mean from that h, gauss_bound_loglik_rows.  Scratch of the workspace:
-// u in f_v[1], the up logits in f_h, the mean in f_v[0] -- imdbn_ws_bytes(V, H, M) covers the call.
-int imdbn_rbm_gauss_bound_step(const imdbn_rbm_desc* d, const float* logvar, const float* v, int64_t ldv, int M, int mode,
-                               imdbn_rng* rng, double* acc, float* out_h, int64_t ldh, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
-    CHK(gauss_check("gauss_bound_step", d, false, logvar));
-    if (M < 1) return fail(IMDBN_E_INVALID, "gauss_bound_step: M = %d rows", M);
-    if (mode != IMDBN_BOUND_ENTROPY && mode != IMDBN_BOUND_LOGQ) return fail(IMDBN_E_INVALID, "gauss_bound_step: unknown mode %d", mode);
-    if (!v || !rng || !acc || !out_h)
-        return fail(IMDBN_E_INVALID, "gauss_bound_step: null %s", !v ? "v" : (!rng ? "rng" : (!acc ? "acc" : "out_h")));
-    if (ldv < d->V) return fail(IMDBN_E_INVALID, "gauss_bound_step: ldv %lld < V %d", (long long)ldv, d->V);
-    if (ldh < d->H) return fail(IMDBN_E_INVALID, "gauss_bound_step: ldh %lld < H %d", (long long)ldh, d->H);
-    CHK(tape_room("gauss_bound_step", rng, (int64_t)M * d->H, 0));
+// One directed layer of the DBN lower bound, and its bottom bracket under a Gaussian visible layer (DESIGN §31;
+// `logvar`, null = Bernoulli visibles).  The up propagation's raw logits, bound_entropy_sample_h (h ~ q(h | v) in the caller's fp32
+// form and both operand forms, entropy / -log q in double), the down propagation's raw logits from that h, and bound_loglik_rows
+// (log p(v | h) in double).  Gaussian: acc[row] += log N(v; b + h W^T, e^z) + E with q(h | v) = Bernoulli(sigmoid(c + u W)),
+// u = v e^{-z} -- the scale launch of gauss_prop_up in front, the up propagation reads u, gauss_bound_loglik_rows closes.
+// Scratch as in imdbn_rbm_ais: the up logits in f_h, the down logits / the mean in f_v[0], u in f_v[1] -- imdbn_ws_bytes(V, H, M)
+// covers the call.  (the body of either entry, after its descriptor checks)
+static int bound_run(const char* name, const imdbn_rbm_desc* d, const float* logvar, const float* v, int64_t ldv, int M, int mode,
+                     imdbn_rng* rng, double* acc, float* out_h, int64_t ldh, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    if (M < 1) return fail(IMDBN_E_INVALID, "%s: M = %d rows", name, M);
+    if (mode != IMDBN_BOUND_ENTROPY && mode != IMDBN_BOUND_LOGQ) return fail(IMDBN_E_INVALID, "%s: unknown mode %d", name, mode);
+    if (!v || !rng || !acc || !out_h) return fail(IMDBN_E_INVALID, "%s: null %s", name, !v ? "v" : (!rng ? "rng" : (!acc ? "acc" : "out_h")));
+    if (ldv < d->V) return fail(IMDBN_E_INVALID, "%s: ldv %lld < V %d", name, (long long)ldv, d->V);
+    if (ldh < d->H) return fail(IMDBN_E_INVALID, "%s: ldh %lld < H %d", name, (long long)ldh, d->H);
+    if (logvar) CHK(tape_room(name, rng, (int64_t)M * d->H, 0));
     Ctx c(d, rng, S(stream));
     CHK(setup(c, M, ws, ws_bytes));
     const Layout& L = c.L;
     BoundArgs a;
     memset(&a, 0, sizeof(a));
     a.M = M; a.Bp = L.Bp; a.V = L.V; a.H = L.H; a.Hpad = L.Hpad; a.mode = mode;
-    a.x = L.f_h; a.ldx = L.H;
+    a.x = L.f_h; a.ldx = L.H; a.a = L.f_v[0]; a.lda = L.V; a.v = v; a.ldv = ldv;
     a.out_h = out_h; a.ldh = ldh; a.rm = L.hid_rm; a.bits = L.hid_bits; a.acc = acc;
     a.uni = c.rng.floats(M, L.H);
-    CHK(gauss_scale(c, d, logvar, v, ldv, M, L.f_v[1]));       // u = v e^{-z}
-    {   // x = c + u W
-        FinishArgs f = new_finish();
-        f.logits_only = 1;
-        f.out_prob = L.f_h; f.ld_prob = L.H;
-        CHK(prep_prop(c, true, L.f_v[1], L.V, f));
+    if (c.rng.bad) return c.rng.finish();      // a short replay tape is an error like the others: before the first launch (the
+                                               // Gaussian entry has refused it above, in tape_room's words)
+    if (logvar) {
+        CHK(gauss_scale(c, d, logvar, v, ldv, M, L.f_v[1]));       // u = v e^{-z}
+        CHK(up_logits(c, L.f_v[1], L.V));                          // x = c + u W
+    } else {
+        CHK(up_logits(c, v, ldv));                                 // x = c + v W
     }
     const dim3 grid(L.Bp / ROW_WAVES), block(64 * ROW_WAVES);
     hipLaunchKernelGGL(bound_entropy_sample_h, grid, block, 0, c.s, a);
     HIPCHK(hipGetLastError());
     c.hid_bits_ok = true;                      // hid_bits describes hid_rm: the down half may read the bit plane
-    {   // m = b + h W^T
-        FinishArgs f = new_finish();
-        f.logits_only = 1;
-        f.out_prob = L.f_v[0]; f.ld_prob = L.V;
-        CHK(prop(c, false, OpIn{L.hid_rm, 1, nullptr}, f));
+    CHK(down_logits(c, L.f_v[0]));             // a = b + h W^T (Gaussian: the mean)
+    if (logvar) {
+        GaussBoundArgs g;
+        memset(&g, 0, sizeof(g));
+        g.M = M; g.V = L.V; g.mean = L.f_v[0]; g.ldm = L.V; g.v = v; g.ldv = ldv; g.logvar = logvar; g.acc = acc;
+        hipLaunchKernelGGL(gauss_bound_loglik_rows, grid, block, 0, c.s, g);
+    } else {
+        hipLaunchKernelGGL(bound_loglik_rows, grid, block, 0, c.s, a);
     }
-    GaussBoundArgs g;
-    memset(&g, 0, sizeof(g));
-    g.M = M; g.V = L.V; g.mean = L.f_v[0]; g.ldm = L.V; g.v = v; g.ldv = ldv; g.logvar = logvar; g.acc = acc;
-    hipLaunchKernelGGL(gauss_bound_loglik_rows, grid, block, 0, c.s, g);
     HIPCHK(hipGetLastError());
     return c.rng.finish();
+}
+
+int imdbn_rbm_bound_step(const imdbn_rbm_desc* d, const float* v, int64_t ldv, int M, int mode, imdbn_rng* rng, double* acc,
+                         float* out_h, int64_t ldh, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(check_desc(d, false));
+    if (d->n_groups > 0) return fail(IMDBN_E_UNSUPPORTED, "bound_step: softmax groups are not supported (n_groups = %d)", d->n_groups);
+    return bound_run("bound_step", d, nullptr, v, ldv, M, mode, rng, acc, out_h, ldh, ws, ws_bytes, stream);
+}
+
+// The bottom bracket of the DBN lower bound under a Gaussian visible layer (kernels_gauss_bound.hpp): bound_run with z.
+int imdbn_rbm_gauss_bound_step(const imdbn_rbm_desc* d, const float* logvar, const float* v, int64_t ldv, int M, int mode,
+                               imdbn_rng* rng, double* acc, float* out_h, int64_t ldh, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(gauss_check("gauss_bound_step", d, false, logvar));
+    return bound_run("gauss_bound_step", d, logvar, v, ldv, M, mode, rng, acc, out_h, ldh, ws, ws_bytes, stream);
 }
 
 // scratch = [S V H | mean B V | u B V | sum u0, sum u1, q0, q1: RP V each | row_part ctiles V | loss partials], every piece padded
@@ -2098,12 +2067,7 @@ int imdbn_rbm_gauss_cd_step(const imdbn_rbm_desc* d, float* logvar, float* logva
     }
     for (int it = 0; it < o->cd_k; ++it) {
         const bool last = (it == o->cd_k - 1);
-        {   // m = b + h W^T
-            FinishArgs f = new_finish();
-            f.logits_only = 1;
-            f.out_prob = mean; f.ld_prob = V;
-            CHK(prop(c, false, OpIn{L.hid_rm, 1, nullptr}, f));
-        }
+        CHK(down_logits(c, mean));         // m = b + h W^T
         {   // v = m (+ e^{z/2} n); u = v e^{-z}; on the last step its column sums, q1 and the loss
             GaussRowsArgs a;
             memset(&a, 0, sizeof(a));
@@ -2235,12 +2199,7 @@ int imdbn_rbm_pt_sweep(const imdbn_rbm_desc* d, float* state, int64_t lds, int R
         x.uni = call.rng.floats(RM, 1);
         x.parity = s & 1; x.n_pairs = (R - x.parity) / 2;
         if (x.n_pairs == 0) continue;
-        {   // x = c + v W of every row
-            FinishArgs f = new_finish();
-            f.logits_only = 1;
-            f.out_prob = call.L.f_h; f.ld_prob = H;
-            CHK(prep_prop(call, true, state, lds, f));
-        }
+        CHK(up_logits(call, state, lds));      // x = c + v W of every row
         hipLaunchKernelGGL(pt_exchange_rows, dim3(cdiv(x.n_pairs * M, ROW_WAVES)), dim3(64 * ROW_WAVES), 0, call.s, x);
         HIPCHK(hipGetLastError());
     }

@@ -344,9 +344,10 @@ class HipEngine:
         self._call("imdbn_rbm_free_energy", C.byref(d), _ptr(v), v.stride(0), B, _ptr(out), *self._ws_tail(dev, d.V, d.H, B))
         return out
 
-    def _anneal(self, name: str, rbm, d, sched_fn, n_rows: int, betas, rng, base_vis_bias, return_state: bool, v=None):
-        """The shared body of ``ais``, ``ais_groups`` and ``reverse_ais``: the entry ``imdbn_rbm_<name>`` over ``n_rows`` chains under
-        the draw schedule ``sched_fn(K)``; ``v``: the start states of the call that takes them."""
+    def _anneal(self, name: str, rbm, d, sched_fn, n_rows: int, betas, rng, base_vis_bias, return_state: bool, v=None, logvar=None):
+        """The shared body of ``ais``, ``ais_groups``, ``reverse_ais`` and ``gauss_ais``: the entry ``imdbn_rbm_<name>`` over ``n_rows``
+        chains under the draw schedule ``sched_fn(K)``; ``v``: the start states of the call that takes them; ``logvar``: the checked
+        log-variances of the Gaussian call, whose entry takes ``logvar, betas, K, M`` where the others take ``M, K, betas``."""
         dev = rbm.W.device if v is None else v.device
         b = [float(x) for x in (betas.tolist() if hasattr(betas, "tolist") else betas)]
         K, M = len(b) - 1, int(n_rows)
@@ -359,7 +360,8 @@ class HipEngine:
         sched = sched_fn(max(K, 1))
         r, keep = self._rng(rng, sched, max(M, 1), dev)
         start = () if v is None else (_ptr(v), v.stride(0))
-        self._call("imdbn_rbm_" + name, C.byref(d), *start, M, K, arr, _ptr(bA), C.byref(r), _ptr(logw), _ptr(state), d.V,
+        head = (*start, M, K, arr) if logvar is None else (_ptr(logvar), arr, K, M)
+        self._call("imdbn_rbm_" + name, C.byref(d), *head, _ptr(bA), C.byref(r), _ptr(logw), _ptr(state), d.V,
                    *self._ws_tail(dev, d.V, d.H, max(M, 1)))
         self._done(rng, r, sched)
         return (logw, state) if return_state else logw
@@ -473,19 +475,24 @@ class HipEngine:
         """One directed layer of the DBN lower bound (imdbn_rbm_bound_step): draws ``h ~ q(h | v)`` and adds
         ``log p(v | h)`` plus the entropy of q (``mode="entropy"``) or ``-log q(h | v)`` (``mode="logq"``) to ``acc``, a float64
         device tensor ``[M]`` (created zeroed when None).  Returns ``(acc, h)``, ``h`` fp32 0/1 ``[M, H]``.  No host sync."""
-        d = self._desc(rbm, False)
+        return self._bound("bound_step", self._desc(rbm, False), None, v, rng, acc, mode)
+
+    def _bound(self, name: str, d, logvar, v, rng, acc, mode: str):
+        """The shared body of ``bound_step`` and ``gauss_bound_step``: the entry ``imdbn_rbm_<name>``; ``logvar``: the checked
+        log-variances of the Gaussian call, which its entry takes in front of ``v``."""
         v = _f32c(v)
         M, dev = v.size(0), v.device
         if mode not in ("entropy", "logq"):
-            raise N.EngineError(f"bound_step: mode must be 'entropy' or 'logq', got {mode!r}")
+            raise N.EngineError(f"{name}: mode must be 'entropy' or 'logq', got {mode!r}")
         if acc is None:
             acc = torch.zeros(max(M, 1), dtype=torch.float64, device=dev)
         elif acc.dtype != torch.float64 or acc.device != dev or acc.numel() != M or not acc.is_contiguous():
-            raise N.EngineError(f"bound_step: acc must be a contiguous float64 [{M}] tensor on {dev}")
+            raise N.EngineError(f"{name}: acc must be a contiguous float64 [{M}] tensor on {dev}")
         h = torch.empty(max(M, 1), d.H, device=dev)
         sched = R.sched_bound(d.H)
         r, keep = self._rng(rng, sched, max(M, 1), dev)
-        self._call("imdbn_rbm_bound_step", C.byref(d), _ptr(v), v.stride(0), M, N.BOUND_LOGQ if mode == "logq" else N.BOUND_ENTROPY,
+        z = () if logvar is None else (_ptr(logvar),)
+        self._call("imdbn_rbm_" + name, C.byref(d), *z, _ptr(v), v.stride(0), M, N.BOUND_LOGQ if mode == "logq" else N.BOUND_ENTROPY,
                    C.byref(r), _ptr(acc), _ptr(h), h.stride(0), *self._ws_tail(dev, d.V, d.H, max(M, 1)))
         self._done(rng, r, sched)
         return acc, h
@@ -756,20 +763,8 @@ class HipEngine:
         d = self._desc(rbm, False)
         dev = rbm.W.device
         z = self._logvar("gauss_ais: logvar", logvar, d.V, dev)
-        b = [float(x) for x in (betas.tolist() if hasattr(betas, "tolist") else betas)]
-        K, M = len(b) - 1, int(n_chains)
-        arr = (C.c_float * max(1, len(b)))(*b)
-        bA = _on(base_vis_bias, dev, torch.float32)
-        if bA is not None and bA.numel() != d.V:
-            raise N.EngineError(f"gauss_ais: base_vis_bias must have {d.V} elements")
-        logw = torch.empty(max(M, 1), dtype=torch.float64, device=dev)
-        state = torch.empty(max(M, 1), d.V, device=dev) if return_state else None
-        sched = R.sched_gauss_ais(d.V, d.H, max(K, 1))
-        r, keep = self._rng(rng, sched, max(M, 1), dev)
-        self._call("imdbn_rbm_gauss_ais", C.byref(d), _ptr(z), arr, K, M, _ptr(bA), C.byref(r), _ptr(logw), _ptr(state), d.V,
-                   *self._ws_tail(dev, d.V, d.H, max(M, 1)))
-        self._done(rng, r, sched)
-        return (logw, state) if return_state else logw
+        return self._anneal("gauss_ais", rbm, d, lambda K: R.sched_gauss_ais(d.V, d.H, K), n_chains, betas, rng, base_vis_bias,
+                            return_state, logvar=z)
 
     def gauss_bound_step(self, rbm, logvar, v, rng, acc: Optional[torch.Tensor] = None, mode: str = "entropy"):
         """The bottom bracket of the DBN lower bound under a Gaussian visible layer (imdbn_rbm_gauss_bound_step):
@@ -779,22 +774,8 @@ class HipEngine:
         sync."""
         d = self._desc(rbm, False)
         v = _f32c(v)
-        M, dev = v.size(0), v.device
-        z = self._logvar("gauss_bound_step: logvar", logvar, d.V, dev)
-        if mode not in ("entropy", "logq"):
-            raise N.EngineError(f"gauss_bound_step: mode must be 'entropy' or 'logq', got {mode!r}")
-        if acc is None:
-            acc = torch.zeros(max(M, 1), dtype=torch.float64, device=dev)
-        elif acc.dtype != torch.float64 or acc.device != dev or acc.numel() != M or not acc.is_contiguous():
-            raise N.EngineError(f"gauss_bound_step: acc must be a contiguous float64 [{M}] tensor on {dev}")
-        h = torch.empty(max(M, 1), d.H, device=dev)
-        sched = R.sched_bound(d.H)
-        r, keep = self._rng(rng, sched, max(M, 1), dev)
-        self._call("imdbn_rbm_gauss_bound_step", C.byref(d), _ptr(z), _ptr(v), v.stride(0), M,
-                   N.BOUND_LOGQ if mode == "logq" else N.BOUND_ENTROPY, C.byref(r), _ptr(acc), _ptr(h), h.stride(0),
-                   *self._ws_tail(dev, d.V, d.H, max(M, 1)))
-        self._done(rng, r, sched)
-        return acc, h
+        z = self._logvar("gauss_bound_step: logvar", logvar, d.V, v.device)
+        return self._bound("gauss_bound_step", d, z, v, rng, acc, mode)
 
     def gauss_cd_step(self, rbm, logvar, logvar_m, data, lr, mom, cd_k, rng, lr_z, z_lo=float("-inf"), z_hi=float("inf"),
                       sample_v=True, monitor: bool = True):

@@ -204,15 +204,14 @@ def _directed_untied(layers, gen, cur, mode, rng):
 
 def _directed(layers, v, dev, n_samples, mode, rng, gen=None):
     """The directed layers ``layers`` (binary, bottom first) above the rows ``v``: every row ``n_samples`` times (row b's samples are
-    the engine rows b S .. b S + S - 1), one ``bound_step`` per layer.  ``(acc, top state, B, S)``; ``acc`` None without layers.
-    ``gen``: the generative twins of an untied model (``_directed_untied``)."""
+    the engine rows b S .. b S + S - 1), one ``bound_step`` per layer -- ``gauss_bound_step`` for a Gaussian one, which only
+    ``_gaussian_stack`` lets through (the other callers take their layers from ``_stack``).  ``(acc, top state, B, S)``; ``acc`` None
+    without layers.  ``gen``: the generative twins of an untied model (``_directed_untied``)."""
     if mode not in ("entropy", "logq"):
         raise ValueError("mode must be 'entropy' or 'logq'")
     S = int(n_samples)
     if S < 1:
         raise ValueError("n_samples must be >= 1")
-    for rbm in layers:
-        _check_binary(rbm)
     cur = rows_on_device(v, dev)
     B = cur.size(0)
     if S > 1:
@@ -221,8 +220,25 @@ def _directed(layers, v, dev, n_samples, mode, rng, gen=None):
         return _directed_untied(layers, gen, cur, mode, rng) + (B, S)
     acc = None
     for rbm in layers:
-        acc, cur = _E.get_engine(rbm.W.data).bound_step(rbm, cur, rng, acc=acc, mode=mode)
+        eng = _E.get_engine(rbm.W.data)
+        if getattr(rbm, "gaussian_visible", False):
+            acc, cur = eng.gauss_bound_step(rbm, rbm.logvar.data, cur, rng, acc=acc, mode=mode)
+        else:
+            acc, cur = eng.bound_step(rbm, cur, rng, acc=acc, mode=mode)
     return acc, cur, B, S
+
+
+def _column_means(who: str, data, device) -> torch.Tensor:
+    """The float64 column means of a tensor ``[N, ...]`` or of a loader of such batches, summed on the device."""
+    tot, n = None, 0
+    for b in ([data] if isinstance(data, torch.Tensor) else batches(data)):
+        x = _first(b)
+        x = rows_on_device(x, device if device is not None else x.device).double()
+        tot = x.sum(0) if tot is None else tot + x.sum(0)
+        n += x.size(0)
+    if tot is None or n == 0:
+        raise ValueError(f"{who}: no rows")
+    return tot / n
 
 
 @torch.no_grad()
@@ -230,19 +246,7 @@ def base_rate_bias(loader_or_tensor, smoothing: float = 0.05, device=None) -> to
     """Visible biases of the base-rate model: the log-odds of the smoothed pixel means, log(p / (1 - p)) with
     p = (mean + smoothing) / (1 + 2 smoothing) (the "base-rate" start of the AIS paper: the closer A is to the data, the lower
     the variance of the estimate).  A tensor ``[N, ...]`` or a loader of such batches; sums are accumulated on the device."""
-    if isinstance(loader_or_tensor, torch.Tensor):
-        it = [loader_or_tensor]
-    else:
-        it = batches(loader_or_tensor)
-    tot, n = None, 0
-    for b in it:
-        x = _first(b)
-        x = rows_on_device(x, device if device is not None else x.device).double()
-        tot = x.sum(0) if tot is None else tot + x.sum(0)
-        n += x.size(0)
-    if tot is None or n == 0:
-        raise ValueError("base_rate_bias: no rows")
-    p = (tot / n + smoothing) / (1.0 + 2.0 * smoothing)
+    p = (_column_means("base_rate_bias", loader_or_tensor, device) + smoothing) / (1.0 + 2.0 * smoothing)
     return (torch.log(p) - torch.log1p(-p)).float()
 
 
@@ -282,24 +286,33 @@ def evaluate_log_likelihood(model, loader=None, log_z: Optional[float] = None, m
     ``log_z`` was passed in instead of estimated with ``estimate_log_partition(**ais_kwargs)``).  The sum is accumulated on the
     device; the host synchronises once, after the last batch.  A ragged last batch is fine; ``max_batches`` stops early.  With a
     ``wandb_run`` on the model the scalars are logged as ``ll/...``."""
+    return _evaluate_ll(model, loader, log_z, max_batches, ais_kwargs, _check_binary, estimate_log_partition)
+
+
+def _evaluate_ll(model, loader, log_z, max_batches, ais_kwargs, check, estimate):
+    """``evaluate_log_likelihood`` / ``evaluate_gaussian_log_likelihood``: ``check`` admits the bottom RBM, ``estimate`` is its AIS."""
     rbm = _bottom(model)
-    _check_binary(rbm)
+    check(rbm)
     loader = loader if loader is not None else getattr(model, "val_loader", None)
     if loader is None:
         return None
-    log_z, se, ess = _known_or_estimated(log_z, estimate_log_partition, rbm, ais_kwargs)
-    (s,), n = _sum_batches(loader, max_batches,
-                           lambda batch: log_likelihood(rbm, rows_on_device(_first(batch), rbm.W.device), log_z).sum().reshape(1), 1)
+    log_z, se, ess = _known_or_estimated(log_z, estimate, rbm, ais_kwargs)
+    (s,), n = _sum_batches(loader, max_batches, lambda batch: (-rbm.free_energy(rows_on_device(_first(batch), rbm.W.device)).double()
+                                                               - log_z).sum().reshape(1), 1)
     res = {"mean_ll": s / max(1, n), "sum_ll": s, "n": n, "log_z": float(log_z), "se": se, "ess": ess}
     _log_scalars(model, "ll/", res, ("mean_ll", "log_z", "se", "ess"))
     return res
 
 
 # ---- the whole stack: variational lower bound and importance-sampled likelihood of the DBN ---------------------------------------
-def _stack(model):
-    """The RBMs of the stack, bottom first: the layers of an iDBN, or `model` itself as a stack of one."""
+def _layers(model):
     layers = getattr(model, "layers", None)
-    layers = list(layers) if layers is not None and len(layers) > 0 else [model]
+    return list(layers) if layers is not None and len(layers) > 0 else [model]
+
+
+def _stack(model):
+    """The RBMs of the stack, bottom first: the layers of an iDBN, or `model` itself as a stack of one.  All Bernoulli."""
+    layers = _layers(model)
     for rbm in layers:
         _check_binary(rbm)
     return layers
@@ -352,20 +365,26 @@ def evaluate_dbn_bound(model, loader=None, log_z_top: Optional[float] = None, n_
     so evaluating between epochs does not change training.  The sum is accumulated on the device; the host synchronises once,
     after the last batch.  A ragged last batch is fine; ``max_batches`` stops early.  With a ``wandb_run`` on the model the
     scalars are logged as ``ll/dbn_...``."""
-    layers = _stack(model)
+    return _evaluate_bound(model, _stack(model), estimate_log_partition, "ll/dbn_", _gen(model), loader, log_z_top, n_samples,
+                           max_batches, importance, ais_kwargs)
+
+
+def _evaluate_bound(model, layers, estimate, prefix, gen, loader, log_z_top, n_samples, max_batches, importance, ais_kwargs):
+    """``evaluate_dbn_bound`` / ``evaluate_gaussian_dbn_bound`` over the checked ``layers``: ``estimate`` is the AIS of the top RBM,
+    ``prefix`` that of the logged scalars, ``gen`` the generative twins of an untied model."""
     loader = loader if loader is not None else getattr(model, "val_loader", None)
     if loader is None:
         return None
-    log_z_top, se, ess = _known_or_estimated(log_z_top, estimate_log_partition, layers[-1], ais_kwargs)
+    log_z_top, se, ess = _known_or_estimated(log_z_top, estimate, layers[-1], ais_kwargs)
     rng = _draws(ais_kwargs.get("seed"))
 
     def sums(batch):
-        w = _sample_values(layers, _first(batch), log_z_top, n_samples, "logq" if importance else "entropy", rng, _gen(model))
+        w = _sample_values(layers, _first(batch), log_z_top, n_samples, "logq" if importance else "entropy", rng, gen)
         return (_logmeanexp_rows(w) if importance else w.mean(1)).sum().reshape(1)
 
     (s,), n = _sum_batches(loader, max_batches, sums, 1)
     res = {"mean_bound": s / max(1, n), "sum_bound": s, "n": n, "log_z_top": float(log_z_top), "se": se, "ess": ess, "n_samples": int(n_samples)}
-    _log_scalars(model, "ll/dbn_", res, ("mean_bound", "log_z_top", "se", "ess", "n_samples"))
+    _log_scalars(model, prefix, res, ("mean_bound", "log_z_top", "se", "ess", "n_samples"))
     return res
 
 
@@ -414,7 +433,7 @@ def _imdbn_values(model, img, y, log_z_joint, n_samples, mode, rng):
     jr = model.joint_rbm
     dev = jr.W.device
     # ALL image layers are directed: the joint RBM sits above the top one
-    acc, cur, B, S = _directed(list(model.image_idbn.layers), img, dev, n_samples, mode, rng)
+    acc, cur, B, S = _directed(_stack(model.image_idbn), img, dev, n_samples, mode, rng)
     gt = _label_index(y.to(dev)).to(torch.int32)
     if S > 1:
         gt = gt.repeat_interleave(S, 0)
@@ -682,7 +701,7 @@ def imdbn_pseudo_log_likelihood(model, img: torch.Tensor, y: torch.Tensor, seed:
     the group empty and makes both outputs of that row NaN.  See the module docstring for ``seed``.  No host sync."""
     jr = model.joint_rbm
     dev = jr.W.device
-    _, z, B, _ = _directed(list(model.image_idbn.layers), img, dev, 1, "entropy", _draws(seed))
+    _, z, B, _ = _directed(_stack(model.image_idbn), img, dev, 1, "entropy", _draws(seed))
     K = int(model.num_labels)
     Dz = z.size(1)
     gt = _label_index(y.to(dev)).long()
@@ -705,16 +724,7 @@ def _check_gaussian(rbm):
 def gaussian_base_rate_bias(data, device=None) -> torch.Tensor:
     """Visible bias of the Gaussian base-rate model: the column means of the data.  A tensor ``[N, ...]`` or a loader of such batches;
     sums are accumulated on the device in float64."""
-    it = [data] if isinstance(data, torch.Tensor) else batches(data)
-    tot, n = None, 0
-    for b in it:
-        x = _first(b)
-        x = rows_on_device(x, device if device is not None else x.device).double()
-        tot = x.sum(0) if tot is None else tot + x.sum(0)
-        n += x.size(0)
-    if tot is None or n == 0:
-        raise ValueError("gaussian_base_rate_bias: no rows")
-    return (tot / n).float()
+    return _column_means("gaussian_base_rate_bias", data, device).float()
 
 
 def _gaussian_log_z_base(rbm, dev) -> torch.Tensor:
@@ -752,25 +762,14 @@ def evaluate_gaussian_log_likelihood(model, loader=None, log_z: Optional[float] 
     ``loader`` (default ``model.val_loader``; None without one): the keys of ``evaluate_log_likelihood``.  ``log_z`` None: estimated
     with ``estimate_gaussian_log_partition(**ais_kwargs)``.  Sums on the device, one host sync after the last batch; with a
     ``wandb_run`` on the model the scalars are logged as ``ll/...``."""
-    rbm = _bottom(model)
-    _check_gaussian(rbm)
-    loader = loader if loader is not None else getattr(model, "val_loader", None)
-    if loader is None:
-        return None
-    log_z, se, ess = _known_or_estimated(log_z, estimate_gaussian_log_partition, rbm, ais_kwargs)
-    (s,), n = _sum_batches(loader, max_batches,
-                           lambda batch: gaussian_log_likelihood(rbm, rows_on_device(_first(batch), rbm.W.device), log_z).sum().reshape(1), 1)
-    res = {"mean_ll": s / max(1, n), "sum_ll": s, "n": n, "log_z": float(log_z), "se": se, "ess": ess}
-    _log_scalars(model, "ll/", res, ("mean_ll", "log_z", "se", "ess"))
-    return res
+    return _evaluate_ll(model, loader, log_z, max_batches, ais_kwargs, _check_gaussian, estimate_gaussian_log_partition)
 
 
 # ---- the whole stack above a Gaussian bottom layer (DESIGN section 31) -------------------------------------------------------------
 def _gaussian_stack(model):
     """The RBMs of a stack with a Gaussian bottom layer, bottom first: the layers of an ``iDBN`` built with ``GAUSSIAN_VISIBLE``, or
     a ``GaussianRBM`` as a stack of one.  Every layer above the bottom one is Bernoulli without softmax groups."""
-    layers = getattr(model, "layers", None)
-    layers = list(layers) if layers is not None and len(layers) > 0 else [model]
+    layers = _layers(model)
     if not getattr(layers[0], "gaussian_visible", False):
         raise ValueError("the Gaussian stack bounds need a GaussianRBM as the bottom layer (an iDBN built with GAUSSIAN_VISIBLE, or a "
                          "GaussianRBM; DESIGN section 31); Bernoulli stacks have dbn_lower_bound / dbn_log_likelihood_is")
@@ -781,25 +780,6 @@ def _gaussian_stack(model):
     return layers
 
 
-def _gaussian_sample_values(layers, v, log_z_top, n_samples, mode, rng) -> torch.Tensor:
-    if mode not in ("entropy", "logq"):
-        raise ValueError("mode must be 'entropy' or 'logq'")
-    S = int(n_samples)
-    if S < 1:
-        raise ValueError("n_samples must be >= 1")
-    bottom, top = layers[0], layers[-1]
-    cur = rows_on_device(v, bottom.W.device)
-    B = cur.size(0)
-    if S > 1:
-        cur = cur.repeat_interleave(S, 0)
-    if len(layers) == 1:      # no directed layer, no draw
-        return gaussian_log_likelihood(bottom, cur, log_z_top).view(B, S)
-    acc, cur = _E.get_engine(bottom.W.data).gauss_bound_step(bottom, bottom.logvar.data, cur, rng, acc=None, mode=mode)
-    for rbm in layers[1:-1]:
-        acc, cur = _E.get_engine(rbm.W.data).bound_step(rbm, cur, rng, acc=acc, mode=mode)
-    return (acc + (-top.free_energy(cur).double() - log_z_top)).view(B, S)
-
-
 @torch.no_grad()
 def gaussian_dbn_sample_values(model, v: torch.Tensor, log_z_top, n_samples: int = 1, mode: str = "entropy",
                                seed: Optional[int] = None) -> torch.Tensor:
@@ -808,7 +788,7 @@ def gaussian_dbn_sample_values(model, v: torch.Tensor, log_z_top, n_samples: int
     ``bound_step`` per directed Bernoulli layer on the same accumulator, ``free_energy`` on the top RBM, no host sync.  ``model``: an
     ``iDBN`` built with ``GAUSSIAN_VISIBLE`` or a ``GaussianRBM`` (a stack of one: no draw, the value is ``gaussian_log_likelihood``
     and ``log_z_top`` is the Gaussian log Z).  ``log_z_top``: log Z of the TOP RBM."""
-    return _gaussian_sample_values(_gaussian_stack(model), v, log_z_top, n_samples, mode, _draws(seed))
+    return _sample_values(_gaussian_stack(model), v, log_z_top, n_samples, mode, _draws(seed))
 
 
 @torch.no_grad()
@@ -835,18 +815,5 @@ def evaluate_gaussian_dbn_bound(model, loader=None, log_z_top: Optional[float] =
     batches; the sum is accumulated on the device and the host synchronises once, after the last batch.  With a ``wandb_run`` on the
     model the scalars are logged as ``ll/gdbn_...``."""
     layers = _gaussian_stack(model)
-    loader = loader if loader is not None else getattr(model, "val_loader", None)
-    if loader is None:
-        return None
     estimate = estimate_log_partition if len(layers) > 1 else estimate_gaussian_log_partition
-    log_z_top, se, ess = _known_or_estimated(log_z_top, estimate, layers[-1], ais_kwargs)
-    rng = _draws(ais_kwargs.get("seed"))
-
-    def sums(batch):
-        w = _gaussian_sample_values(layers, _first(batch), log_z_top, n_samples, "logq" if importance else "entropy", rng)
-        return (_logmeanexp_rows(w) if importance else w.mean(1)).sum().reshape(1)
-
-    (s,), n = _sum_batches(loader, max_batches, sums, 1)
-    res = {"mean_bound": s / max(1, n), "sum_bound": s, "n": n, "log_z_top": float(log_z_top), "se": se, "ess": ess, "n_samples": int(n_samples)}
-    _log_scalars(model, "ll/gdbn_", res, ("mean_bound", "log_z_top", "se", "ess", "n_samples"))
-    return res
+    return _evaluate_bound(model, layers, estimate, "ll/gdbn_", None, loader, log_z_top, n_samples, max_batches, importance, ais_kwargs)

@@ -1,17 +1,24 @@
-"""``tests/oracle_engine.OracleEngine`` plus the ``HipEngine.gauss_*`` calls on the twin of tests/gauss_oracle.py in float32: the CPU
-suite runs the host logic of ``GaussianRBM`` and of ``iDBN(GAUSSIAN_VISIBLE)`` through it.
+"""``tests/oracle_engine.OracleEngine`` plus the ``HipEngine.gauss_*`` calls in float32 -- the twin of tests/gauss_oracle.py,
+``gauss_ais`` on the restatement of tests/gauss_ais_oracle.py, ``gauss_bound_step`` on that of tests/gauss_bound_oracle.py -- and the
+Bernoulli likelihood calls of ``tests/bound_oracle.LikelihoodOracleEngine`` (``bound_step``, ``ais``) for the layers above a Gaussian
+one: the CPU suite runs the host logic of ``GaussianRBM``, of ``iDBN(GAUSSIAN_VISIBLE)`` and of the Gaussian likelihood functions
+(imdbn/utils/likelihood.py) through it.  ``calls`` records the order of the bracket calls and of ``free_energy`` with
+the shapes they saw.
 
 TEST INFRASTRUCTURE ONLY."""
 import numpy as np
 import torch
 
+import gauss_ais_oracle as GA
+import gauss_bound_oracle as GB
 import gauss_oracle as G
-from oracle_engine import OracleEngine, _Src, _np
+from bound_oracle import LikelihoodOracleEngine
+from oracle_engine import _Src, _np
 
 F32 = np.float32
 
 
-class GaussOracleEngine(OracleEngine):
+class GaussOracleEngine(LikelihoodOracleEngine):
     name = "oracle-test-double-gauss"
 
     @staticmethod
@@ -69,3 +76,34 @@ class GaussOracleEngine(OracleEngine):
         loss = G.cd_step(st, _np(data), cd_k, s, lr, mom, lr_z, z_lo, z_hi, sample_v)
         s.done()
         return self._t(np.array(loss, F32)).reshape(()) if monitor else None
+
+    def gauss_ais(self, rbm, logvar, betas, n_chains: int, rng, base_vis_bias=None, return_state: bool = False):
+        b = np.asarray(betas.tolist() if hasattr(betas, "tolist") else betas, F32)
+        self.calls.append(("gauss_ais", int(n_chains), int(b.size - 1), base_vis_bias is not None))
+        s = _Src(rng)
+        logw, v, _ = GA.gauss_ais_logw(_np(rbm.W.data), _np(rbm.vis_bias.data), _np(rbm.hid_bias.data), _np(logvar),
+                                       None if base_vis_bias is None else _np(base_vis_bias), b, int(n_chains), s, dt=F32)
+        s.done()
+        lw = torch.from_numpy(np.ascontiguousarray(logw, np.float64))
+        return (lw, self._t(v)) if return_state else lw
+
+    def gauss_bound_step(self, rbm, logvar, v, rng, acc=None, mode="entropy"):
+        self.calls.append(("gauss_bound_step", tuple(v.shape), mode))
+        s = _Src(rng)
+        a, h, self.last_margin, _, _ = GB.gauss_bound_step(_np(rbm.W.data), _np(rbm.vis_bias.data), _np(rbm.hid_bias.data), _np(logvar),
+                                                           _np(v), mode, s, dt=F32)
+        s.done()
+        a = torch.from_numpy(np.ascontiguousarray(a, np.float64))
+        if acc is None:
+            acc = a
+        else:
+            acc += a
+        return acc, self._t(h)
+
+    def bound_step(self, rbm, v, rng, acc=None, mode="entropy"):
+        self.calls.append(("bound_step", tuple(v.shape), mode))
+        return LikelihoodOracleEngine.bound_step(self, rbm, v, rng, acc=acc, mode=mode)
+
+    def free_energy(self, rbm, v):
+        self.calls.append(("free_energy", tuple(v.shape)))
+        return LikelihoodOracleEngine.free_energy(self, rbm, v)

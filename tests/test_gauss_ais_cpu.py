@@ -17,7 +17,7 @@ import anneal_oracle as A
 import gauss_ais_cases as Cs
 import gauss_ais_oracle as GA
 import gauss_oracle as G
-from gauss_ais_engine_double import GaussAisOracleEngine
+from gauss_engine_double import GaussOracleEngine
 from imdbn import engine as E
 from imdbn.engine import native, rng as R
 from imdbn.utils import likelihood as LK
@@ -29,7 +29,7 @@ F32, F64 = np.float32, np.float64
 
 @pytest.fixture()
 def double():
-    eng = GaussAisOracleEngine()
+    eng = GaussOracleEngine()
     E.set_engine_for_testing(eng)
     yield eng
     E.set_engine_for_testing(None)

@@ -20,7 +20,7 @@ import bound_oracle as B
 import gauss_bound_cases as Cs
 import gauss_bound_oracle as GB
 import gauss_oracle as G
-from gauss_bound_engine_double import GaussBoundOracleEngine
+from gauss_engine_double import GaussOracleEngine
 from imdbn import engine as E
 from imdbn.engine import native, rng as R
 from imdbn.utils import likelihood as LK
@@ -33,7 +33,7 @@ PARAMS = {"LEARNING_RATE": 0.05, "WEIGHT_PENALTY": 1e-4, "INIT_MOMENTUM": 0.5, "
 
 @pytest.fixture()
 def double():
-    eng = GaussBoundOracleEngine()
+    eng = GaussOracleEngine()
     E.set_engine_for_testing(eng)
     yield eng
     E.set_engine_for_testing(None)
