@@ -544,6 +544,33 @@ int imdbn_rbm_gauss_cd_step(const imdbn_rbm_desc* d, float* logvar, float* logva
 int imdbn_rbm_gauss_ais(const imdbn_rbm_desc* d, const float* logvar, const float* betas, int K, int M, const float* base_vis_bias,
                         imdbn_rng* rng, double* logw, float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- reverse annealed importance sampling over Gaussian visibles (imdbn/utils/likelihood.py: gaussian_reverse_ais_log_likelihood;
+ * DESIGN section 33) -------------------------------------------------------------------------------------------------------------
+ * The forward chain of imdbn_rbm_gauss_ais read as a generative model p_ann over real rows (v_1 ~ N(b_A, exp(z)), v_{k+1} ~
+ * T_k(. | v_k) for k = 1..K, one transition at beta_K = 1 included; the sample is v_{K+1}), run backwards from the rows v [R][V]
+ * (real, row stride ldv; the caller replicates a test row once per chain).  In the notation of imdbn_rbm_gauss_ais, with
+ * t_v(v) = sum_i (b_i - b_A,i) exp(-z_i) (v_i - (b_i + b_A,i) / 2) and T_k: h = 1[sigmoid(beta_k x(v)) > U], then
+ * v' = ((1 - beta_k) b_A + beta_k (b + h W^T)) + exp(z / 2) n (fp32, in this order) -- a Gibbs step of the joint at beta_k, its own
+ * reversal:
+ *   logw = -q_B(v) + sum_j softplus(x_j(v))                                                                          (= -F(v))
+ *   for k = K..1:  u_k ~ T_k(. | u_{k+1})                                              (u_{K+1} = v)          ("u", H), ("n", V)
+ *                  logw -= (beta_k - beta_{k-1}) t_v(u_k) + sum_j [softplus(beta_k x_j(u_k)) - softplus(beta_{k-1} x_j(u_k))]
+ *                                                                                      (both sums in double, one expression)
+ * logw [R] (device, double) is OVERWRITTEN; exp(logw) / Z_A is an unbiased estimate of the density p_ann(v), log Z_A = H log 2 +
+ * (V / 2) log 2 pi + sum_i z_i / 2 (NOT included).  base_vis_bias NULL means b_A = b, as in imdbn_rbm_gauss_ais.  out_v (nullable):
+ * the final state u_1 [R][V], row stride ldo >= V.  A row holding a non-finite element gets logw = NaN, that row only (checked on
+ * the device).
+ * Draws: K times ("u", H), ("n", V): draws_used = 2 K.  Sums, logits and the Philox key as in imdbn_rbm_gauss_ais: row i is the
+ * same chain whatever R, no atomics, and the same call on the same state gives the same bits.
+ * Plain launches on the caller's stream: no host sync, no allocation, no memcpy.  Workspace: imdbn_ws_bytes(V, H, R).
+ * An argument error names the offending value, comes before the first launch and leaves logw and out_v untouched.  IMDBN_E_INVALID:
+ * R < 1, K < 1, betas[0] != 0, betas[K] != 1, betas not strictly increasing, a null logvar / v / betas / rng / logw, ldv < V, ldo < V
+ * with out_v; IMDBN_E_UNSUPPORTED: softmax groups; IMDBN_E_WORKSPACE: a short workspace; IMDBN_E_RNG: a replay tape shorter than
+ * K R (H + V) floats.  The caller's parameters, logvar and v are only read. */
+int imdbn_rbm_gauss_reverse_ais(const imdbn_rbm_desc* d, const float* logvar, const float* v, int64_t ldv, int R, int K,
+                                const float* betas, const float* base_vis_bias, imdbn_rng* rng, double* logw, float* out_v, int64_t ldo,
+                                void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- the bottom bracket of the DBN lower bound under a Gaussian visible layer (imdbn/utils/likelihood.py:
  * gaussian_dbn_sample_values) ---------------------------------------------------------------------------------------
  * imdbn_rbm_bound_step for the Gaussian-visible RBM of (d, logvar).  For every row of v [M][V] (real, row stride ldv), with

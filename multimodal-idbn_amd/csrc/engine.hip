@@ -1900,7 +1900,47 @@ int imdbn_rbm_gauss_free_energy(const imdbn_rbm_desc* d, const float* logvar, co
 // last -- the down propagation's raw mean b + h W^T and gauss_ais_visible, which leaves v, u and the row's visible weight term.
 // Built from the anneal_* pieces of imdbn_rbm_ais.  State buffers are scratch of the workspace no propagation of this call touches:
 // logits in f_h, the mean in f_vp, the fp32 state in f_v[0] (or the caller's out_v), u in f_v[1], the M visible terms (doubles) at
-// the head of vis_rm[1] (>= 96 Bp bytes) -- imdbn_ws_bytes(V, H, M) covers the call.
+// the head of vis_rm[1] (>= 96 Bp bytes) -- imdbn_ws_bytes(V, H, M) covers the call.  The reverse call runs the same
+// transitions backwards from the caller's rows; the gauss_anneal_* pieces below are what the two share.
+
+// what every kernel of either Gaussian annealing call is told, after anneal_setup; `rows`: M chains or R rows
+static GaussAisArgs gauss_anneal_args(const Anneal& n, const imdbn_rbm_desc* d, const float* logvar, const float* base_vis_bias, int rows,
+                                      double* logw) {
+    const Layout& L = n.c.L;
+    GaussAisArgs g;
+    memset(&g, 0, sizeof(g));
+    g.M = rows; g.Bp = L.Bp; g.V = L.V; g.H = L.H; g.Hpad = L.Hpad;
+    g.vis_bias = d->vis_bias; g.base_bias = base_vis_bias ? base_vis_bias : d->vis_bias; g.logvar = logvar;
+    g.state = n.a.state; g.lds = n.a.lds; g.u = L.f_v[1]; g.ldu = L.V;
+    g.tv = reinterpret_cast<double*>(L.vis_rm[1]);
+    g.x = L.f_h; g.ldx = L.H; g.logw = logw;
+    return g;
+}
+
+// The weight step `w` (its k, form and direction are the caller's) on the logits of the current state; `sample`: it also draws h for
+// the transition at w.beta_draw.
+static int gauss_anneal_weigh(Anneal& n, GaussAisArgs w, bool sample) {
+    const Layout& L = n.c.L;
+    w.sample = sample ? 1 : 0;
+    if (sample) { w.uni = n.c.rng.floats(w.M, L.H); w.rm = L.hid_rm; w.bits = L.hid_bits; }
+    hipLaunchKernelGGL(gauss_ais_weight_sample_h, n.grid, n.block, 0, n.c.s, w);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the next state from that h: m = b + h W^T, then v = ((1 - beta) b_A + beta m) + e^{z/2} n, with u and the visible weight term
+static int gauss_anneal_visible(Anneal& n, GaussAisArgs s, float beta) {
+    Ctx& c = n.c;
+    const Layout& L = c.L;
+    c.hid_bits_ok = true;                  // hid_bits describes hid_rm: the down half may read the bit plane
+    CHK(down_logits(c, L.f_vp));
+    s.mean = L.f_vp; s.ldm = L.V; s.beta = beta;
+    s.nz = c.rng.floats(s.M, L.V);
+    hipLaunchKernelGGL(gauss_ais_visible, n.grid, n.block, 0, c.s, s);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 int imdbn_rbm_gauss_ais(const imdbn_rbm_desc* d, const float* logvar, const float* betas, int K, int M, const float* base_vis_bias,
                         imdbn_rng* rng, double* logw, float* out_v, int64_t ldo, void* ws, size_t ws_bytes, imdbn_stream_t stream) {
     CHK(gauss_check("gauss_ais", d, false, logvar));
@@ -1908,39 +1948,53 @@ int imdbn_rbm_gauss_ais(const imdbn_rbm_desc* d, const float* logvar, const floa
     CHK(tape_room("gauss_ais", rng, (int64_t)M * d->V + (int64_t)(K - 1) * M * ((int64_t)d->H + d->V), 0));
     Anneal n(d, rng, stream);
     CHK(anneal_setup(n, d, M, nullptr, logw, out_v, ldo, ws, ws_bytes));
-    Ctx& c = n.c;
-    const Layout& L = c.L;
-    GaussAisArgs g;
-    memset(&g, 0, sizeof(g));
-    g.M = M; g.Bp = L.Bp; g.V = L.V; g.H = L.H; g.Hpad = L.Hpad;
-    g.vis_bias = d->vis_bias; g.base_bias = base_vis_bias ? base_vis_bias : d->vis_bias; g.logvar = logvar;
-    g.state = n.a.state; g.lds = n.a.lds; g.u = L.f_v[1]; g.ldu = L.V;
-    g.tv = reinterpret_cast<double*>(L.vis_rm[1]);
-    g.x = L.f_h; g.ldx = L.H; g.logw = logw;
+    const GaussAisArgs g = gauss_anneal_args(n, d, logvar, base_vis_bias, M, logw);
     {   // v_1 = b_A + e^{z/2} n, logw = 0
         GaussAisArgs s = g;
-        s.nz = c.rng.floats(M, L.V);
-        hipLaunchKernelGGL(gauss_ais_visible, n.grid, n.block, 0, c.s, s);
+        s.nz = n.c.rng.floats(M, d->V);
+        hipLaunchKernelGGL(gauss_ais_visible, n.grid, n.block, 0, n.c.s, s);
         HIPCHK(hipGetLastError());
     }
     for (int k = 1; k <= K; ++k) {
         CHK(anneal_logits(n, g.u));        // x = c + u_k W
         GaussAisArgs w = g;
-        w.beta_prev = betas[k - 1]; w.beta = betas[k];
-        w.sample = k < K ? 1 : 0;          // the last temperature only weighs
-        if (w.sample) { w.uni = c.rng.floats(M, L.H); w.rm = L.hid_rm; w.bits = L.hid_bits; }
-        hipLaunchKernelGGL(gauss_ais_weight_sample_h, n.grid, n.block, 0, c.s, w);
-        HIPCHK(hipGetLastError());
-        if (k == K) break;
-        c.hid_bits_ok = true;              // hid_bits describes hid_rm: the down half may read the bit plane
-        CHK(down_logits(c, L.f_vp));       // m = b + h W^T
-        GaussAisArgs s = g;
-        s.mean = L.f_vp; s.ldm = L.V; s.beta = betas[k];
-        s.nz = c.rng.floats(M, L.V);
-        hipLaunchKernelGGL(gauss_ais_visible, n.grid, n.block, 0, c.s, s);
+        w.beta_prev = betas[k - 1]; w.beta = w.beta_draw = betas[k];
+        CHK(gauss_anneal_weigh(n, w, k < K));      // + Delta_k(v_k); the last temperature only weighs
+        if (k < K) CHK(gauss_anneal_visible(n, g, betas[k]));
+    }
+    return n.c.rng.finish();
+}
+
+// Reverse annealed importance sampling over Gaussian visibles: R chains from the caller's rows, and logw collects
+// -F(v) - sum_k Delta_k(u_k).  gauss_rais_load_v, then K + 1 weight steps, and between two of them the transition at the temperature
+// the weight kernel drew h for: per temperature the launches of imdbn_rbm_gauss_ais, on its state buffers.
+int imdbn_rbm_gauss_reverse_ais(const imdbn_rbm_desc* d, const float* logvar, const float* v, int64_t ldv, int R, int K,
+                                const float* betas, const float* base_vis_bias, imdbn_rng* rng, double* logw, float* out_v, int64_t ldo,
+                                void* ws, size_t ws_bytes, imdbn_stream_t stream) {
+    CHK(gauss_check("gauss_reverse_ais", d, false, logvar));
+    CHK(anneal_check("gauss_reverse_ais", d, true, v, ldv, R, K, betas, rng, logw, out_v, ldo));
+    CHK(tape_room("gauss_reverse_ais", rng, (int64_t)K * R * ((int64_t)d->H + d->V), 0));
+    Anneal n(d, rng, stream);
+    CHK(anneal_setup(n, d, R, nullptr, logw, out_v, ldo, ws, ws_bytes));
+    const GaussAisArgs g = gauss_anneal_args(n, d, logvar, base_vis_bias, R, logw);
+    {   // u_{K+1} = the caller's rows, logw = -q_B(v)
+        GaussRaisLoadArgs l;
+        memset(&l, 0, sizeof(l));
+        l.a = g; l.v = v; l.ldv = ldv;
+        hipLaunchKernelGGL(gauss_rais_load_v, n.grid, n.block, 0, n.c.s, l);
         HIPCHK(hipGetLastError());
     }
-    return c.rng.finish();
+    for (int k = K + 1; k >= 1; --k) {     // k = K + 1: the start row's softplus term; k <= K: -Delta_k(u_k)
+        const bool first = k == K + 1;
+        CHK(anneal_logits(n, g.u));        // x = c + u_k W
+        GaussAisArgs w = g;
+        w.reverse = 1; w.first = first ? 1 : 0;
+        if (!first) { w.beta_prev = betas[k - 1]; w.beta = betas[k]; }
+        w.beta_draw = first ? betas[K] : betas[k - 1];      // temperature of the transition that follows
+        CHK(gauss_anneal_weigh(n, w, k > 1));               // the last step (k = 1) only weighs
+        if (k > 1) CHK(gauss_anneal_visible(n, g, w.beta_draw));
+    }
+    return n.c.rng.finish();
 }
 
 // One directed layer of the DBN lower bound, and its bottom bracket under a Gaussian visible layer (DESIGN §31;

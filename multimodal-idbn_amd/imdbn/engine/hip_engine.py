@@ -345,9 +345,10 @@ class HipEngine:
         return out
 
     def _anneal(self, name: str, rbm, d, sched_fn, n_rows: int, betas, rng, base_vis_bias, return_state: bool, v=None, logvar=None):
-        """The shared body of ``ais``, ``ais_groups``, ``reverse_ais`` and ``gauss_ais``: the entry ``imdbn_rbm_<name>`` over ``n_rows``
-        chains under the draw schedule ``sched_fn(K)``; ``v``: the start states of the call that takes them; ``logvar``: the checked
-        log-variances of the Gaussian call, whose entry takes ``logvar, betas, K, M`` where the others take ``M, K, betas``."""
+        """The shared body of ``ais``, ``ais_groups``, ``reverse_ais``, ``gauss_ais`` and ``gauss_reverse_ais``: the entry
+        ``imdbn_rbm_<name>`` over ``n_rows`` chains under the draw schedule ``sched_fn(K)``; ``v``: the start states of the calls that
+        take them; ``logvar``: the checked log-variances of the Gaussian calls -- the forward one's entry takes ``logvar, betas, K, M``
+        where the others take ``M, K, betas``."""
         dev = rbm.W.device if v is None else v.device
         b = [float(x) for x in (betas.tolist() if hasattr(betas, "tolist") else betas)]
         K, M = len(b) - 1, int(n_rows)
@@ -360,7 +361,10 @@ class HipEngine:
         sched = sched_fn(max(K, 1))
         r, keep = self._rng(rng, sched, max(M, 1), dev)
         start = () if v is None else (_ptr(v), v.stride(0))
-        head = (*start, M, K, arr) if logvar is None else (_ptr(logvar), arr, K, M)
+        if logvar is None:
+            head = (*start, M, K, arr)
+        else:
+            head = (_ptr(logvar), arr, K, M) if v is None else (_ptr(logvar), *start, M, K, arr)
         self._call("imdbn_rbm_" + name, C.byref(d), *head, _ptr(bA), C.byref(r), _ptr(logw), _ptr(state), d.V,
                    *self._ws_tail(dev, d.V, d.H, max(M, 1)))
         self._done(rng, r, sched)
@@ -765,6 +769,21 @@ class HipEngine:
         z = self._logvar("gauss_ais: logvar", logvar, d.V, dev)
         return self._anneal("gauss_ais", rbm, d, lambda K: R.sched_gauss_ais(d.V, d.H, K), n_chains, betas, rng, base_vis_bias,
                             return_state, logvar=z)
+
+    def gauss_reverse_ais(self, rbm, logvar, v_rows, betas, rng, base_vis_bias: Optional[torch.Tensor] = None, return_state: bool = False):
+        """Reverse annealed importance sampling over Gaussian visibles (imdbn_rbm_gauss_reverse_ais): one chain per
+        row of ``v_rows`` ``[R, V]`` (real; the caller replicates a test row once per chain) runs the transitions of ``gauss_ais``
+        backwards through ``betas``, T_K first.  Returns the per-chain log weights, a float64 device tensor ``[R]`` (and the final
+        states u_1 ``[R, V]`` with ``return_state``): ``-log Z_A + logmeanexp`` over a test row's chains is a stochastic lower bound on
+        the log-density log p_ann(row), log Z_A as ``gauss_ais`` states it.  ``base_vis_bias`` None = the RBM's own ``vis_bias``.  A
+        row holding a non-finite element gets NaN.  No host sync."""
+        d = self._desc(rbm, False)
+        if not v_rows.is_cuda or v_rows.dim() != 2 or v_rows.size(1) != d.V:
+            raise N.EngineError(f"gauss_reverse_ais needs a HIP tensor v_rows [R, {d.V}]")
+        v = _f32c(v_rows)
+        z = self._logvar("gauss_reverse_ais: logvar", logvar, d.V, v.device)
+        return self._anneal("gauss_reverse_ais", rbm, d, lambda K: R.sched_gauss_reverse_ais(d.V, d.H, K), v.size(0), betas, rng,
+                            base_vis_bias, return_state, v=v, logvar=z)
 
     def gauss_bound_step(self, rbm, logvar, v, rng, acc: Optional[torch.Tensor] = None, mode: str = "entropy"):
         """The bottom bracket of the DBN lower bound under a Gaussian visible layer (imdbn_rbm_gauss_bound_step):

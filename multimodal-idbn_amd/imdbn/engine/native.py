@@ -141,6 +141,8 @@ SIGNATURES = {
     "imdbn_rbm_gauss_cd_step": (_INT, [C.POINTER(RbmDesc), _P, _P, _P, _I64, _INT, C.POINTER(CdOpts), _F, _F, _F, _INT, C.POINTER(Rng), _P,
                                        _P, _P, _SZ, _P]),
     "imdbn_rbm_gauss_ais": (_INT, [C.POINTER(RbmDesc), _P, C.POINTER(_F), _INT, _INT, _P, C.POINTER(Rng), _P, _P, _I64, _P, _SZ, _P]),
+    "imdbn_rbm_gauss_reverse_ais": (_INT, [C.POINTER(RbmDesc), _P, _P, _I64, _INT, _INT, C.POINTER(_F), _P, C.POINTER(Rng), _P, _P, _I64, _P,
+                                           _SZ, _P]),
     "imdbn_rbm_gauss_bound_step": (_INT, [C.POINTER(RbmDesc), _P, _P, _I64, _INT, _INT, C.POINTER(Rng), _P, _P, _I64, _P, _SZ, _P]),
     "imdbn_rbm_delta_step": (_INT, [C.POINTER(RbmDesc), _INT, _P, _I64, _P, _I64, _INT, C.POINTER(CdOpts), _P, _P, _SZ, _P]),
     "imdbn_rbm_backprop_step": (_INT, [C.POINTER(RbmDesc), _P, _I64, _P, _I64, _P, _I64, _P, _I64, _INT, C.POINTER(CdOpts), _P, _I64, _P, _I64,

@@ -139,6 +139,12 @@ def sched_reverse_ais(V: int, H: int, groups: Sequence[Tuple[int, int]], K: int)
     return int(K) * ([("u", H)] + sched_sample_visible(V, groups))
 
 
+def sched_gauss_reverse_ais(V: int, H: int, K: int) -> Schedule:
+    """imdbn_rbm_gauss_reverse_ais over K temperatures: one (h, v) transition per temperature, T_K first, h uniform and v normal:
+    2 K draws."""
+    return int(K) * [("u", H), ("n", V)]
+
+
 def sched_bound(H: int) -> Schedule:
     """imdbn_rbm_bound_step: the one draw of h ~ q(h | v)."""
     return [("u", int(H))]

@@ -11,7 +11,8 @@ layer is Bernoulli, so ``forward`` feeds a Bernoulli RBM above it (``iDBN`` with
 methods that assume Bernoulli visibles -- AIS, the pseudo-log-likelihood, the persistent / centered / label / clamped trainers and
 the chains -- raise ``ValueError``: none of them may return a number computed for the wrong model.  The density of THIS model has
 methods of its own, ``gaussian_log_partition`` (AIS over Gaussian visibles, ``HipEngine.gauss_ais``) and ``gaussian_log_likelihood``
-(-F(v) - log Z), over ``imdbn.utils.likelihood``.
+(-F(v) - log Z), over ``imdbn.utils.likelihood``, and ``gaussian_log_likelihood_conservative``, the reverse-AIS
+side that needs no log Z (``HipEngine.gauss_reverse_ais``).
 """
 from __future__ import annotations
 
@@ -157,6 +158,14 @@ class GaussianRBM(RBM):
         """log p(v) = -F(v) - log Z per row, float64 ``[B]`` (``imdbn.utils.likelihood.gaussian_log_likelihood``)."""
         from imdbn.utils.likelihood import gaussian_log_likelihood
         return gaussian_log_likelihood(self, self._in(v), log_z)
+
+    def gaussian_log_likelihood_conservative(self, v: torch.Tensor, n_chains: int = 16, n_betas: int = 1000, betas=None,
+                                             base_vis_bias=None, seed=None, max_rows: int = 4096) -> dict:
+        """Reverse-AIS estimate of the log-density of the annealing model per row: ``{"ll", "ess", "logw"}``
+        (``imdbn.utils.likelihood.gaussian_reverse_ais_log_likelihood``; no AIS estimate of log Z enters)."""
+        from imdbn.utils.likelihood import gaussian_reverse_ais_log_likelihood
+        return gaussian_reverse_ais_log_likelihood(self, self._in(v), n_chains=n_chains, n_betas=n_betas, betas=betas,
+                                                   base_vis_bias=base_vis_bias, seed=seed, max_rows=max_rows)
 
     # ---- what assumes Bernoulli visibles --------------------------------------------------------
     log_partition = _refuse("log_partition")

@@ -346,6 +346,12 @@ class iDBN:
         from imdbn.utils.likelihood import gaussian_dbn_log_likelihood_is, gaussian_dbn_lower_bound
         return (gaussian_dbn_log_likelihood_is if importance else gaussian_dbn_lower_bound)(self, v, log_z_top, n_samples, seed)
 
+    def gaussian_log_likelihood_bound_conservative(self, v: torch.Tensor, **kw) -> torch.Tensor:
+        """The lower bound of a stack built with ``GAUSSIAN_VISIBLE`` with the reverse-AIS estimate as its top term, float64 ``[B]``
+        (``imdbn.utils.likelihood.gaussian_dbn_conservative_bound``; no AIS estimate of log Z enters)."""
+        from imdbn.utils.likelihood import gaussian_dbn_conservative_bound
+        return gaussian_dbn_conservative_bound(self, v, **kw)
+
     def save_model(self, path: str):
         """idbn.py:370-372: pickle of {"layers", "params"} (live RBM modules)."""
         model_copy = {"layers": self.layers, "params": self.params}

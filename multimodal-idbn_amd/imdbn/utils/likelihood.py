@@ -74,6 +74,15 @@ accumulator and draw source.  ``gaussian_dbn_sample_values`` / ``gaussian_dbn_lo
 ``evaluate_gaussian_dbn_bound`` are log-DENSITIES; the ``dbn_*`` functions go on refusing a Gaussian layer and these refuse a stack
 whose bottom layer is not Gaussian.
 
+The conservative side under Gaussian visibles: AIS over continuous visibles with learned variances under-estimates
+log Z when a chain misses a narrow mode, so ``gaussian_log_likelihood`` with an AIS log Z is the number to trust least.
+``gaussian_reverse_ais_log_likelihood`` runs the chain of ``estimate_gaussian_log_partition`` backwards from each held-out row (ONE
+``HipEngine.gauss_reverse_ais`` call per chunk of rows, imdbn_rbm_gauss_reverse_ais): a stochastic LOWER bound on the log-density
+log p_ann(v).  ``evaluate_gaussian_log_likelihood_sandwich`` reports both sides and their gap; ``gaussian_dbn_conservative_bound`` /
+``evaluate_gaussian_dbn_bound_conservative`` put a reverse estimate in place of the top term of ``gaussian_dbn_lower_bound`` -- the
+Bernoulli one on the sampled top states for two layers and more, the Gaussian one for a stack of one.  These are the functions of the
+Bernoulli paragraph above on another engine call and another log Z_A; each family refuses the other's layers.
+
 Data parallelism: the chains are NOT sharded over ranks -- every rank that calls runs all ``n_chains`` chains and gets the same
 estimate (same seed) or an independent one; sharding the chains is a follow-up.
 """
@@ -94,7 +103,9 @@ __all__ = ["base_rate_bias", "linear_betas", "estimate_log_partition", "log_like
            "reverse_ais_log_likelihood", "evaluate_log_likelihood_sandwich", "dbn_conservative_bound", "evaluate_dbn_bound_conservative",
            "pseudo_log_likelihood", "evaluate_pseudo_likelihood", "imdbn_pseudo_log_likelihood",
            "gaussian_base_rate_bias", "estimate_gaussian_log_partition", "gaussian_log_likelihood", "evaluate_gaussian_log_likelihood",
-           "gaussian_dbn_sample_values", "gaussian_dbn_lower_bound", "gaussian_dbn_log_likelihood_is", "evaluate_gaussian_dbn_bound"]
+           "gaussian_dbn_sample_values", "gaussian_dbn_lower_bound", "gaussian_dbn_log_likelihood_is", "evaluate_gaussian_dbn_bound",
+           "gaussian_reverse_ais_log_likelihood", "evaluate_gaussian_log_likelihood_sandwich", "gaussian_dbn_conservative_bound",
+           "evaluate_gaussian_dbn_bound_conservative"]
 
 
 def _bottom(model):
@@ -500,9 +511,19 @@ def evaluate_imdbn_bound(model, loader=None, log_z_joint: Optional[float] = None
 
 
 # ---- the conservative side: reverse annealed importance sampling ------------------------------------------------------------------
-def _reverse_rows(rbm, v, n_chains, betas, base_vis_bias, rng, max_rows):
-    """``(ll [B], ess [B], logw [B, M])`` of ``reverse_ais_log_likelihood`` under the draw source ``rng``, which advances by ONE
-    schedule however many chunks ran: every chunk draws from the same draw numbers, keyed on its global rows."""
+def _bernoulli_reverse(eng, rbm, rows, betas, rng, base_vis_bias):
+    return eng.reverse_ais(rbm, rows, betas, rng, base_vis_bias=base_vis_bias)
+
+
+# A side of the reverse estimate: (the name its errors carry, the engine call over one chunk of rows, log Z_A of the base-rate model)
+_REVERSE_BERNOULLI = ("reverse_ais_log_likelihood", _bernoulli_reverse, _log_z_base)
+
+
+def _reverse_rows(rbm, v, n_chains, betas, base_vis_bias, rng, max_rows, side=_REVERSE_BERNOULLI):
+    """``(ll [B], ess [B], logw [B, M])`` of ``reverse_ais_log_likelihood`` -- ``side=_REVERSE_GAUSSIAN``: of
+    ``gaussian_reverse_ais_log_likelihood`` -- under the draw source ``rng``, which advances by ONE schedule however many chunks ran:
+    every chunk draws from the same draw numbers, keyed on its global rows."""
+    who, run, log_z_base = side
     M = int(n_chains)
     if M < 1:
         raise ValueError("n_chains must be >= 1")
@@ -510,18 +531,18 @@ def _reverse_rows(rbm, v, n_chains, betas, base_vis_bias, rng, max_rows):
         raise ValueError("max_rows must be >= 1")
     dev = rbm.W.device
     if v.size(0) < 1:
-        raise ValueError("reverse_ais_log_likelihood: no rows")
+        raise ValueError(f"{who}: no rows")
     v = rows_on_device(v, dev)
     B = v.size(0)
     if v.size(1) != rbm.W.shape[0]:
-        raise ValueError(f"reverse_ais_log_likelihood: rows of {v.size(1)} elements, the RBM has {rbm.W.shape[0]} visible units")
+        raise ValueError(f"{who}: rows of {v.size(1)} elements, the RBM has {rbm.W.shape[0]} visible units")
     if base_vis_bias is not None and base_vis_bias.numel() != rbm.W.shape[0]:
         raise ValueError(f"base_vis_bias must have {rbm.W.shape[0]} elements")
     eng = _E.get_engine(rbm.W.data)
     per = max(1, int(max_rows) // M)
     philox = isinstance(rng, _E.PhiloxRng)
     if not philox and B > per:
-        raise ValueError("reverse_ais_log_likelihood: more than one chunk of rows needs a PhiloxRng (draws keyed on the global row)")
+        raise ValueError(f"{who}: more than one chunk of rows needs a PhiloxRng (draws keyed on the global row)")
     parts, used = [], 0
     for s in range(0, B, per):
         rows = v[s:s + per].repeat_interleave(M, 0) if M > 1 else v[s:s + per]
@@ -529,14 +550,14 @@ def _reverse_rows(rbm, v, n_chains, betas, base_vis_bias, rng, max_rows):
         if philox:
             r = _E.PhiloxRng(rng.seed, row0=rng.row0 + s * M)
             r.offset, r.device_counter = rng.offset, rng.device_counter
-        parts.append(eng.reverse_ais(rbm, rows, betas, r, base_vis_bias=base_vis_bias))
+        parts.append(run(eng, rbm, rows, betas, r, base_vis_bias))
         if philox:
             used = r.offset - rng.offset
     if philox:
         rng.advance(used)
     logw = parts[0] if len(parts) == 1 else torch.cat(parts)
     lme, ess = eng.rows_logmeanexp(logw, M)
-    return lme - _log_z_base(rbm, base_vis_bias, logw.device), ess, logw.view(B, M)
+    return lme - log_z_base(rbm, base_vis_bias, logw.device), ess, logw.view(B, M)
 
 
 @torch.no_grad()
@@ -568,8 +589,15 @@ def evaluate_log_likelihood_sandwich(model, loader=None, max_batches: Optional[i
     ``max_rows`` for the reverse side, which shares the ladder and the base-rate bias; one draw source carries the AIS run and then
     every batch.  Binary visibles only (the AIS side).  Everything is accumulated on the device; the host synchronises ONCE, after
     the last batch.  With a ``wandb_run`` on the model the scalars are logged as ``ll/...``."""
+    return _evaluate_sandwich("evaluate_log_likelihood_sandwich", model, loader, max_batches, kwargs, _check_binary,
+                              lambda eng, rbm, betas, M, rng, bA: eng.ais(rbm, betas, M, rng, base_vis_bias=bA), _REVERSE_BERNOULLI, "ll/")
+
+
+def _evaluate_sandwich(who, model, loader, max_batches, kwargs, check, ais, side, prefix):
+    """``evaluate_log_likelihood_sandwich`` / ``evaluate_gaussian_log_likelihood_sandwich``: ``check`` admits the bottom RBM, ``ais`` is
+    its forward engine call, ``side`` its reverse side (whose log Z_A is the forward one's), ``prefix`` that of the logged scalars."""
     rbm = _bottom(model)
-    _check_binary(rbm)
+    check(rbm)
     loader = loader if loader is not None else getattr(model, "val_loader", None)
     if loader is None:
         return None
@@ -579,15 +607,15 @@ def evaluate_log_likelihood_sandwich(model, loader=None, max_batches: Optional[i
     betas = linear_betas(kwargs.pop("n_betas", 1000)) if betas is None else betas
     bA, seed, max_rows = kwargs.pop("base_vis_bias", None), kwargs.pop("seed", None), kwargs.pop("max_rows", 4096)
     if kwargs:
-        raise TypeError(f"evaluate_log_likelihood_sandwich: unexpected arguments {sorted(kwargs)}")
+        raise TypeError(f"{who}: unexpected arguments {sorted(kwargs)}")
     rng = _draws(seed)
-    logw = _E.get_engine(rbm.W.data).ais(rbm, betas, M, rng, base_vis_bias=bA)
-    stats = _weight_stats_device(logw, _log_z_base(rbm, bA, logw.device))      # log_z, log_z_base, ess, se
+    logw = ais(_E.get_engine(rbm.W.data), rbm, betas, M, rng, bA)
+    stats = _weight_stats_device(logw, side[2](rbm, bA, logw.device))          # log_z, log_z_base, ess, se
     log_z = stats[0]
 
     def sums(batch):
         v = rows_on_device(_first(batch), rbm.W.device)
-        ll_r, ess_r, _ = _reverse_rows(rbm, v, Mr, betas, bA, rng, max_rows)
+        ll_r, ess_r, _ = _reverse_rows(rbm, v, Mr, betas, bA, rng, max_rows, side)
         ll_a = -rbm.free_energy(v).double().to(log_z.device) - log_z
         return torch.stack([ll_a.sum(), ll_r.sum(), ess_r.sum()])
 
@@ -595,16 +623,16 @@ def evaluate_log_likelihood_sandwich(model, loader=None, max_batches: Optional[i
     d = max(1, n)
     res = {"mean_ll_ais": host[0] / d, "mean_ll_reverse": host[1] / d, "gap": (host[0] - host[1]) / d, "n": n,
            "log_z": host[3], "se": host[6], "ess": host[5], "ess_reverse": host[2] / d}
-    _log_scalars(model, "ll/", res, ("mean_ll_ais", "mean_ll_reverse", "gap", "log_z", "se", "ess", "ess_reverse"))
+    _log_scalars(model, prefix, res, ("mean_ll_ais", "mean_ll_reverse", "gap", "log_z", "se", "ess", "ess_reverse"))
     return res
 
 
-def _conservative_values(layers, v, n_samples, n_chains, betas, base_vis_bias, rng, max_rows, gen=None):
-    """``(w [B, S], ess [B, S])``: the directed layers as ``_sample_values`` in mode ``entropy``, the top term from reverse AIS on the
-    sampled top-layer states."""
+def _conservative_values(layers, v, n_samples, n_chains, betas, base_vis_bias, rng, max_rows, gen=None, side=_REVERSE_BERNOULLI):
+    """``(w [B, S], ess [B, S])``: the directed layers as ``_sample_values`` in mode ``entropy``, the top term from reverse AIS
+    (``side``: the top RBM's) on the sampled top-layer states."""
     top = layers[-1]
     acc, cur, B, S = _directed(layers[:-1], v, top.W.device, n_samples, "entropy", rng, gen)
-    w, ess, _ = _reverse_rows(top, cur, n_chains, betas, base_vis_bias, rng, max_rows)
+    w, ess, _ = _reverse_rows(top, cur, n_chains, betas, base_vis_bias, rng, max_rows, side)
     if acc is not None:
         w = acc.to(w.device) + w
     return w.view(B, S), ess.view(B, S)
@@ -630,7 +658,14 @@ def evaluate_dbn_bound_conservative(model, loader=None, n_samples: int = 8, n_ch
     ``mean_bound``, ``sum_bound``, ``n``, ``ess_reverse`` (mean over rows and samples), ``n_samples``, ``n_chains``.  One draw source
     carries every batch (``seed``: a private one).  Sums on the device, one host sync after the last batch.  With a ``wandb_run`` on
     the model the scalars are logged as ``ll/dbn_conservative_...``."""
-    layers = _stack(model)
+    return _evaluate_conservative(model, _stack(model), _REVERSE_BERNOULLI, "ll/dbn_conservative_", _gen(model), loader, n_samples,
+                                  n_chains, max_batches, n_betas, betas, base_vis_bias, seed, max_rows)
+
+
+def _evaluate_conservative(model, layers, side, prefix, gen, loader, n_samples, n_chains, max_batches, n_betas, betas, base_vis_bias, seed,
+                           max_rows):
+    """``evaluate_dbn_bound_conservative`` / ``evaluate_gaussian_dbn_bound_conservative`` over the checked ``layers``: ``side`` is the
+    reverse side of the top RBM, ``prefix`` that of the logged scalars, ``gen`` the generative twins of an untied model."""
     loader = loader if loader is not None else getattr(model, "val_loader", None)
     if loader is None:
         return None
@@ -638,13 +673,13 @@ def evaluate_dbn_bound_conservative(model, loader=None, n_samples: int = 8, n_ch
     rng = _draws(seed)
 
     def sums(batch):
-        w, ess = _conservative_values(layers, _first(batch), n_samples, n_chains, betas, base_vis_bias, rng, max_rows, _gen(model))
+        w, ess = _conservative_values(layers, _first(batch), n_samples, n_chains, betas, base_vis_bias, rng, max_rows, gen, side)
         return torch.stack([w.mean(1).sum(), ess.mean(1).sum()])
 
     t, n = _sum_batches(loader, max_batches, sums, 2)
     d = max(1, n)
     res = {"mean_bound": t[0] / d, "sum_bound": t[0], "n": n, "ess_reverse": t[1] / d, "n_samples": int(n_samples), "n_chains": int(n_chains)}
-    _log_scalars(model, "ll/dbn_conservative_", res, ("mean_bound", "ess_reverse", "n_samples", "n_chains"))
+    _log_scalars(model, prefix, res, ("mean_bound", "ess_reverse", "n_samples", "n_chains"))
     return res
 
 
@@ -817,3 +852,69 @@ def evaluate_gaussian_dbn_bound(model, loader=None, log_z_top: Optional[float] =
     layers = _gaussian_stack(model)
     estimate = estimate_log_partition if len(layers) > 1 else estimate_gaussian_log_partition
     return _evaluate_bound(model, layers, estimate, "ll/gdbn_", None, loader, log_z_top, n_samples, max_batches, importance, ais_kwargs)
+
+
+# ---- the conservative side under Gaussian visibles -------------------------------------------------------------
+def _gaussian_reverse(eng, rbm, rows, betas, rng, base_vis_bias):
+    return eng.gauss_reverse_ais(rbm, rbm.logvar.data, rows, betas, rng, base_vis_bias=base_vis_bias)
+
+
+_REVERSE_GAUSSIAN = ("gaussian_reverse_ais_log_likelihood", _gaussian_reverse, lambda rbm, base_vis_bias, dev: _gaussian_log_z_base(rbm, dev))
+
+
+@torch.no_grad()
+def gaussian_reverse_ais_log_likelihood(rbm, v: torch.Tensor, n_chains: int = 16, n_betas: int = 1000, betas=None,
+                                        base_vis_bias: Optional[torch.Tensor] = None, seed: Optional[int] = None, max_rows: int = 4096) -> dict:
+    """Reverse-AIS estimate of the log-density log p_ann(v) per row of ``v`` (real) under a ``GaussianRBM``: the keys and shapes of
+    ``reverse_ais_log_likelihood`` (``ll``, ``ess`` float64 ``[B]``, ``logw`` float64 ``[B, n_chains]``, on the device).
+    ``ll = -log Z_A + logmeanexp(logw)`` with log Z_A = H log 2 + (V / 2) log 2 pi + sum(logvar) / 2: exp(ll) is an unbiased estimate
+    of p_ann(v), the density of the annealing model of ``estimate_gaussian_log_partition`` on the same ladder, so ``ll`` is
+    conservative where ``gaussian_log_likelihood`` with an AIS log Z is optimistic.  ``base_vis_bias`` None: the RBM's own visible
+    bias.  A row with a non-finite element gives NaN in that row.  Chunks, draws (``2 K`` draw tensors) and ``seed`` as in
+    ``reverse_ais_log_likelihood``.  No host sync."""
+    _check_gaussian(rbm)
+    betas = linear_betas(n_betas) if betas is None else betas
+    ll, ess, logw = _reverse_rows(rbm, v, n_chains, betas, base_vis_bias, _draws(seed), max_rows, _REVERSE_GAUSSIAN)
+    return {"ll": ll, "ess": ess, "logw": logw}
+
+
+@torch.no_grad()
+def evaluate_gaussian_log_likelihood_sandwich(model, loader=None, max_batches: Optional[int] = None, **kwargs) -> Optional[dict]:
+    """``evaluate_log_likelihood_sandwich`` for a ``GaussianRBM`` -- or the BOTTOM layer of an ``iDBN`` built with
+    ``GAUSSIAN_VISIBLE``: the same keys, ``mean_ll_ais`` from ``gaussian_log_likelihood`` with the ``gauss_ais`` log Z and
+    ``mean_ll_reverse`` from ``gaussian_reverse_ais_log_likelihood``, log-densities both; the same ``kwargs``.  One draw source
+    carries the AIS run and then every batch; the host synchronises ONCE, after the last batch.  With a ``wandb_run`` on the model
+    the scalars are logged as ``ll/gaussian_...``."""
+    return _evaluate_sandwich("evaluate_gaussian_log_likelihood_sandwich", model, loader, max_batches, kwargs, _check_gaussian,
+                              lambda eng, rbm, betas, M, rng, bA: eng.gauss_ais(rbm, rbm.logvar.data, betas, M, rng, base_vis_bias=bA),
+                              _REVERSE_GAUSSIAN, "ll/gaussian_")
+
+
+def _top_side(layers):
+    """The reverse side of the top RBM of a Gaussian stack: the Gaussian one for a stack of one, else the Bernoulli one."""
+    return _REVERSE_GAUSSIAN if len(layers) == 1 else _REVERSE_BERNOULLI
+
+
+@torch.no_grad()
+def gaussian_dbn_conservative_bound(model, v: torch.Tensor, n_samples: int = 8, n_chains: int = 16, n_betas: int = 1000, betas=None,
+                                    base_vis_bias: Optional[torch.Tensor] = None, seed: Optional[int] = None,
+                                    max_rows: int = 4096) -> torch.Tensor:
+    """``dbn_conservative_bound`` for a stack with a Gaussian bottom layer: the bottom bracket through ``gauss_bound_step`` in mode
+    ``entropy``, the Bernoulli layers above through ``bound_step``, and in place of ``-F_top - log Z_top`` the Bernoulli reverse-AIS
+    estimate at the sampled top-layer states (``base_vis_bias``: the TOP RBM's base-rate model).  Float64 ``[B]`` on the device, a
+    log-density, no host sync.  A ``GaussianRBM`` alone is a stack of one: ``gaussian_reverse_ais_log_likelihood``."""
+    layers = _gaussian_stack(model)
+    betas = linear_betas(n_betas) if betas is None else betas
+    return _conservative_values(layers, v, n_samples, n_chains, betas, base_vis_bias, _draws(seed), max_rows, None, _top_side(layers))[0].mean(1)
+
+
+@torch.no_grad()
+def evaluate_gaussian_dbn_bound_conservative(model, loader=None, n_samples: int = 8, n_chains: int = 16, max_batches: Optional[int] = None,
+                                             n_betas: int = 1000, betas=None, base_vis_bias: Optional[torch.Tensor] = None,
+                                             seed: Optional[int] = None, max_rows: int = 4096) -> Optional[dict]:
+    """Mean held-out ``gaussian_dbn_conservative_bound`` over ``loader`` (default ``model.val_loader``; None without one): the keys of
+    ``evaluate_dbn_bound_conservative``.  One draw source carries every batch, sums on the device, one host sync after the last
+    batch.  With a ``wandb_run`` on the model the scalars are logged as ``ll/gdbn_conservative_...``."""
+    layers = _gaussian_stack(model)
+    return _evaluate_conservative(model, layers, _top_side(layers), "ll/gdbn_conservative_", None, loader, n_samples, n_chains, max_batches,
+                                  n_betas, betas, base_vis_bias, seed, max_rows)
