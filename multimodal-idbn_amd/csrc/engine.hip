@@ -964,8 +964,9 @@ static int cd_prologue(Ctx& c, const imdbn_cd_opts* o, PrepArgs& pn, bool& rides
         const Layout& L = c.L;
         const int t = o->next_slot - 1;
         pn.in = o->next_data; pn.ld = o->ld_next; pn.B = L.B; pn.Bp = L.Bp; pn.N = L.V;
-        pn.op.rm = L.pf_rm[t]; pn.op.ldrm = L.Vpad; pn.op.rm_ts = (int64_t)L.Bp * L.Vpad; pn.op.rm_terms = 3; pn.op.Bp = L.Bp;
-        pn.op.tr = L.pf_tr[t]; pn.op.tr_ts = (int64_t)L.V * L.Bp; pn.op.tr_terms = 3;
+        const int terms = c.nw == 1 ? 1 : 3;      // (FAST: the one term every reader takes is the nearest bf16, as prep() writes it)
+        pn.op.rm = L.pf_rm[t]; pn.op.ldrm = L.Vpad; pn.op.rm_ts = (int64_t)L.Bp * L.Vpad; pn.op.rm_terms = terms; pn.op.Bp = L.Bp;
+        pn.op.tr = L.pf_tr[t]; pn.op.tr_ts = (int64_t)L.V * L.Bp; pn.op.tr_terms = terms;
         pn.flag = L.pf_flags[t]; pn.colsum_part = L.pf_cs[t];
         pn.op.bits = L.pf_bits[t]; pn.op.bits_shape = 0;
     }

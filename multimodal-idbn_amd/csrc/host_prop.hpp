@@ -320,6 +320,9 @@ int prep(Ctx& c, const float* in, int64_t ld, int N, bf16_t* rm, int ldrm, bf16_
          float* colsum = nullptr, int terms = 3, uint8_t* bits = nullptr) {
     PrepArgs p;
     memset(&p, 0, sizeof(p));
+    // FAST mode reads ONE term of every operand: it must be the nearest bf16 (store_forms, terms == 1), not the first term of the
+    // three-term truncation split, which is the operand rounded toward zero
+    if (c.nw == 1) terms = 1;
     p.op.bits = bits; p.op.bits_shape = 0;
     p.zero = c.L.k1s_cnt; p.n_zero = (c.L.Bp / 64) * c.L.k1s_tiles;      // first launch of a call: arrival counters of k1_stream
     c.cnt_ok = true;
