@@ -666,6 +666,49 @@ int imdbn_rbm_backprop_step(const imdbn_rbm_desc* d,
                             float* err_h_out, int64_t ldoh,   /* nullable, needs the down pair */
                             void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- one back-propagation step through a Gaussian visible layer (imdbn/models/idbn.py: gaussian_autoencoder_step) --
+ * The bottom layer of a stack with Gaussian visibles in the unrolled autoencoder, in its two roles.  d, logvar (z, sigma_i^2 =
+ * exp(z_i)) as in the imdbn_rbm_gauss_* calls; v [B][V] the data (always needed); all gradients are ascent directions on minus
+ *     J = (1/B) sum_b sum_i [ (v_bi - m_bi)^2 exp(-z_i) / 2 + z_i / 2 ]
+ * and come from the parameters on entry.
+ *   down pair x_h [B][H] (the layer is the decoder's output):  m = b + x_h W^T, bit for bit imdbn_rbm_gauss_prop_down;
+ *       e_0 = (v - m) exp(-z);  gW = e_0^T x_h / B;  gb = colsum(e_0) / B;  gzeta_i = exp(-z_i) sum_b (v_bi - m_bi)^2 / (2 B) - 1/2
+ *       err_h_out (nullable) = (e_0 W) x_h (1 - x_h), the e_v imdbn_rbm_backprop_step expects one layer up
+ *       loss_out (nullable, two floats) = J and mean((v - m)^2)
+ *   up pair e_h [B][H] (the layer is the encoder's input, e_h the error at its hidden pre-activations):  u = v exp(-z);
+ *       gW = u^T e_h / B;  gc = colsum(e_h) / B;  gz_i = -(1/B) sum_j W_ij (u^T e_h)_ij
+ *   both pairs (a single tied layer): one weight pass over u^T e_h + e_0^T x_h, and logvar moves by gzeta + gz.
+ * o != NULL, the update (lr, momentum, weight_decay are read; cd_k, sparsity, the prefetch fields and fwd_out must be zero):
+ *   W_m = momentum W_m + lr (gW - weight_decay W), W += W_m;  with the up pair hb_m = momentum hb_m + lr gc, hid_bias += hb_m;  with the
+ *   down pair vb_m = momentum vb_m + lr gb, vis_bias += vb_m (a bias without its pair is not touched, nor its momentum);
+ *   lr_z != 0:  logvar_m = momentum logvar_m + lr_z g, logvar = min(max(logvar + logvar_m, z_lo), z_hi)
+ *   (lr_z == 0: logvar and logvar_m -- which may then be NULL -- are not touched).
+ * o == NULL evaluates only (err_h_out, loss_out) and writes no parameter.
+ * Launches, plain, on `stream`, no host sync, no draws, no allocation: with the down pair the two launches of
+ * imdbn_rbm_gauss_prop_down; gauss_bp_rows (one pass over v and m: e_0 row-major and as planes, u, the column partials, the loss
+ * partials, the zero planes of an absent pair's slot); for err_h_out the sequence of imdbn_rbm_backprop_step (operand preparation of
+ * e_0, memset node, bias-free logits-only propagation, backprop_apply); with o the operand preparations, backprop_rows of e_h, then
+ * with the up pair the update kernel in its statistics mode and gauss_apply (which returns r_i = sum_j W_ij S_ij; with both pairs
+ * the share of the down pair, t_i = sum_b e_0,bi (m_bi - b_i), is taken out: gz_i = -(r_i - t_i) / B), with the down pair alone the
+ * update kernel as imdbn_rbm_backprop_step runs it; gauss_bp_finish last (biases, logvar, the two loss figures).
+ * Sums: column partials over 8 rows in row order, added in index order; r as in imdbn_rbm_gauss_cd_step; the loss in double over the
+ * blocks' fp32 tree sums.  No floating-point atomics, every order fixed by (V, H, B) and the CU count; the row padding of W / W_m is
+ * neither read nor written.
+ * scratch: device, imdbn_gauss_backprop_scratch_floats(V, H, B) floats, 16-byte aligned for the float4 kernel.  Workspace:
+ * imdbn_ws_bytes(V, H, B).
+ * IMDBN_E_INVALID (naming the value) before the first launch, nothing touched: a null logvar / v / scratch, no pair, err_h_out or
+ * loss_out without the down pair, o == NULL with nothing to output, a leading dimension below its width, B < 1, NaN lr_z, z_lo > z_hi
+ * or NaN, lr_z != 0 with a null logvar_m, with o: a null momentum buffer, a non-zero cd_k / sparsity / prefetch field / fwd_out.
+ * IMDBN_E_UNSUPPORTED: a descriptor with softmax groups. */
+size_t imdbn_gauss_backprop_scratch_floats(int V, int H, int B);
+int imdbn_rbm_gauss_backprop_step(const imdbn_rbm_desc* d, float* logvar, float* logvar_m, const float* v, int64_t ldv,
+                                  const float* e_h, int64_t ldeh,   /* up pair, nullable:   e_h [B][H] */
+                                  const float* x_h, int64_t ldxh,   /* down pair, nullable: x_h [B][H] */
+                                  int B, const imdbn_cd_opts* o /* NULL: evaluate only */, float lr_z, float z_lo, float z_hi,
+                                  float* err_h_out, int64_t ldoh,   /* nullable, needs the down pair */
+                                  float* loss_out,                  /* nullable, needs the down pair: {J, mean((v - m)^2)} */
+                                  float* scratch, void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- parallel tempering over persistent chains (Desjardins et al. 2010; Cho, Raiko & Ilin 2010) -----------------
  * state [R M][V]: fp32, 0/1, one-hot inside softmax groups, row stride lds >= V, IN PLACE; replica r owns the rows [r M, (r + 1) M)
  * and samples p_beta(v) ~ exp(beta b.v + S(beta, v)), S(beta, v) = sum_j softplus(beta x_j(v)), x(v) = c + v W, at beta = betas[r].

@@ -43,6 +43,7 @@
 #include "kernels_gauss_bound.hpp"
 #include "kernels_delta.hpp"
 #include "kernels_backprop.hpp"
+#include "kernels_gauss_backprop.hpp"
 
 using namespace imdbn;
 
@@ -2169,6 +2170,22 @@ int imdbn_rbm_gauss_cd_step(const imdbn_rbm_desc* d, float* logvar, float* logva
     hipLaunchKernelGGL(gauss_finish, dim3(cdiv(std::max(V, H), 256) + 1), dim3(256), 0, c.s, a);
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+// ---- one back-propagation step through a Gaussian visible layer (host_gauss_backprop.hpp; kernels_gauss_backprop.hpp) ------
+#include "host_gauss_backprop.hpp"
+
+size_t imdbn_gauss_backprop_scratch_floats(int V, int H, int B) {
+    if (V <= 0 || H <= 0 || B <= 0) return 0;
+    return gauss_bp_scratch(V, H, B).total;
+}
+
+int imdbn_rbm_gauss_backprop_step(const imdbn_rbm_desc* d, float* logvar, float* logvar_m, const float* v, int64_t ldv, const float* e_h,
+                                  int64_t ldeh, const float* x_h, int64_t ldxh, int B, const imdbn_cd_opts* o, float lr_z, float z_lo,
+                                  float z_hi, float* err_h_out, int64_t ldoh, float* loss_out, float* scratch, void* ws, size_t ws_bytes,
+                                  imdbn_stream_t stream) {
+    return gauss_backprop_step(d, logvar, logvar_m, v, ldv, e_h, ldeh, x_h, ldxh, B, o, lr_z, z_lo, z_hi, err_h_out, ldoh, loss_out, scratch,
+                               ws, ws_bytes, S(stream));
 }
 
 // ---- one delta-rule step of a directed layer (host_delta.hpp; kernels_delta.hpp) ------------------------------------------

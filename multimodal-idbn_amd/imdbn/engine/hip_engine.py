@@ -1009,6 +1009,102 @@ class HipEngine:
             f = self.backprop_step(rec_layers[l - 1], up=(a[l - 1], f), lr=epoch_scalars[l - 1][0], mom=epoch_scalars[l - 1][1], want_v=l > 1)[0]
         return {"recon": dec[0], "code": a[L], "xent": xent, "mse": mse}
 
+    # ---- backprop fine-tuning of a stack with a Gaussian bottom layer ------------------------------------
+    def gauss_backprop_step(self, rbm, logvar, logvar_m, data, up=None, down=None, lr=0.0, mom=0.0, lr_z=0.0, z_lo=float("-inf"),
+                            z_hi=float("inf"), apply=True, want_h=False, monitor=False):
+        """One back-propagation step through the Gaussian visible layer ``rbm`` (imdbn_rbm_gauss_backprop_step).  ``data`` ``[B, V]``
+        is the layer's real-valued input; ``up`` = ``e_h`` ``[B, H]``, the error at its hidden pre-activations (the layer as the
+        encoder's input, operand ``data exp(-logvar)``); ``down`` = ``x_h`` ``[B, H]``, the layer's input in the downward direction
+        (the layer as the decoder's output, mean ``m = vis_bias + x_h W^T``, error ``(data - m) exp(-logvar)``).  Returns
+        ``(err_h, nll, mse)``: ``(e_0 W) x_h (1 - x_h)`` with ``want_h`` and, with ``monitor``, the Gaussian negative log-density
+        ``J`` of ``data`` under the mean (without the ``log 2 pi / 2`` constant) and ``mean((data - m)^2)`` as 0-d device scalars --
+        both need ``down``, all from the parameters on entry; a part not asked for is None.  With ``apply`` the weights move along
+        ``(u^T e_h + e_0^T x_h) / B``, the bias of every pair present along its error's column mean, by ``lr``, ``mom`` and the RBM's
+        weight decay, and -- with ``lr_z != 0`` -- ``logvar`` / ``logvar_m`` ``[V]`` (fp32, in place, ``logvar`` clamped into
+        ``[z_lo, z_hi]``) by ``lr_z``.  No draws, no host sync."""
+        if up is None and down is None:
+            raise N.EngineError("gauss_backprop_step: needs an up pair, a down pair or both")
+        if (want_h or monitor) and down is None:
+            raise N.EngineError("gauss_backprop_step: want_h and monitor need the down pair")
+        if not apply and not want_h and not monitor:
+            raise N.EngineError("gauss_backprop_step: apply=False without want_h or monitor leaves nothing to do")
+        d = self._desc(rbm, bool(apply))
+        x = _f32c(data)
+        if x.dim() != 2 or x.size(1) != d.V:
+            raise N.EngineError(f"gauss_backprop_step: needs data [B, {d.V}]")
+        B, dev = x.size(0), x.device
+        z = self._logvar("gauss_backprop_step: logvar", logvar, d.V, dev)
+        learn_z = bool(apply) and float(lr_z) != 0.0
+        zm = self._logvar("gauss_backprop_step: logvar_m", logvar_m, d.V, dev) if learn_z else None
+        ops = []
+        for nm, t in (("up", up), ("down", down)):
+            if t is not None:
+                t = _f32c(t)
+                if t.dim() != 2 or t.size(1) != d.H or t.size(0) != B or t.device != dev:
+                    raise N.EngineError(f"gauss_backprop_step: the {nm} pair needs [{B}, {d.H}] rows on {dev}")
+            ops.append(t)
+        eh, xh = ops
+        o = self._opts(rbm, lr, mom, 0) if apply else None
+        err_h = torch.empty(B, d.H, device=dev) if want_h else None
+        loss = torch.empty(2, device=dev) if monitor else None
+        need = int(self._lib.imdbn_gauss_backprop_scratch_floats(d.V, d.H, B))
+        scratch = self._buffer(("gauss_backprop", dev, d.V, d.H, B, torch.cuda.current_stream(dev).cuda_stream),
+                               lambda: torch.empty(need, dtype=torch.float32, device=dev), need)
+        ld = lambda t: 0 if t is None else t.stride(0)
+        self._call("imdbn_rbm_gauss_backprop_step", C.byref(d), _ptr(z), _ptr(zm), _ptr(x), x.stride(0), _ptr(eh), ld(eh), _ptr(xh), ld(xh), B,
+                   _ref(o), float(lr_z) if learn_z else 0.0, float(z_lo), float(z_hi), _ptr(err_h), ld(err_h), _ptr(loss), _ptr(scratch),
+                   *self._ws_tail(dev, d.V, d.H, B))
+        return err_h, (loss[0] if monitor else None), (loss[1] if monitor else None)
+
+    def gauss_autoencoder_step(self, rec_layers, gen_layers, data, epoch_scalars, monitor: bool = True):
+        """``autoencoder_step`` for a stack whose bottom layer is a ``GaussianRBM`` with linear-Gaussian visibles (Hinton &
+        Salakhutdinov 2006): the loss is the Gaussian negative log-density ``J = mean_b sum_i (data - d_0)^2 exp(-zeta) / 2 + zeta / 2``
+        of the data under the reconstruction ``d_0``, ``zeta`` the log-variance of the decoder's bottom layer (twin 0; with one layer
+        the RBM's own ``logvar``, tied).  On one stream, no host sync, no draws: ``a_1 = gauss_forward`` of layer 0, ``a_l = forward``
+        above; ``d_L = a_L``, ``d_{l-1}`` the deterministic ``backward`` through the top RBM or twin l - 1 and ``d_0 = gauss_backward``
+        through twin 0 -- ``iDBN.reconstruct(data)``, bit for bit.  Then ``gauss_backprop_step(gen[0], down=d_1, want_h=True)`` (the
+        output layer), the middle twins, the top RBM and the encoder as ``autoencoder_step`` runs them, and last
+        ``gauss_backprop_step(rec[0], up=f_1)``.  With one layer: an evaluate-only call with ``want_h``, then one call with both
+        pairs.  ``epoch_scalars``: ``(lr, mom)`` per layer, twin l uses entry l; every Gaussian layer learns its ``logvar`` with
+        ``lr_sigma_mult`` times that ``lr`` inside its own clamps.  Returns ``{"recon": d_0, "code": a_L, "nll": J, "mse"}``, the
+        monitors 0-d device scalars on the parameters on entry, None with ``monitor=False``."""
+        from . import dp
+        if dp.active():
+            raise NotImplementedError("gauss_autoencoder_step has no data-parallel split")
+        L = len(rec_layers)
+        if L < 1 or len(gen_layers) != L - 1 or len(epoch_scalars) != L:
+            raise N.EngineError(f"gauss_autoencoder_step: {L} layers need {max(L - 1, 0)} generative twins and {L} (lr, mom) pairs")
+        top, enc = rec_layers[-1], rec_layers[0]
+        out_layer = gen_layers[0] if L > 1 else enc
+        x = _f32c(data)
+        a = [x, self.gauss_forward(enc, enc._z(), x)]
+        a[1]._imdbn_binary = False
+        for rbm in rec_layers[1:]:
+            out = self.forward(rbm, a[-1], data_binary=self.binary_hint(a[-1]))
+            out._imdbn_binary = False
+            a.append(out)
+        down = list(gen_layers) + [top]
+        dec = [None] * L + [a[L]]
+        for l in range(L, 1, -1):
+            dec[l - 1] = self.prop_down(down[l - 1], dec[l])
+        dec[0] = self.gauss_backward(out_layer, out_layer._z(), dec[1])
+        gz = lambda r, lr: dict(lr_z=r.lr_sigma_mult * lr, z_lo=r.logvar_min, z_hi=r.logvar_max)
+        lr, mom = epoch_scalars[0]
+        if L == 1:
+            f, nll, mse = self.gauss_backprop_step(enc, enc._z(), enc._zm(), x, down=a[1], apply=False, want_h=True, monitor=monitor)
+            self.gauss_backprop_step(enc, enc._z(), enc._zm(), x, up=f, down=a[1], lr=lr, mom=mom, **gz(enc, lr))
+            return {"recon": dec[0], "code": a[1], "nll": nll, "mse": mse}
+        e, nll, mse = self.gauss_backprop_step(out_layer, out_layer._z(), out_layer._zm(), x, down=dec[1], lr=lr, mom=mom, want_h=True,
+                                               monitor=monitor, **gz(out_layer, lr))
+        for l in range(2, L):
+            e = self.backprop_step(gen_layers[l - 1], down=(dec[l], e), lr=epoch_scalars[l - 1][0], mom=epoch_scalars[l - 1][1], want_h=True)[1]
+        f = self.backprop_step(top, down=(a[L], e), apply=False, want_h=True)[1]
+        f = self.backprop_step(top, up=(a[L - 1], f), down=(a[L], e), lr=epoch_scalars[L - 1][0], mom=epoch_scalars[L - 1][1], want_v=True)[0]
+        for l in range(L - 1, 1, -1):
+            f = self.backprop_step(rec_layers[l - 1], up=(a[l - 1], f), lr=epoch_scalars[l - 1][0], mom=epoch_scalars[l - 1][1], want_v=True)[0]
+        self.gauss_backprop_step(enc, enc._z(), enc._zm(), x, up=f, lr=lr, mom=mom, **gz(enc, lr))
+        return {"recon": dec[0], "code": a[L], "nll": nll, "mse": mse}
+
     # ---- discriminative fine-tuning of a stack through the joint RBM's exact class posterior (DESIGN §27) ------------
     def label_backprop_step(self, rbm, z: torch.Tensor, K: int, gt: torch.Tensor, lr: float = 0.0, mom: float = 0.0, apply: bool = True,
                             want_pred: bool = False):

@@ -147,6 +147,9 @@ SIGNATURES = {
     "imdbn_rbm_delta_step": (_INT, [C.POINTER(RbmDesc), _INT, _P, _I64, _P, _I64, _INT, C.POINTER(CdOpts), _P, _P, _SZ, _P]),
     "imdbn_rbm_backprop_step": (_INT, [C.POINTER(RbmDesc), _P, _I64, _P, _I64, _P, _I64, _P, _I64, _INT, C.POINTER(CdOpts), _P, _I64, _P, _I64,
                                        _P, _SZ, _P]),
+    "imdbn_gauss_backprop_scratch_floats": (_SZ, [_INT, _INT, _INT]),
+    "imdbn_rbm_gauss_backprop_step": (_INT, [C.POINTER(RbmDesc), _P, _P, _P, _I64, _P, _I64, _P, _I64, _INT, C.POINTER(CdOpts), _F, _F, _F,
+                                             _P, _I64, _P, _P, _P, _SZ, _P]),
     "imdbn_rbm_pt_sweep": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _INT, C.POINTER(_F), _INT, C.POINTER(Rng), _P, _P, _P, _SZ, _P]),
     "imdbn_packed_delta_floats": (_SZ, [_INT, _INT]),
     "imdbn_rbm_prefetch_ok": (_INT, [C.POINTER(RbmDesc), _INT]),

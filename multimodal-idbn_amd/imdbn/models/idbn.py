@@ -213,10 +213,10 @@ class iDBN:
         the shape, row pitch, device and hyper-parameters of ``layers[l]`` holding copies of its ``W`` and ``vis_bias`` (the two
         parameters a top-down pass reads) and zero momenta; ``layers`` stay the recognition weights.  Idempotent.  ``__init__`` does
         not create the attribute: a model that is never untied keeps its attribute set and its pickle."""
+        self._no_gaussian("untie")                     # first: a Gaussian stack is refused whether or not gaussian_untie has run
         gen = self.__dict__.get("gen_layers")
         if gen is not None:
             return gen
-        self._no_gaussian("untie")
         gen = []
         for r in self.layers[:-1]:
             g = RBM.__new__(RBM)                      # not the constructor: it would draw an initial W from torch's generator
@@ -321,6 +321,82 @@ class iDBN:
                 self.autoencoder_history.append((epoch, x, s))
                 if self.wandb_run:
                     self.wandb_run.log({"idbn/autoencoder_xent": x, "idbn/autoencoder_mse": s, "epoch": epoch})
+
+    # ---- backprop fine-tuning of a stack with a Gaussian bottom layer (extension; Hinton & Salakhutdinov 2006) ----
+    @torch.no_grad()
+    def gaussian_untie(self) -> List[RBM]:
+        """``untie`` for a stack built with ``GAUSSIAN_VISIBLE``: the twin of layer 0 is a ``GaussianRBM`` (built without its
+        constructor: no torch draws) holding copies of the layer's ``W``, ``vis_bias`` and ``logvar`` -- the decoder's own
+        log-variance --, zero momenta (``logvar_m`` included) and the layer's ``lr_sigma_mult``, ``logvar_min`` and ``logvar_max``;
+        the twins above are ``untie``'s.  Idempotent; ``ValueError`` on a stack without a Gaussian bottom layer."""
+        gen = self.__dict__.get("gen_layers")
+        if gen is not None:
+            return gen
+        if not (self.layers and isinstance(self.layers[0], GaussianRBM)):
+            raise ValueError("iDBN.gaussian_untie: needs a stack whose layer 0 is a GaussianRBM (params['GAUSSIAN_VISIBLE']); use untie")
+        gen = []
+        for r in self.layers[:-1]:
+            gauss = isinstance(r, GaussianRBM)
+            cls = GaussianRBM if gauss else RBM
+            g = cls.__new__(cls)                      # not the constructor: it would draw an initial W from torch's generator
+            torch.nn.Module.__init__(g)
+            for k in ("num_visible", "num_hidden", "lr", "weight_decay", "momentum", "dynamic_lr", "final_momentum", "sparsity_factor"):
+                setattr(g, k, getattr(r, k))
+            g.sparsity, g.softmax_groups = False, []
+            dev = r.W.device
+            W = torch.empty_strided(tuple(r.W.shape), tuple(r.W.stride()), dtype=torch.float32, device=dev)
+            W.copy_(r.W.data)
+            g.W = torch.nn.Parameter(W, requires_grad=False)
+            g.hid_bias = torch.nn.Parameter(r.hid_bias.data.clone(), requires_grad=False)
+            g.vis_bias = torch.nn.Parameter(r.vis_bias.data.clone(), requires_grad=False)
+            g.W_m = torch.empty_strided(tuple(W.shape), tuple(W.stride()), dtype=torch.float32, device=dev).zero_()
+            g.hb_m, g.vb_m = torch.zeros_like(g.hid_bias.data), torch.zeros_like(g.vis_bias.data)
+            if gauss:
+                g.lr_sigma_mult, g.logvar_min, g.logvar_max = r.lr_sigma_mult, r.logvar_min, r.logvar_max
+                g.logvar = torch.nn.Parameter(r.logvar.data.clone(), requires_grad=False)
+                g.logvar_m = torch.zeros_like(g.logvar.data)
+            gen.append(g)
+        self.gen_layers = gen
+        return gen
+
+    @torch.no_grad()
+    def gaussian_autoencoder_step(self, data: torch.Tensor, epoch: int, max_epochs: int, lr_scale: float = 1.0, monitor: bool = True):
+        """``autoencoder_step`` for a stack built with ``GAUSSIAN_VISIBLE`` (unties the model with ``gaussian_untie`` on first use):
+        the engine's ``gauss_autoencoder_step`` -- the decoder's bottom layer is linear-Gaussian, the loss the Gaussian negative
+        log-density of ``data`` under ``reconstruct(data)`` with the decoder's learned variances.  Every layer uses its own RBM's
+        learning-rate and momentum schedule (``lr`` times ``lr_scale``) and weight decay, every Gaussian layer ``lr_sigma_mult``
+        times that rate for its ``logvar``, inside its clamps.  Returns ``{"nll", "mse"}`` as 0-d device scalars -- the batch mean of
+        ``sum_i (data - recon)^2 exp(-zeta) / 2 + zeta / 2`` and the mean squared reconstruction error, both before this call's
+        update -- or None with ``monitor=False``.  No host sync; no data-parallel split."""
+        from imdbn import engine as _E
+        if _E.dp.active():
+            raise NotImplementedError("gaussian_autoencoder_step has no data-parallel split")
+        gen = self.gaussian_untie()
+        x = rows_on_device(data, self.device)
+        scalars = []
+        for r in self.layers:
+            lr, mom = r._lr_mom(epoch)
+            scalars.append((lr * float(lr_scale), mom))
+        out = self.layers[-1]._eng().gauss_autoencoder_step(self.layers, gen, x, scalars, monitor=monitor)
+        return {k: out[k] for k in ("nll", "mse")} if monitor else None
+
+    def finetune_gaussian_autoencoder(self, epochs: int, lr_scale: float = 0.1, log_every: int = 0):
+        """``epochs`` passes of ``gaussian_autoencoder_step`` over ``self.dataloader`` (explicit only).  ``log_every`` > 0: the
+        monitors of every ``log_every``-th epoch are evaluated, fetched in ONE host read after the epoch's last batch and appended
+        to ``self.gaussian_autoencoder_history`` as ``(epoch, nll, mse)`` batch means; otherwise the host never reads."""
+        self.gaussian_autoencoder_history = getattr(self, "gaussian_autoencoder_history", [])
+        for epoch in range(int(epochs)):
+            watch = int(log_every) > 0 and epoch % int(log_every) == 0
+            mons = []
+            for item in batches(self.dataloader):
+                m = self.gaussian_autoencoder_step(rows_on_device(item[0], self.device), epoch, epochs, lr_scale=lr_scale, monitor=watch)
+                if watch:
+                    mons.append(torch.stack([m["nll"].double(), m["mse"].double()]))
+            if mons:
+                x, s = torch.stack(mons).mean(0).cpu().tolist()
+                self.gaussian_autoencoder_history.append((epoch, x, s))
+                if self.wandb_run:
+                    self.wandb_run.log({"idbn/gaussian_autoencoder_nll": x, "idbn/gaussian_autoencoder_mse": s, "epoch": epoch})
 
     @torch.no_grad()
     def log_likelihood_bound(self, v: torch.Tensor, log_z_top, **kw) -> torch.Tensor:
