@@ -735,6 +735,42 @@ int imdbn_rbm_gauss_backprop_step(const imdbn_rbm_desc* d, float* logvar, float*
 int imdbn_rbm_pt_sweep(const imdbn_rbm_desc* d, float* state, int64_t lds, int R, int M, const float* betas, int n_sweeps, imdbn_rng* rng,
                        int64_t* swap_try, int64_t* swap_acc, void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- exact log Z and exact marginals by enumeration (imdbn/utils/likelihood.py: exact_log_partition) ----------
+ * One side of the RBM -- E, n <= 30 units, bias e -- is enumerated: state s has unit k of E on iff bit k of s is set; the other side
+ * -- S, D units, bias f -- is summed out in closed form.  side: 0 the smaller side (ties: hidden), 1 hidden, 2 visible.
+ *   E hidden, Bernoulli visibles, softmax groups allowed (x = b + W h):
+ *       log Z = LSE_h [ c.h + sum_{i outside groups} softplus(x_i) + sum_g LSE_{k in g} x_k ]
+ *   E hidden, Gaussian visibles (logvar = z given; a = W h):
+ *       log Z = sum_i (log 2 pi + z_i) / 2 + LSE_h [ c.h + sum_i (b_i a_i + a_i^2 / 2) exp(-z_i) ]
+ *   E visible, Bernoulli, no groups (x = c + v W):
+ *       log Z = LSE_v [ b.v + sum_j softplus(x_j) ]
+ * out: device double [2] = {log Z, the log of the largest state weight (the same constant included)}.
+ * vis_mean [V] / hid_mean [H] (fp32, both or neither): the exact model marginals.  With w(s) = exp(t(s) - LSE_s t(s)), t the bracket
+ * above: E gets sum_s w(s) s_k; S gets sum_s w(s) sigmoid(x_i), inside a softmax group sum_s w(s) softmax_g(x)_k, and for Gaussian
+ * visibles E[v_i] = sum_s w(s) (b_i + a_i).
+ * Launches: one prep launch (the n columns or rows of W of side E into a dense [n][D] block; row padding is never read); per 2^22
+ * states one walk launch, the high bits in ascending order (n <= 22: one); one finishing launch; with marginals the walk launches once
+ * more and a second finishing launch.
+ * Sums: a pre-activation x_i(s) is reached from f_i by at most n + 26 fp32 additions (a fresh base every 32 states from the set bits
+ * k >= 5 in ascending order, then a Gray-code walk of the 5 low bits); the terms of S add in fp32 inside a chunk of 128 columns
+ * (two per lane) and in double across chunks and lanes (fixed butterfly); e.s and t(s) are doubles.  The LSE over states keeps
+ * (max, scaled sum) pairs in double per lane, joined over the wave, the block's four waves in wave order, and one slot per block and
+ * launch; the finishing launch folds the slots in a fixed order.  The marginals add w(s) times the fp32 term in double, per block,
+ * and the finishing launch adds the blocks in index order.  No floating-point atomics: the same call on the same state gives the
+ * same bits, whatever the scratch held.  Parameters are only read; no draws, no host sync, no allocation, no memcpy.
+ * scratch: device, imdbn_exact_scratch_bytes(V, H, side) bytes (0 for an argument the call would refuse), 256-byte aligned.  It
+ * always holds room for the marginal partials: min(2^min(n, 22) / 128, 512) (D + 32) doubles.
+ * IMDBN_E_INVALID, naming the value, before the first launch and with nothing touched: a null d / out / scratch, side outside 0..2,
+ * scratch too small or misaligned, exactly one of vis_mean / hid_mean, side = 2 with a non-null logvar.  IMDBN_E_UNSUPPORTED: more
+ * than 30 units on the enumerated side; the visible side enumerated with softmax groups or (side = 0, V < H) Gaussian visibles;
+ * Gaussian visibles with softmax groups.  With imdbn_profile_enable the whole call is bracketed by one event pair. */
+size_t imdbn_exact_scratch_bytes(int V, int H, int side);
+int imdbn_rbm_exact_logz(const imdbn_rbm_desc* d, const float* logvar /* NULL: Bernoulli visibles */,
+                         int side /* 0: the smaller side (ties: hidden); 1: hidden; 2: visible */,
+                         double* out /* device [2]: log Z, log of the largest state weight */,
+                         float* vis_mean /* nullable, [V] */, float* hid_mean /* nullable, [H] */,
+                         void* scratch, size_t scratch_bytes, imdbn_stream_t stream);
+
 /* ---- data-parallel split of the same update ------------------------------ */
 /* packed layout (floats): [dW V*H][dc H][db V][sum P+ H][sq-err sum 1][pad to 4] */
 size_t imdbn_packed_delta_floats(int V, int H);

@@ -44,6 +44,7 @@
 #include "kernels_delta.hpp"
 #include "kernels_backprop.hpp"
 #include "kernels_gauss_backprop.hpp"
+#include "kernels_exact.hpp"
 
 using namespace imdbn;
 
@@ -1511,6 +1512,9 @@ int imdbn_rbm_pseudo_loglik(const imdbn_rbm_desc* d, const float* v, int64_t ldv
     HIPCHK(hipGetLastError());
     return 0;
 }
+
+// ---- exact log Z and marginals by enumeration (imdbn/utils/likelihood.py; kernels_exact.hpp) ------------------------------
+#include "host_exact.hpp"
 
 // ---- cross-modal label metrics (imdbn/utils/cross_eval.py; kernels_metrics.hpp) ---------------------------------------------
 int imdbn_cross_metrics(const float* p, int64_t ldp, int B, int K, const float* y, int64_t ldy, const int32_t* gt, const float* row_mse,

@@ -475,6 +475,36 @@ class HipEngine:
                    *self._ws_tail(dev, d.V, d.H, max(n, 1)))
         return (pll, site) if return_sites else pll
 
+    def exact_log_z(self, rbm, logvar=None, side="auto", marginals=False, max_bits=24):
+        """Exact log Z by enumerating one side of ``rbm`` on the device (imdbn_rbm_exact_logz).  ``side``:
+        ``"hidden"``, ``"visible"`` or ``"auto"`` -- the smaller side (ties: hidden); hidden whenever the visible layer has softmax
+        groups or is Gaussian (``logvar`` ``[V]`` given), because such a layer cannot be enumerated.  Returns ``{"log_z": 0-d float64
+        device tensor, "log_w_max": the log of the largest state weight (0-d float64), "side": "hidden" | "visible", "bits": n,
+        "vis_mean", "hid_mean"}``; the means are the exact model marginals, fp32 ``[V]`` / ``[H]`` (E[v_i] for Gaussian visibles), with
+        ``marginals``, else None.  ``max_bits`` guards the cost (2^n states times the other side's width): a wider enumerated side
+        raises; the library itself stops at 30.  No draws, no host sync."""
+        d = self._desc(rbm, False)
+        dev = rbm.W.device
+        z = None if logvar is None else self._logvar("exact_log_z: logvar", logvar, d.V, dev)
+        if side not in ("auto", "hidden", "visible"):
+            raise N.EngineError(f"exact_log_z: side must be 'auto', 'hidden' or 'visible', got {side!r}")
+        if side == "auto":
+            side = "hidden" if (z is not None or d.n_groups > 0 or d.H <= d.V) else "visible"
+        n = d.H if side == "hidden" else d.V
+        if n > int(max_bits):
+            raise N.EngineError(f"exact_log_z: n = {n} units on the enumerated ({side}) side is above max_bits = {int(max_bits)}: "
+                                f"2^{n} states; pass max_bits={n} to allow it (the library's limit is 30)")
+        code = 1 if side == "hidden" else 2
+        need = int(self._lib.imdbn_exact_scratch_bytes(d.V, d.H, code))
+        scratch = self._buffer(("exact", dev, d.V, d.H, code, torch.cuda.current_stream(dev).cuda_stream),
+                               lambda: torch.empty(max(need, 256), dtype=torch.uint8, device=dev), need)
+        out = torch.empty(2, dtype=torch.float64, device=dev)
+        vm = torch.empty(d.V, device=dev) if marginals else None
+        hm = torch.empty(d.H, device=dev) if marginals else None
+        self._call("imdbn_rbm_exact_logz", C.byref(d), _ptr(z), code, _ptr(out), _ptr(vm), _ptr(hm), _ptr(scratch), scratch.numel(),
+                   self._stream(dev))
+        return {"log_z": out[0], "log_w_max": out[1], "side": side, "bits": n, "vis_mean": vm, "hid_mean": hm}
+
     def bound_step(self, rbm, v, rng, acc: Optional[torch.Tensor] = None, mode: str = "entropy"):
         """One directed layer of the DBN lower bound (imdbn_rbm_bound_step): draws ``h ~ q(h | v)`` and adds
         ``log p(v | h)`` plus the entropy of q (``mode="entropy"``) or ``-log q(h | v)`` (``mode="logq"``) to ``acc``, a float64

@@ -151,6 +151,8 @@ SIGNATURES = {
     "imdbn_rbm_gauss_backprop_step": (_INT, [C.POINTER(RbmDesc), _P, _P, _P, _I64, _P, _I64, _P, _I64, _INT, C.POINTER(CdOpts), _F, _F, _F,
                                              _P, _I64, _P, _P, _P, _SZ, _P]),
     "imdbn_rbm_pt_sweep": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _INT, C.POINTER(_F), _INT, C.POINTER(Rng), _P, _P, _P, _SZ, _P]),
+    "imdbn_exact_scratch_bytes": (_SZ, [_INT, _INT, _INT]),
+    "imdbn_rbm_exact_logz": (_INT, [C.POINTER(RbmDesc), _P, _INT, _P, _P, _P, _P, _SZ, _P]),
     "imdbn_packed_delta_floats": (_SZ, [_INT, _INT]),
     "imdbn_rbm_prefetch_ok": (_INT, [C.POINTER(RbmDesc), _INT]),
     "imdbn_factor_compact_bytes": (_INT, [_INT, _INT, _INT, _INT, C.POINTER(_SZ)]),

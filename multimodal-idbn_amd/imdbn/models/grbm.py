@@ -167,7 +167,15 @@ class GaussianRBM(RBM):
         return gaussian_reverse_ais_log_likelihood(self, self._in(v), n_chains=n_chains, n_betas=n_betas, betas=betas,
                                                    base_vis_bias=base_vis_bias, seed=seed, max_rows=max_rows)
 
+    def gaussian_log_partition_exact(self, **kw) -> dict:
+        """Exact log Z by on-device enumeration of the hidden side (``imdbn.utils.likelihood.exact_gaussian_log_partition``; at most
+        ``max_bits`` = 24 hidden units); with ``marginals=True`` also E[v_i] and p(h_j = 1)."""
+        from imdbn.utils.likelihood import exact_gaussian_log_partition
+        return exact_gaussian_log_partition(self, **kw)
+
     # ---- what assumes Bernoulli visibles --------------------------------------------------------
+    log_partition_exact = _refuse("log_partition_exact")      # (the two exact names are not in REFUSED: they take no rows)
+    exact_marginals = _refuse("exact_marginals")
     log_partition = _refuse("log_partition")
     pseudo_log_likelihood = _refuse("pseudo_log_likelihood")
     log_likelihood = _refuse("log_likelihood")

@@ -158,6 +158,19 @@ class RBM(nn.Module):
         from imdbn.utils.likelihood import estimate_log_partition
         return estimate_log_partition(self, **kw)
 
+    def log_partition_exact(self, **kw) -> dict:
+        """Exact log Z by on-device enumeration of the smaller side (``imdbn.utils.likelihood.exact_log_partition``; at most
+        ``max_bits`` = 24 units there, softmax groups accepted)."""
+        from imdbn.utils.likelihood import exact_log_partition
+        return exact_log_partition(self, **kw)
+
+    def exact_marginals(self, **kw):
+        """``(vis_mean [V], hid_mean [H])``: the exact model marginals p(v_i = 1), p(h_j = 1) -- what a persistent or tempered
+        particle cloud should reproduce (``imdbn.utils.likelihood.exact_log_partition(marginals=True)``)."""
+        from imdbn.utils.likelihood import exact_log_partition
+        res = exact_log_partition(self, marginals=True, **kw)
+        return res["vis_mean"], res["hid_mean"]
+
     @torch.no_grad()
     def pseudo_log_likelihood(self, v: torch.Tensor, return_sites: bool = False):
         """Exact pseudo-log-likelihood sum_sites log p(v_site | v_rest) per row, float64 ``[B]``

@@ -83,6 +83,15 @@ log p_ann(v).  ``evaluate_gaussian_log_likelihood_sandwich`` reports both sides 
 Bernoulli one on the sampled top states for two layers and more, the Gaussian one for a stack of one.  These are the functions of the
 Bernoulli paragraph above on another engine call and another log Z_A; each family refuses the other's layers.
 
+The ground truth: everything above is an estimate.  When the smaller side of the RBM has at most 30 units the engine
+enumerates it on the device and sums the other side out in closed form: ``exact_log_partition`` (Bernoulli visibles, softmax groups
+accepted) and ``exact_gaussian_log_partition`` are ONE ``HipEngine.exact_log_z`` call (imdbn_rbm_exact_logz) and return the exact
+log Z and, on request, the exact model marginals p(v_i = 1) / E[v_i] and p(h_j = 1).  ``evaluate_log_likelihood_exact`` /
+``evaluate_gaussian_log_likelihood_exact`` are ``evaluate_log_likelihood`` with that log Z; ``ais_calibration`` /
+``gaussian_ais_calibration`` run the AIS estimator unchanged and report its distance from the truth on the caller's own parameters;
+``chain_marginal_gap`` compares the column means of a PCD or tempering particle cloud with the exact visible marginals.  ``max_bits``
+(24) guards the cost of 2^n states times the other side's width.
+
 Data parallelism: the chains are NOT sharded over ranks -- every rank that calls runs all ``n_chains`` chains and gets the same
 estimate (same seed) or an independent one; sharding the chains is a follow-up.
 """
@@ -105,7 +114,9 @@ __all__ = ["base_rate_bias", "linear_betas", "estimate_log_partition", "log_like
            "gaussian_base_rate_bias", "estimate_gaussian_log_partition", "gaussian_log_likelihood", "evaluate_gaussian_log_likelihood",
            "gaussian_dbn_sample_values", "gaussian_dbn_lower_bound", "gaussian_dbn_log_likelihood_is", "evaluate_gaussian_dbn_bound",
            "gaussian_reverse_ais_log_likelihood", "evaluate_gaussian_log_likelihood_sandwich", "gaussian_dbn_conservative_bound",
-           "evaluate_gaussian_dbn_bound_conservative"]
+           "evaluate_gaussian_dbn_bound_conservative",
+           "exact_log_partition", "exact_gaussian_log_partition", "evaluate_log_likelihood_exact",
+           "evaluate_gaussian_log_likelihood_exact", "ais_calibration", "gaussian_ais_calibration", "chain_marginal_gap"]
 
 
 def _bottom(model):
@@ -114,10 +125,10 @@ def _bottom(model):
     return layers[0] if layers is not None and len(layers) > 0 else model
 
 
-def _check_binary(rbm):
+def _check_binary(rbm, groups_ok: bool = False):
     if getattr(rbm, "gaussian_visible", False):
         raise ValueError("the likelihood estimators need Bernoulli visibles: this RBM's visible layer is Gaussian (DESIGN section 29)")
-    if getattr(rbm, "softmax_groups", None):
+    if getattr(rbm, "softmax_groups", None) and not groups_ok:
         raise ValueError("AIS likelihood needs an RBM with binary visibles and no softmax groups")
 
 
@@ -277,10 +288,15 @@ def estimate_log_partition(rbm, n_chains: int = 256, n_betas: int = 1000, betas=
     ``ess`` = (sum w)^2 / sum w^2 (effective sample size) and ``se`` = std(w) / (mean(w) sqrt(M)), the relative standard error of
     the mean weight = the standard error of log Z to first order; both on weights shifted by their maximum.  ``betas`` overrides
     the ``n_betas`` evenly spaced temperatures.  One device-to-host copy.  See the module docstring for ``seed``."""
+    return _weight_stats(*_ais_weights(rbm, n_chains, n_betas, betas, base_vis_bias, seed))
+
+
+def _ais_weights(rbm, n_chains=256, n_betas=1000, betas=None, base_vis_bias=None, seed=None):
+    """``(logw, log Z_A)`` of ``estimate_log_partition``, both on the device."""
     _check_binary(rbm)
     betas = linear_betas(n_betas) if betas is None else betas
     logw = _E.get_engine(rbm.W.data).ais(rbm, betas, int(n_chains), _draws(seed), base_vis_bias=base_vis_bias)
-    return _weight_stats(logw, _log_z_base(rbm, base_vis_bias, logw.device))
+    return logw, _log_z_base(rbm, base_vis_bias, logw.device)
 
 
 @torch.no_grad()
@@ -435,9 +451,14 @@ def estimate_joint_log_partition(rbm, n_chains: int = 256, n_betas: int = 1000, 
     """``estimate_log_partition`` for an RBM with softmax groups (the joint RBM of an ``iMDBN``): the same dict, from
     ``HipEngine.ais_groups``, with ``log_z_base`` = H log 2 + sum_{i outside groups} softplus(b_A,i) + sum_g logsumexp(b_A[g])
     (no ``base_vis_bias``: zeros, i.e. log 2 per Bernoulli column and log(width) per group).  One device-to-host copy."""
+    return _weight_stats(*_joint_ais_weights(rbm, n_chains, n_betas, betas, base_vis_bias, seed))
+
+
+def _joint_ais_weights(rbm, n_chains=256, n_betas=1000, betas=None, base_vis_bias=None, seed=None):
+    """``(logw, log Z_A)`` of ``estimate_joint_log_partition``, both on the device."""
     betas = linear_betas(n_betas) if betas is None else betas
     logw = _E.get_engine(rbm.W.data).ais_groups(rbm, betas, int(n_chains), _draws(seed), base_vis_bias=base_vis_bias)
-    return _weight_stats(logw, _log_z_base(rbm, base_vis_bias, logw.device))
+    return logw, _log_z_base(rbm, base_vis_bias, logw.device)
 
 
 def _imdbn_values(model, img, y, log_z_joint, n_samples, mode, rng):
@@ -774,12 +795,17 @@ def estimate_gaussian_log_partition(rbm, n_chains: int = 256, n_betas: int = 100
     """AIS estimate of log Z of a ``GaussianRBM``: the keys of ``estimate_log_partition`` (``log_z``, ``log_z_base``, ``logw``,
     ``ess``, ``se``).  ``base_vis_bias`` None: the RBM's own visible bias (module docstring).  One device-to-host copy; ``seed`` as
     in ``estimate_log_partition``."""
+    return _weight_stats(*_gaussian_ais_weights(rbm, n_chains, n_betas, betas, base_vis_bias, seed))
+
+
+def _gaussian_ais_weights(rbm, n_chains=256, n_betas=1000, betas=None, base_vis_bias=None, seed=None):
+    """``(logw, log Z_A)`` of ``estimate_gaussian_log_partition``, both on the device."""
     _check_gaussian(rbm)
     if base_vis_bias is not None and base_vis_bias.numel() != rbm.W.shape[0]:
         raise ValueError(f"base_vis_bias must have {rbm.W.shape[0]} elements")
     betas = linear_betas(n_betas) if betas is None else betas
     logw = _E.get_engine(rbm.W.data).gauss_ais(rbm, rbm.logvar.data, betas, int(n_chains), _draws(seed), base_vis_bias=base_vis_bias)
-    return _weight_stats(logw, _gaussian_log_z_base(rbm, logw.device))
+    return logw, _gaussian_log_z_base(rbm, logw.device)
 
 
 @torch.no_grad()
@@ -918,3 +944,87 @@ def evaluate_gaussian_dbn_bound_conservative(model, loader=None, n_samples: int 
     layers = _gaussian_stack(model)
     return _evaluate_conservative(model, layers, _top_side(layers), "ll/gdbn_conservative_", None, loader, n_samples, n_chains, max_batches,
                                   n_betas, betas, base_vis_bias, seed, max_rows)
+
+
+# ---- the ground truth: exact log Z and marginals by on-device enumeration ----------------------------------------
+def _exact(rbm, logvar, side, max_bits, marginals) -> dict:
+    return _E.get_engine(rbm.W.data).exact_log_z(rbm, logvar=logvar, side=side, marginals=bool(marginals), max_bits=int(max_bits))
+
+
+@torch.no_grad()
+def exact_log_partition(rbm, side: str = "auto", max_bits: int = 24, marginals: bool = False) -> dict:
+    """Exact log Z of a Bernoulli RBM, softmax groups accepted, by enumerating one side on the device (ONE ``HipEngine.exact_log_z``
+    call): ``{"log_z": 0-d float64 device tensor, "log_w_max", "side": "hidden" | "visible", "bits": n, "vis_mean", "hid_mean"}``.
+    ``side="auto"``: the smaller side, the hidden one when the visible layer has softmax groups (a one-hot group cannot be
+    enumerated bit by bit).  The enumerated side may hold ``max_bits`` units at most (the library stops at 30).  ``marginals``: also
+    the exact p(v_i = 1) (the category probabilities inside a group) and p(h_j = 1), fp32 ``[V]`` / ``[H]``.  No draws, no host sync."""
+    _check_binary(rbm, groups_ok=True)
+    return _exact(rbm, None, side, max_bits, marginals)
+
+
+@torch.no_grad()
+def exact_gaussian_log_partition(rbm, max_bits: int = 24, marginals: bool = False) -> dict:
+    """Exact log Z of a ``GaussianRBM`` by enumerating its hidden side: the keys of ``exact_log_partition``; ``vis_mean`` is E[v_i]."""
+    _check_gaussian(rbm)
+    return _exact(rbm, rbm.logvar.data, "hidden", max_bits, marginals)
+
+
+def _exact_estimate(exact):
+    """``exact`` in the shape ``_known_or_estimated`` asks of an estimator: log Z on the host, no standard error, no sample size."""
+    def estimate(rbm, max_bits=24):
+        return {"log_z": float(exact(rbm, max_bits=max_bits)["log_z"]), "se": None, "ess": None}
+    return estimate
+
+
+@torch.no_grad()
+def evaluate_log_likelihood_exact(model, loader=None, max_batches: Optional[int] = None, max_bits: int = 24) -> Optional[dict]:
+    """``evaluate_log_likelihood`` with the exact log Z of ``exact_log_partition`` in place of an AIS estimate (``se`` and ``ess``
+    None): the mean held-out log-likelihood of an ``RBM`` -- or of the BOTTOM layer of an ``iDBN`` -- itself, not an estimate of it.
+    Softmax groups are accepted.  With a ``wandb_run`` on the model the scalars are logged as ``ll/...``."""
+    return _evaluate_ll(model, loader, None, max_batches, {"max_bits": max_bits}, lambda r: _check_binary(r, groups_ok=True),
+                        _exact_estimate(exact_log_partition))
+
+
+@torch.no_grad()
+def evaluate_gaussian_log_likelihood_exact(model, loader=None, max_batches: Optional[int] = None, max_bits: int = 24) -> Optional[dict]:
+    """``evaluate_gaussian_log_likelihood`` with the exact log Z of ``exact_gaussian_log_partition``: the mean held-out log-density."""
+    return _evaluate_ll(model, loader, None, max_batches, {"max_bits": max_bits}, _check_gaussian, _exact_estimate(exact_gaussian_log_partition))
+
+
+def _calibration(rbm, weights, exact, max_bits, ais_kwargs) -> dict:
+    """The AIS run of ``weights`` (what its ``estimate_*`` runs), then the exact call; every figure in ONE device-to-host copy."""
+    logw, lzb = weights(rbm, **ais_kwargs)
+    lz = exact(rbm, max_bits=max_bits)["log_z"]
+    host = torch.cat([_weight_stats_device(logw, lzb), lz.reshape(1).to(logw.device)]).cpu().tolist()
+    return {"log_z": host[0], "log_z_base": host[1], "logw": logw, "ess": host[2], "se": host[3], "log_z_exact": host[4],
+            "log_z_gap": host[0] - host[4]}
+
+
+@torch.no_grad()
+def ais_calibration(rbm, max_bits: int = 24, **ais_kwargs) -> dict:
+    """How far AIS is from the truth on ``rbm``'s own parameters: the dict of ``estimate_log_partition(rbm, **ais_kwargs)`` -- of
+    ``estimate_joint_log_partition`` for an RBM with softmax groups -- plus ``log_z_exact`` and ``log_z_gap`` = AIS minus exact."""
+    _check_binary(rbm, groups_ok=True)
+    weights = _joint_ais_weights if getattr(rbm, "softmax_groups", None) else _ais_weights
+    return _calibration(rbm, weights, exact_log_partition, max_bits, ais_kwargs)
+
+
+@torch.no_grad()
+def gaussian_ais_calibration(rbm, max_bits: int = 24, **ais_kwargs) -> dict:
+    """``ais_calibration`` for a ``GaussianRBM``: ``estimate_gaussian_log_partition`` against ``exact_gaussian_log_partition``."""
+    _check_gaussian(rbm)
+    return _calibration(rbm, _gaussian_ais_weights, exact_gaussian_log_partition, max_bits, ais_kwargs)
+
+
+@torch.no_grad()
+def chain_marginal_gap(rbm, particles: torch.Tensor, max_bits: int = 24) -> dict:
+    """The distance between a particle cloud and the model it should sample: ``{"max_gap", "rms_gap"}``, the largest and the
+    root-mean-square difference between the column means of ``particles`` ``[M, V]`` (the chains of ``train_epoch_persistent``; of a
+    tempering state ``[R M, V]`` pass the last replica's rows, ``state[-M:]``, the ones at beta = 1) and the exact ``vis_mean`` of
+    ``exact_log_partition``; 0-d float64 device tensors, no host sync."""
+    _check_binary(rbm, groups_ok=True)
+    if particles.dim() != 2 or particles.size(1) != rbm.W.shape[0] or particles.size(0) < 1:
+        raise ValueError(f"chain_marginal_gap: particles must be [M, {rbm.W.shape[0]}], got {tuple(particles.shape)}")
+    want = exact_log_partition(rbm, max_bits=max_bits, marginals=True)["vis_mean"].double()
+    gap = rows_on_device(particles, want.device).double().mean(0) - want
+    return {"max_gap": gap.abs().max(), "rms_gap": gap.pow(2).mean().sqrt()}
