@@ -1000,6 +1000,29 @@ int imdbn_rbm_pair_scores(const imdbn_rbm_desc* d, int D1, const float* z1, int6
                           const float* z2, int64_t ld2, int N, const int32_t* gt_q, const int32_t* gt_n, int k,
                           const imdbn_pair_out* out, void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- unit moments: sufficient statistics of act[B][H] for tuning curves and per-unit regressions (imdbn/utils/unit_tuning.py) ------
+ * act[B][H] fp32 with row stride lda >= H (only 4-byte alignment is assumed; nothing beyond column H is read); cls[B] int32 is a
+ * class per row (null with K = 0); x[B][R] fp32 with row stride ldx >= R are regressors (null with R = 0).  z = [1, x_1 .. x_R].
+ *   A row is USED when its class lies in [0, K) (every row without cls) and its R regressors are finite.  Every other row is left
+ *   out of every sum and counted in rows[1], so the curves and the regression describe the same rows.
+ *   accumulators -- ADDED to, never overwritten, so a loop over batches leaves one result (zero them before the first call)
+ *     cls_sum[K][H], cls_sumsq[K][H] (double), cls_count[K] (int64): per class sum a, sum a^2, rows (required with cls);
+ *     xa[R + 1][H] (double): row q = sum z_q a over the used rows;   aa[H]: sum a^2;   xx[R + 1][R + 1]: sum z_p z_q;
+ *     rows[2] (int64): used rows, skipped rows.  xa, aa, xx and rows are always required.
+ *   Every product is formed in double from its fp32 factors (exact); every sum is a double sum in an order fixed by (B, H, K, R)
+ *   and by which rows are used in which class (csrc/kernels_tuning.hpp): the same call leaves the same bits.  No floating-point
+ *   atomics.  A non-finite activation poisons its own column only.  An accumulator row that receives no term (an empty class,
+ *   a call whose rows are all skipped) is not written.  No host synchronisation.
+ *   Limits (IMDBN_E_INVALID otherwise, naming the value, before the first launch and with no accumulator touched): B >= 1, H >= 1,
+ *     0 <= R <= 8, 0 <= K <= 1024, K >= 1 with cls and K = 0 without, lda >= H, ldx >= R, x given exactly when R > 0, a null
+ *     accumulator that the inputs require, ceil(H / 64) (max(K, 1) + ceil(B / 256)) + 81 above 2^31 - 1.
+ *   Workspace: 256-byte aligned, at least imdbn_unit_moments_ws_bytes(B, H, K, R) (0 for arguments outside the limits); anything
+ *     smaller is IMDBN_E_INVALID as well.  Its contents on entry do not matter. */
+size_t imdbn_unit_moments_ws_bytes(int B, int H, int K, int R);
+int imdbn_unit_moments(const float* act, int64_t lda, int B, int H, const int32_t* cls, int K, const float* x, int64_t ldx, int R,
+                       double* cls_sum, double* cls_sumsq, long long* cls_count, double* xa, double* aa, double* xx, long long* rows,
+                       void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- whole RBM.train_epoch_clamped (rbm.py:402-483) -------------------------------------- */
 /* positive phase = chain(n_init steps) ; negative = cd_k steps from v+ ; update with o->lr */
 int imdbn_rbm_clamped_step(const imdbn_rbm_desc* d, const float* v_known, const float* mask, int64_t ldk, int B,

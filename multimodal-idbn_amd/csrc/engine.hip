@@ -45,6 +45,7 @@
 #include "kernels_backprop.hpp"
 #include "kernels_gauss_backprop.hpp"
 #include "kernels_exact.hpp"
+#include "kernels_tuning.hpp"
 
 using namespace imdbn;
 
@@ -1549,6 +1550,9 @@ int imdbn_cross_metrics(const float* p, int64_t ldp, int B, int K, const float* 
 
 // ---- pairwise free-energy scores and retrieval ranks (imdbn/utils/retrieval.py; kernels_pair.hpp) -------------------
 #include "host_pair.hpp"
+
+// ---- unit moments for tuning curves and per-unit regressions (imdbn/utils/unit_tuning.py; kernels_tuning.hpp) ----------
+#include "host_tuning.hpp"
 
 // rbm.py:443-471: v+ by conditional inference, H+, CD-k from v+ (optionally re-clamped / sampled), H-.
 // Leaves the statistics operands in the workspace exactly as cd_phases does.

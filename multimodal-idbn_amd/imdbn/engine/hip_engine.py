@@ -1570,8 +1570,50 @@ class HipEngine:
                    int(npix), int(topk), C.byref(out), _ptr(ws), ws.numel(), self._stream(dev))
         return o
 
+    # ---- unit moments (imdbn/utils/unit_tuning.py) --------------------------------------------------------------------------
+    def unit_moments(self, act: torch.Tensor, cls: Optional[torch.Tensor] = None, n_classes: int = 0, x: Optional[torch.Tensor] = None,
+                     acc: Optional[dict] = None) -> dict:
+        """Sufficient statistics of the activations ``act`` ``[B, H]`` for per-unit tuning curves and regressions
+        (imdbn_unit_moments): with ``cls`` ``[B]`` (a class in ``[0, n_classes)`` per row) ``cls_sum``, ``cls_sumsq`` ``[K, H]`` float64
+        and ``cls_count`` ``[K]`` int64; with regressors ``x`` ``[B, R]`` (R <= 8) and z = [1, x]: ``xa`` ``[R + 1, H]`` = sum z a,
+        ``aa`` ``[H]`` = sum a^2, ``xx`` ``[R + 1, R + 1]`` = sum z z^T, all float64; ``rows`` ``[2]`` int64 = rows used, rows skipped (a
+        class outside the range or a non-finite regressor).  ``acc`` is an earlier result: it is ADDED to (a loop over the batches of
+        a split leaves one result); without it the dict is allocated as zeros.  ``act`` may be a row view with ``stride(1) == 1``
+        of a wider tensor; it is not copied.  Returns device tensors; no host sync."""
+        if not act.is_cuda or act.dim() != 2:
+            raise N.EngineError("unit_moments needs a HIP tensor act [B, H]")
+        act = _f32c(act)
+        B, H = act.shape
+        dev = act.device
+        K = int(n_classes) if cls is not None else 0
+        c = _on(cls, dev, torch.int32)
+        xt = None
+        if x is not None:
+            xt = _on(x.reshape(B, -1) if x.dim() != 2 else x, dev, torch.float32)
+        R = 0 if xt is None else xt.size(1)
+        if (c is not None and c.numel() != B) or (xt is not None and xt.size(0) != B):
+            raise N.EngineError("unit_moments: cls [B] and x [B, R] must match act")
+        if R == 0:
+            xt = None
+        shapes = {"cls_sum": ((K, H), torch.float64), "cls_sumsq": ((K, H), torch.float64), "cls_count": ((K,), torch.int64),
+                  "xa": ((R + 1, H), torch.float64), "aa": ((H,), torch.float64), "xx": ((R + 1, R + 1), torch.float64),
+                  "rows": ((2,), torch.int64)}
+        if acc is None:
+            acc = {k: torch.zeros(*shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
+        for k, (shape, dt) in shapes.items():
+            t = acc.get(k)
+            if t is None or t.device != dev or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise N.EngineError(f"unit_moments: acc[{k!r}] must be a contiguous {dt} tensor {list(shape)} on {dev}")
+        need = int(self._lib.imdbn_unit_moments_ws_bytes(B, H, K, R))
+        ws = self._buffer(("unit_moments", dev, torch.cuda.current_stream(dev).cuda_stream),
+                          lambda: torch.empty(need, dtype=torch.uint8, device=dev), at_least=need)
+        self._call("imdbn_unit_moments", _ptr(act), act.stride(0), B, H, _ptr(c), K, _ptr(xt), R if xt is not None else 0, R,
+                   _ptr(acc["cls_sum"]) if K else None, _ptr(acc["cls_sumsq"]) if K else None, _ptr(acc["cls_count"]) if K else None,
+                   _ptr(acc["xa"]), _ptr(acc["aa"]), _ptr(acc["xx"]), _ptr(acc["rows"]), _ptr(ws), ws.numel(), self._stream(dev))
+        return acc
+
     # ---- latent nearest-neighbour search (imdbn/utils/imdbn_logging.py) ----------------------------------------------------
-    LATENT_METRICS = {"cosine": 0, "inner": 1, "ip": 1, "l2": 2}
+    LATENT_METRICS ={"cosine": 0, "inner": 1, "ip": 1, "l2": 2}
 
     def row_stats(self, x: torch.Tensor) -> torch.Tensor:
         """``[N, 2]`` fp32 device tensor: per-row sum and sum of squares of ``x`` (rows flattened), in a fixed order

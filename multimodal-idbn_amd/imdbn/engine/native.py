@@ -184,6 +184,8 @@ SIGNATURES = {
     "imdbn_cross_metrics": (_INT, [_P, _I64, _INT, _INT, _P, _I64, _P, _P, _INT, _INT, C.POINTER(CrossMetricsOut), _P, _SZ, _P]),
     "imdbn_pair_ws_bytes": (_SZ, [_INT, _INT, _INT, _INT, _INT]),
     "imdbn_rbm_pair_scores": (_INT, [C.POINTER(RbmDesc), _INT, _P, _I64, _INT, _P, _I64, _INT, _P, _P, _INT, C.POINTER(PairOut), _P, _SZ, _P]),
+    "imdbn_unit_moments_ws_bytes": (_SZ, [_INT, _INT, _INT, _INT]),
+    "imdbn_unit_moments": (_INT, [_P, _I64, _INT, _INT, _P, _INT, _P, _I64, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "imdbn_rbm_clamped_step": (_INT, [C.POINTER(RbmDesc), _P, _P, _I64, _INT, _INT, C.POINTER(ChainStep), _P, _I64, _INT,
                                       C.POINTER(CdOpts), C.POINTER(Rng), _P, _P, _SZ, _P]),
     "imdbn_rbm_assoc_update": (_INT, [C.POINTER(RbmDesc), _P, _I64, _P, _I64, _P, _I64, _P, _I64, _INT, C.POINTER(CdOpts), _P, _SZ, _P]),

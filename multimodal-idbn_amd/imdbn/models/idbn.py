@@ -428,6 +428,12 @@ class iDBN:
         from imdbn.utils.likelihood import gaussian_dbn_conservative_bound
         return gaussian_dbn_conservative_bound(self, v, **kw)
 
+    def unit_tuning(self, upto_layer: Optional[int] = None, **kw) -> dict:
+        """Per-unit tuning curves and feature regressions of layer ``upto_layer`` (default: the top) over the validation split
+        (``imdbn.utils.unit_tuning.evaluate_unit_tuning``)."""
+        from imdbn.utils.unit_tuning import evaluate_unit_tuning
+        return evaluate_unit_tuning(self, upto_layer=upto_layer, **kw)
+
     def save_model(self, path: str):
         """idbn.py:370-372: pickle of {"layers", "params"} (live RBM modules)."""
         model_copy = {"layers": self.layers, "params": self.params}

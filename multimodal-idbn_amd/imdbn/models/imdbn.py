@@ -525,6 +525,14 @@ class iMDBN(nn.Module):
         from imdbn.utils import likelihood as _LK
         return _LK.imdbn_lower_bound(self, img, y, log_z_joint, **kw)
 
+    def unit_tuning(self, joint: bool = True, upto_layer: Optional[int] = None, **kw) -> dict:
+        """Per-unit tuning curves and feature regressions of the joint layer over the validation split, or with ``joint=False`` of
+        layer ``upto_layer`` of the image stack (``imdbn.utils.unit_tuning.evaluate_unit_tuning``)."""
+        from imdbn.utils.unit_tuning import evaluate_unit_tuning
+        if joint:
+            return evaluate_unit_tuning(self, joint=True, **kw)
+        return evaluate_unit_tuning(self.image_idbn, upto_layer=upto_layer, **kw)
+
     # ---- persistence (imdbn.py:815-934, SURVEY.md Appendix C) -------------------------------------
     def save_model(self, path: str):
         all_layers = list(self.image_idbn.layers) + [self.joint_rbm]
