@@ -475,6 +475,39 @@ int imdbn_rbm_centered_step(const imdbn_rbm_desc* d, const float* data, int64_t 
                             const imdbn_cd_opts* o, imdbn_rng* rng, float* mu, float* lam, float slide, int mode,
                             float* loss_out, float* scratch, void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- extended mean field: TAP training and log Z (imdbn/utils/tap.py; Gabrie, Tramel & Krzakala 2015) ------------
+ * Bernoulli units on both sides, no softmax groups.  Magnetisations mv [B][V] (row stride ldmv >= V), mh [B][H] (ldmh >= H): device
+ * fp32 in [0, 1], READ AND OVERWRITTEN in place; the padding of their rows is neither read nor written.  cv = mv - mv^2,
+ * ch = mh - mh^2, W2 = fl32(W W) (made in registers, never stored); order 1 (naive mean field) drops every W2 term.
+ *   hidden half-step    x = c + mv W - (mh - 1/2) o (cv W2),       mh <- damp mh + (1 - damp) sigmoid(x)
+ *   visible half-step   y = a + mh W^T - (mv - 1/2) o (ch W2^T),   mv <- damp mv + (1 - damp) sigmoid(y)     (with the new mh)
+ * One iteration = a hidden then a visible half-step.  The residual of a row: the largest |sigmoid(.) - m_old| over both half-steps
+ * of the last iteration, before damping (0 with n_iters = 0).  Free energy of a row, with 0 ln 0 = 0:
+ *   Gamma = sum_i [mv ln mv + (1 - mv) ln(1 - mv)] + sum_j [same for mh] - a.mv - c.mh - mv W mh^T - 1/2 cv W2 ch^T    (last: order 2)
+ * and log Z ~ -Gamma at a fixed point.
+ * imdbn_rbm_tap_iterate: n_iters >= 0 iterations, then out_gamma (double [B], nullable: one more weight pass) and out_res (float [B],
+ *   nullable) of the state as it stands.  The caller's parameters are only read.
+ * imdbn_rbm_tap_step: one update with n = B.  Positive phase as imdbn_rbm_cd_step (data V+, H+ = sigmoid(c + V+ W)); negative phase:
+ *   n_iters >= 0 iterations on mv, mh;  gW = (V+^T H+ - mv^T mh - W o (cv^T ch)) / n  (last term: order 2, W before this update),
+ *   ga = (sum V+ - sum mv) / n, gc = (sum H+ - sum mh) / n, then the momentum / weight-decay / sparsity rule of imdbn_rbm_cd_step.
+ *   loss_out (nullable: that propagation is then not launched) = the mean-field reconstruction error of the data, as
+ *   imdbn_rbm_pcd_step.  o->cd_k is not read; o->data_binary as in imdbn_rbm_cd_step; the prefetch fields and fwd_out must be zero.
+ *   scratch: device, imdbn_rbm_tap_scratch_floats(V, H) floats (the statistics, then cv^T ch), 16-byte aligned for the float4
+ *   kernels; contents unspecified on return.
+ * Plain launches (and one memset node) on `stream`, no host sync, no allocation.  No floating-point atomics; every sum has an order
+ * fixed by (V, H, B) and the device's CU count: the same call on the same state gives the same bits.  The row padding of W / W_m is
+ * neither read nor written.  Workspace: 256-byte aligned, imdbn_rbm_tap_ws_bytes(V, H, B); nothing in it needs to survive a call.
+ * IMDBN_E_INVALID (naming the value) before the first launch, nothing touched: a null d / parameter / (tap_step) momentum buffer,
+ * softmax groups, null mv / mh / ws / (tap_step) data / o / scratch, a leading dimension below its row length, B < 1, n_iters < 0,
+ * order outside {1, 2}, damp outside [0, 1) or NaN, a short or misaligned workspace, a short scratch, a non-zero prefetch field. */
+size_t imdbn_rbm_tap_ws_bytes(int V, int H, int B);
+size_t imdbn_rbm_tap_scratch_floats(int V, int H);
+int imdbn_rbm_tap_iterate(const imdbn_rbm_desc* d, float* mv, int64_t ldmv, float* mh, int64_t ldmh, int B, int n_iters, float damp,
+                          int order, double* out_gamma, float* out_res, void* ws, size_t ws_bytes, imdbn_stream_t stream);
+int imdbn_rbm_tap_step(const imdbn_rbm_desc* d, const float* data, int64_t ldd, int B, float* mv, int64_t ldmv, float* mh, int64_t ldmh,
+                       const imdbn_cd_opts* o, int n_iters, float damp, int order, float* loss_out, float* scratch, size_t scratch_floats,
+                       void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- Gaussian visible units with learned variances (imdbn/models/grbm.py: GaussianRBM; Cho, Ilin & Raiko 2011) ----
  * The parameters of the descriptor plus logvar [V] (device), sigma_i^2 = exp(logvar_i); with u = v exp(-logvar):
  *     p(h_j | v) = sigmoid(c_j + (u W)_j),   p(v_i | h) = N(b_i + (h W^T)_i, sigma_i^2),

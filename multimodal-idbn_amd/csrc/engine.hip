@@ -46,6 +46,7 @@
 #include "kernels_gauss_backprop.hpp"
 #include "kernels_exact.hpp"
 #include "kernels_tuning.hpp"
+#include "kernels_tap.hpp"
 
 using namespace imdbn;
 
@@ -1800,6 +1801,9 @@ int imdbn_rbm_centered_step(const imdbn_rbm_desc* d, const float* data, int64_t 
     HIPCHK(hipGetLastError());
     return 0;
 }
+
+// ---- extended mean field: TAP training and log Z (imdbn/utils/tap.py; kernels_tap.hpp) -----------------------------------
+#include "host_tap.hpp"
 
 // ---- Gaussian visible units (imdbn/models/grbm.py; kernels_gauss.hpp) ----------------------------------------------------
 // p(h | v) is the Bernoulli engine applied to u = v e^{-z}, the mean of p(v | h) its logits path: K1 / K2 / K3 are called as they are.

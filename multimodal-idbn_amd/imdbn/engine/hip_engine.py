@@ -719,6 +719,57 @@ class HipEngine:
                  _ptr(scratch), prefetch=False, particles=p, nullable_chains=True)
         return loss.reshape(()) if monitor else None
 
+    # ---- extended mean field (imdbn_rbm_tap_*) ----------------------------------------
+    @staticmethod
+    def _magnetisations(who: str, mv, mh, B: int, V: int, H: int, dev):
+        """Magnetisations are updated IN PLACE, as the chains are: a tensor that would have to be copied is refused."""
+        for nm, t, n in (("mv", mv, V), ("mh", mh, H)):
+            if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32 and t.dim() == 2 and t.size(0) == B
+                    and t.size(1) == n and t.stride(1) == 1 and (B == 1 or t.stride(0) >= n)):
+                raise N.EngineError(f"{who}: {nm} must be an fp32 tensor [{B}, {n}] on {dev} with unit inner stride (updated in place)")
+        return mv, mh
+
+    def _tap_ws(self, dev, V, H, B):
+        """``(workspace, bytes, stream)`` of the TAP entries: the workspace of the shape plus the split-K slabs and row partials."""
+        need = int(self._lib.imdbn_rbm_tap_ws_bytes(V, H, B))
+        ws = self._buffer(("tap_ws", dev, V, H, B, torch.cuda.current_stream(dev).cuda_stream),
+                          lambda: torch.empty(need, dtype=torch.uint8, device=dev), need)
+        return _ptr(ws), ws.numel(), self._stream(dev)
+
+    def tap_iterate(self, rbm, mv, mh, n_iters, damp=0.5, order=2, want_gamma=True, want_res=True):
+        """``n_iters`` >= 0 TAP iterations (imdbn_rbm_tap_iterate) on the magnetisations ``mv`` ``[B, V]`` /
+        ``mh`` ``[B, H]`` (fp32, updated in place; row views with a pitch are taken as they are).  Returns ``(gamma, res)``: the
+        free energy Gamma of every row as it stands after them (float64 ``[B]``; log Z ~ -Gamma at a fixed point) and the residual of
+        the last iteration (fp32 ``[B]``), or None for the one not wanted.  ``order`` 1: naive mean field.  No host sync."""
+        d = self._desc(rbm, False)
+        dev = rbm.W.data.device
+        B = mv.size(0) if isinstance(mv, torch.Tensor) and mv.dim() == 2 else 0
+        self._magnetisations("tap_iterate", mv, mh, B, d.V, d.H, dev)
+        gamma = torch.empty(B, dtype=torch.float64, device=dev) if want_gamma else None
+        res = torch.empty(B, dtype=torch.float32, device=dev) if want_res else None
+        self._call("imdbn_rbm_tap_iterate", C.byref(d), _ptr(mv), max(mv.stride(0), d.V), _ptr(mh), max(mh.stride(0), d.H), B, int(n_iters), float(damp),
+                   int(order), _ptr(gamma), _ptr(res), *self._tap_ws(dev, d.V, d.H, B))
+        return gamma, res
+
+    def tap_step(self, rbm, data, mv, mh, lr, mom, n_iters, damp=0.5, order=2, data_binary=None, monitor=True):
+        """One TAP update (imdbn_rbm_tap_step): the positive phase of ``cd_step``, ``n_iters`` >= 0 iterations on
+        the persistent magnetisations ``mv`` / ``mh`` (updated in place) as the negative phase, the deterministic gradient and the
+        update rule of ``cd_step``.  Returns the mean-field reconstruction error of the data as a 0-d device tensor, or None with
+        ``monitor=False`` (that propagation is then not launched).  No draws, no host sync."""
+        d = self._desc(rbm, True)
+        x = _f32c(data)
+        B, dev = x.size(0), x.device
+        self._magnetisations("tap_step", mv, mh, B, d.V, d.H, dev)
+        o = self._opts(rbm, lr, mom, 0, sparsity=getattr(rbm, "sparsity", False))
+        o.data_binary = self._hint(data, data_binary)
+        loss = torch.empty(1, device=dev) if monitor else None
+        need = int(self._lib.imdbn_rbm_tap_scratch_floats(d.V, d.H))
+        scratch = self._buffer(("tap", dev, d.V, d.H, torch.cuda.current_stream(dev).cuda_stream),
+                               lambda: torch.empty(need, dtype=torch.float32, device=dev), need)
+        self._call("imdbn_rbm_tap_step", C.byref(d), _ptr(x), x.stride(0), B, _ptr(mv), max(mv.stride(0), d.V), _ptr(mh), max(mh.stride(0), d.H), C.byref(o),
+                   int(n_iters), float(damp), int(order), _ptr(loss), _ptr(scratch), scratch.numel(), *self._tap_ws(dev, d.V, d.H, B))
+        return loss.reshape(()) if monitor else None
+
     # ---- Gaussian visible units (imdbn_rbm_gauss_*; DESIGN section 29) ---------------------------------
     @staticmethod
     def _logvar(who: str, t, n: int, dev) -> torch.Tensor:

@@ -17,6 +17,7 @@ import torch
 from imdbn.models.grbm import GaussianRBM
 from imdbn.models.rbm import RBM
 from imdbn.utils import batches, rows_on_device
+from imdbn.utils.tap import tap_layer_ok, tap_params
 
 
 def binary_input(v: torch.Tensor) -> bool:
@@ -125,6 +126,13 @@ class iDBN:
         centered = self.params.get("CENTERED", False)
         centered = None if centered is None or centered is False else (0.01 if centered is True else float(centered))
         ctr_offsets = self.params.get("CENTERED_OFFSETS", "data")
+        # extension, off by default: params["TAP"] (True: 3 iterations, order 2, damp 0.5; a dict: n_iters / order / damp)
+        # trains every Bernoulli layer without softmax groups by RBM.train_epoch_tap; not together with PERSISTENT or CENTERED
+        tap = tap_params(self.params)
+        if tap is not None:
+            from imdbn import engine as _E
+            if _E.dp.active():
+                raise NotImplementedError("iDBN.train: params['TAP'] has no data-parallel split")
         for epoch in range(int(epochs)):
             losses = []
             # one batch of lookahead: the first layer prepares the operand forms of the following batch during its
@@ -141,6 +149,10 @@ class iDBN:
                     # dropped by the reference, idbn.py:203) has no side effect and is not run
                     if isinstance(rbm, GaussianRBM):      # its own CD update; no persistent or centered form
                         loss = rbm.train_epoch(v, epoch, epochs, CD=self.cd_k)
+                        if li < last:
+                            v = rbm.forward(v)
+                    elif tap is not None and tap_layer_ok(rbm):
+                        loss = rbm.train_epoch_tap(v, epoch, epochs, n_iters=tap[0], order=tap[1], damp=tap[2])
                         if li < last:
                             v = rbm.forward(v)
                     elif centered is not None:

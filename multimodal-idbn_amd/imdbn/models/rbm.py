@@ -90,7 +90,8 @@ class RBM(nn.Module):
         state = self.__dict__.copy()
         state.pop("_imdbn_desc", None)                 # the engine's cached native descriptor (raw addresses): never part of the state
         # persistent chains, their swap counters and the centering offsets: a loaded model restarts its chains and re-initialises its offsets
-        for k in ("_pcd", "_pcd_replicas", "_pt_try", "_pt_acc", "_ctr_mu", "_ctr_lam"):
+        # (and the magnetisations of train_epoch_tap)
+        for k in ("_pcd", "_pcd_replicas", "_pt_try", "_pt_acc", "_ctr_mu", "_ctr_lam", "_tap_mv", "_tap_mh"):
             state.pop(k, None)
         params = state["_parameters"].copy()
         W = params.get("W")
@@ -371,6 +372,17 @@ class RBM(nn.Module):
         """``(mu [V], lam [H])``, the offsets of train_epoch_centered as they stand (the live tensors), or None before its first call."""
         mu, lam = self.__dict__.get("_ctr_mu"), self.__dict__.get("_ctr_lam")
         return None if mu is None or lam is None else (mu, lam)
+
+    # ---- extended mean field: TAP training and log Z (extension; DESIGN §38; imdbn/utils/tap.py) -------
+    def train_epoch_tap(self, data: torch.Tensor, epoch: int, max_epochs: int, **kw):
+        """One deterministic TAP update on one mini-batch (``imdbn.utils.tap.train_epoch_tap``: ``n_iters``, ``damp``, ``order``, ``monitor``)."""
+        from imdbn.utils.tap import train_epoch_tap
+        return train_epoch_tap(self, data, epoch, max_epochs, **kw)
+
+    def log_partition_tap(self, **kw) -> dict:
+        """``-Gamma*``, the TAP approximation of log Z at any layer size (``imdbn.utils.tap.tap_log_partition``)."""
+        from imdbn.utils.tap import tap_log_partition
+        return tap_log_partition(self, **kw)
 
     # ---- supervised step on the labels (extension; DESIGN §22) ---------------------------------------
     @torch.no_grad()
