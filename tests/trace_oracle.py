@@ -154,29 +154,104 @@ class SmallOracle:
     def decode_layers(self):
         return [(W, vb) for W, _, vb in self.img]
 
+    Dz, K = 20, 8                           # the code and label widths (StackOracle sets its own)
+
     def img2txt(self, x, u, T, **kw):
-        """x [B, 100], u [B, 28] initial uniforms."""
+        """x [B, D], u [B, Dz + K] initial uniforms."""
+        Dz, V = self.Dz, self.Dz + self.K
         z = self.represent(np.asarray(x, np.float64))
         B = z.shape[0]
-        vk = np.zeros((B, 28)); vk[:, :20] = z
-        m = np.zeros((B, 28)); m[:, :20] = 1
+        vk = np.zeros((B, V)); vk[:, :Dz] = z
+        m = np.zeros((B, V)); m[:, :Dz] = 1
         v0 = vk * m + (1 - m) * u
-        y0 = v_probs(self.W, self.vb, h_probs(self.W, self.hb, v0), self.groups)[:, 20:]
-        ys = mean_field_chain(self.W, self.hb, self.vb, self.groups, v0, vk, m, T)[:, :, 20:]
+        y0 = v_probs(self.W, self.vb, h_probs(self.W, self.hb, v0), self.groups)[:, Dz:]
+        ys = mean_field_chain(self.W, self.hb, self.vb, self.groups, v0, vk, m, T)[:, :, Dz:]
         return label_scan(y0, ys, **kw)
 
     def txt2img(self, x, y, T, zcm=True, beta=0.0, **kw):
+        Dz, V = self.Dz, self.Dz + self.K
         y = np.asarray(y, np.float64)
         B = y.shape[0]
-        vk = np.zeros((B, 28)); vk[:, 20:] = y
-        m = np.zeros((B, 28)); m[:, 20:] = 1
+        vk = np.zeros((B, V)); vk[:, Dz:] = y
+        m = np.zeros((B, V)); m[:, Dz:] = 1
         if zcm:
             z0 = self.zcm[y.argmax(1)]
         else:
-            z0 = v_probs(self.W, self.vb, h_probs(self.W, self.hb, vk), self.groups)[:, :20]
-        v0 = vk.copy(); v0[:, :20] = z0
-        zs = mean_field_chain(self.W, self.hb, self.vb, self.groups, v0, vk, m, T)[:, :, :20]
+            z0 = v_probs(self.W, self.vb, h_probs(self.W, self.hb, vk), self.groups)[:, :Dz]
+        v0 = vk.copy(); v0[:, :Dz] = z0
+        zs = mean_field_chain(self.W, self.hb, self.vb, self.groups, v0, vk, m, T)[:, :, :Dz]
         zn, dz = code_scan(zs, z0, beta)
         mse = np.stack([decode_sqerr(self.decode_layers(), zn[t], np.asarray(x, np.float64)) for t in range(T)], 1)
         steps, best, margin = patience_scan(dz, mse, **kw)
         return {"z_l2": dz, "image_mse": mse, "steps": steps, "best_mse": best, "margin": margin, "z_new": zn}
+
+
+# ---- fp32 twins: the kernels of csrc/kernels_trace.hpp restated in numpy, in their order of operations --------------------------
+F32 = np.float32
+
+
+def _butterfly(x):
+    """wave_sum_all: 64 lane values [..., 64] meet in the xor butterfly 32, 16, .. 1 (fp32 addition commutes, so every lane ends with
+    the value of the halving tree)."""
+    x = np.asarray(x, F32)
+    w = 32
+    while w >= 1:
+        x = (x[..., :w] + x[..., w:2 * w]).astype(F32)
+        w //= 2
+    return x[..., 0]
+
+
+def code_scan_f32(zs, z0, beta=0.0):
+    """trace_code_scan in fp32: lane l takes columns l, l + 64, ... in ascending order, the lanes meet in the butterfly, one sqrt."""
+    zs, prev = np.asarray(zs, F32), np.asarray(z0, F32)
+    T, B, Dz = zs.shape
+    b, one = F32(beta), F32(1)
+    zn, dz = np.zeros_like(zs), np.zeros((B, T), F32)
+    for t in range(T):
+        z = ((one - b) * prev + b * zs[t]).astype(F32) if b > 0 else zs[t]
+        d = (z - prev).astype(F32)
+        sq = np.zeros((B, (Dz + 63) // 64 * 64), F32)
+        sq[:, :Dz] = d * d
+        acc = np.zeros((B, 64), F32)
+        for k in range(sq.shape[1] // 64):
+            acc = (acc + sq[:, 64 * k:64 * k + 64]).astype(F32)
+        dz[:, t] = np.sqrt(_butterfly(acc)).astype(F32)
+        zn[t] = z
+        prev = z
+    return zn, dz
+
+
+def row_sqerr_f32(x, ref):
+    """row_sqerr in fp32: thread tid sums its columns tid, tid + 256, ... in ascending order, an 8-level halving tree, one division."""
+    x, ref = np.asarray(x, F32), np.asarray(ref, F32)
+    B, N = x.shape
+    d = (x - ref).astype(F32)
+    sq = np.zeros((B, (N + 255) // 256 * 256), F32)
+    sq[:, :N] = d * d
+    red = np.zeros((B, 256), F32)
+    for k in range(sq.shape[1] // 256):
+        red = (red + sq[:, 256 * k:256 * k + 256]).astype(F32)
+    w = 128
+    while w >= 1:
+        red = (red[:, :w] + red[:, w:2 * w]).astype(F32)
+        w //= 2
+    return (red[:, 0] / F32(N)).astype(F32)
+
+
+def decode_probs(layers, z):
+    """float64 decode(z) of decode_sqerr: the visible probabilities of the bottom layer."""
+    cur = np.asarray(z, np.float64)
+    for W, vb in reversed(layers):
+        cur = sigmoid(cur @ W.T + vb)
+    return cur
+
+
+class StackOracle(SmallOracle):
+    """SmallOracle for any image stack and joint RBM: w as small_model_arrays' dict, the code Dz and K labels wide."""
+
+    def __init__(self, w, Dz, K):
+        n = len([k for k in w if k.startswith("img") and k.endswith("_W")])
+        self.img = [tuple(w[f"img{i}_{k}"].astype(np.float64) for k in ("W", "hid_bias", "vis_bias")) for i in range(n)]
+        self.W, self.hb, self.vb = (w[k].astype(np.float64) for k in ("joint_W", "joint_hid_bias", "joint_vis_bias"))
+        self.zcm = w["z_class_mean"].astype(np.float64)
+        self.Dz, self.K, self.groups = Dz, K, [(Dz, Dz + K)]
