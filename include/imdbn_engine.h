@@ -508,6 +508,38 @@ int imdbn_rbm_tap_step(const imdbn_rbm_desc* d, const float* data, int64_t ldd, 
                        const imdbn_cd_opts* o, int n_iters, float damp, int order, float* loss_out, float* scratch, size_t scratch_floats,
                        void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- deep Boltzmann machine: one half-step of a layer that hears from below and from above (imdbn/models/dbm.py; Salakhutdinov &
+ *      Hinton 2009) ----------------------------------------------------------------------------------------------
+ *   pre[b][n] = s_lo sum_k x_lo[b][k] W_lo[k][n] + s_hi sum_j x_hi[b][j] W_hi[n][j] + bias[n],   p = sigmoid(pre)
+ * Raw device pointers, fp32: W_lo [K_lo][ldw_lo] (ldw_lo >= N: the lower RBM's W, the layer is its columns), W_hi [N][ldw_hi]
+ * (ldw_hi >= K_hi: the upper RBM's W, or a row block of it; the layer is its rows), x_lo [B][K_lo] (ldx_lo >= K_lo), x_hi [B][K_hi]
+ * (ldx_hi >= K_hi), bias [N].  A side is absent with x = NULL or K = 0 (its W and scale are then not read); both absent is an error.
+ * mode: IMDBN_PARITY_F32 | IMDBN_FAST_BF16 as imdbn_rbm_desc.mode; both run the same fp32 arithmetic here.
+ * Arithmetic: fp32 fused multiply-adds.  The reduction axis is [0, K_lo) ++ [0, K_hi), cut into slices of equal length (a multiple
+ * of 32 steps; a function of K_lo + K_hi, N, B and the device's CU count).  Per slice the products of each side are added in index
+ * order, the finished side sums are scaled (s_lo, s_hi meet sums, never products) and added, lo first; the slices are added in slice
+ * order by the block that arrives last (an integer counter, left at zero); then the bias.  No floating-point atomics: the same call
+ * gives the same bits.
+ *   mean field (m != NULL, s == NULL): m [B][N] (ldm >= N) is READ AND OVERWRITTEN: m <- damp m + (1 - damp) p, damp in [0, 1).
+ *     res (float [B], nullable): max_n |p - m_old| of every row, before damping.  rng is not read.
+ *   sample (s != NULL, m == NULL): s [B][N] (lds >= N) = 1[p > U], U the call's one ("u", N) draw: PHILOX keyed on (seed, draw,
+ *     row0 + b, n), REPLAY B N floats of the tape; rng->tape_used / draws_used (= 1) are filled in.  p (nullable, ldp >= N): the
+ *     probabilities.
+ * Row padding (of either W, of x, m, s, p) is neither read nor written.  Plain launches (and one memset node when the axis is split)
+ * on `stream`, no host sync, no allocation.  Workspace: 256-byte aligned, imdbn_dbm_layer_ws_bytes(K_lo, K_hi, N, B) (0 for shapes
+ * the call refuses); nothing in it needs to survive a call.
+ * IMDBN_E_INVALID (naming the value) before the first launch, nothing touched: N < 1, B < 1, a negative K, both sides absent, a null
+ * W of a present side, a null bias, a leading dimension below its row length, mode outside {0, 1}, both or neither of m / s, damp
+ * outside [0, 1) or NaN, a null rng in sample mode, a misaligned workspace; IMDBN_E_WORKSPACE: a null or short workspace;
+ * IMDBN_E_RNG: a replay tape shorter than the draw. */
+size_t imdbn_dbm_layer_ws_bytes(int K_lo, int K_hi, int N, int B);
+int imdbn_dbm_layer(const float* W_lo, int64_t ldw_lo, int K_lo, const float* x_lo, int64_t ldx_lo, float s_lo,
+                    const float* W_hi, int64_t ldw_hi, int K_hi, const float* x_hi, int64_t ldx_hi, float s_hi,
+                    const float* bias, int N, int B, int mode,
+                    float* m, int64_t ldm, float damp, float* res,
+                    imdbn_rng* rng, float* s, int64_t lds, float* p, int64_t ldp,
+                    void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- Gaussian visible units with learned variances (imdbn/models/grbm.py: GaussianRBM; Cho, Ilin & Raiko 2011) ----
  * The parameters of the descriptor plus logvar [V] (device), sigma_i^2 = exp(logvar_i); with u = v exp(-logvar):
  *     p(h_j | v) = sigmoid(c_j + (u W)_j),   p(v_i | h) = N(b_i + (h W^T)_i, sigma_i^2),

@@ -47,6 +47,7 @@
 #include "kernels_exact.hpp"
 #include "kernels_tuning.hpp"
 #include "kernels_tap.hpp"
+#include "kernels_dbm.hpp"
 
 using namespace imdbn;
 
@@ -1804,6 +1805,9 @@ int imdbn_rbm_centered_step(const imdbn_rbm_desc* d, const float* data, int64_t 
 
 // ---- extended mean field: TAP training and log Z (imdbn/utils/tap.py; kernels_tap.hpp) -----------------------------------
 #include "host_tap.hpp"
+
+// ---- deep Boltzmann machine: the two-sided layer half-step (imdbn/models/dbm.py; kernels_dbm.hpp) -------------------------
+#include "host_dbm.hpp"
 
 // ---- Gaussian visible units (imdbn/models/grbm.py; kernels_gauss.hpp) ----------------------------------------------------
 // p(h | v) is the Bernoulli engine applied to u = v e^{-z}, the mean of p(v | h) its logits path: K1 / K2 / K3 are called as they are.

@@ -770,6 +770,170 @@ class HipEngine:
                    int(n_iters), float(damp), int(order), _ptr(loss), _ptr(scratch), scratch.numel(), *self._tap_ws(dev, d.V, d.H, B))
         return loss.reshape(()) if monitor else None
 
+    # ---- deep Boltzmann machine (imdbn_dbm_layer) --------------------------------------
+    def dbm_layer(self, lo, hi, x_lo, x_hi, bias, m=None, damp=0.0, s_lo=1.0, s_hi=1.0, sample=False, rng=None, want_p=False,
+                  want_res=False):
+        """One half-step of a layer between two RBMs (imdbn_dbm_layer): ``pre = s_lo x_lo W_lo + s_hi x_hi
+        W_hi^T + bias`` with ``W_lo`` the ``W`` of ``lo`` (the layer is its hidden side) and ``W_hi`` the ``W`` of ``hi`` (the layer
+        is its visible side); either RBM may be None with its ``x`` (a one-sided form), not both.  ``bias`` ``[N]`` is the layer's.
+        Mean field (``sample=False``): ``m`` ``[B, N]`` fp32 is updated in place, ``m <- damp m + (1 - damp) sigmoid(pre)``;
+        returns the rows' ``max |sigmoid(pre) - m_old|`` (fp32 ``[B]``) with ``want_res``, else None.  Sample: one ``("u", N)``
+        draw of ``rng``; returns ``s = 1[sigmoid(pre) > U]``, or ``(p, s)`` with ``want_p``.  No host sync."""
+        return self._dbm_layer(lo, hi, x_lo, x_hi, bias, m, damp, s_lo, s_hi, sample, rng, want_p, want_res)
+
+    def _dbm_layer(self, lo, hi, x_lo, x_hi, bias, m, damp, s_lo, s_hi, sample, rng, want_p, want_res, s_out=None):
+        """``dbm_layer``; ``s_out``: an fp32 ``[B, N]`` tensor with unit inner stride that receives the samples in place of a fresh
+        one (``dbm_gibbs`` writes a layer's new state straight into its particles: a layer is never its own input)."""
+        if lo is None and hi is None:
+            raise N.EngineError("dbm_layer: needs the RBM below, the RBM above or both")
+        if bool(sample) == (m is not None):
+            raise N.EngineError("dbm_layer: mean field takes m (updated in place), sample=True takes none")
+        Wl = None if lo is None else lo.W.data
+        Wh = None if hi is None else hi.W.data
+        first = Wl if Wl is not None else Wh
+        dev = first.device
+        n = Wl.size(1) if Wl is not None else Wh.size(0)
+        for nm, W in (("lo", Wl), ("hi", Wh)):
+            if W is not None and not (W.is_cuda and W.dtype == torch.float32 and W.dim() == 2 and W.stride(1) == 1 and W.device == dev):
+                raise N.EngineError(f"dbm_layer: {nm}.W must be fp32 [V, H] with unit inner stride on {dev}")
+        if Wl is not None and Wh is not None and Wh.size(0) != n:
+            raise N.EngineError(f"dbm_layer: lo has {n} hidden units, hi has {Wh.size(0)} visible units")
+        xs = []
+        for nm, W, x, k in (("x_lo", Wl, x_lo, None if Wl is None else Wl.size(0)), ("x_hi", Wh, x_hi, None if Wh is None else Wh.size(1))):
+            if W is None:
+                xs.append(None)
+                continue
+            if x is None:
+                raise N.EngineError(f"dbm_layer: {nm} is missing")
+            x = _f32c(x)
+            if x.dim() != 2 or x.size(1) != k or x.device != dev:
+                raise N.EngineError(f"dbm_layer: {nm} must be [B, {k}] on {dev}")
+            xs.append(x)
+        xl, xh = xs
+        B = (xl if xl is not None else xh).size(0)
+        if xl is not None and xh is not None and xh.size(0) != B:
+            raise N.EngineError("dbm_layer: x_lo and x_hi need the same rows")
+        b = bias.data if isinstance(bias, torch.nn.Parameter) else bias
+        if not (isinstance(b, torch.Tensor) and b.device == dev and b.dtype == torch.float32 and b.numel() == n and b.is_contiguous()):
+            raise N.EngineError(f"dbm_layer: bias must be a contiguous fp32 [{n}] tensor on {dev}")
+        ld = lambda t: 0 if t is None else max(t.stride(0), t.size(1))
+        kl, kh = (0 if xl is None else xl.size(1)), (0 if xh is None else xh.size(1))
+        need = int(self._lib.imdbn_dbm_layer_ws_bytes(kl, kh, n, B))
+        ws = self._buffer(("dbm_ws", dev, kl, kh, n, B, torch.cuda.current_stream(dev).cuda_stream),
+                          lambda: torch.empty(max(need, 256), dtype=torch.uint8, device=dev), need)
+        res = p = smp = r = None
+        sched = [("u", n)] if sample else []
+        if sample:
+            smp = torch.empty(B, n, device=dev) if s_out is None else s_out
+            if not (smp.device == dev and smp.dtype == torch.float32 and smp.dim() == 2 and smp.size(0) == B and smp.size(1) == n
+                    and smp.stride(1) == 1 and (B == 1 or smp.stride(0) >= n)):
+                raise N.EngineError(f"dbm_layer: the sample output must be an fp32 tensor [{B}, {n}] on {dev} with unit inner stride")
+            p = torch.empty(B, n, device=dev) if want_p else None
+            r, keep = self._rng(rng, sched, B, dev)
+        else:
+            if not (isinstance(m, torch.Tensor) and m.device == dev and m.dtype == torch.float32 and m.dim() == 2 and m.size(0) == B
+                    and m.size(1) == n and m.stride(1) == 1 and (B == 1 or m.stride(0) >= n)):
+                raise N.EngineError(f"dbm_layer: m must be an fp32 tensor [{B}, {n}] on {dev} with unit inner stride (updated in place)")
+            res = torch.empty(B, device=dev) if want_res else None
+        self._call("imdbn_dbm_layer", _ptr(Wl), ld(Wl), kl, _ptr(xl), ld(xl), float(s_lo), _ptr(Wh), ld(Wh), kh, _ptr(xh), ld(xh), float(s_hi),
+                   _ptr(b), n, B, self.mode, _ptr(m), ld(m), float(damp), _ptr(res), _ref(r), _ptr(smp), ld(smp), _ptr(p), ld(p),
+                   _ptr(ws), ws.numel(), self._stream(dev))
+        if sample:
+            self._done(rng, r, sched)
+            return (p, smp) if want_p else smp
+        return res
+
+    @staticmethod
+    def _dbm_check(who: str, layers, biases):
+        L = len(layers)
+        if L < 1 or len(biases) != L + 1:
+            raise N.EngineError(f"{who}: {L} RBMs need {L + 1} layer biases, got {len(biases)}")
+        return L
+
+    def dbm_gibbs(self, layers, biases, particles, n_sweeps, rng, clamp_bottom=None):
+        """``n_sweeps`` block-Gibbs sweeps of a DBM on ``particles``, the list of its ``L + 1`` 0/1 state
+        tensors ``[M, N_l]``, in place: the odd layers given the even ones, bottom to top, then the even layers given the odd ones.
+        ``layers``: the ``L`` RBMs bottom first; ``biases``: the ``L + 1`` layer biases, ``biases[0]`` being ``layers[0].vis_bias``
+        (layer 0 goes through ``prop_down`` + ``sample_visible``, which read it there).  Draws per sweep: ``rng.sched_dbm_gibbs``.
+        With ``clamp_bottom`` ``[M, N_0]`` layer 0 is held at that tensor and draws nothing.  Returns ``particles``.  No host sync."""
+        L = self._dbm_check("dbm_gibbs", layers, biases)
+        if len(particles) != L + 1:
+            raise N.EngineError(f"dbm_gibbs: {L} RBMs need {L + 1} state tensors, got {len(particles)}")
+        if clamp_bottom is not None:
+            particles[0].copy_(clamp_bottom)
+        for _ in range(int(n_sweeps)):
+            for parity in (1, 0):
+                for l in range(parity, L + 1, 2):
+                    if l == 0:
+                        if clamp_bottom is None:
+                            particles[0].copy_(self.sample_visible(layers[0], self.prop_down(layers[0], particles[1]), rng))
+                        continue
+                    hi = layers[l] if l < L else None
+                    self._dbm_layer(layers[l - 1], hi, particles[l - 1], particles[l + 1] if l < L else None, biases[l], None, 0.0, 1.0, 1.0,
+                                    True, rng, False, False, s_out=particles[l])
+        return particles
+
+    def dbm_infer(self, layers, biases, v, n_mf, damp=0.0, init=None, want_res=True):
+        """Mean-field posterior of a DBM given the bottom layer ``v`` ``[B, N_0]``.  Start (``init`` None): the
+        bottom-up pass ``mu_l = sigmoid(s mu_{l-1} W_{l-1} + b_l)`` with ``s = 2`` below the top layer and ``s = 1`` at it
+        (Salakhutdinov & Hinton 2009, section 3.1), the one-sided form of ``dbm_layer``; else ``init``, the ``L`` tensors
+        ``[B, N_l]`` (updated in place).  Then ``n_mf`` sweeps over the layers ``1 .. L`` in order, each from its freshest
+        neighbours, damped by ``damp``.  Returns ``([mu_1 .. mu_L], res)``: ``res`` fp32 ``[B]``, the largest ``|sigmoid - mu_old|``
+        over the layers of the last sweep (zeros with ``n_mf = 0``), or None without ``want_res``.  No host sync."""
+        L = self._dbm_check("dbm_infer", layers, biases)
+        x = _f32c(v)
+        B, dev = x.size(0), x.device
+        if init is None:
+            mu = []
+            for l in range(1, L + 1):
+                m = torch.zeros(B, biases[l].numel(), device=dev)
+                self.dbm_layer(layers[l - 1], None, x if l == 1 else mu[-1], None, biases[l], m=m, s_lo=2.0 if l < L else 1.0)
+                mu.append(m)
+        else:
+            mu = list(init)
+            if len(mu) != L:
+                raise N.EngineError(f"dbm_infer: init needs {L} tensors, got {len(mu)}")
+        res = torch.zeros(B, device=dev) if want_res else None
+        for it in range(int(n_mf)):
+            last = want_res and it == int(n_mf) - 1
+            for l in range(1, L + 1):
+                r = self.dbm_layer(layers[l - 1], layers[l] if l < L else None, x if l == 1 else mu[l - 2], mu[l] if l < L else None,
+                                   biases[l], m=mu[l - 1], damp=damp, want_res=last)
+                if last:
+                    res = r if l == 1 else torch.maximum(res, r)
+        return mu, res
+
+    def dbm_step(self, layers, data, particles, epoch_scalars, n_mf, damp, gibbs_k, rng, monitor=True):
+        """One training step of a DBM (Salakhutdinov & Hinton 2009) on one stream, no host sync.  ``layers``: the
+        ``L`` RBMs bottom first; the model's biases live in them (layer 0: ``layers[0].vis_bias``, layer l >= 1:
+        ``layers[l-1].hid_bias``).  (1) ``dbm_infer`` on ``data`` (``n_mf`` sweeps, ``damp``); (2) ``gibbs_k`` sweeps of
+        ``dbm_gibbs`` on ``particles`` (``L + 1`` tensors of as many rows as ``data``, in place); (3) when every phase tensor exists,
+        one ``assoc_update`` per RBM l from ``(pos_l, pos_{l+1}, neg_l, neg_{l+1})`` -- ``pos_0 = data``, ``pos_l = mu_l``, ``neg``
+        the particles -- with ``epoch_scalars[l] = (lr, mom)``, the RBM's weight decay and no sparsity term.  The update also moves
+        ``layers[l].vis_bias`` for l >= 1, which is no parameter of the model and is never read.  Returns ``{"mu", "particles",
+        "res", "recon_loss"}``; ``recon_loss``: the mean squared error of ``sigmoid(mu_1 W_0^T + b_0)`` against the data under the
+        parameters on entry, a 0-d device tensor, or None with ``monitor=False`` (that propagation is then not launched)."""
+        from . import dp
+        if dp.active():
+            raise NotImplementedError("dbm_step has no data-parallel split")
+        L = len(layers)
+        if L < 1 or len(epoch_scalars) != L or len(particles) != L + 1:
+            raise N.EngineError(f"dbm_step: {L} RBMs need {L} (lr, mom) pairs and {L + 1} particle tensors")
+        x = _f32c(data)
+        if any(p.size(0) != x.size(0) for p in particles):
+            raise N.EngineError("dbm_step: the particles need as many rows as the data")
+        biases = [layers[0].vis_bias.data] + [r.hid_bias.data for r in layers]
+        mu, res = self.dbm_infer(layers, biases, x, n_mf, damp=damp)
+        recon = None
+        if monitor:
+            recon = (self.prop_down(layers[0], mu[0]) - x).square().mean()
+        self.dbm_gibbs(layers, biases, particles, gibbs_k, rng)
+        pos = [x] + mu
+        for l, rbm in enumerate(layers):
+            lr, mom = epoch_scalars[l]
+            self._assoc(rbm, pos[l], pos[l + 1], particles[l], particles[l + 1], lr, mom, False)
+        return {"mu": mu, "particles": particles, "res": res, "recon_loss": recon}
+
     # ---- Gaussian visible units (imdbn_rbm_gauss_*; DESIGN section 29) ---------------------------------
     @staticmethod
     def _logvar(who: str, t, n: int, dev) -> torch.Tensor:
@@ -936,10 +1100,13 @@ class HipEngine:
 
     def assoc_update(self, rbm, vpos, hpos, vneg, hneg, lr, mom):
         """The weight / bias update alone (rbm.py:209-224) from the four phase tensors (imdbn_rbm_assoc_update)."""
+        self._assoc(rbm, vpos, hpos, vneg, hneg, lr, mom, getattr(rbm, "sparsity", False))
+
+    def _assoc(self, rbm, vpos, hpos, vneg, hneg, lr, mom, sparsity):
         d = self._desc(rbm, True)
         ts = [_f32c(t) for t in (vpos, hpos, vneg, hneg)]
         B, dev = ts[0].size(0), ts[0].device
-        o = self._opts(rbm, lr, mom, 1, sparsity=getattr(rbm, "sparsity", False))
+        o = self._opts(rbm, lr, mom, 1, sparsity=sparsity)
         self._call("imdbn_rbm_assoc_update", C.byref(d), _ptr(ts[0]), ts[0].stride(0), _ptr(ts[1]), ts[1].stride(0), _ptr(ts[2]),
                    ts[2].stride(0), _ptr(ts[3]), ts[3].stride(0), B, C.byref(o), *self._ws_tail(dev, d.V, d.H, B))
 

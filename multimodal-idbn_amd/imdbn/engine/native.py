@@ -138,6 +138,9 @@ SIGNATURES = {
     "imdbn_rbm_tap_iterate": (_INT, [C.POINTER(RbmDesc), _P, _I64, _P, _I64, _INT, _INT, _F, _INT, _P, _P, _P, _SZ, _P]),
     "imdbn_rbm_tap_step": (_INT, [C.POINTER(RbmDesc), _P, _I64, _INT, _P, _I64, _P, _I64, C.POINTER(CdOpts), _INT, _F, _INT, _P, _P, _SZ,
                                   _P, _SZ, _P]),
+    "imdbn_dbm_layer_ws_bytes": (_SZ, [_INT, _INT, _INT, _INT]),
+    "imdbn_dbm_layer": (_INT, [_P, _I64, _INT, _P, _I64, _F, _P, _I64, _INT, _P, _I64, _F, _P, _INT, _INT, _INT, _P, _I64, _F, _P,
+                               C.POINTER(Rng), _P, _I64, _P, _I64, _P, _SZ, _P]),
     "imdbn_rbm_gauss_prop_up": (_INT, [C.POINTER(RbmDesc), _P, _P, _I64, _INT, _F, C.POINTER(Rng), _P, _I64, _P, _I64, _P, _SZ, _P]),
     "imdbn_rbm_gauss_prop_down": (_INT, [C.POINTER(RbmDesc), _P, _P, _I64, _INT, C.POINTER(Rng), _P, _I64, _P, _I64, _P, _SZ, _P]),
     "imdbn_rbm_gauss_sample_visible": (_INT, [C.POINTER(RbmDesc), _P, _P, _I64, _INT, C.POINTER(Rng), _P, _I64, _P]),

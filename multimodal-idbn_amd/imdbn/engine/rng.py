@@ -148,3 +148,16 @@ def sched_gauss_reverse_ais(V: int, H: int, K: int) -> Schedule:
 def sched_bound(H: int) -> Schedule:
     """imdbn_rbm_bound_step: the one draw of h ~ q(h | v)."""
     return [("u", int(H))]
+
+
+def sched_dbm_gibbs(sizes: Sequence[int], n_sweeps: int, clamp_bottom: bool = False) -> Schedule:
+    """HipEngine.dbm_gibbs on layers of ``sizes`` units (bottom first): per sweep the odd layers bottom to top, one ("u", N_l) each,
+    then the even layers bottom to top; layer 0 draws as ``sample_visible`` of a Bernoulli layer, or nothing when it is clamped."""
+    L = len(sizes) - 1
+    sweep: Schedule = [("u", int(sizes[l])) for l in range(1, L + 1, 2)]
+    for l in range(0, L + 1, 2):
+        if l == 0:
+            sweep += [] if clamp_bottom else sched_sample_visible(int(sizes[0]), [])
+        else:
+            sweep.append(("u", int(sizes[l])))
+    return int(n_sweeps) * sweep

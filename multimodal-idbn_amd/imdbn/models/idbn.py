@@ -446,6 +446,11 @@ class iDBN:
         from imdbn.utils.unit_tuning import evaluate_unit_tuning
         return evaluate_unit_tuning(self, upto_layer=upto_layer, **kw)
 
+    def to_dbm(self, **kw):
+        """This stack as a deep Boltzmann machine (``imdbn.models.dbm.DBM.from_idbn``): deep copies, this model is untouched."""
+        from imdbn.models.dbm import DBM
+        return DBM.from_idbn(self, **kw)
+
     def save_model(self, path: str):
         """idbn.py:370-372: pickle of {"layers", "params"} (live RBM modules)."""
         model_copy = {"layers": self.layers, "params": self.params}
