@@ -540,6 +540,55 @@ int imdbn_dbm_layer(const float* W_lo, int64_t ldw_lo, int K_lo, const float* x_
                     imdbn_rng* rng, float* s, int64_t lds, float* p, int64_t ldp,
                     void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- deep Boltzmann machine as a density model: annealed importance sampling over the odd layers and the layer term of the
+ *      variational bound (imdbn/utils/likelihood.py: estimate_dbm_log_partition, dbm_variational_bound; Salakhutdinov & Hinton 2009,
+ *      section 4.1) ---------------------------------------------------------------------------------------------
+ * imdbn_dbm_rowsum_layer: the operands, the arithmetic and the summation order of pre are imdbn_dbm_layer's with s_lo = s_hi = 1.
+ * Per batch row the call ADDS one double to acc[b] (float64 [B]), summed per tile of 64 units in a fixed butterfly and over the tiles
+ * in tile order by one thread per row: no floating-point atomics, the same call gives the same bits.
+ *   IMDBN_DBM_WEIGH   acc[b] += sum_n sp(e_n(beta)) - sp(e_n(beta_prev)),  e(t) = t pre + (1 - t) base_n in double from the fp32 pre
+ *                     (base [N], nullable = zeros), sp(t) = max(t, 0) + log1p(exp(-|t|)); 0 <= beta_prev < beta <= 1.  With s != NULL
+ *                     the units are also drawn at beta, as SAMPLE draws them (s NULL: the weight only, rng is not read).
+ *   IMDBN_DBM_SAMPLE  p = sigmoid(fl(fl(beta pre) + fl(fl(1 - beta) base_n))) in fp32 (base NULL: fl(beta pre)), s [B][N] = 1[p > U],
+ *                     U the call's one ("u", N) draw (PHILOX keyed on (seed, draw, row0 + b, n), or REPLAY B N floats); p nullable.
+ *                     At beta = 1 without a base, s and p are imdbn_dbm_layer's sample mode bit for bit.  acc (nullable):
+ *                     acc[b] += dbeta_next sum_n bias_n s_n.
+ *   IMDBN_DBM_BOUND   one-sided from below (K_hi = 0): acc[b] += sum_n mu[b][n] pre[b][n] + h(mu[b][n]), h the Bernoulli entropy
+ *                     (h(0) = h(1) = 0), mu [B][N] (ldmu >= N).  Here base (nullable) is the bias of the layer BELOW, [K_lo]:
+ *                     acc[b] += sum_k base_k x_lo[b][k] first (one wave per row, lane l the terms l, l + 64, .. in order, butterfly).
+ * Workspace: 256-byte aligned, imdbn_dbm_rowsum_layer_ws_bytes(K_lo, K_hi, N, B) (0 for shapes the call refuses).  Plain launches
+ * (one memset node when the axis is split), no host sync, no allocation.  Padding is neither read nor written.
+ * Errors as imdbn_dbm_layer, before the first launch, nothing touched; further IMDBN_E_INVALID: a mode outside the three, beta
+ * outside [0, 1], beta_prev outside [0, beta), a null s in SAMPLE, p without s, s or p or a hi side in BOUND, a null mu or ldmu < N
+ * in BOUND, a null acc in WEIGH / BOUND.
+ *
+ * imdbn_dbm_ais: M chains of a DBM of L + 1 layers (sizes [L + 1], W [L] device pointers with pitches ldw [L], W[l] being
+ * [sizes[l]][ldw[l]] with ldw[l] >= sizes[l + 1]; biases [L + 1] device pointers; the four arrays live on the HOST) from the base model
+ * (no weights, biases zero but layer 0's, which is base [sizes[0]], nullable = zeros) through betas [K + 1] (host; 0 = betas[0] < ..
+ * < betas[K] = 1).  The state is the odd layers; the even ones are summed out.  Start: odd layers 1[0.5 > U], one ("u", N_l) each,
+ * bottom first.  For k = 1 .. K: logw[m] += (beta_k - beta_{k-1}) sum_{l odd} b_l s_l + sum_{l even} WEIGH_l(beta_k, beta_{k-1}); for
+ * k < K the transition at beta_k: every even layer bottom to top (drawn inside its WEIGH pass), then every odd layer bottom to top
+ * from the new even states.  Draws: M sum_{l odd} N_l + (K - 1) M sum_l N_l floats (imdbn/engine/rng.py: sched_dbm_ais).
+ * log Z ~= sum_{l >= 1} N_l log 2 + sum_i sp(base_i) + logmeanexp(logw).  logw: float64 [M], written.  out_s (nullable): a host array
+ * of L + 1 device pointers read at the odd entries only; a non-null entry l receives the final state of layer l, [M][ld_out[l]].
+ * One memset node and plain launches on `stream`, no host sync, no allocation; workspace imdbn_dbm_ais_ws_bytes(L, sizes, M).
+ * The argument checks are those of imdbn_rbm_ais, in its words, and run before the first launch. */
+#define IMDBN_DBM_WEIGH 0
+#define IMDBN_DBM_SAMPLE 1
+#define IMDBN_DBM_BOUND 2
+#define IMDBN_DBM_MAX_LAYERS 16
+size_t imdbn_dbm_rowsum_layer_ws_bytes(int K_lo, int K_hi, int N, int B);
+int imdbn_dbm_rowsum_layer(const float* W_lo, int64_t ldw_lo, int K_lo, const float* x_lo, int64_t ldx_lo,
+                           const float* W_hi, int64_t ldw_hi, int K_hi, const float* x_hi, int64_t ldx_hi,
+                           const float* bias, int N, int B, int mode, float beta, float beta_prev, double dbeta_next,
+                           const float* base, const float* mu, int64_t ldmu,
+                           imdbn_rng* rng, float* s, int64_t lds, float* p, int64_t ldp, double* acc,
+                           void* ws, size_t ws_bytes, imdbn_stream_t stream);
+size_t imdbn_dbm_ais_ws_bytes(int L, const int* sizes, int M);
+int imdbn_dbm_ais(int L, const float* const* W, const int64_t* ldw, const int* sizes, const float* const* biases, const float* base,
+                  const float* betas, int K, int M, imdbn_rng* rng, double* logw, float* const* out_s, const int64_t* ld_out,
+                  void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- Gaussian visible units with learned variances (imdbn/models/grbm.py: GaussianRBM; Cho, Ilin & Raiko 2011) ----
  * The parameters of the descriptor plus logvar [V] (device), sigma_i^2 = exp(logvar_i); with u = v exp(-logvar):
  *     p(h_j | v) = sigmoid(c_j + (u W)_j),   p(v_i | h) = N(b_i + (h W^T)_i, sigma_i^2),

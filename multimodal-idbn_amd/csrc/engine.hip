@@ -48,6 +48,7 @@
 #include "kernels_tuning.hpp"
 #include "kernels_tap.hpp"
 #include "kernels_dbm.hpp"
+#include "kernels_dbm_ais.hpp"
 
 using namespace imdbn;
 
@@ -1808,6 +1809,9 @@ int imdbn_rbm_centered_step(const imdbn_rbm_desc* d, const float* data, int64_t 
 
 // ---- deep Boltzmann machine: the two-sided layer half-step (imdbn/models/dbm.py; kernels_dbm.hpp) -------------------------
 #include "host_dbm.hpp"
+
+// ---- deep Boltzmann machine: AIS log Z and the variational bound (imdbn/utils/likelihood.py; kernels_dbm_ais.hpp) ----------
+#include "host_dbm_ais.hpp"
 
 // ---- Gaussian visible units (imdbn/models/grbm.py; kernels_gauss.hpp) ----------------------------------------------------
 // p(h | v) is the Bernoulli engine applied to u = v e^{-z}, the mean of p(v | h) its logits path: K1 / K2 / K3 are called as they are.

@@ -9,6 +9,8 @@
 //                          owns the slice [g0, g1) of that axis; it streams the lo part of the slice (units are columns), then the
 //                          hi part (units are rows, transposed through LDS), DBM_KC steps at a time.  Wave w owns the batch rows
 //                          16 w .. 16 w + 15 of the chunk, a lane one output unit.
+//   dbm_pre_tile           everything of that kernel up to its epilogue, as one device function: dbm_rowsum_layer
+//                          (kernels_dbm_ais.hpp) runs the same block, split and summation order under another epilogue.
 //   dbm_rows_finish        one thread per batch row: the row's residual, the maximum over the tiles.
 //
 // Arithmetic: fp32 vector FMAs (not the bf16x3 MFMA split), one fused multiply-add per product.  Summation order of one output:
@@ -96,11 +98,11 @@ __device__ __forceinline__ void dbm_side(float (&acc)[16], float* s_w, float* s_
     }
 }
 
-template <bool SAMPLE>
-__global__ __launch_bounds__(256) void dbm_layer(const DbmLayerArgs a) {
-    __shared__ float s_w[DBM_KC * DBM_LDW];
-    __shared__ __attribute__((aligned(16))) float s_x[DBM_BM * DBM_KC];
-    __shared__ int s_last;
+// The pre-activation sums of the block's tile, without the bias: acc[r] = sum over the slices of t_q (header) for the unit n0 + lane and
+// the rows b0 + 16 w + r.  `A` carries the operand and split-K fields of DbmLayerArgs under the same names.  False: another block is
+// the last arriver of this tile and this one is done (ks > 1); every thread of the block gets the same answer.
+template <class A>
+__device__ __forceinline__ bool dbm_pre_tile(const A& a, float (&acc)[16], float* s_w, float* s_x, int* s_last) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int tile = blockIdx.x, sl = blockIdx.y, z = blockIdx.z;
     const int n0 = tile * DBM_TN, b0 = z * DBM_BM;
@@ -110,7 +112,7 @@ __global__ __launch_bounds__(256) void dbm_layer(const DbmLayerArgs a) {
     const int lo_b = min(g0, a.K_lo), lo_e = min(g1, a.K_lo);
     const int hi_b = max(g0, a.K_lo) - a.K_lo, hi_e = max(g1, a.K_lo) - a.K_lo;
 
-    float acc[16], t[16];
+    float t[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     dbm_side<true>(acc, s_w, s_x, a.W_lo, a.ldw_lo, a.x_lo, a.ldx_lo, lo_b, lo_e, n0, a.N, b0, a.B);
@@ -130,9 +132,9 @@ __global__ __launch_bounds__(256) void dbm_layer(const DbmLayerArgs a) {
         for (int r = 0; r < 16; ++r) __hip_atomic_store(mine + r * DBM_TN, __float_as_uint(acc[r]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");      // every storing wave drains before the counter add
         int* cnt = a.counters + z * a.ntiles + tile;
-        if (tid == 0) s_last = (__hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.ks - 1) ? 1 : 0;
+        if (tid == 0) *s_last = (__hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.ks - 1) ? 1 : 0;
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (!s_last) return;
+        if (!*s_last) return false;
         if (tid == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // zero again for the next launch
         const gu32* p0 = (const gu32*)(a.slabs + (zt + tile) * TILE) + (16 * w) * DBM_TN + lane;
         for (int q = 0; q < a.ks; ++q) {
@@ -143,6 +145,19 @@ __global__ __launch_bounds__(256) void dbm_layer(const DbmLayerArgs a) {
             for (int r = 0; r < 16; ++r) acc[r] = q == 0 ? t[r] : acc[r] + t[r];
         }
     }
+    return true;
+}
+
+template <bool SAMPLE>
+__global__ __launch_bounds__(256) void dbm_layer(const DbmLayerArgs a) {
+    __shared__ float s_w[DBM_KC * DBM_LDW];
+    __shared__ __attribute__((aligned(16))) float s_x[DBM_BM * DBM_KC];
+    __shared__ int s_last;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tile = blockIdx.x, z = blockIdx.z;
+    const int n0 = tile * DBM_TN, b0 = z * DBM_BM;
+    float acc[16];
+    if (!dbm_pre_tile(a, acc, s_w, s_x, &s_last)) return;
 
     // ---- epilogue: lane = output unit n, rows 16 w .. 16 w + 15 of the chunk
     const int n = n0 + lane;

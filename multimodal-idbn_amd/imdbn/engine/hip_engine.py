@@ -781,13 +781,12 @@ class HipEngine:
         draw of ``rng``; returns ``s = 1[sigmoid(pre) > U]``, or ``(p, s)`` with ``want_p``.  No host sync."""
         return self._dbm_layer(lo, hi, x_lo, x_hi, bias, m, damp, s_lo, s_hi, sample, rng, want_p, want_res)
 
-    def _dbm_layer(self, lo, hi, x_lo, x_hi, bias, m, damp, s_lo, s_hi, sample, rng, want_p, want_res, s_out=None):
-        """``dbm_layer``; ``s_out``: an fp32 ``[B, N]`` tensor with unit inner stride that receives the samples in place of a fresh
-        one (``dbm_gibbs`` writes a layer's new state straight into its particles: a layer is never its own input)."""
+    @staticmethod
+    def _dbm_operands(who: str, lo, hi, x_lo, x_hi, bias):
+        """The checked operands of a DBM layer call: ``(dev, n, B, Wl, Wh, xl, xh, b, kl, kh, ld)``; ``ld(t)``: the pitch of an optional
+        tensor (0 for None)."""
         if lo is None and hi is None:
-            raise N.EngineError("dbm_layer: needs the RBM below, the RBM above or both")
-        if bool(sample) == (m is not None):
-            raise N.EngineError("dbm_layer: mean field takes m (updated in place), sample=True takes none")
+            raise N.EngineError(f"{who}: needs the RBM below, the RBM above or both")
         Wl = None if lo is None else lo.W.data
         Wh = None if hi is None else hi.W.data
         first = Wl if Wl is not None else Wh
@@ -795,29 +794,37 @@ class HipEngine:
         n = Wl.size(1) if Wl is not None else Wh.size(0)
         for nm, W in (("lo", Wl), ("hi", Wh)):
             if W is not None and not (W.is_cuda and W.dtype == torch.float32 and W.dim() == 2 and W.stride(1) == 1 and W.device == dev):
-                raise N.EngineError(f"dbm_layer: {nm}.W must be fp32 [V, H] with unit inner stride on {dev}")
+                raise N.EngineError(f"{who}: {nm}.W must be fp32 [V, H] with unit inner stride on {dev}")
         if Wl is not None and Wh is not None and Wh.size(0) != n:
-            raise N.EngineError(f"dbm_layer: lo has {n} hidden units, hi has {Wh.size(0)} visible units")
+            raise N.EngineError(f"{who}: lo has {n} hidden units, hi has {Wh.size(0)} visible units")
         xs = []
         for nm, W, x, k in (("x_lo", Wl, x_lo, None if Wl is None else Wl.size(0)), ("x_hi", Wh, x_hi, None if Wh is None else Wh.size(1))):
             if W is None:
                 xs.append(None)
                 continue
             if x is None:
-                raise N.EngineError(f"dbm_layer: {nm} is missing")
+                raise N.EngineError(f"{who}: {nm} is missing")
             x = _f32c(x)
             if x.dim() != 2 or x.size(1) != k or x.device != dev:
-                raise N.EngineError(f"dbm_layer: {nm} must be [B, {k}] on {dev}")
+                raise N.EngineError(f"{who}: {nm} must be [B, {k}] on {dev}")
             xs.append(x)
         xl, xh = xs
         B = (xl if xl is not None else xh).size(0)
         if xl is not None and xh is not None and xh.size(0) != B:
-            raise N.EngineError("dbm_layer: x_lo and x_hi need the same rows")
+            raise N.EngineError(f"{who}: x_lo and x_hi need the same rows")
         b = bias.data if isinstance(bias, torch.nn.Parameter) else bias
         if not (isinstance(b, torch.Tensor) and b.device == dev and b.dtype == torch.float32 and b.numel() == n and b.is_contiguous()):
-            raise N.EngineError(f"dbm_layer: bias must be a contiguous fp32 [{n}] tensor on {dev}")
+            raise N.EngineError(f"{who}: bias must be a contiguous fp32 [{n}] tensor on {dev}")
         ld = lambda t: 0 if t is None else max(t.stride(0), t.size(1))
         kl, kh = (0 if xl is None else xl.size(1)), (0 if xh is None else xh.size(1))
+        return dev, n, B, Wl, Wh, xl, xh, b, kl, kh, ld
+
+    def _dbm_layer(self, lo, hi, x_lo, x_hi, bias, m, damp, s_lo, s_hi, sample, rng, want_p, want_res, s_out=None):
+        """``dbm_layer``; ``s_out``: an fp32 ``[B, N]`` tensor with unit inner stride that receives the samples in place of a fresh
+        one (``dbm_gibbs`` writes a layer's new state straight into its particles: a layer is never its own input)."""
+        if bool(sample) == (m is not None):
+            raise N.EngineError("dbm_layer: mean field takes m (updated in place), sample=True takes none")
+        dev, n, B, Wl, Wh, xl, xh, b, kl, kh, ld = self._dbm_operands("dbm_layer", lo, hi, x_lo, x_hi, bias)
         need = int(self._lib.imdbn_dbm_layer_ws_bytes(kl, kh, n, B))
         ws = self._buffer(("dbm_ws", dev, kl, kh, n, B, torch.cuda.current_stream(dev).cuda_stream),
                           lambda: torch.empty(max(need, 256), dtype=torch.uint8, device=dev), need)
@@ -933,6 +940,114 @@ class HipEngine:
             lr, mom = epoch_scalars[l]
             self._assoc(rbm, pos[l], pos[l + 1], particles[l], particles[l + 1], lr, mom, False)
         return {"mu": mu, "particles": particles, "res": res, "recon_loss": recon}
+
+    # ---- the DBM as a density model (imdbn_dbm_rowsum_layer, imdbn_dbm_ais) ------------
+    _DBM_MODES = {"weigh": N.DBM_WEIGH, "sample": N.DBM_SAMPLE, "bound": N.DBM_BOUND}
+
+    def dbm_rowsum_layer(self, lo, hi, x_lo, x_hi, bias, mode, acc=None, beta=1.0, beta_prev=0.0, dbeta_next=0.0, base=None, mu=None,
+                         sample=True, rng=None, want_p=False, s_out=None):
+        """One layer of a DBM with a row sum for its epilogue (imdbn_dbm_rowsum_layer); the operands and
+        ``pre`` are ``dbm_layer``'s with ``s_lo = s_hi = 1``.  ``acc``: a float64 ``[B]`` device tensor the call ADDS to (None: a
+        fresh one of zeros, except in ``"sample"`` mode, which then sums nothing).  ``mode``:
+        ``"weigh"``  ``acc += sum_n sp(e_n(beta)) - sp(e_n(beta_prev))``, ``e(t) = t pre + (1 - t) base`` (``base`` ``[N]``, None =
+        zeros); with ``sample`` the units are also drawn at ``beta`` (one ``("u", N)`` draw of ``rng``).
+        ``"sample"`` ``s = 1[sigmoid(beta pre + (1 - beta) base) > U]``; ``acc += dbeta_next sum_n bias_n s_n``.
+        ``"bound"``  from below only (``hi`` None): ``acc += sum_n mu_n pre_n + h(mu_n)`` for the magnetisations ``mu`` ``[B, N]``;
+        here ``base`` is the bias of the layer BELOW, whose ``sum_k base_k x_lo[., k]`` is added too.
+        Returns ``(acc, s, p)``: ``s`` the drawn states (``s_out`` when given) and ``p`` their probabilities with ``want_p``, None
+        where nothing was drawn.  No host sync."""
+        if mode not in self._DBM_MODES:
+            raise N.EngineError(f"dbm_rowsum_layer: mode must be one of {sorted(self._DBM_MODES)}, got {mode!r}")
+        dev, n, B, Wl, Wh, xl, xh, b, kl, kh, ld = self._dbm_operands("dbm_rowsum_layer", lo, hi, x_lo, x_hi, bias)
+        draws = mode == "sample" or (mode == "weigh" and bool(sample))
+        if mode == "bound" and (Wh is not None or mu is None):
+            raise N.EngineError("dbm_rowsum_layer: the bound is one-sided from below and needs mu")
+        nb = kl if mode == "bound" else n
+        bA = _on(base, dev, torch.float32)
+        if bA is not None and bA.numel() != nb:
+            raise N.EngineError(f"dbm_rowsum_layer: base must have {nb} elements")
+        if mu is not None:
+            mu = _f32c(mu)
+            if mu.dim() != 2 or mu.size(0) != B or mu.size(1) != n or mu.device != dev:
+                raise N.EngineError(f"dbm_rowsum_layer: mu must be [{B}, {n}] on {dev}")
+        if acc is None and mode != "sample":
+            acc = torch.zeros(B, dtype=torch.float64, device=dev)
+        if acc is not None and not (acc.device == dev and acc.dtype == torch.float64 and acc.numel() == B and acc.is_contiguous()):
+            raise N.EngineError(f"dbm_rowsum_layer: acc must be a contiguous float64 [{B}] tensor on {dev}")
+        need = int(self._lib.imdbn_dbm_rowsum_layer_ws_bytes(kl, kh, n, B))
+        ws = self._buffer(("dbm_rowsum_ws", dev, kl, kh, n, B, torch.cuda.current_stream(dev).cuda_stream),
+                          lambda: torch.empty(max(need, 256), dtype=torch.uint8, device=dev), need)
+        smp = p = r = None
+        sched = [("u", n)] if draws else []
+        if draws:
+            smp = torch.empty(B, n, device=dev) if s_out is None else s_out
+            if not (smp.device == dev and smp.dtype == torch.float32 and smp.dim() == 2 and smp.size(0) == B and smp.size(1) == n
+                    and smp.stride(1) == 1 and (B == 1 or smp.stride(0) >= n)):
+                raise N.EngineError(f"dbm_rowsum_layer: the sample output must be an fp32 tensor [{B}, {n}] on {dev} with unit inner stride")
+            p = torch.empty(B, n, device=dev) if want_p else None
+            r, keep = self._rng(rng, sched, B, dev)
+        self._call("imdbn_dbm_rowsum_layer", _ptr(Wl), ld(Wl), kl, _ptr(xl), ld(xl), _ptr(Wh), ld(Wh), kh, _ptr(xh), ld(xh), _ptr(b), n, B,
+                   self._DBM_MODES[mode], float(beta), float(beta_prev), float(dbeta_next), _ptr(bA), _ptr(mu), ld(mu), _ref(r),
+                   _ptr(smp), ld(smp), _ptr(p), ld(p), _ptr(acc), _ptr(ws), ws.numel(), self._stream(dev))
+        if draws:
+            self._done(rng, r, sched)
+        return acc, smp, p
+
+    def dbm_ais(self, layers, biases, betas, n_chains: int, rng, base_bias: Optional[torch.Tensor] = None, return_state: bool = False):
+        """Annealed importance sampling of a DBM over its odd layers, the even ones summed out (imdbn_dbm_ais; Salakhutdinov &
+        Hinton 2009, section 4.1): ``n_chains`` chains from the base model (no weights, zero biases but layer
+        0's ``base_bias``, None = zeros) through ``betas`` (0 = betas[0] < ... < betas[K] = 1) in ONE call.  Returns the log
+        importance weights, a float64 device tensor ``[n_chains]`` (and the final states of the odd layers, bottom first, with
+        ``return_state``); log Z ~= sum_{l >= 1} N_l log 2 + sum softplus(base_bias) + logmeanexp(logw).  Draws:
+        ``rng.sched_dbm_ais``.  No host sync."""
+        L = self._dbm_check("dbm_ais", layers, biases)
+        if L > N.DBM_MAX_LAYERS:
+            raise N.EngineError(f"dbm_ais: at most {N.DBM_MAX_LAYERS} RBMs, got {L}")
+        Ws = [r.W.data for r in layers]
+        dev = Ws[0].device
+        sizes = [Ws[0].size(0)] + [W.size(1) for W in Ws]
+        bs = [b.data if isinstance(b, torch.nn.Parameter) else b for b in biases]
+        for l, W in enumerate(Ws):
+            if not (W.is_cuda and W.dtype == torch.float32 and W.dim() == 2 and W.stride(1) == 1 and W.device == dev and W.size(0) == sizes[l]):
+                raise N.EngineError(f"dbm_ais: layers[{l}].W must be fp32 [{sizes[l]}, H] with unit inner stride on {dev}")
+        for l, b in enumerate(bs):
+            if not (isinstance(b, torch.Tensor) and b.device == dev and b.dtype == torch.float32 and b.numel() == sizes[l] and b.is_contiguous()):
+                raise N.EngineError(f"dbm_ais: biases[{l}] must be a contiguous fp32 [{sizes[l]}] tensor on {dev}")
+        bt = [float(x) for x in (betas.tolist() if hasattr(betas, "tolist") else betas)]
+        K, M = len(bt) - 1, int(n_chains)
+        arr = (C.c_float * max(1, len(bt)))(*bt)
+        bA = _on(base_bias, dev, torch.float32)
+        if bA is not None and bA.numel() != sizes[0]:
+            raise N.EngineError(f"dbm_ais: base_bias must have {sizes[0]} elements")
+        logw = torch.empty(max(M, 1), dtype=torch.float64, device=dev)
+        states = [torch.empty(max(M, 1), sizes[l], device=dev) if return_state and l % 2 == 1 else None for l in range(L + 1)]
+        csz = (C.c_int * (L + 1))(*sizes)
+        need = int(self._lib.imdbn_dbm_ais_ws_bytes(L, csz, max(M, 1)))
+        ws = self._buffer(("dbm_ais_ws", dev, tuple(sizes), M, torch.cuda.current_stream(dev).cuda_stream),
+                          lambda: torch.empty(max(need, 256), dtype=torch.uint8, device=dev), need)
+        sched = R.sched_dbm_ais(sizes, max(K, 1))
+        r, keep = self._rng(rng, sched, max(M, 1), dev)
+        ptrs = lambda ts, n: (C.c_void_p * n)(*[None if t is None else t.data_ptr() for t in ts])
+        self._call("imdbn_dbm_ais", L, ptrs(Ws, L), (C.c_int64 * L)(*[max(W.stride(0), W.size(1)) for W in Ws]), csz, ptrs(bs, L + 1),
+                   _ptr(bA), arr, K, M, C.byref(r), _ptr(logw), ptrs(states, L + 1), (C.c_int64 * (L + 1))(*sizes), _ptr(ws), ws.numel(),
+                   self._stream(dev))
+        self._done(rng, r, sched)
+        return (logw, [s for s in states if s is not None]) if return_state else logw
+
+    def dbm_bound(self, layers, biases, v, mus):
+        """``b_0 v + sum_{l >= 1} sum_n mu_{l,n} (mu_{l-1} W_{l-1} + b_l)_n + h(mu_{l,n})`` per row of ``v`` ``[B, N_0]``, ``mu_0 = v``:
+        the variational bound on log p(v) of a DBM for the factorised posterior ``mus`` (``L`` tensors, as ``dbm_infer`` returns
+        them) WITHOUT its ``- log Z``.  ``L`` ``dbm_rowsum_layer`` calls in bound mode on one float64 ``[B]``
+        accumulator.  No host sync."""
+        L = self._dbm_check("dbm_bound", layers, biases)
+        if len(mus) != L:
+            raise N.EngineError(f"dbm_bound: {L} RBMs need {L} magnetisation tensors, got {len(mus)}")
+        x = _f32c(v)
+        acc = None
+        for l in range(1, L + 1):
+            acc, _, _ = self.dbm_rowsum_layer(layers[l - 1], None, x if l == 1 else mus[l - 2], None, biases[l], "bound", acc=acc,
+                                              base=biases[0] if l == 1 else None, mu=mus[l - 1])
+        return acc
 
     # ---- Gaussian visible units (imdbn_rbm_gauss_*; DESIGN section 29) ---------------------------------
     @staticmethod

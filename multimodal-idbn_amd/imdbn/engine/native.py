@@ -13,6 +13,8 @@ MAX_GROUPS = 4
 ABI_VERSION = 4
 PARITY_F32, FAST_BF16 = 0, 1
 RNG_PHILOX, RNG_REPLAY = 0, 1
+DBM_WEIGH, DBM_SAMPLE, DBM_BOUND = 0, 1, 2                  # imdbn_dbm_rowsum_layer (IMDBN_DBM_*)
+DBM_MAX_LAYERS = 16
 BOUND_ENTROPY, BOUND_LOGQ = 0, 1                      # imdbn_rbm_bound_step mode (IMDBN_BOUND_*)
 DELTA_UP, DELTA_DOWN = 0, 1                           # imdbn_rbm_delta_step dir (IMDBN_DELTA_*)
 DATA_UNKNOWN, DATA_BINARY, DATA_REAL = 0, 1, 2      # imdbn_cd_opts.data_binary / next_binary (IMDBN_DATA_*)
@@ -141,6 +143,12 @@ SIGNATURES = {
     "imdbn_dbm_layer_ws_bytes": (_SZ, [_INT, _INT, _INT, _INT]),
     "imdbn_dbm_layer": (_INT, [_P, _I64, _INT, _P, _I64, _F, _P, _I64, _INT, _P, _I64, _F, _P, _INT, _INT, _INT, _P, _I64, _F, _P,
                                C.POINTER(Rng), _P, _I64, _P, _I64, _P, _SZ, _P]),
+    "imdbn_dbm_rowsum_layer_ws_bytes": (_SZ, [_INT, _INT, _INT, _INT]),
+    "imdbn_dbm_rowsum_layer": (_INT, [_P, _I64, _INT, _P, _I64, _P, _I64, _INT, _P, _I64, _P, _INT, _INT, _INT, _F, _F, C.c_double, _P, _P, _I64,
+                                      C.POINTER(Rng), _P, _I64, _P, _I64, _P, _P, _SZ, _P]),
+    "imdbn_dbm_ais_ws_bytes": (_SZ, [_INT, C.POINTER(_INT), _INT]),
+    "imdbn_dbm_ais": (_INT, [_INT, C.POINTER(_P), C.POINTER(_I64), C.POINTER(_INT), C.POINTER(_P), _P, C.POINTER(_F), _INT, _INT,
+                             C.POINTER(Rng), _P, C.POINTER(_P), C.POINTER(_I64), _P, _SZ, _P]),
     "imdbn_rbm_gauss_prop_up": (_INT, [C.POINTER(RbmDesc), _P, _P, _I64, _INT, _F, C.POINTER(Rng), _P, _I64, _P, _I64, _P, _SZ, _P]),
     "imdbn_rbm_gauss_prop_down": (_INT, [C.POINTER(RbmDesc), _P, _P, _I64, _INT, C.POINTER(Rng), _P, _I64, _P, _I64, _P, _SZ, _P]),
     "imdbn_rbm_gauss_sample_visible": (_INT, [C.POINTER(RbmDesc), _P, _P, _I64, _INT, C.POINTER(Rng), _P, _I64, _P]),

@@ -161,3 +161,13 @@ def sched_dbm_gibbs(sizes: Sequence[int], n_sweeps: int, clamp_bottom: bool = Fa
         else:
             sweep.append(("u", int(sizes[l])))
     return int(n_sweeps) * sweep
+
+
+def sched_dbm_ais(sizes: Sequence[int], K: int) -> Schedule:
+    """imdbn_dbm_ais over K temperatures on layers of ``sizes`` units (bottom first): the start state, one ("u", N_l) per odd layer
+    bottom to top, then one transition per temperature but the last: the even layers bottom to top, then the odd layers bottom to
+    top."""
+    L = len(sizes) - 1
+    odd: Schedule = [("u", int(sizes[l])) for l in range(1, L + 1, 2)]
+    even: Schedule = [("u", int(sizes[l])) for l in range(0, L + 1, 2)]
+    return odd + (int(K) - 1) * (even + odd)

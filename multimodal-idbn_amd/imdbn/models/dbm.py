@@ -119,6 +119,17 @@ class DBM:
         mu, _ = self.infer(v, n_mf, damp)
         return self._eng().prop_down(self.layers[0], mu[0])
 
+    # ---- the density model (imdbn.utils.likelihood) ------------------------------------------------------------
+    def log_partition(self, **ais_kwargs) -> dict:
+        """``imdbn.utils.likelihood.estimate_dbm_log_partition(self, **ais_kwargs)``: AIS over the odd layers."""
+        from imdbn.utils.likelihood import estimate_dbm_log_partition
+        return estimate_dbm_log_partition(self, **ais_kwargs)
+
+    def log_likelihood_bound(self, v: torch.Tensor, log_z, n_mf: int = 10, damp: float = 0.0) -> torch.Tensor:
+        """``imdbn.utils.likelihood.dbm_variational_bound``: the mean-field lower bound on log p(v) per row, float64 ``[B]``."""
+        from imdbn.utils.likelihood import dbm_variational_bound
+        return dbm_variational_bound(self, v, log_z, n_mf=n_mf, damp=damp)
+
     # ---- particles ----------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def init_particles(self, data: torch.Tensor) -> List[torch.Tensor]:

@@ -92,6 +92,12 @@ log Z and, on request, the exact model marginals p(v_i = 1) / E[v_i] and p(h_j =
 ``chain_marginal_gap`` compares the column means of a PCD or tempering particle cloud with the exact visible marginals.  ``max_bits``
 (24) guards the cost of 2^n states times the other side's width.
 
+The deep Boltzmann machine (``imdbn.models.DBM``): its layers are joined by undirected weights, so none of the stack
+figures above describes it.  ``estimate_dbm_log_partition`` is the AIS of Salakhutdinov & Hinton (2009, section 4.1): the chains live
+on the odd layers, the even layers are summed out analytically, ONE ``HipEngine.dbm_ais`` call (imdbn_dbm_ais);
+``dbm_variational_bound`` is the mean-field lower bound on log p(v) (``HipEngine.dbm_infer``, then ``HipEngine.dbm_bound``) and
+``evaluate_dbm_log_likelihood`` its mean over a loader.  Bernoulli layers only.
+
 Data parallelism: the chains are NOT sharded over ranks -- every rank that calls runs all ``n_chains`` chains and gets the same
 estimate (same seed) or an independent one; sharding the chains is a follow-up.
 """
@@ -116,7 +122,8 @@ __all__ = ["base_rate_bias", "linear_betas", "estimate_log_partition", "log_like
            "gaussian_reverse_ais_log_likelihood", "evaluate_gaussian_log_likelihood_sandwich", "gaussian_dbn_conservative_bound",
            "evaluate_gaussian_dbn_bound_conservative",
            "exact_log_partition", "exact_gaussian_log_partition", "evaluate_log_likelihood_exact",
-           "evaluate_gaussian_log_likelihood_exact", "ais_calibration", "gaussian_ais_calibration", "chain_marginal_gap"]
+           "evaluate_gaussian_log_likelihood_exact", "ais_calibration", "gaussian_ais_calibration", "chain_marginal_gap",
+           "estimate_dbm_log_partition", "dbm_variational_bound", "evaluate_dbm_log_likelihood"]
 
 
 def _bottom(model):
@@ -1028,3 +1035,71 @@ def chain_marginal_gap(rbm, particles: torch.Tensor, max_bits: int = 24) -> dict
     want = exact_log_partition(rbm, max_bits=max_bits, marginals=True)["vis_mean"].double()
     gap = rows_on_device(particles, want.device).double().mean(0) - want
     return {"max_gap": gap.abs().max(), "rms_gap": gap.pow(2).mean().sqrt()}
+
+
+# ---- the deep Boltzmann machine (imdbn.models.DBM) -----------------------------------------------------------------
+def _check_dbm(who: str, dbm):
+    """The refusals of ``DBM.from_idbn``, for a model that was changed after its conversion; no data-parallel split."""
+    from imdbn.models.grbm import GaussianRBM
+    for l, r in enumerate(dbm.layers):
+        if isinstance(r, GaussianRBM):
+            raise ValueError(f"{who}: layer {l} is a GaussianRBM; a DBM has Bernoulli units only (DESIGN section 40)")
+        if getattr(r, "softmax_groups", None):
+            raise ValueError(f"{who}: layer {l} has softmax groups; a DBM has Bernoulli units only (DESIGN section 40)")
+    if _E.dp.active():
+        raise NotImplementedError(f"{who} has no data-parallel split")
+
+
+def _dbm_log_z_base(dbm, base_bias, dev) -> torch.Tensor:
+    """log Z_A of the DBM's base model (float64 scalar on ``dev``): sum_{l >= 1} N_l log 2 + sum_i softplus(a_i)."""
+    sizes = dbm.sizes
+    a = torch.zeros(sizes[0], dtype=torch.float64, device=dev) if base_bias is None else base_bias.to(dev).double().reshape(-1)
+    if a.numel() != sizes[0]:
+        raise ValueError(f"base_bias must have {sizes[0]} elements")
+    return torch.nn.functional.softplus(a).sum() + sum(sizes[1:]) * math.log(2.0)
+
+
+@torch.no_grad()
+def estimate_dbm_log_partition(dbm, n_chains: int = 256, n_betas: int = 1000, betas=None, base_bias: Optional[torch.Tensor] = None,
+                               seed: Optional[int] = None) -> dict:
+    """AIS estimate of log Z of a ``DBM`` (Salakhutdinov & Hinton 2009, section 4.1): the chains live on the odd layers, the even
+    layers -- layer 0 included -- are summed out analytically, and the base model A has no weights, zero biases above layer 0 and
+    ``base_bias`` on layer 0 (None = zeros; ``base_rate_bias`` of the data is the usual choice).  The whole run is ONE
+    ``HipEngine.dbm_ais`` call (imdbn_dbm_ais).  The dict is ``estimate_log_partition``'s; one device-to-host
+    copy; ``seed`` as in the module docstring."""
+    _check_dbm("estimate_dbm_log_partition", dbm)
+    betas = linear_betas(n_betas) if betas is None else betas
+    lzb = _dbm_log_z_base(dbm, base_bias, dbm.layers[0].W.device)      # (first: it refuses a base_bias of the wrong length)
+    logw = dbm._eng().dbm_ais(dbm.layers, dbm.biases(), betas, int(n_chains), _draws(seed), base_bias=base_bias)
+    return _weight_stats(logw, lzb)
+
+
+@torch.no_grad()
+def dbm_variational_bound(dbm, v: torch.Tensor, log_z, n_mf: int = 10, damp: float = 0.0) -> torch.Tensor:
+    """The mean-field lower bound on log p(v) of a ``DBM`` per row, a float64 device tensor ``[B]``: with ``mu`` the posterior of
+    ``dbm.infer(v, n_mf, damp)`` and ``mu_0 = v``, ``b_0 v + sum_{l >= 1} sum_n mu_{l,n} (mu_{l-1} W_{l-1} + b_l)_n + h(mu_{l,n})
+    - log Z`` (``HipEngine.dbm_bound``).  It holds for ANY ``mu``, so more sweeps only tighten it; with an AIS ``log_z`` the figure
+    is as optimistic as that estimate.  No host sync."""
+    _check_dbm("dbm_variational_bound", dbm)
+    x = rows_on_device(v, dbm.device)
+    eng = dbm._eng()
+    mu, _ = eng.dbm_infer(dbm.layers, dbm.biases(), x, int(n_mf), damp=float(damp), want_res=False)
+    return eng.dbm_bound(dbm.layers, dbm.biases(), x, mu) - log_z
+
+
+@torch.no_grad()
+def evaluate_dbm_log_likelihood(dbm, loader=None, log_z: Optional[float] = None, max_batches: Optional[int] = None, n_mf: int = 10,
+                                damp: float = 0.0, **ais_kwargs) -> Optional[dict]:
+    """Mean held-out variational bound of a ``DBM`` over ``loader`` (default ``dbm.val_loader``, then ``dbm.dataloader``; None
+    without one): ``mean_bound``, ``sum_bound``, ``n``, ``log_z``, ``se``, ``ess`` (the last two None when ``log_z`` was passed in
+    instead of estimated with ``estimate_dbm_log_partition(**ais_kwargs)``).  Summed on the device, ONE host sync after the last
+    batch; with a ``wandb_run`` on the model the scalars are logged as ``ll/dbm_...``."""
+    _check_dbm("evaluate_dbm_log_likelihood", dbm)
+    loader = loader if loader is not None else (getattr(dbm, "val_loader", None) or getattr(dbm, "dataloader", None))
+    if loader is None:
+        return None
+    log_z, se, ess = _known_or_estimated(log_z, estimate_dbm_log_partition, dbm, ais_kwargs)
+    (s,), n = _sum_batches(loader, max_batches, lambda batch: dbm_variational_bound(dbm, _first(batch), log_z, n_mf, damp).sum().reshape(1), 1)
+    res = {"mean_bound": s / max(1, n), "sum_bound": s, "n": n, "log_z": float(log_z), "se": se, "ess": ess}
+    _log_scalars(dbm, "ll/dbm_", res, ("mean_bound", "log_z", "se", "ess"))
+    return res
