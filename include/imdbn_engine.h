@@ -589,6 +589,35 @@ int imdbn_dbm_ais(int L, const float* const* W, const int64_t* ldw, const int* s
                   const float* betas, int K, int M, imdbn_rng* rng, double* logw, float* const* out_s, const int64_t* ld_out,
                   void* ws, size_t ws_bytes, imdbn_stream_t stream);
 
+/* ---- multimodal deep Boltzmann machine: one half-step of a layer of CATEGORICAL units (imdbn/models/mdbm.py; Srivastava &
+ *      Salakhutdinov 2012) -------------------------------------------------------------------------------------
+ * The operands, their pitches, the split of the reduction axis and the summation order of
+ *   pre[b][n] = s_lo sum_k x_lo[b][k] W_lo[k][n] + s_hi sum_j x_hi[b][j] W_hi[n][j] + bias[n]
+ * are imdbn_dbm_layer's, bit for bit (the label layer of the multimodal DBM passes the hi side only, W_hi being the rows
+ * [Dz, Dz + K) of the joint RBM's W).  The N units are tiled exactly by n_groups consecutive softmax groups: group g is the columns
+ * [group_end[g - 1], group_end[g]) with group_end[-1] = 0 and group_end[n_groups - 1] = N (group_end: a HOST array);
+ * 1 <= n_groups <= IMDBN_MAX_GROUPS, widths 2 .. 256.  Per row and group, in fp32:
+ *   mx = max_j pre_j,  e_j = expf(pre_j - mx),  p_j = e_j / sum,  where sum adds, per lane l of one wave, the columns l, l + 64,
+ *   l + 128, l + 192 of the group in that order and then the 64 lane sums in the xor butterfly 32, 16, .. 1.
+ *   mean field (m != NULL, s == NULL): m <- damp m + (1 - damp) p in place; res (float [B], nullable) = max_n |p - m_old| over the
+ *     whole row.  rng is not read.
+ *   sample (s != NULL, m == NULL): one ("c", width) draw per group, in group order, from the categorical source of rng: REPLAY
+ *     reads n_groups B indices of cat_tape, [g][b]; PHILOX walks the inverse CDF over clamp(p_j, 1e-8, 1) in column order (fp32,
+ *     left to right) against U total, U the uniform of (seed, draw + g, row0 + b, 0), as imdbn_rbm_sample_visible does.  s [B][N]
+ *     is the one-hot rows; p (nullable) the probabilities.  rng->cat_used / draws_used (= n_groups) are filled in.
+ * The logits stay in the workspace: [memset] one layer launch and one finish launch on `stream`, no host sync, no allocation, no
+ * floating-point atomics (the same call gives the same bits).  Padding is neither read nor written.  Workspace: 256-byte aligned,
+ * imdbn_dbm_group_layer_ws_bytes(K_lo, K_hi, N, B) (0 for shapes the call refuses); nothing in it needs to survive a call.
+ * Errors as imdbn_dbm_layer, in its words, before the first launch, nothing touched; further IMDBN_E_INVALID: n_groups outside
+ * 1 .. IMDBN_MAX_GROUPS or a null group_end, a width outside 2 .. 256, ends that do not tile [0, N). */
+size_t imdbn_dbm_group_layer_ws_bytes(int K_lo, int K_hi, int N, int B);
+int imdbn_dbm_group_layer(const float* W_lo, int64_t ldw_lo, int K_lo, const float* x_lo, int64_t ldx_lo, float s_lo,
+                          const float* W_hi, int64_t ldw_hi, int K_hi, const float* x_hi, int64_t ldx_hi, float s_hi,
+                          const float* bias, int N, int B, int mode, int n_groups, const int* group_end,
+                          float* m, int64_t ldm, float damp, float* res,
+                          imdbn_rng* rng, float* s, int64_t lds, float* p, int64_t ldp,
+                          void* ws, size_t ws_bytes, imdbn_stream_t stream);
+
 /* ---- Gaussian visible units with learned variances (imdbn/models/grbm.py: GaussianRBM; Cho, Ilin & Raiko 2011) ----
  * The parameters of the descriptor plus logvar [V] (device), sigma_i^2 = exp(logvar_i); with u = v exp(-logvar):
  *     p(h_j | v) = sigmoid(c_j + (u W)_j),   p(v_i | h) = N(b_i + (h W^T)_i, sigma_i^2),

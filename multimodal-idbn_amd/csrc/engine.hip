@@ -49,6 +49,7 @@
 #include "kernels_tap.hpp"
 #include "kernels_dbm.hpp"
 #include "kernels_dbm_ais.hpp"
+#include "kernels_dbm_group.hpp"
 
 using namespace imdbn;
 
@@ -1812,6 +1813,9 @@ int imdbn_rbm_centered_step(const imdbn_rbm_desc* d, const float* data, int64_t 
 
 // ---- deep Boltzmann machine: AIS log Z and the variational bound (imdbn/utils/likelihood.py; kernels_dbm_ais.hpp) ----------
 #include "host_dbm_ais.hpp"
+
+// ---- multimodal deep Boltzmann machine: the half-step of a layer of categorical units (imdbn/models/mdbm.py; kernels_dbm_group.hpp) ----
+#include "host_dbm_group.hpp"
 
 // ---- Gaussian visible units (imdbn/models/grbm.py; kernels_gauss.hpp) ----------------------------------------------------
 // p(h | v) is the Bernoulli engine applied to u = v e^{-z}, the mean of p(v | h) its logits path: K1 / K2 / K3 are called as they are.

@@ -784,11 +784,11 @@ class HipEngine:
     @staticmethod
     def _dbm_operands(who: str, lo, hi, x_lo, x_hi, bias):
         """The checked operands of a DBM layer call: ``(dev, n, B, Wl, Wh, xl, xh, b, kl, kh, ld)``; ``ld(t)``: the pitch of an optional
-        tensor (0 for None)."""
+        tensor (0 for None).  ``lo`` / ``hi``: an RBM, or a 2-D fp32 view with unit inner stride standing for its ``W`` (a row block
+        ``joint.W.data[:Dz]``: the layer is those rows)."""
         if lo is None and hi is None:
             raise N.EngineError(f"{who}: needs the RBM below, the RBM above or both")
-        Wl = None if lo is None else lo.W.data
-        Wh = None if hi is None else hi.W.data
+        Wl, Wh = (None if r is None else (r if isinstance(r, torch.Tensor) else r.W.data) for r in (lo, hi))      # an RBM, or a view of a W
         first = Wl if Wl is not None else Wh
         dev = first.device
         n = Wl.size(1) if Wl is not None else Wh.size(0)
@@ -939,6 +939,180 @@ class HipEngine:
         for l, rbm in enumerate(layers):
             lr, mom = epoch_scalars[l]
             self._assoc(rbm, pos[l], pos[l + 1], particles[l], particles[l + 1], lr, mom, False)
+        return {"mu": mu, "particles": particles, "res": res, "recon_loss": recon}
+
+    # ---- multimodal deep Boltzmann machine (imdbn_dbm_group_layer) ----------------------
+    def dbm_group_layer(self, lo, hi, x_lo, x_hi, bias, groups, m=None, damp=0.0, sample=False, rng=None, want_p=False, want_res=False,
+                        s_out=None):
+        """One half-step of a DBM layer of categorical units (imdbn_dbm_group_layer): ``pre = x_lo W_lo + x_hi
+        W_hi^T + bias`` as ``dbm_layer`` forms it; ``lo`` / ``hi``: an RBM or a 2-D fp32 view with unit inner stride standing for its
+        ``W`` (the label layer passes ``hi = joint.W.data[Dz:]`` alone).  ``groups``: ``(start, end)`` pairs that tile ``[0, N)`` in
+        order, at most ``MAX_GROUPS`` of width 2 to 256; ``p`` is the softmax of ``pre`` within each.  Mean field: ``m`` ``[B, N]``
+        fp32 (a column block of a wider tensor is fine) is updated in place, ``m <- damp m + (1 - damp) p``; returns the rows' ``max
+        |p - m_old|`` with ``want_res``, else None.  Sample: one ``("c", width)`` draw of ``rng`` per group; returns the one-hot rows
+        (written into ``s_out`` when given), or ``(p, s)`` with ``want_p``.  No host sync."""
+        from . import dp
+        if dp.active():
+            raise NotImplementedError("dbm_group_layer has no data-parallel split")
+        if bool(sample) == (m is not None):
+            raise N.EngineError("dbm_group_layer: mean field takes m (updated in place), sample=True takes none")
+        dev, n, B, Wl, Wh, xl, xh, b, kl, kh, ld = self._dbm_operands("dbm_group_layer", lo, hi, x_lo, x_hi, bias)
+        gs = [(int(s), int(e)) for s, e in groups]
+        if not 1 <= len(gs) <= N.MAX_GROUPS or gs[0][0] != 0 or gs[-1][1] != n or any(a[1] != c[0] for a, c in zip(gs, gs[1:])):
+            raise N.EngineError(f"dbm_group_layer: 1 to {N.MAX_GROUPS} groups must tile [0, {n}) in order, got {gs}")
+        ends = (C.c_int * len(gs))(*[e for _, e in gs])
+        need = int(self._lib.imdbn_dbm_group_layer_ws_bytes(kl, kh, n, B))
+        ws = self._buffer(("dbm_group_ws", dev, kl, kh, n, B, torch.cuda.current_stream(dev).cuda_stream),
+                          lambda: torch.empty(max(need, 256), dtype=torch.uint8, device=dev), need)
+        block = lambda t: (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32 and t.dim() == 2 and t.size(0) == B
+                           and t.size(1) == n and t.stride(1) == 1 and (B == 1 or t.stride(0) >= n))
+        res = p = smp = r = None
+        sched = [("c", e - s) for s, e in gs] if sample else []
+        if sample:
+            smp = torch.empty(B, n, device=dev) if s_out is None else s_out
+            if not block(smp):
+                raise N.EngineError(f"dbm_group_layer: the sample output must be an fp32 tensor [{B}, {n}] on {dev} with unit inner stride")
+            p = torch.empty(B, n, device=dev) if want_p else None
+            r, keep = self._rng(rng, sched, B, dev)
+        else:
+            if not block(m):
+                raise N.EngineError(f"dbm_group_layer: m must be an fp32 tensor [{B}, {n}] on {dev} with unit inner stride (updated in place)")
+            res = torch.empty(B, device=dev) if want_res else None
+        self._call("imdbn_dbm_group_layer", _ptr(Wl), ld(Wl), kl, _ptr(xl), ld(xl), 1.0, _ptr(Wh), ld(Wh), kh, _ptr(xh), ld(xh), 1.0,
+                   _ptr(b), n, B, self.mode, len(gs), ends, _ptr(m), ld(m), float(damp), _ptr(res), _ref(r), _ptr(smp), ld(smp), _ptr(p), ld(p),
+                   _ptr(ws), ws.numel(), self._stream(dev))
+        if sample:
+            self._done(rng, r, sched)
+            return (p, smp) if want_p else smp
+        return res
+
+    @staticmethod
+    def _mdbm_check(who: str, image_layers, joint, biases):
+        """``(L, Dz, K, J)`` of a multimodal DBM: ``L`` image RBMs, the joint RBM over ``[z_img (Dz) | y (K, one softmax group)]`` with
+        ``J`` hidden units, and the ``L + 3`` layer biases ``b_0 .. b_L, b_J, b_Y``."""
+        L = len(image_layers)
+        if L < 1 or len(biases) != L + 3:
+            raise N.EngineError(f"{who}: {L} image RBMs and the joint RBM need {L + 3} layer biases, got {len(biases)}")
+        Dz = image_layers[-1].W.size(1)
+        V, J = joint.W.shape
+        K = V - Dz
+        if [tuple(map(int, g)) for g in (getattr(joint, "softmax_groups", None) or [])] != [(Dz, V)]:
+            raise N.EngineError(f"{who}: the joint RBM's visible side must be [z_img ({Dz}) | y] with y its one softmax group")
+        return L, Dz, K, J
+
+    def mdbm_infer(self, image_layers, joint, biases, v, y, n_mf, damp=0.0, want_res=True):
+        """Mean-field posterior of a multimodal DBM given the image ``v`` ``[B, N_0]`` and, with ``y`` a one-hot
+        ``[B, K]``, the label; with ``y`` None the labels are free and start at ``softmax(b_Y)``.  Start: the doubled-weights pass of
+        ``dbm_infer`` up to ``z`` (``s = 2`` at every image layer), then ``J`` from ``[mu_L | y]`` with ``s = 1``.  Then ``n_mf``
+        Gauss-Seidel sweeps over the layers ``1 .. L`` (``z`` hears from the image stack and, through the rows ``[0, Dz)`` of the joint
+        ``W``, from ``J``), ``J``, and ``Y`` when free.  Returns ``([mu_1 .. mu_L, mu_J, mu_Y], res)``: ``mu_L`` and ``mu_Y`` are the
+        column blocks of ONE ``[B, Dz + K]`` tensor, the joint RBM's visible row (``mu_L._base``); ``res`` as ``dbm_infer``'s.  No
+        host sync."""
+        from . import dp
+        if dp.active():
+            raise NotImplementedError("mdbm_infer has no data-parallel split")
+        L, Dz, K, J = self._mdbm_check("mdbm_infer", image_layers, joint, biases)
+        x = _f32c(v)
+        B, dev = x.size(0), x.device
+        free = y is None
+        zy = torch.zeros(B, Dz + K, device=dev)
+        mz, my = zy[:, :Dz], zy[:, Dz:]
+        Wz, Wy = joint.W.data[:Dz], joint.W.data[Dz:]
+        mj = torch.zeros(B, J, device=dev)
+        if free:                                  # softmax(b_Y) by the layer's own kernel: a silent J leaves pre = b_Y exactly
+            self.dbm_group_layer(None, Wy, None, mj, biases[L + 2], [(0, K)], m=my)
+        else:
+            my.copy_(y)
+        mu = [torch.zeros(B, biases[l].numel(), device=dev) for l in range(1, L)] + [mz]
+        for l in range(1, L + 1):
+            self._dbm_layer(image_layers[l - 1], None, x if l == 1 else mu[l - 2], None, biases[l], mu[l - 1], 0.0, 2.0, 1.0, False, None,
+                            False, False)
+        self._dbm_layer(joint, None, zy, None, biases[L + 1], mj, 0.0, 1.0, 1.0, False, None, False, False)
+        res = torch.zeros(B, device=dev) if want_res else None
+        for it in range(int(n_mf)):
+            last = want_res and it == int(n_mf) - 1
+            rs = []
+            for l in range(1, L + 1):
+                rs.append(self._dbm_layer(image_layers[l - 1], image_layers[l] if l < L else Wz, x if l == 1 else mu[l - 2],
+                                          mu[l] if l < L else mj, biases[l], mu[l - 1], damp, 1.0, 1.0, False, None, False, last))
+            rs.append(self._dbm_layer(joint, None, zy, None, biases[L + 1], mj, damp, 1.0, 1.0, False, None, False, last))
+            if free:
+                rs.append(self.dbm_group_layer(None, Wy, None, mj, biases[L + 2], [(0, K)], m=my, damp=damp, want_res=last))
+            if last:
+                res = torch.stack(rs).amax(0)
+        return mu + [mj, my], res
+
+    def mdbm_gibbs(self, image_layers, joint, biases, particles, n_sweeps, rng, clamp_bottom=None, clamp_labels=None):
+        """``n_sweeps`` block-Gibbs sweeps of a multimodal DBM on ``particles``, in place: the ``L + 2`` tensors
+        ``[s_0 .. s_{L-1}, zy, s_J]`` with ``zy`` ``[M, Dz + K]`` holding ``z_img`` and the one-hot label side by side.  Two-colouring:
+        ``J`` is one class with the layers of parity ``L + 1``; ``Y`` goes with layer ``L``.  Per sweep the class of ``J`` bottom to
+        top, then the other class bottom to top with ``Y`` right after layer ``L``.  Draws: ``rng.sched_mdbm_gibbs``.  With
+        ``clamp_bottom`` ``[M, N_0]`` / ``clamp_labels`` one-hot ``[M, K]`` that layer is held and draws nothing.  Returns
+        ``particles``.  No host sync."""
+        from . import dp
+        if dp.active():
+            raise NotImplementedError("mdbm_gibbs has no data-parallel split")
+        L, Dz, K, J = self._mdbm_check("mdbm_gibbs", image_layers, joint, biases)
+        if len(particles) != L + 2:
+            raise N.EngineError(f"mdbm_gibbs: {L} image RBMs and the joint RBM need {L + 2} state tensors, got {len(particles)}")
+        zy = particles[L]
+        if zy.dim() != 2 or zy.size(1) != Dz + K:
+            raise N.EngineError(f"mdbm_gibbs: particles[{L}] must be [M, {Dz + K}], z_img and the label side by side")
+        state = lambda l: zy[:, :Dz] if l == L else particles[l]
+        Wz, Wy = joint.W.data[:Dz], joint.W.data[Dz:]
+        if clamp_bottom is not None:
+            particles[0].copy_(clamp_bottom)
+        if clamp_labels is not None:
+            zy[:, Dz:].copy_(clamp_labels)
+        for _ in range(int(n_sweeps)):
+            for parity in ((L + 1) & 1, L & 1):
+                for l in range(parity, L + 2, 2):
+                    if l == 0:
+                        if clamp_bottom is None:
+                            particles[0].copy_(self.sample_visible(image_layers[0], self.prop_down(image_layers[0], state(1)), rng))
+                    elif l <= L:
+                        self._dbm_layer(image_layers[l - 1], image_layers[l] if l < L else Wz, state(l - 1), state(l + 1), biases[l], None, 0.0,
+                                        1.0, 1.0, True, rng, False, False, s_out=state(l))
+                        if l == L and clamp_labels is None:
+                            self.dbm_group_layer(None, Wy, None, particles[L + 1], biases[L + 2], [(0, K)], sample=True, rng=rng,
+                                                 s_out=zy[:, Dz:])
+                    else:
+                        self._dbm_layer(joint, None, zy, None, biases[L + 1], None, 0.0, 1.0, 1.0, True, rng, False, False,
+                                        s_out=particles[L + 1])
+        return particles
+
+    def mdbm_step(self, image_layers, joint, data, labels, particles, epoch_scalars, n_mf, damp, gibbs_k, rng, monitor=True):
+        """One training step of a multimodal DBM (Srivastava & Salakhutdinov 2012) on one stream, no host sync.
+        The biases live in the RBMs: ``b_0 = image_layers[0].vis_bias``, ``b_l = image_layers[l-1].hid_bias``, ``b_J =
+        joint.hid_bias``, ``b_Y = joint.vis_bias[Dz:]``.  (1) ``mdbm_infer`` on ``(data, labels)`` with the label clamped; (2)
+        ``gibbs_k`` sweeps of ``mdbm_gibbs`` on ``particles`` (as many rows as ``data``, in place); (3) one ``assoc_update`` per image
+        RBM as ``dbm_step`` does, and one for the joint RBM from ``([mu_L | y], mu_J, [s_L | s_Y], s_J)``, with ``epoch_scalars[l] =
+        (lr, mom)`` (the joint RBM last), every RBM's own weight decay and no sparsity term.  The update also moves
+        ``image_layers[l].vis_bias`` for l >= 1 and ``joint.vis_bias[:Dz]``, which are no parameters of the model and are never read.
+        Returns ``{"mu", "particles", "res", "recon_loss"}`` as ``dbm_step``."""
+        from . import dp
+        if dp.active():
+            raise NotImplementedError("mdbm_step has no data-parallel split")
+        L = len(image_layers)
+        if L < 1 or len(epoch_scalars) != L + 1 or len(particles) != L + 2:
+            raise N.EngineError(f"mdbm_step: {L} image RBMs and the joint RBM need {L + 1} (lr, mom) pairs and {L + 2} particle tensors")
+        x = _f32c(data)
+        if any(p.size(0) != x.size(0) for p in particles):
+            raise N.EngineError("mdbm_step: the particles need as many rows as the data")
+        Dz = image_layers[-1].W.size(1)
+        biases = ([image_layers[0].vis_bias.data] + [r.hid_bias.data for r in image_layers]
+                  + [joint.hid_bias.data, joint.vis_bias.data[Dz:]])
+        mu, res = self.mdbm_infer(image_layers, joint, biases, x, labels, n_mf, damp=damp)
+        recon = None
+        if monitor:
+            recon = (self.prop_down(image_layers[0], mu[0]) - x).square().mean()
+        self.mdbm_gibbs(image_layers, joint, biases, particles, gibbs_k, rng)
+        pos = [x] + mu[:L]
+        for l, rbm in enumerate(image_layers):
+            lr, mom = epoch_scalars[l]
+            self._assoc(rbm, pos[l], pos[l + 1], particles[l], particles[l + 1][:, :Dz] if l + 1 == L else particles[l + 1], lr, mom, False)
+        lr, mom = epoch_scalars[L]
+        self._assoc(joint, mu[L - 1]._base, mu[L], particles[L], particles[L + 1], lr, mom, False)      # _base: the [mu_L | y] row
         return {"mu": mu, "particles": particles, "res": res, "recon_loss": recon}
 
     # ---- the DBM as a density model (imdbn_dbm_rowsum_layer, imdbn_dbm_ais; DESIGN section 41) ------------

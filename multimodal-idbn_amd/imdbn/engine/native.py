@@ -149,6 +149,9 @@ SIGNATURES = {
     "imdbn_dbm_ais_ws_bytes": (_SZ, [_INT, C.POINTER(_INT), _INT]),
     "imdbn_dbm_ais": (_INT, [_INT, C.POINTER(_P), C.POINTER(_I64), C.POINTER(_INT), C.POINTER(_P), _P, C.POINTER(_F), _INT, _INT,
                              C.POINTER(Rng), _P, C.POINTER(_P), C.POINTER(_I64), _P, _SZ, _P]),
+    "imdbn_dbm_group_layer_ws_bytes": (_SZ, [_INT, _INT, _INT, _INT]),
+    "imdbn_dbm_group_layer": (_INT, [_P, _I64, _INT, _P, _I64, _F, _P, _I64, _INT, _P, _I64, _F, _P, _INT, _INT, _INT, _INT, C.POINTER(_INT),
+                                     _P, _I64, _F, _P, C.POINTER(Rng), _P, _I64, _P, _I64, _P, _SZ, _P]),
     "imdbn_rbm_gauss_prop_up": (_INT, [C.POINTER(RbmDesc), _P, _P, _I64, _INT, _F, C.POINTER(Rng), _P, _I64, _P, _I64, _P, _SZ, _P]),
     "imdbn_rbm_gauss_prop_down": (_INT, [C.POINTER(RbmDesc), _P, _P, _I64, _INT, C.POINTER(Rng), _P, _I64, _P, _I64, _P, _SZ, _P]),
     "imdbn_rbm_gauss_sample_visible": (_INT, [C.POINTER(RbmDesc), _P, _P, _I64, _INT, C.POINTER(Rng), _P, _I64, _P]),

@@ -163,6 +163,24 @@ def sched_dbm_gibbs(sizes: Sequence[int], n_sweeps: int, clamp_bottom: bool = Fa
     return int(n_sweeps) * sweep
 
 
+def sched_mdbm_gibbs(sizes: Sequence[int], n_labels: int, n_sweeps: int, clamp_bottom: bool = False, clamp_labels: bool = False) -> Schedule:
+    """HipEngine.mdbm_gibbs: ``sizes`` are the image layers ``0 .. L`` bottom first and then the joint hidden layer (index L + 1);
+    the label layer is one categorical of ``n_labels``.  Per sweep the class of the joint layer (parity L + 1) bottom to top, then
+    the other class bottom to top with the label's ("c", n_labels) right after layer L; a sigmoid layer draws one ("u", N_l), layer 0
+    as ``sample_visible`` of a Bernoulli layer; a clamped layer draws nothing."""
+    L = len(sizes) - 2
+    sweep: Schedule = []
+    for parity in ((L + 1) & 1, L & 1):
+        for l in range(parity, L + 2, 2):
+            if l == 0:
+                sweep += [] if clamp_bottom else sched_sample_visible(int(sizes[0]), [])
+            else:
+                sweep.append(("u", int(sizes[l])))
+            if l == L and not clamp_labels:
+                sweep.append(("c", int(n_labels)))
+    return int(n_sweeps) * sweep
+
+
 def sched_dbm_ais(sizes: Sequence[int], K: int) -> Schedule:
     """imdbn_dbm_ais over K temperatures on layers of ``sizes`` units (bottom first): the start state, one ("u", N_l) per odd layer
     bottom to top, then one transition per temperature but the last: the even layers bottom to top, then the odd layers bottom to

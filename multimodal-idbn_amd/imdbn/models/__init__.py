@@ -7,10 +7,11 @@ from .grbm import GaussianRBM
 from .idbn import iDBN
 from .dbm import DBM
 from .imdbn import iMDBN
+from .mdbm import MultimodalDBM
 from .imdbn_bimodal import iMDBN_BiModal
 from . import gdbn_model_complete  # noqa: F401  (monolith path used by reference-written pickles)
 
-__all__ = ["RBM", "GaussianRBM", "iDBN", "DBM", "iMDBN", "iMDBN_BiModal"]
+__all__ = ["RBM", "GaussianRBM", "iDBN", "DBM", "iMDBN", "MultimodalDBM", "iMDBN_BiModal"]
 
 # Legacy Groundeep pickles name their classes src.classes.{rbm_model,dbn_model,gdbn_model}.*
 _this = sys.modules[__name__]

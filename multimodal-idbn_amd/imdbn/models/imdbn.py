@@ -533,6 +533,12 @@ class iMDBN(nn.Module):
             return evaluate_unit_tuning(self, joint=True, **kw)
         return evaluate_unit_tuning(self.image_idbn, upto_layer=upto_layer, **kw)
 
+    def to_dbm(self, **kw):
+        """The whole model -- image stack, joint RBM, label layer -- as one deep Boltzmann machine
+        (``imdbn.models.mdbm.MultimodalDBM.from_imdbn``): deep copies, this model is untouched."""
+        from imdbn.models.mdbm import MultimodalDBM
+        return MultimodalDBM.from_imdbn(self, **kw)
+
     # ---- persistence (imdbn.py:815-934, SURVEY.md Appendix C) -------------------------------------
     def save_model(self, path: str):
         all_layers = list(self.image_idbn.layers) + [self.joint_rbm]
